@@ -30,9 +30,16 @@ spread between the launches beside a cheap piece (shop-stream seeding: ALU) and 
 `python bench.py --gpus N` without torchrun (WORLD_SIZE unset) starts N child ranks itself -- before this process touches a GPU -- and
 exits non-zero with a message if fewer than N devices are visible.
 
-Beside the headline the line carries `step_path`: the same workload driven through bg_step (one call per step, actions
-from a device tensor: the surface RL code calls, balatro_env_2.py:616-637) and bg_step_many (K steps per call), timed on a
-short sample outside the headline's timed region.
+A plain run does only what the headline needs: set up, warm up, time the K steps, print the line.  Everything else is measured
+with `--full`: `samples` and `sustained` (above), the copy / fill kernels behind `roofline.peak_measured*`, `small_n` (4 096 envs),
+`step_path` -- the same workload driven through bg_step (one call per step, actions from a device tensor: the surface RL code calls,
+balatro_env_2.py:616-637) and bg_step_many (K steps per call), timed on a short sample outside the headline's timed region -- and
+`cpu_baseline`.
+
+`--dump-outputs DIR` writes what the last timed step computed -- every observation key of every env, and with the packed records
+(the default) its reward / action / terminated, plus the rollout counters -- as DIR/<name>.npy (float32 where that is exact, float64
+otherwise; a fixed, seeded sample of the envs when the whole would pass 64 MB).  The inputs are fixed by the arguments, so two builds
+can be compared output for output.
 """
 from __future__ import annotations
 
@@ -146,6 +153,47 @@ def matching_traffic(kernel: str, n: int, fused: float):
     return best
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_SAMPLE_SEED = 20251001
+EXACT_IN_F32 = ("int8", "uint8", "int16", "float32")   # every other dtype of the outputs is written as float64
+
+
+def last_step_outputs(env, buf, c):
+    """What a caller of the timed path holds after its last step, as device tensors with the env as leading dim: the c-th (last written)
+    row of the launch's output buffers, or the live observation arrays when the launch kept no per-step buffers."""
+    from balatro_gym_amd import _native as nat
+    from balatro_gym_amd.vec_env import RowBuffers
+    if isinstance(buf, RowBuffers):
+        out = {k: buf.tensors[k][c - 1] for k in nat.OBS_KEYS}
+        out.update(reward=buf.reward[c - 1], action=buf.action[c - 1], terminated=buf.terminated[c - 1])
+        return out
+    if buf is not None and buf.steps > 1:
+        return {k: buf.tensors[k][c - 1] for k in nat.OBS_KEYS}
+    return {k: env.obs[k] for k in nat.OBS_KEYS}
+
+
+def dump_outputs(path, outputs, stats, env_index0):
+    """outputs: name -> device tensor [N, ...].  Writes path/<name>.npy, and path/env_index.npy when only a sample of the envs fits."""
+    import numpy as np
+    import torch
+    n = next(iter(outputs.values())).shape[0]
+    f32 = {k for k, v in outputs.items() if str(v.dtype).replace("torch.", "") in EXACT_IN_F32}
+    per_env = sum((4 if k in f32 else 8) * (v[0].numel()) for k, v in outputs.items())
+    keep = min(n, (DUMP_LIMIT_BYTES - (1 << 20)) // per_env)
+    idx = None
+    if keep < n:
+        idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(n, keep, replace=False))
+    os.makedirs(path, exist_ok=True)
+    sel = None if idx is None else torch.from_numpy(idx).to(next(iter(outputs.values())).device)
+    for k, v in outputs.items():
+        v = v if sel is None else v.index_select(0, sel)
+        np.save(os.path.join(path, f"{k}.npy"), v.to(torch.float32 if k in f32 else torch.float64).cpu().numpy())
+    np.save(os.path.join(path, "rollout_stats.npy"),
+            np.array([stats[k] for k in ("steps", "episodes", "plays", "score_sum")], dtype=np.float64))
+    if idx is not None:
+        np.save(os.path.join(path, "env_index.npy"), (idx + env_index0).astype(np.float64))
+
+
 def spawn_ranks(n_gpus: int, need_devices: int) -> int:
     """`--gpus N` without a launcher: start N ranks of this script as child processes.  Nothing in THIS process has touched a GPU
     (torch.cuda.device_count() does not initialise HIP on this image), and it never re-executes itself."""
@@ -187,7 +235,11 @@ def main():
     ap.add_argument("--internal-warmup-s", type=float, default=None, help="(older spelling) converted to launches at 4 ms each")
     ap.add_argument("--dist-backend", default="nccl", help="nccl = RCCL over xGMI (the product path); gloo only for the two-ranks-on-one-GPU test")
     ap.add_argument("--share-gpu", action="store_true", help="testing only: every rank uses GPU 0 (needs --dist-backend gloo: RCCL refuses two ranks on one device)")
-    ap.add_argument("--samples", type=int, default=30, help="repeats of the K-step region after the timed one (median / p10 / p90)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline also measure samples, sustained, the copy / fill peaks of the roofline, small_n, step_path and cpu_baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--samples", type=int, default=30, help="--full: repeats of the K-step region after the timed one (median / p10 / p90)")
     ap.add_argument("--row-stride", type=int, default=384,
                     help="bytes between packed records: 384 = every record as three whole 128-byte lines (the fast layout), 352 = dense")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -264,9 +316,10 @@ def main():
     gather_done = [None] * len(bufs)
     launch_no = 0
     gather_bytes = 0
+    last_launch = (None, 0)   # (output buffers, steps) of the latest launch: its last row is what the caller sees last
 
     def run(nsteps, t0):
-        nonlocal gather_bytes, launch_no
+        nonlocal gather_bytes, launch_no, last_launch
         done = 0
         while done < nsteps:
             c = min(chunk, nsteps - done)
@@ -276,6 +329,7 @@ def main():
                 cur.wait_event(gather_done[b])
             env.rollout(c, policy=POLICY_CYCLE3, policy_seed=POLICY_SEED, env_index0=lo, t0=t0 + done,
                         obs_buffers=bufs[b], zero_stats=False)  # a shorter last call fills the first c rows
+            last_launch = (bufs[b], c)
             if do_gather:
                 gather_stream.wait_stream(cur)
                 with torch.cuda.stream(gather_stream):
@@ -369,29 +423,32 @@ def main():
     stats = env.stats()  # also checks the device error word
     stats["steps"] -= n * args.warmup   # (the statistics were zeroed before the warm-up steps)
     gather_bytes_timed = gather_bytes
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, last_step_outputs(env, *last_launch), stats, lo)
 
-    # ---- the same K-step region again, `--samples` times (each between two synchronisations; every rank runs the same count), then
-    # a SUSTAINED window: enough back-to-back repeats to span one lazy-refill period, no synchronisation in between
+    # ---- --full: the same K-step region again, `--samples` times (each between two synchronisations; every rank runs the same count),
+    # then a SUSTAINED window: enough back-to-back repeats to span one lazy-refill period, no synchronisation in between
     sample_s = []
-    barrier()
-    for _ in range(max(0, args.samples)):
-        stream_barrier()
+    if args.full:
+        barrier()
+        for _ in range(max(0, args.samples)):
+            stream_barrier()
+            t0s = time.perf_counter()
+            run(args.steps, t_off)
+            stream_barrier()
+            sample_s.append(time.perf_counter() - t0s)
+            t_off += args.steps
+        barrier()
+        prof_samples = env.get_profile()
+        reps = max(2, -(-env.max_fused_steps // max(1, args.steps)) + 1)
+        barrier()
         t0s = time.perf_counter()
-        run(args.steps, t_off)
-        stream_barrier()
-        sample_s.append(time.perf_counter() - t0s)
-        t_off += args.steps
-    barrier()
-    prof_samples = env.get_profile()
-    reps = max(2, -(-env.max_fused_steps // max(1, args.steps)) + 1)
-    barrier()
-    t0s = time.perf_counter()
-    for _ in range(reps):
-        run(args.steps, t_off)
-        t_off += args.steps
-    barrier()
-    sustained_s = time.perf_counter() - t0s
-    prof_sustained = env.get_profile()
+        for _ in range(reps):
+            run(args.steps, t_off)
+            t_off += args.steps
+        barrier()
+        sustained_s = time.perf_counter() - t0s
+        prof_sustained = env.get_profile()
     env.set_profiling(False)
     env.check()
     if world > 1 and sample_s:
@@ -420,7 +477,7 @@ def main():
         mean_launch_s = prof["rollout_ms"] / launches * 1e-3
         achieved = bytes_per_launch / mean_launch_s / 1e9 if mean_launch_s > 0 else 0.0
         traffic = matching_traffic(kernel, n, fused) if args.obs_layout == "rows" else None
-        peak_measured, peak_write = measured_copy_gbps(dev)
+        peak_measured, peak_write = measured_copy_gbps(dev) if args.full else (None, None)
         write_gbps = (OBS_ROW_WRITE_BYTES + STATE_BYTES / max(1.0, fused)) * n * fused / mean_launch_s / 1e9 if mean_launch_s > 0 else 0.0
         out = {
             "metric": "env-steps/sec at 65536 envs, random policy; achieved HBM GB/s vs peak",
@@ -480,11 +537,12 @@ def main():
                               "mean_launch_us": prof_samples["rollout_ms"] / nl * 1e3, "launches": nl,
                               "refill_launches": prof_samples["refill_launches"],
                               "median_roofline_frac": pick(0.5) * a_step / world / 1e9 / HBM_PEAK_GBPS}
-        out["sustained"] = {"value": total * args.steps * reps / sustained_s, "unit": "env-steps/s", "regions": reps,
-                            "what": f"{reps} back-to-back repeats of the {args.steps}-step region, no synchronisation in between",
-                            "refill_launches_inside": prof_sustained["refill_launches"], "launches": prof_sustained["rollout_launches"],
-                            "over_value": total * args.steps * reps / sustained_s / value,
-                            "roofline_frac": total * args.steps * reps / sustained_s * a_step / world / 1e9 / HBM_PEAK_GBPS}
+        if args.full:
+            out["sustained"] = {"value": total * args.steps * reps / sustained_s, "unit": "env-steps/s", "regions": reps,
+                                "what": f"{reps} back-to-back repeats of the {args.steps}-step region, no synchronisation in between",
+                                "refill_launches_inside": prof_sustained["refill_launches"], "launches": prof_sustained["rollout_launches"],
+                                "over_value": total * args.steps * reps / sustained_s / value,
+                                "roofline_frac": total * args.steps * reps / sustained_s * a_step / world / 1e9 / HBM_PEAK_GBPS}
         out["roofline"]["refill_launches_in_timed_region"] = prof["refill_launches"]
         out["roofline"]["refill_kernel_us_in_timed_region"] = prof["refill_ms"] * 1e3
         if use_dist:
@@ -498,7 +556,7 @@ def main():
     env.close()
     del ob, bufs
 
-    if rank == 0 and world == 1 and not args.no_small_n:
+    if rank == 0 and world == 1 and args.full and not args.no_small_n:
         # ---- BASELINE configs[1]'s size: 4 096 envs on one GPU (what the reference's own users run is smaller still), same workload and launch shape
         sn = 4096
         es = BalatroVecEnv(sn, [1000 + g for g in range(sn)], device=local_rank, scorer_jokers=True, autoreset=True, max_ante=MAX_ANTE)
@@ -524,7 +582,7 @@ def main():
                           "what": "BASELINE configs[1]'s env count with the workload of the headline line: 8 launches back to back"}
         del rbs
 
-    if rank == 0 and world == 1 and not args.no_step_path:
+    if rank == 0 and world == 1 and args.full and not args.no_step_path:
         # ---- the Gymnasium-surface path: bg_step with actions from a device tensor (recorded from a fused rollout of a twin
         # handle, so every action is the valid policy action of that state), then the same steps through bg_step_many
         ks = 800   # more than two refill periods (372 steps): the look-ahead refill runs beside these launches too (in pieces), and is inside the figure
@@ -591,7 +649,7 @@ def main():
                             **res}
 
     if rank == 0:
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             threads = os.cpu_count() or 1
             n_cpu, t_cpu = 256 * threads, 3000
             v, dt = cpu_baseline(n_cpu, t_cpu, threads)

@@ -16,6 +16,8 @@ Files:
                        calculate_score (2 000 cases: enhancements, editions, seals, joker-major chain, global-stream position)
   F8 sb3_fixed.npz     SafeBalatroEnv(BalatroEnvFixed(seed)) (train_balatro_fixed.py) stepped like a VecEnv: fixed space + observations
   F7 kat.json          the reference's own known answers (tests/chips_test.py:5-24, balatro_trajectories.json)
+  F9 reflog_<test>.npz the reference's answers to every question a test of tests/test_oracle_vs_reference.py asks it (tests/reflog.py)
+  F10 reference_spaces.npz  BalatroEnv's observation space and BalatroEnvFixed's over it; reference_jokers.json: JOKER_LIBRARY ids / costs
 """
 from __future__ import annotations
 
@@ -613,9 +615,54 @@ def gen_kat():
     print("F7 kat.json", len(kat["chips_test"]), "+", len(kat["trajectories"]), "known answers")
 
 
+def gen_reference_logs():
+    """F9: every test of tests/test_oracle_vs_reference.py that takes `ref`, run against the live reference through a recorder (the oracle
+    side of each test runs and asserts as in the suite, on the answers the replay will give)."""
+    import inspect
+    sys.path.insert(0, ROOT)
+    from tests import reflog
+    from tests import test_oracle_vs_reference as mod
+    for name, fn in sorted(vars(mod).items()):
+        if not name.startswith("test_") or "ref" not in inspect.signature(fn).parameters:
+            continue
+        params = [None]
+        for m in getattr(fn, "pytestmark", []):
+            if m.name == "parametrize":
+                params = list(m.args[1])
+        for p in params:
+            node = name if p is None else f"{name}[{p}]"
+            rec = reflog.Recorder(node)
+            fn(ref=rec) if p is None else fn(p, ref=rec)
+            rec.save()
+            print("F9", os.path.basename(reflog.log_path(node)), len(rec.calls), "answers")
+
+
+def gen_reference_spaces():
+    """F10: the observation space of balatro_env_2.BalatroEnv and the fixed space BalatroEnvFixed (train_balatro_fixed.py) builds over it,
+    as tests/reflog.describe_space gives them; and the joker library's ids / base costs."""
+    import contextlib
+    import io
+    sys.path.insert(0, ROOT)
+    from tests import reflog
+    tbf = rh.load_fixed_wrappers()
+    with contextlib.redirect_stdout(io.StringIO()):
+        fixed = tbf.BalatroEnvFixed(seed=1)
+    rec = {"env_" + k: v for k, v in reflog.describe_space(fixed.env.observation_space).items()}
+    rec.update({"fixed_" + k: v for k, v in reflog.describe_space(fixed.observation_space).items()})
+    np.savez_compressed(reflog.reference_space_path(), **rec)
+    jokers = [{"id": int(j.id), "name": str(j.name), "base_cost": int(j.base_cost)} for j in rh.load_reference()["jokers"].JOKER_LIBRARY]
+    with open(os.path.join(GOLD, "reference_jokers.json"), "w") as f:
+        json.dump(jokers, f)
+    print("F10 reference_spaces.npz", len(rec["env_keys"]), "->", len(rec["fixed_keys"]), "keys; reference_jokers.json", len(jokers), "jokers")
+
+
 def main():
     os.makedirs(GOLD, exist_ok=True)
-    which = sys.argv[1:] or ["mt", "classify", "score", "traces", "consumables", "boss", "kat", "sim", "sb3"]
+    which = sys.argv[1:] or ["mt", "classify", "score", "traces", "consumables", "boss", "kat", "sim", "sb3", "reference_logs", "reference_spaces"]
+    if "reference_logs" in which:
+        gen_reference_logs()
+    if "reference_spaces" in which:
+        gen_reference_spaces()
     if "mt" in which:
         gen_mt()
     if "classify" in which:

@@ -1,7 +1,8 @@
-"""CPU tests that run the imported Python reference side by side with the C oracle.
+"""CPU tests that hold the C oracle against the Python reference, step by step.
 
-Only runs where /root/reference exists (the build container); skipped on the GPU box.  This is the direct pin of
-the oracle: same seeds, same counter-hash policy, every observation key / reward / info compared bit-exactly.
+The reference's side is replayed from logs recorded with it (tests/golden/reflog_<test>.npz, tests/reflog.py; regenerate with
+`python oracle/gen_golden.py reference_logs` where the reference tree is present); the oracle runs live.  This is the direct pin of the
+oracle: same seeds, same counter-hash policy, every observation key / reward / info compared bit-exactly.
 """
 import random
 
@@ -10,16 +11,23 @@ import pytest
 
 from oracle import pyoracle as po
 from oracle import refharness as rh
+from tests import reflog
 from tests.helpers import OBS_KEYS, assert_obs_equal
 
-pytestmark = pytest.mark.skipif(not rh.reference_available(), reason="reference tree not present")
+
+@pytest.fixture
+def ref(request):
+    log = reflog.Replayer(request.node.name)
+    yield log
+    log.finish()
+
 
 TERMS = ["progress", "milestone", "score", "hand_quality", "efficiency", "synergy", "strategy", "ante_bonus"]
 
 
-def lockstep(seed, steps, policy, scorer=False, jokers=None, max_ante=0, env_index=0, money=None, ante=None,
+def lockstep(ref, seed, steps, policy, scorer=False, jokers=None, max_ante=0, env_index=0, money=None, ante=None,
              cards=None, levels=None, pseed=11, consumables=None):
-    r = rh.RefEnv(seed, scorer_jokers=scorer, max_ante=max_ante)
+    r = ref.env(seed, scorer_jokers=scorer, max_ante=max_ante)
     o = po.OracleEnv(seed, scorer_jokers=scorer, max_ante=max_ante)
 
     def inject():
@@ -62,57 +70,57 @@ def lockstep(seed, steps, policy, scorer=False, jokers=None, max_ante=0, env_ind
 
 
 @pytest.mark.parametrize("policy", [rh.POLICY_SMALL_ONLY, rh.POLICY_CYCLE3, rh.POLICY_UNIFORM])
-def test_env_lockstep_no_jokers(policy):
+def test_env_lockstep_no_jokers(policy, ref):
     for s in range(12):
-        lockstep(7000 + s, 500, policy, env_index=s)
+        lockstep(ref, 7000 + s, 500, policy, env_index=s)
 
 
-def test_env_lockstep_scorer_jokers():
+def test_env_lockstep_scorer_jokers(ref):
     from oracle.gen_golden import IMPLEMENTED
     for s in range(12):
-        lockstep(8000 + s, 500, rh.POLICY_CYCLE3, scorer=True, jokers=random.Random(s).sample(IMPLEMENTED, 5),
+        lockstep(ref, 8000 + s, 500, rh.POLICY_CYCLE3, scorer=True, jokers=random.Random(s).sample(IMPLEMENTED, 5),
                  max_ante=4, env_index=s)
 
 
-def test_env_lockstep_rich_shop_and_late_antes():
+def test_env_lockstep_rich_shop_and_late_antes(ref):
     for s in range(10):
-        lockstep(9000 + s, 600, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=22,
+        lockstep(ref, 9000 + s, 600, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=22,
                  money=[500, 3000, 100000][s % 3], ante=[1, 2, 5, 9, 20][s % 5],
                  jokers=random.Random(s).sample(range(1, 151), s % 6))
 
 
-def test_env_lockstep_card_states_and_levels():
+def test_env_lockstep_card_states_and_levels(ref):
     for s in range(10):
         rr = random.Random(40 + s)
         cards = [(d, rr.choice([0, 0, 1, 2, 3, 4, 5, 6, 7, 8]), rr.choice([0, 0, 1, 2, 3]), rr.choice([0, 0, 1, 2, 3]))
                  for d in range(12)]
         levels = [(ht, rr.randint(1, 15)) for ht in range(9)]
-        lockstep(9500 + s, 400, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=20, cards=cards,
+        lockstep(ref, 9500 + s, 400, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=20, cards=cards,
                  levels=levels, jokers=rr.sample(range(1, 151), s % 6))
 
 
-def test_env_lockstep_consumables():
+def test_env_lockstep_consumables(ref):
     """Tarot / spectral / planet use (balatro_env_2.py:1066-1172, consumables.py) incl. the cases where the reference
     raises (harness convention: reward -1.0, state as the exception left it), and Immolate / Cryptid (deck length changes)."""
     pool = list(range(1, 23)) + list(range(30, 42)) + list(range(50, 68))
     for s in range(26):
         rr = random.Random(70 + s)
         cards = [(d, rr.choice([0, 0, 4, 8]), 0, rr.choice([0, 4])) for d in range(16)] if s % 2 else None
-        lockstep(9700 + s, 400, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=20, cards=cards,
+        lockstep(ref, 9700 + s, 400, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=20, cards=cards,
                  consumables=[pool[(2 * s) % len(pool)], pool[(2 * s + 1) % len(pool)]], money=[None, 30][s % 2],
                  jokers=([53] if s % 3 == 0 else []) + rr.sample(range(1, 53), s % 5))
 
 
-def test_env_lockstep_immolate_cryptid():
+def test_env_lockstep_immolate_cryptid(ref):
     """Immolate (five sampled cards leave the live deck list: every later index shifts) and Cryptid (two foreign copies
     appended) over and over, with The Fool copying them and Blue Joker reading len(deck)."""
     for s in range(16):
-        lockstep(9800 + s, 500, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=20,
+        lockstep(ref, 9800 + s, 500, rh.POLICY_UNIFORM, scorer=bool(s & 1), env_index=s, max_ante=20,
                  consumables=[[59, 65], [65, 59], [59, 1], [65, 1], [59, 59], [1, 59]][s % 6], jokers=[53, 1][: 1 + s % 2],
                  cards=[(d, [0, 7, 4][d % 3], 0, [0, 4][d % 2]) for d in range(20)] if s % 4 == 0 else None)
 
 
-def test_env_lockstep_forced_rare_hands():
+def test_env_lockstep_forced_rare_hands(ref):
     """Decks arranged so that the first play IS a chosen hand type (straight flush, four of a kind, flush ... at
     deck[0..k-1]; classification reads deck[position]), at antes 1..8, small / big / boss blinds, with and without
     scorer-level jokers: reference and oracle in lockstep through the play and 40 more steps."""
@@ -122,7 +130,7 @@ def test_env_lockstep_forced_rare_hands():
     for s in range(9 * 12):
         ht, scorer = s % 9, bool((s // 9) & 1)
         seed = 9900 + s
-        r = rh.RefEnv(seed, scorer_jokers=scorer)
+        r = ref.env(seed, scorer_jokers=scorer)
         o = po.OracleEnv(seed, scorer_jokers=scorer)
         deck, k = forced_deck(ht, rr)
         jokers = rr.sample(range(1, 151), rr.randint(0, 5)) if scorer else [113, 40, 33][: s % 4]
@@ -151,7 +159,7 @@ def test_env_lockstep_forced_rare_hands():
     assert min(seen) >= 6, seen
 
 
-def test_sim_evaluate_and_score_lockstep():
+def test_sim_evaluate_and_score_lockstep(ref):
     """balatro_sim.BalatroSimulator (imported with the SURVEY App. C shim) against oracle/bo_sim.c on fresh random hands."""
     import ctypes as C
     from oracle.gen_golden import IMPLEMENTED, sim_random_hand
@@ -159,14 +167,14 @@ def test_sim_evaluate_and_score_lockstep():
     for i in range(1500):
         cards = sim_random_hand(r)
         ff, sc = bool(i & 1), bool(i & 2)
-        assert rh.sim_evaluate(cards, ff, sc) == po.sim_evaluate(cards, ff, sc), (cards, ff, sc)
+        assert ref.sim_evaluate(cards, ff, sc) == po.sim_evaluate(cards, ff, sc), (cards, ff, sc)
     L = po.lib()
     for i in range(600):
         cards = sim_random_hand(r, n=r.choice([1, 2, 3, 4, 5, 5, 5]))
         jokers = r.sample(IMPLEMENTED + [18, 69, 100], r.randint(0, 5))
         gs = None if i % 2 else {"hands_left": r.randint(1, 4), "discards_left": r.randint(0, 3)}
         dl, seed = r.choice([0, 40, 52]), r.randrange(2 ** 32)
-        score, money, probe = rh.sim_score(cards, jokers, gs, dl, seed)
+        score, money, probe = ref.sim_score(cards, jokers, gs, dl, seed)
         o = po.sim_score(cards, jokers, 1 if gs is None else gs["hands_left"], 0 if gs is None else gs["discards_left"], dl, seed)
         mt = po.MT()
         L.bo_mt_seed(C.byref(mt), seed)
@@ -175,9 +183,9 @@ def test_sim_evaluate_and_score_lockstep():
         assert (o.score, o.money, L.bo_mt_u32(C.byref(mt))) == (score, money, probe), (cards, jokers, gs, dl, seed)
 
 
-def test_reseed_reproduces_first_shuffle():
+def test_reseed_reproduces_first_shuffle(ref):
     """reset(seed=s) rebuilds the streams (balatro_env_2.py:507-509); reset() continues them."""
-    r = rh.RefEnv(42)
+    r = ref.env(42)
     o = po.OracleEnv(42)
     for e in (r, o):
         e.step(45)
@@ -194,7 +202,7 @@ def test_reseed_reproduces_first_shuffle():
     assert r.obs()["hand"].tolist() == first and o.obs()["hand"].tolist() == first
 
 
-def test_consumable_deck_fence_placement():
+def test_consumable_deck_fence_placement(ref):
     """WHERE the `BG_ERR_CONSUMABLE_DECK` fence stands relative to the reference.
     Immolate (consumables.py:519-531) removes five sampled cards from the live deck list.  The restatement follows it while the hand's deck indexes
     (always 0..7) stay valid behind the use, i.e. while 13 or more real cards are left -- EIGHT uses in one episode, 52 -> 12 cards, in lockstep with the
@@ -202,7 +210,7 @@ def test_consumable_deck_fence_placement():
     The reference accepts it (reward 7.0) and plays on with a deck of 7, 2, 0 cards while its hand still holds indexes up to 7: from there on its
     unguarded deck[i] reads (balatro_env_2.py:577,670,937) raise IndexError as soon as a play or a boss blind touches one -- the first step after the
     deck is empty at the latest.  So the fence now stands where the reference's own state stops being one it can step from."""
-    r = rh.RefEnv(4242, scorer_jokers=False, max_ante=20)
+    r = ref.env(4242, scorer_jokers=False, max_ante=20)
     o = po.OracleEnv(4242, scorer_jokers=False, max_ante=20)
     for e in (r, o):
         e.step(45)
@@ -221,7 +229,7 @@ def test_consumable_deck_fence_placement():
                 assert ro == rr == 7.0 and int(obs_r["deck_size"]) == 47 - 5 * it
                 uses_followed += 1
             else:   # the fence: the reference goes on, the restatement refuses
-                assert rr == 7.0 and len(r.env.state.deck) == 7
+                assert rr == 7.0 and r.deck_len() == 7
                 assert ro == -1.0 and io.error == 12 and int(obs_o["deck_size"]) == 12
     assert uses_followed == 8
     # ... and the reference alone: down to an empty deck, then IndexError on the next play
@@ -229,23 +237,22 @@ def test_consumable_deck_fence_placement():
         r.set_consumables([59])
         for act in (2, 3, 10):
             r.step(act)
-    assert len(r.env.state.deck) == 0
+    assert r.deck_len() == 0
     with pytest.raises(IndexError):
         for act in (2, 3, 0):
             r.step(act)
 
 
-def test_immolate_pool_with_cryptid_copies_vs_reference():
+def test_immolate_pool_with_cryptid_copies_vs_reference(ref):
     """random.sample's POOL method (n <= 21) over a deck that ends in Cryptid's copies (consumables.Card objects behind the real cards): two Cryptids,
     then Immolates down to 12 real cards -- the last ones draw from a pool whose tail are copies (a picked copy leaves through deck.remove of an equal
     copy, a picked real card shifts every later index) -- in lockstep with the reference, observation by observation."""
-    r = rh.RefEnv(5151, scorer_jokers=False, max_ante=20)
+    r = ref.env(5151, scorer_jokers=False, max_ante=20)
     o = po.OracleEnv(5151, scorer_jokers=False, max_ante=20)
     for e in (r, o):
         e.step(45)
     def counts():
-        real = sum(1 for c in r.env.state.deck if type(c).__module__.endswith("cards"))
-        return real, len(r.env.state.deck)
+        return r.deck_real_cards(), r.deck_len()
     pool_with_copies, uses = 0, 0
     for it, cid in enumerate([65, 65] + [59] * 10):
         real, total = counts()
@@ -263,11 +270,11 @@ def test_immolate_pool_with_cryptid_copies_vs_reference():
     assert pool_with_copies >= 1 and uses >= 10, (pool_with_copies, uses)   # the pool method really ran with copies in the pool
 
 
-def test_cryptid_int8_fence_placement():
+def test_cryptid_int8_fence_placement(ref):
     """Cryptid (consumables.py:581-591) appends two copies per use; `deck_size` is np.int8(len(deck)) (balatro_env_2.py:1491).  The restatement follows the
     reference up to 126 cards (37 uses on a full deck) and refuses the use that would make 128 -- where the reference's OWN observation stops being
     defined: np.int8(128) raises OverflowError under numpy >= 2 and wraps to -128 under numpy 1 (it was fenced at 60 copies before)."""
-    r = rh.RefEnv(6262, scorer_jokers=False, max_ante=20)
+    r = ref.env(6262, scorer_jokers=False, max_ante=20)
     o = po.OracleEnv(6262, scorer_jokers=False, max_ante=20)
     for e in (r, o):
         e.step(45)
@@ -279,7 +286,7 @@ def test_cryptid_int8_fence_placement():
             obs_o, ro, to, _, io = o.step(act)
             assert_obs_equal(obs_o, obs_r, f"Cryptid {it} action {act}")
             assert ro == rr, (it, act)
-    assert int(obs_o["deck_size"]) == 126 and len(r.env.state.deck) == 126
+    assert int(obs_o["deck_size"]) == 126 and r.deck_len() == 126
     o.set_consumables([65]); r.set_consumables([65])
     for act in (2, 3):
         o.step(act); r.step(act)
@@ -287,48 +294,36 @@ def test_cryptid_int8_fence_placement():
     assert ro == -1.0 and io.error == 12 and int(obs_o["deck_size"]) == 126
     try:
         obs_r, rr, *_ = r.step(10)
-        assert int(obs_r["deck_size"]) == -128 and len(r.env.state.deck) == 128      # numpy 1: wrapped
+        assert int(obs_r["deck_size"]) == -128 and r.deck_len() == 128               # numpy 1: wrapped
     except OverflowError:
-        assert len(r.env.state.deck) == 128                                            # numpy >= 2: the reference's step raises out of _get_observation
+        assert r.deck_len() == 128                                                     # numpy >= 2: the reference's step raises out of _get_observation
 
 
 def test_reference_wrapper_over_the_drop_in_space():
-    """The reference's own `BalatroEnvFixed.__init__` (train_balatro_fixed.py:20-124) run over the DROP-IN's observation space instead
-    of the reference env's: it walks `self.env.observation_space.spaces.items()`, so it must come out with the same 51-key fixed
-    space it builds over `balatro_env_2.BalatroEnv` (the space recorded in tests/golden/sb3_fixed.npz) -- key order, dtypes, shapes and
-    the bounds of every Box it keeps as is.  No GPU: a stand-in env class that carries only the two spaces takes the drop-in's place."""
-    import contextlib
+    """The reference's own `BalatroEnvFixed.__init__` (train_balatro_fixed.py:20-124) builds its fixed space by walking
+    `self.env.observation_space.spaces.items()` and reading, key by key, only the space's kind (Box / Discrete / MultiBinary), shape,
+    dtype, bounds and n.  So over the DROP-IN's space it comes out with the same 51-key fixed space it builds over
+    `balatro_env_2.BalatroEnv` (the space recorded in tests/golden/sb3_fixed.npz) -- key order, dtypes, shapes, the bounds of every Box
+    it keeps as is, the same transforms -- when the drop-in's space equals the reference env's in all of those, key by key and in order.
+    Both spaces the reference built are recorded in tests/golden/reference_spaces.npz.  No GPU."""
     import importlib
-    import io
     import os
-    tbf = rh.load_fixed_wrappers()          # (installs the gymnasium stand-in the reference is imported with)
+    rh._install_gymnasium_shim()            # (the gymnasium stand-in the reference is imported with)
     import balatro_gym_amd.env as envmod
     envmod = importlib.reload(envmod)        # the drop-in builds its space from whatever `gymnasium` is importable: now the stand-in
-    space = envmod.make_observation_space()
-
-    class SpacesOnly:
-        def __init__(self, seed=None):
-            self.observation_space = space
-            self.action_space = envmod._spaces.Discrete(60)
-
-    ref_cls = tbf.OriginalBalatroEnv
-    try:
-        tbf.OriginalBalatroEnv = SpacesOnly
-        with contextlib.redirect_stdout(io.StringIO()):
-            over_drop_in = tbf.BalatroEnvFixed(seed=1)
-        tbf.OriginalBalatroEnv = ref_cls
-        with contextlib.redirect_stdout(io.StringIO()):
-            over_reference = tbf.BalatroEnvFixed(seed=1)
-    finally:
-        tbf.OriginalBalatroEnv = ref_cls
-    a, b = over_drop_in.observation_space.spaces, over_reference.observation_space.spaces
-    assert list(a) == list(b) and len(a) == 51
-    assert over_drop_in.space_transforms == over_reference.space_transforms
-    for k in a:
-        assert a[k].dtype == b[k].dtype and tuple(a[k].shape) == tuple(b[k].shape), k
-        assert np.array_equal(np.asarray(a[k].low, dtype=np.float64), np.asarray(b[k].low, dtype=np.float64)), k
-        assert np.array_equal(np.asarray(a[k].high, dtype=np.float64), np.asarray(b[k].high, dtype=np.float64)), k
+    got = reflog.describe_space(envmod.make_observation_space())
+    with np.load(reflog.reference_space_path()) as z:
+        want = {k[len("env_"):]: z[k] for k in z.files if k.startswith("env_")}
+        fixed = {k[len("fixed_"):]: z[k] for k in z.files if k.startswith("fixed_")}
+    assert list(got["keys"]) == list(want["keys"])
+    for attr in ("kind", "dtype", "shape", "n"):
+        assert list(got[attr]) == list(want[attr]), attr
+    for k in want["keys"]:
+        for b in ("low", "high"):
+            g, w = got[f"{b}_{k}"], want[f"{b}_{k}"]
+            assert g.dtype == w.dtype and np.array_equal(g, w), (b, k)
+    assert len(fixed["keys"]) == 51
     from tests.helpers import GOLD
     with np.load(os.path.join(GOLD, "sb3_fixed.npz")) as z:
-        assert [str(x) for x in z["keys"]] == list(a)
-        assert [str(x) for x in z["dtypes"]] == [a[k].dtype.name for k in a]
+        assert [str(x) for x in z["keys"]] == list(fixed["keys"])
+        assert [str(x) for x in z["dtypes"]] == list(fixed["dtype"])

@@ -115,7 +115,7 @@ def test_bench_two_ranks_one_gpu():
     """bench.py --gpus 2 started WITHOUT a launcher: it spawns the ranks itself; both ranks run the fixed-count warm-up, the gather
     of the current record inside the timed region, the repeated samples and the sustained window, and rank 0 prints the line."""
     out = _bench(["--gpus", "2", "--share-gpu", "--dist-backend", "gloo", "--envs-per-gpu", "2048", "--steps", "20", "--warmup", "5",
-                  "--samples", "3", "--internal-warmup-launches", "5", "--no-cpu-baseline"])
+                  "--full", "--samples", "3", "--internal-warmup-launches", "5", "--no-cpu-baseline"])
     assert out.returncode == 0, out.stderr[-2000:]
     line = [l for l in out.stdout.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
