@@ -692,26 +692,22 @@ struct bg_handle {
   long refill_done;      // highest refill index KNOWN to have completed (hipEventQuery): launches that read its view need no stream wait any more
   long view_min;         // index of the last SYNCHRONOUS refill: no launch may read producer counters older than its
   bool async_refill;     // BG_ASYNC_REFILL (default on): bg_rollout overlaps refill #i with rollout chunk i+1
-  hipStream_t side, side2, side3; // side: overlapped refills; side2/3: the deck and block kernels of one refill run beside the shop kernel
-  hipEvent_t ev_scan, ev_deck, ev_gblk;
+  hipStream_t side;      // overlapped refills, at the lowest stream priority (bg_create_ex)
   hipEvent_t ev_refill[2];
   hipEvent_t ev_rollout;
   std::vector<hipEvent_t> ev_rollout_t, ev_refill_t, ev_step_t; // start/stop pairs
   std::vector<int> rollout_steps;                         // fused steps of each timed rollout launch
-  // tunables read ONCE per handle in bg_create (environment variables)
-  int refill_blocks, refill_blocks_shop, dev_skip_refill, refill_order, refill_min;
+  // tunables read ONCE per handle in bg_create_ex (environment variables)
   // a refill in PIECES (bg_refill_pieces): the kernels of refill #(refill_seq - 1) that are still to be issued, one (or a few) beside every short launch
   struct RefillPiece { int kind; uint32_t part, nparts; int grid; uint32_t cursor, max_made; };   // kind: 0 deck, 1 seed ring, 2 global blocks, 3 shop streams
   std::vector<RefillPiece> pieces;
   size_t piece_next;
   BgDev piece_dev;
-  int refill_sliced, piece_parts[4], piece_grid[4];
-  int deck_passes, deck_rounds, refill_interleave, refill_sliced_div;
-  uint32_t eng_run, eng_play, eng_other, eng_part, eng_more, eng_smask; int eng_waves, eng_copiers; // queue thresholds of the step engine (BG_ENG_RUN / _PLAY / _OTHER)
+  int refill_sliced, piece_parts[4], deck_passes;   // BG_REFILL_SLICED, BG_REFILL_PARTS; deck passes over the list (3, fewer if the parts would need more cursors)
+  uint32_t eng_smask; int eng_copiers;   // bg_engine.h: the service waves (BG_ENG_SMASK) and copier waves (BG_ENG_COPIERS; 0 = by launch length)
   int engine;            // BG_ENGINE: 3 = bg_engine3.h (owner + service waves in one workgroup) for packed-record rollouts (default), 1 = bg_engine.h everywhere
-  // bg_engine3.h: workgroup shape (BG_E3_CFG = 100 * owner waves + 10 * slices + service waves; 0 = by env count) and the service waves' batch
-  // thresholds (BG_E3_TH requests, or after BG_E3_WAIT ticks of 10 ns)
-  int e3_cfg, e3_epw; uint32_t e3_th, e3_wait;
+  // bg_engine3.h: workgroup shape (BG_E3_CFG = 100 * owner waves + 10 * slices + service waves; 0 = by env count) and live envs per 64-env workgroup (BG_E3_EPW)
+  int e3_cfg, e3_epw;
   // sharded jobs (bg_set_gather_peers): every rank's gather buffer as mapped into THIS process, the size of the job and this handle's rank
   uint8_t* gpeer[8]; uint8_t** d_gpeer; int gworld, grank;   // d_gpeer: the same eight pointers in device memory (what the kernel reads)
 };
@@ -828,9 +824,6 @@ static int bg_gsteps(int flags, int blocks) { // inverse: steps that `blocks` fu
   return t < 0 ? 0 : (int)t;
 }
 
-// development aid: choose which refill kernels run (bit set = skipped; tools/refill_alone.py)
-int bg_debug_set_skip(bg_handle* h, int skip) { if (!h) return BG_E_ARG; h->dev_skip_refill = skip; return 0; }
-
 // development aid: the four work-list lengths of the most recent refill (decks, seed rings, global blocks, shop streams)
 int bg_debug_worklists(bg_handle* h, unsigned int* out4) {
   if (!h || !out4) return BG_E_ARG;
@@ -877,43 +870,29 @@ int bg_create_ex(int n_envs, int device_id, uint32_t flags, int max_ante, int fu
   { const char* av = getenv("BG_ASYNC_REFILL"); h->async_refill = av ? atoi(av) != 0 : true; }
   { // every tunable is read here, once per handle (a process may A/B two handles with different settings)
     auto geti = [](const char* k, int dflt) { const char* v = getenv(k); return v ? atoi(v) : dflt; };
-    h->refill_blocks = geti("BG_REFILL_BLOCKS", 4096); h->refill_blocks_shop = geti("BG_REFILL_BLOCKS_SHOP", 0);
-    h->dev_skip_refill = geti("BG_DEV_SKIP_REFILL", 0);
-    h->refill_order = geti("BG_REFILL_ORDER", 2);
-    // BG_REFILL_MIN = m > 0: a rollout launch of >= m steps (since the last refill) takes a refill beside it.  Default 0 = only when the rings demand one:
-    // 20 steps' worth of refill is ~320 us of five small latency-bound kernels against 129 us per 20 steps in bulk (profiles/r05/refill_policy_ab.txt:
-    // a refill beside every 20-step launch costs 21 % of the sustained rate)
-    h->refill_min = geti("BG_REFILL_MIN", 0);
     // BG_REFILL_SLICED = 1: the refill a run of SHORT launches demands (every 18th launch at 20 steps) is issued in pieces -- its scan beside the launch that
-    // demanded it, then one dense kernel over a PART of a work list beside each of the next launches (BG_REFILL_PARTS = deck,seedring,blocks,shop parts;
-    // BG_REFILL_GRIDS = their grids: no more one-wave workgroups than fit beside a resident engine, so that none is left to be placed in the gap between
-    // two launches, where it would take the registers the next engine workgroup needs)
+    // demanded it, then one dense kernel over a PART of a work list beside each of the next launches (BG_REFILL_PARTS = deck,seedring,blocks,shop parts)
     h->refill_sliced = geti("BG_REFILL_SLICED", 1);
-    { const int dp[4] = {2, 1, 2, 8}, dg[4] = {512, 768, 1024, 1024};
-      for (int k = 0; k < 4; k++) { h->piece_parts[k] = dp[k]; h->piece_grid[k] = dg[k]; }
+    { const int dp[4] = {2, 1, 2, 8};
+      for (int k = 0; k < 4; k++) h->piece_parts[k] = dp[k];
       auto get4 = [](const char* k, int* out, int lo, int hi) { const char* v = getenv(k); if (!v) return; int a[4]; if (sscanf(v, "%d,%d,%d,%d", &a[0], &a[1], &a[2], &a[3]) == 4) for (int i = 0; i < 4; i++) out[i] = a[i] < lo ? lo : a[i] > hi ? hi : a[i]; };
-      get4("BG_REFILL_PARTS", h->piece_parts, 1, 16); get4("BG_REFILL_GRIDS", h->piece_grid, 64, 65536); }
+      get4("BG_REFILL_PARTS", h->piece_parts, 1, 16); }
     h->piece_next = 0;
-    h->refill_interleave = geti("BG_REFILL_INTERLEAVE", 1);
-    h->refill_sliced_div = geti("BG_REFILL_SLICED_DIV", 2); if (h->refill_sliced_div < 1) h->refill_sliced_div = 1;   // launches of at most max_chunk / div steps get the refill in pieces
-    h->deck_passes = geti("BG_REFILL_DECK_PASSES", 3); h->deck_rounds = geti("BG_REFILL_DECK_ROUNDS", 6);
-    if (h->deck_passes < 1) h->deck_passes = 1; if (h->deck_rounds < 1) h->deck_rounds = 1;
+    h->deck_passes = 3;
     while (h->deck_passes * h->piece_parts[0] > BG_WL_COUNTERS - 8) { if (h->deck_passes > 1) h->deck_passes--; else h->piece_parts[0]--; }
-    h->eng_run = (uint32_t)geti("BG_ENG_RUN", 64); h->eng_play = (uint32_t)geti("BG_ENG_PLAY", 64); h->eng_other = (uint32_t)geti("BG_ENG_OTHER", 64);
-    h->eng_part = (uint32_t)geti("BG_ENG_PART", 1); h->eng_more = (uint32_t)geti("BG_ENG_MORE", 0); h->eng_smask = (uint32_t)geti("BG_ENG_SMASK", BG_ENG_SMASK_DEFAULT); h->eng_waves = geti("BG_ENG_WAVES", 0); h->eng_copiers = geti("BG_ENG_COPIERS", 0); if (h->eng_copiers < 0 || h->eng_copiers > 3) h->eng_copiers = 0;   // 0 = by launch length (bg_engine_launch)
+    h->eng_smask = (uint32_t)geti("BG_ENG_SMASK", BG_ENG_SMASK_DEFAULT); h->eng_copiers = geti("BG_ENG_COPIERS", 0); if (h->eng_copiers < 0 || h->eng_copiers > 3) h->eng_copiers = 0;   // 0 = by launch length (bg_engine_launch)
     if (h->eng_smask == 0 || h->eng_smask >= (1u << BG_ENG_NW) || __builtin_popcount(h->eng_smask) > BG_ENG_NSV) h->eng_smask = BG_ENG_SMASK_DEFAULT;
     h->engine = geti("BG_ENGINE", 3);
     if (h->engine != 1 && h->engine != 3) { delete h; g_create_err = "bg_create: BG_ENGINE must be 3 (bg_engine3.h, the default) or 1 (bg_engine.h); the two-kernel engine 2 was retired in round 5"; return BG_E_ARG; }
     h->e3_cfg = geti("BG_E3_CFG", 0);
-    if (h->e3_cfg != 0 && h->e3_cfg != 113 && h->e3_cfg != 213 && h->e3_cfg != 413 && h->e3_cfg != 414) { delete h; g_create_err = "bg_create: BG_E3_CFG must be 113, 213, 413 or 414 (100 x owner waves + 10 x slices + service waves)"; return BG_E_ARG; }
-    h->e3_th = (uint32_t)geti("BG_E3_TH", 0x7fffffff); h->e3_wait = (uint32_t)geti("BG_E3_WAIT", 0);
+    if (h->e3_cfg != 0 && h->e3_cfg != 113 && h->e3_cfg != 213 && h->e3_cfg != 413) { delete h; g_create_err = "bg_create: BG_E3_CFG must be 113, 213 or 413 (100 x owner waves + 10 x slices + service waves)"; return BG_E_ARG; }
     for (int g = 0; g < 8; g++) h->gpeer[g] = nullptr;
     h->d_gpeer = nullptr;
     h->gworld = 0; h->grank = 0;
     h->e3_epw = geti("BG_E3_EPW", 0);   // live envs per 64-env workgroup (0 = by env count)
     if (h->e3_epw != 0 && (h->e3_epw < 1 || h->e3_epw > 64)) { delete h; g_create_err = "bg_create: BG_E3_EPW must be in [1, 64]"; return BG_E_ARG; }
   }
-  h->d_prod[0] = h->d_prod[1] = nullptr; h->refill_seq = 0; h->view_min = 0; h->refill_done = -1; h->side = h->side2 = h->side3 = nullptr; h->ev_scan = h->ev_deck = h->ev_gblk = nullptr;
+  h->d_prod[0] = h->d_prod[1] = nullptr; h->refill_seq = 0; h->view_min = 0; h->refill_done = -1; h->side = nullptr;
   h->ev_refill[0] = h->ev_refill[1] = nullptr; h->ev_rollout = nullptr;
   h->d_seeds = nullptr; h->d_mask = nullptr; h->d_jtab = nullptr; h->steps_since_refill = 0;
   memset(&h->dev, 0, sizeof(h->dev));
@@ -971,13 +950,7 @@ int bg_create_ex(int n_envs, int device_id, uint32_t flags, int max_ante, int fu
   // would otherwise take every free register before the few, latency-bound deck / seed-ring / block waves are placed
   int prio_least = 0, prio_greatest = 0;
   if (e == hipSuccess) e = hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest);
-  { const char* pv = getenv("BG_REFILL_PRIO"); if (pv && atoi(pv) == 0) prio_least = 0; } // development: 0 = default priority
   if (e == hipSuccess) e = hipStreamCreateWithPriority(&h->side, hipStreamNonBlocking, prio_least);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side2, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->side3, hipStreamNonBlocking);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_scan, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_deck, hipEventDisableTiming);
-  if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_gblk, hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_refill[0], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_refill[1], hipEventDisableTiming);
   if (e == hipSuccess) e = hipEventCreateWithFlags(&h->ev_rollout, hipEventDisableTiming);
@@ -1012,11 +985,6 @@ int bg_destroy(bg_handle* h) {
   BgDev& d = h->dev;
   (void)hipDeviceSynchronize();
   if (h->side) (void)hipStreamDestroy(h->side);
-  if (h->side2) (void)hipStreamDestroy(h->side2);
-  if (h->side3) (void)hipStreamDestroy(h->side3);
-  if (h->ev_scan) (void)hipEventDestroy(h->ev_scan);
-  if (h->ev_deck) (void)hipEventDestroy(h->ev_deck);
-  if (h->ev_gblk) (void)hipEventDestroy(h->ev_gblk);
   for (int i = 0; i < 2; i++) if (h->ev_refill[i]) (void)hipEventDestroy(h->ev_refill[i]);
   if (h->ev_rollout) (void)hipEventDestroy(h->ev_rollout);
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
@@ -1115,31 +1083,33 @@ static int bg_refill_on(bg_handle* h, hipStream_t s, int steps_hint = -1, bool s
   // beside a resident step-engine workgroup (only one SIMD per CU has free registers) -- the whole refill would wait for the engine
   hipLaunchKernelGGL(bg_refill_zero_kernel, dim3(1), dim3(BG_BLOCK), 0, s, d);
   hipLaunchKernelGGL(bg_refill_scan_kernel, dim3(bg_grid(h)), dim3(BG_BLOCK), 0, s, d);
-  if (sliced && s == h->side && h->dev_skip_refill == 0) {
+  if (sliced && s == h->side) {
     bg_ev_end(h, h->ev_refill_t, s);
     BG_HIP(hipGetLastError());
     h->pieces.clear(); h->piece_next = 0; h->piece_dev = d;
     // the order of the serial refill: decks, seed rings, blocks, shop streams (the shop items of THIS refill were listed by the scan from seeds drawn earlier)
     // decks: an env's shuffles are one serial chain (~17 per 372 steps, up to the ring), so the deck work is cut in DEPTH as well -- `deck_passes` passes
-    // over the list, all but the last one giving every env at most `deck_rounds` decks
+    // over the list, all but the last one giving every env at most 6 decks
+    // The grids: no more one-wave workgroups than fit beside a resident engine, so that none is left to be placed in the gap between two launches, where it
+    // would take the registers the next engine workgroup needs
+    static const int grid[4] = {512, 768, 1024, 1024};
     std::vector<bg_handle::RefillPiece> q[4];
     for (int pass = 0; pass < h->deck_passes; pass++)
       for (int p = 0; p < h->piece_parts[0]; p++)
-        q[0].push_back({0, (uint32_t)p, (uint32_t)h->piece_parts[0], h->piece_grid[0], (uint32_t)(8 + pass * h->piece_parts[0] + p), pass + 1 < h->deck_passes ? (uint32_t)h->deck_rounds : 0u});
+        q[0].push_back({0, (uint32_t)p, (uint32_t)h->piece_parts[0], grid[0], (uint32_t)(8 + pass * h->piece_parts[0] + p), pass + 1 < h->deck_passes ? 6u : 0u});
     for (int kind = 1; kind < 4; kind++)
-      for (int p = 0; p < h->piece_parts[kind]; p++) q[kind].push_back({kind, (uint32_t)p, (uint32_t)h->piece_parts[kind], h->piece_grid[kind], 0u, 0u});
+      for (int p = 0; p < h->piece_parts[kind]; p++) q[kind].push_back({kind, (uint32_t)p, (uint32_t)h->piece_parts[kind], grid[kind], 0u, 0u});
     // The four kinds are independent once the lists exist (the shop items were listed from seeds drawn by EARLIER refills): they are interleaved -- always
     // the kind with the largest share of its pieces still to go, the shop streams first -- so that the memory-bound pieces (an env's MT state is 2.5 KB
     // of its own: the deck and seed-ring kernels read 64 different lines per instruction, and a launch beside one takes ~40 us longer) do not sit beside
-    // consecutive launches, with the ALU-bound shop pieces (~7 us) between them.  BG_REFILL_INTERLEAVE=0: kind after kind, decks first.
+    // consecutive launches, with the ALU-bound shop pieces (~7 us) between them
     static const int order[4] = {3, 0, 2, 1};
     size_t taken[4] = {0, 0, 0, 0};
     for (;;) {
       int best = -1; double share = 0.0;
-      for (int o = 0; o < 4; o++) {
-        const int k = h->refill_interleave ? order[o] : o;
+      for (const int k : order) {
         if (taken[k] >= q[k].size()) continue;
-        const double sh = h->refill_interleave ? (double)(q[k].size() - taken[k]) / (double)q[k].size() : 1.0;
+        const double sh = (double)(q[k].size() - taken[k]) / (double)q[k].size();
         if (best < 0 || sh > share + 1e-9) { best = k; share = sh; }
       }
       if (best < 0) break;
@@ -1154,32 +1124,16 @@ static int bg_refill_on(bg_handle* h, hipStream_t s, int steps_hint = -1, bool s
   // workgroups (bg_engine.h: one SIMD per CU and ~5 KB of LDS are left to them) or, with nothing else running, several per SIMD.
   // (a refill behind a short launch finds short work lists: a grid sized for 372 steps' worth would be thousands of one-wave workgroups that are
   //  placed beside the engine only to find nothing to do)
-  int dense = h->refill_blocks;
-  if (steps_hint >= 0 && steps_hint < 372) { dense = (int)((long)dense * (steps_hint + 24) / 372); if (dense < 512) dense = 512; if (dense > h->refill_blocks) dense = h->refill_blocks; }
-  // the three kinds of work are independent once the lists exist: side by side on three streams, joined before the completion event
-  if (h->refill_order != 2) {
-    BG_HIP(hipEventRecord(h->ev_scan, s));
-    BG_HIP(hipStreamWaitEvent(h->side2, h->ev_scan, 0));
-    BG_HIP(hipStreamWaitEvent(h->side3, h->ev_scan, 0));
-  }
-  const int skip = h->dev_skip_refill; // development: contention experiments only (breaks the rings)
-  const int dense_shop = h->refill_blocks_shop > 0 ? h->refill_blocks_shop : dense;
-  // refill_order 0: the shop seeding (ALU-bound: 17 k waves of 64 registers, four fill the SIMD the engine leaves free) runs beside the
-  // latency-bound deck / seed-ring / block waves, which then wait for registers behind it; 1: it runs AFTER them; 2: all five kernels
-  // one after the other on `s` (a kernel's duration is then its own work, not its wait for a neighbour's registers)
-  const bool shop_last = h->refill_order >= 1, serial = h->refill_order == 2;
-  hipStream_t s_deck = serial ? s : h->side2, s_blk = serial ? s : h->side3;
-  if (!shop_last && !(skip & 1)) hipLaunchKernelGGL(bg_refill_shop_kernel, dim3(dense_shop), dim3(BG_BLOCK), 0, s, d, whole); // lowest-priority stream
-  if (!(skip & 2)) hipLaunchKernelGGL(bg_refill_deck_kernel, dim3(dense), dim3(BG_BLOCK), 0, s_deck, d, whole, 4u, 0u);
-  if (!(skip & 4)) hipLaunchKernelGGL(bg_refill_seedring_kernel, dim3(dense), dim3(BG_BLOCK), 0, s_blk, d, whole);
-  if (!(skip & 8)) hipLaunchKernelGGL(bg_refill_gblk_kernel, dim3(dense), dim3(BG_BLOCK), 0, s_blk, d, whole);
-  if (!serial) {
-    BG_HIP(hipEventRecord(h->ev_deck, h->side2));
-    BG_HIP(hipEventRecord(h->ev_gblk, h->side3));
-    BG_HIP(hipStreamWaitEvent(s, h->ev_deck, 0));
-    BG_HIP(hipStreamWaitEvent(s, h->ev_gblk, 0));
-  }
-  if (shop_last && !(skip & 1)) hipLaunchKernelGGL(bg_refill_shop_kernel, dim3(dense_shop), dim3(BG_BLOCK), 0, s, d, whole);
+  const int full = 4096;
+  int dense = full;
+  if (steps_hint >= 0 && steps_hint < 372) { dense = (int)((long)full * (steps_hint + 24) / 372); if (dense < 512) dense = 512; if (dense > full) dense = full; }
+  // The four kernels one after the other on `s`, the shop seeding (ALU-bound: 17 k waves of 64 registers, four fill the SIMD the engine leaves free)
+  // last: a kernel's duration is then its own work, not its wait for a neighbour's registers (the latency-bound deck / seed-ring / block waves waited
+  // behind the shop's when they ran side by side on three streams: DESIGN.md section 3, round 3)
+  hipLaunchKernelGGL(bg_refill_deck_kernel, dim3(dense), dim3(BG_BLOCK), 0, s, d, whole, 4u, 0u);
+  hipLaunchKernelGGL(bg_refill_seedring_kernel, dim3(dense), dim3(BG_BLOCK), 0, s, d, whole);
+  hipLaunchKernelGGL(bg_refill_gblk_kernel, dim3(dense), dim3(BG_BLOCK), 0, s, d, whole);
+  hipLaunchKernelGGL(bg_refill_shop_kernel, dim3(dense), dim3(BG_BLOCK), 0, s, d, whole);
   bg_ev_end(h, h->ev_refill_t, s);
   BG_HIP(hipGetLastError());
   BG_HIP(hipEventRecord(h->ev_refill[h->refill_seq & 1], s));
@@ -1289,9 +1243,8 @@ int bg_reset(bg_handle* h, const uint8_t* mask_dev, const bg_obs_ptrs* obs, void
 }
 
 // one launch of the step engine (bg_engine.h): T steps of every env of the handle
-// worker waves for a launch of T fused steps (BG_ENG_WAVES overrides)
-static int bg_engine_waves(const bg_handle* h, int T) {
-  if (h->eng_waves >= 4 && h->eng_waves <= BG_ENG_NW) return h->eng_waves;
+// worker waves for a launch of T fused steps
+static int bg_engine_waves(int T) {
   // measured (tools/ab_waves.sh with BG_ENGINE=1, us per launch at 4 / 5 / 6 / 7 waves): T = 4: 80 / 79 / 80 / 78; 10: 150 / 149 / 145 / 146; 20: 260 / 254 /
   // 249 / 249; 40: 507 / 490 / 489 / 481; 80: 925 / 920 / 928 / 926; 160: 1 847 / 1 770 / 1 831 / 1 835; 372: 4 010 / 3 805 / 3 674 / 3 632.
   // (Rounds 2-3 ran short launches on FOUR waves: their measurements -- T = 20: 312 / 326 / 347 / 380 -- had six statistics atomics per WAVE in them,
@@ -1305,11 +1258,10 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
   const bool cards = h->dev.cstate != nullptr;
   EngineArgs a = a0;
   if (h->engine == 3 && a.obs.rows && !info && !a.actions_in && !a.reward && !a.term && !a.actions_out) { // packed-record rollouts: owner waves + service waves (bg_engine3.h)
-    { // batch thresholds of the service waves: BG_E3_TH requests, or after BG_E3_WAIT ticks of 10 ns.  Default: never by threshold and no waiting --
-      // a free service wave takes the FULLER of the two queues at once (measured at 372 steps: thresholds 32 / 48 / 64 with waits of 3 - 20 us all lose
-      // 1 - 8 %, and serving plays as soon as one is queued -- batches of a few lanes -- loses a third: profiles/r04_engine3/thresholds_ab.txt)
-      a.th_play = a.th_other = h->e3_th; a.th_more = h->e3_wait;   // (read once per handle in bg_create_ex, like every tunable)
-    }
+    // batch thresholds of the service waves: never by threshold and no waiting -- a free service wave takes the FULLER of the two queues at once
+    // (measured at 372 steps: thresholds 32 / 48 / 64 with waits of 3 - 20 us all lose 1 - 8 %, and serving plays as soon as one is queued --
+    // batches of a few lanes -- loses a third: profiles/r04_engine3/thresholds_ab.txt)
+    a.th_play = a.th_other = 0x7fffffffu; a.th_more = 0u;
     // Shape of a workgroup: owner waves x slices of 64 envs x service waves.  BG_E3_CFG = 100 * owners + 10 * slices + service waves overrides.
     // 65 536 envs: 4 x 1 x 3 = 256 envs on seven waves per CU (the refill keeps its SIMD).  A small job spreads over more CUs: 64 envs per
     // workgroup up to 16 384 envs (256 workgroups = one per CU: 2.89 G env-steps/s against 2.59 G at 128 per workgroup), 128 up to 32 768
@@ -1334,14 +1286,13 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
     switch (cfg) {   // (other shapes were measured and dropped: profiles/r04_engine3/wave_split_ab.txt, small_jobs.txt, profiles/r05/scheduling_ab.txt)
       case 113: BG_E3(1, 1, 3); break;
       case 213: BG_E3(2, 1, 3); break;
-      case 414: BG_E3(4, 1, 4); break;   // eight waves: no room for the refill beside the launch (it then runs when the workgroups retire)
       default: BG_E3(4, 1, 3); break;
     }
 #undef BG_E3
 #undef BG_E3K
     return;
   }
-  a.n_waves = (uint32_t)bg_engine_waves(h, (int)a.T);
+  a.n_waves = (uint32_t)bg_engine_waves((int)a.T);
   // a ONE-step launch with the caller's actions (bg_step / bg_step_rows): the prologue has queued every service request of the launch before the first wave
   // enters its loop -- nothing more will arrive, so a service-capable wave takes a service queue as it finds it instead of looking at the run queue first
   if (a.T == 1 && a.actions_in) a.th_play = a.th_other = 1u;
@@ -1372,6 +1323,10 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
   else BG_ENG(false, false, false);
 #undef BG_ENG
 }
+
+// bg_engine.h's queue thresholds -- a queue is served once it holds 64 requests, or 1 while other waves are busy, with no further cheap steps inside a
+// batch -- and the handle's service waves (bg_engine_launch adjusts both to the launch's shape)
+static void bg_engine_queues(const bg_handle* h, EngineArgs& a) { a.th_run = a.th_play = a.th_other = 64u; a.th_part = 1u; a.th_more = 0u; a.serve_mask = h->eng_smask; }
 
 // Steps that may run between two refills when the refill is NOT overlapped (bg_step / bg_step_many): see bg_chunk_limit
 static int bg_step_budget(const bg_handle* h) {
@@ -1416,7 +1371,7 @@ static int bg_step_impl(bg_handle* h, int K, const int32_t* actions_dev, const b
       ea.trunc = truncated_dev ? truncated_dev + off : nullptr;
       ea.info = bg_info(info);
       if (off) bg_info_advance(ea.info, off);
-      ea.th_run = h->eng_run; ea.th_play = h->eng_play; ea.th_other = h->eng_other; ea.th_part = h->eng_part; ea.th_more = h->eng_more; ea.serve_mask = h->eng_smask;
+      bg_engine_queues(h, ea);
       ea.autoreset = (h->dev.flags & BG_FLAG_AUTORESET) ? 1u : 0u;
       bg_engine_launch(h, dv, ea, false, true, st, ev_a, ev_b);
     }
@@ -1499,9 +1454,9 @@ static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed
     if (rows_dev) { o.rows = rows_dev + off * row_stride; o.row_stride = (uint32_t)row_stride; }
     if (off) bg_obs_advance(o, off);
     if (h->profiling) h->rollout_steps.push_back(chunk);
-    // (BG_REFILL_MIN = m > 0 makes them eager: a launch of >= m steps takes its own small refill beside it -- measured, not the default: bg_create_ex.)
-    const bool must = h->steps_since_refill + chunk > max_chunk;
-    const bool need = must || (async && h->refill_min > 0 && h->steps_since_refill + chunk >= h->refill_min);
+    // (not eagerly beside every launch: 20 steps' worth of refill is ~320 us of five small latency-bound kernels against 129 us per 20 steps in bulk --
+    //  a refill beside every 20-step launch cost 21 % of the sustained rate, profiles/r05/refill_policy_ab.txt)
+    const bool need = h->steps_since_refill + chunk > max_chunk;
     const long s0 = h->refill_seq;
     // Overlapped and the chunk reads the view of the refill BEFORE this one (the usual case): the engine is launched FIRST, the refill's six small
     // kernels are queued on the side stream behind it -- their host-side issue time (~30 us) is then not in front of a 220 us launch.
@@ -1561,7 +1516,7 @@ static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed
       memset(&ea, 0, sizeof(ea));
       ea.T = chunk; ea.policy = pol; ea.policy_seed = policy_seed; ea.env_index0 = env_index0; ea.t0 = tt;
       ea.obs = o; ea.obs_stride_steps = obs_stride_steps; ea.reward = rw; ea.term = tm; ea.actions_out = ac; ea.stats = stats_dev;
-      ea.th_run = h->eng_run; ea.th_play = h->eng_play; ea.th_other = h->eng_other; ea.th_part = h->eng_part; ea.th_more = h->eng_more; ea.serve_mask = h->eng_smask; ea.autoreset = 1;
+      bg_engine_queues(h, ea); ea.autoreset = 1;
       if (h->gworld > 0 && rows_dev && h->engine == 3 && done + chunk == T) { // the call's LAST launch: its last step is every env's current record
         ea.gpeer = h->d_gpeer;
         ea.gworld = (uint32_t)h->gworld; ea.grank = (uint32_t)h->grank;
@@ -1577,7 +1532,7 @@ static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed
       // when a launch ends takes the whole machine in the gap before the next one): the scan now, the dense kernels in pieces beside this launch and the ones
       // to come.  A launch that is a period of its own keeps the whole refill beside it (in pieces the refill -- held to what is resident beside the engine --
       // takes longer than the launch, and the next launch needs it: 372 steps 8.1 -> 7.4 G, profiles/r05/refill_pieces.txt).
-      const bool sliced = h->refill_sliced != 0 && h->refill_sliced_div * chunk <= max_chunk;
+      const bool sliced = h->refill_sliced != 0 && 2 * chunk <= max_chunk;
       rc = bg_refill_on(h, h->side, h->steps_since_refill + chunk, sliced); // (sets steps_since_refill = 0: the chunk beside it counts below)
       if (rc) return rc;
     }
