@@ -24,6 +24,18 @@ def _align(n: int, a: int = 256) -> int:
     return (n + a - 1) // a * a
 
 
+def _check_out_tensor(name: str, t: Optional[torch.Tensor], dtype: torch.dtype, device: torch.device, n: int, rows: Optional[int]):
+    """A caller tensor the library writes through its data_ptr(): `dtype`, on `device`, contiguous, and [n] (rows None) or [>= rows, n]."""
+    if t is None:
+        return
+    if t.dtype != dtype or t.device != device or not t.is_contiguous():
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor on {device} (got {t.dtype} on {t.device}"
+                         f"{'' if t.is_contiguous() else ', not contiguous'})")
+    ok = tuple(t.shape) == (n,) if rows is None else (t.dim() == 2 and t.shape[1] == n and t.shape[0] >= rows)
+    if not ok:
+        raise ValueError(f"{name} has shape {tuple(t.shape)}; expected " + (f"[{n}]" if rows is None else f"[>= {rows}, {n}] (one row per step)"))
+
+
 def obs_flat_bytes(n: int, steps: int = 1) -> int:
     """Bytes of the flat observation buffer of `n` envs (every key's array, each aligned like `ObsBuffers` lays them out)."""
     off = 0
@@ -244,6 +256,8 @@ class BalatroVecEnv:
 
     def step(self, actions: torch.Tensor):
         """One lockstep `step(action)` (balatro_env_2.py:616).  actions: int32 [N] on this device."""
+        if actions.numel() != self.num_envs:
+            raise ValueError(f"actions must hold {self.num_envs} elements, one per env (got {tuple(actions.shape)})")
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         # (no torch.cuda.device() context: every entry point of the library switches to the handle's device itself, and a step is
@@ -264,9 +278,12 @@ class BalatroVecEnv:
 
     def step_many(self, actions: torch.Tensor, obs_buffers: Optional["ObsBuffers"] = None, reward: Optional[torch.Tensor] = None,
                   terminated: Optional[torch.Tensor] = None):
-        """K consecutive `step()` calls in one launch (bg_step_many): actions int32 [K, N].  With `obs_buffers` of K rows
-        (and optional [K, N] reward / terminated tensors) every call's outputs are kept; otherwise the live tensors hold the last
-        call's observation / reward / terminated / info."""
+        """K consecutive `step()` calls in one launch (bg_step_many): actions int32 [K, N].  With `obs_buffers` of at least K rows
+        every call's observation is kept, and so are its reward / terminated when float64 / uint8 [>= K, N] tensors on this device are
+        given; the returned truncated and info are None, and so is reward / terminated when no tensor was given for it: this call
+        writes none of them (a per-step output never goes into the live [N] tensors; bg_step_many with per-step info buffers gives
+        the info).  Otherwise the live tensors hold the last call's observation / reward / terminated / truncated / info, and
+        reward / terminated must not be given."""
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if actions.dim() != 2 or actions.shape[1] != self.num_envs:
@@ -275,18 +292,25 @@ class BalatroVecEnv:
         keep = obs_buffers is not None and obs_buffers.steps > 1
         if keep and obs_buffers.steps < K:
             raise ValueError("obs_buffers has fewer rows than steps")
+        if not keep and (reward is not None or terminated is not None):
+            raise ValueError("reward / terminated tensors need per-step obs_buffers: without them the live tensors hold the last call's values")
+        _check_out_tensor("reward", reward, torch.float64, self.device, self.num_envs, K)
+        _check_out_tensor("terminated", terminated, torch.uint8, self.device, self.num_envs, K)
         ob = obs_buffers if keep else self._obs
-        rw = reward if (keep and reward is not None) else self.reward
-        tm = terminated if (keep and terminated is not None) else self.terminated
+        # per-step outputs are [K, N]: the live [N] tensors cannot take them, an output without a per-step tensor is not written (NULL)
+        rw = reward if keep else self.reward
+        tm = terminated if keep else self.terminated
         with torch.cuda.device(self.device):
             self._check(self._L.bg_step_many(
-                self._h, K, C.c_void_p(actions.data_ptr()), C.byref(ob.ptrs), 1 if keep else 0, C.c_void_p(rw.data_ptr()),
-                C.c_void_p(tm.data_ptr()), None if keep else C.c_void_p(self.truncated.data_ptr()),
+                self._h, K, C.c_void_p(actions.data_ptr()), C.byref(ob.ptrs), 1 if keep else 0, None if rw is None else C.c_void_p(rw.data_ptr()),
+                None if tm is None else C.c_void_p(tm.data_ptr()), None if keep else C.c_void_p(self.truncated.data_ptr()),
                 None if keep else C.byref(self._info_ptrs), self._stream()), "bg_step_many")
         if self._rowbuf is not None:
             self.observe()   # (obs_layout "rows": the live records follow)
             if not keep:
                 return self._row_tensors, rw, tm, self.truncated, self.info
+        if keep:
+            return ob.tensors, rw, tm, None, None
         return ob.tensors, rw, tm, self.truncated, self.info
 
     def observe(self):
@@ -304,7 +328,8 @@ class BalatroVecEnv:
                 zero_stats: bool = True):
         """Fused random-policy rollout (bg_rollout).  With obs_buffers of `steps` rows every step's observation is
         kept ([T, N, ...]); otherwise the live observation tensors are overwritten each step.  A `RowBuffers` selects
-        the packed-record output (bg_rollout_rows): same values, one record per (step, env)."""
+        the packed-record output (bg_rollout_rows): same values, one record per (step, env).  reward / terminated / actions
+        (optional; float64 / uint8 / int32, contiguous, on this device) are [>= T, N] with per-step obs_buffers, else [N]."""
         if isinstance(obs_buffers, RowBuffers):
             if obs_buffers.steps < steps and obs_buffers.steps > 1:
                 raise ValueError("obs_buffers has fewer rows than steps")
@@ -331,9 +356,11 @@ class BalatroVecEnv:
             # reward / terminated / actions share the observation's row stride (bg_rollout: row = env + t * N only when obs_stride_steps != 0):
             # without per-step observation buffers every step writes ROW 0 of them.  A [steps, N] tensor here would come back with one filled row.
             for name, tns in (("reward", reward), ("terminated", terminated), ("actions", actions)):
-                if tns is not None and tns.dim() > 1 and tns.shape[0] > 1:
-                    raise ValueError(f"{name} has {tns.shape[0]} rows but no per-step obs_buffers were given: every step would overwrite row 0 "
-                                     f"(pass ObsBuffers(n, device, steps={steps}), or a [N] tensor for the last step's values)")
+                if tns is not None and ((tns.dim() > 1 and tns.shape[0] > 1) or tns.numel() > self.num_envs):
+                    raise ValueError(f"{name} has {tns.numel()} elements in shape {tuple(tns.shape)} but no per-step obs_buffers were given: every "
+                                     f"step would overwrite row 0 (pass ObsBuffers(n, device, steps={steps}), or a [N] tensor for the last step's values)")
+        for name, tns, dt in (("reward", reward, torch.float64), ("terminated", terminated, torch.uint8), ("actions", actions, torch.int32)):
+            _check_out_tensor(name, tns, dt, self.device, self.num_envs, int(steps) if stride else None)
         if zero_stats:
             self._stats.zero_()
         with torch.cuda.device(self.device):

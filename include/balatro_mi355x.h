@@ -197,7 +197,8 @@ int bg_observe(bg_handle* h, const bg_obs_ptrs* obs, void* stream);
  * policy network reads after `obs_as_tensor` + concatenation anyway.  A cheap step then patches the record image and the copier waves
  * write it (a step that emits 31 arrays spends most of its instructions on address arithmetic): the one-step launch is ~10 % shorter (19.5 against 21.6 us of kernel time at 65 536 envs: bench.py step_path).
  * Same step semantics, same reward / terminated / truncated / info arrays as bg_step (balatro_env_2.py:616-637, :1473-1541);
- * bg_observe_rows (bytes 352.. of a record untouched) after bg_reset(h, mask, NULL, stream) gives the records of a reset.
+ * bg_observe_rows (bytes 352.. of a record untouched; the record's reward / action / terminated written as 0) after bg_reset(h, mask, NULL, stream)
+ * gives the records of a reset.
  * rows_dev: 16-byte aligned, row_stride_bytes a multiple of 16, >= BG_ROW_BYTES; BG_RECORD_STRIDE_LINES on a 128-byte aligned buffer is the fast layout. */
 int bg_step_rows(bg_handle* h, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes, double* reward_dev,
                  uint8_t* terminated_dev, uint8_t* truncated_dev, const bg_info_ptrs* info, void* stream);
@@ -352,8 +353,8 @@ int bg_classify_batch_ex(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t
  *   [28] hand level  [29] number of jokers  [30..34] joker ids (jokers.py)  [35] hands_left  [36] discards_left
  *   [37] len(game_state['deck'])  [38] gseed (< 2**32)  [39] 0
  * and one int64[BG_SCORE_OUT_WORDS] result: score, final chips, final mult, bits of the float64 x_mult, money gained, words
- * of the global stream consumed, the word the NEXT getrandbits(32) would return (identifies the stream position), 0.
- * Synchronises the stream. */
+ * of the global stream consumed, the word the NEXT getrandbits(32) would return (identifies the stream position), 0 (word 7 is
+ * always written, as 0).  Synchronises the stream. */
 #define BG_SCORE_CASE_WORDS 40
 #define BG_SCORE_OUT_WORDS 8
 int bg_score_hand_batch(const int32_t* cases_dev, int64_t* out_dev, int m, void* stream);
@@ -371,7 +372,8 @@ int bg_score_hand_batch_ex(const int32_t* cases_dev, int64_t* out_dev, int m, in
  * Replaces: `BalatroSimulator.evaluate_hand(cards)` (balatro_sim.py:220-366 over get_x_same :108-126, get_flush :128-149,
  * get_straight :151-214).  hands_dev is int32 [M, 8, 6], n_dev[i] in [0, 8] cards are valid, flags_dev[i] bit 0 = a Four Fingers
  * joker is owned, bit 1 = Shortcut.  out_dev is int8 [M, BG_SIM_EVAL_BYTES]: [0] results['top']; [1..12] len(results[type]);
- * [13..24] len(results[type][0]); [32 + 8 * type + k] = position in the hand of card k of results[type][0] (-1 padded). */
+ * [13..24] len(results[type][0]); [32 + 8 * type + k] = position in the hand of card k of results[type][0] (-1 padded).
+ * Bytes 25..31 of a row are not written: they keep what the caller's buffer held. */
 #define BG_SIM_EVAL_BYTES 128
 int bg_sim_evaluate_batch(const int32_t* hands_dev, const int32_t* n_dev, const int32_t* flags_dev, int8_t* out_dev, int m, void* stream);
 

@@ -249,8 +249,7 @@ def classify(codes) -> int:
     return lib().bo_classify(arr, len(codes))
 
 
-def score_hand(cards, scoring, hand_type, name_style, level, jokers, hands_left, discards_left, deck_len, seed):
-    """cards/scoring: lists of (rank, suit, chips).  Returns (ScoreOut, draws) with a global stream seeded `seed`."""
+def _score_hand_mt(cards, scoring, hand_type, name_style, level, jokers, hands_left, discards_left, deck_len, seed):
     L = lib()
     ca = (SCard * max(1, len(cards)))(*[SCard(*c) for c in cards])
     sa = (SCard * max(1, len(scoring)))(*[SCard(*c) for c in scoring])
@@ -260,7 +259,19 @@ def score_hand(cards, scoring, hand_type, name_style, level, jokers, hands_left,
     out = ScoreOut()
     L.bo_score_hand(ca, len(cards), sa, len(scoring), hand_type, name_style, level, ja, len(jokers), hands_left,
                     discards_left, deck_len, C.byref(mt), C.byref(out))
-    return out
+    return out, mt
+
+
+def score_hand(cards, scoring, hand_type, name_style, level, jokers, hands_left, discards_left, deck_len, seed):
+    """cards/scoring: lists of (rank, suit, chips).  Returns (ScoreOut, draws) with a global stream seeded `seed`."""
+    return _score_hand_mt(cards, scoring, hand_type, name_style, level, jokers, hands_left, discards_left, deck_len, seed)[0]
+
+
+def score_hand_words(cards, scoring, hand_type, name_style, level, jokers, hands_left, discards_left, deck_len, seed):
+    """score_hand as the 8 int64 words of a bg_score_hand_batch result (include/balatro_mi355x.h): score, chips, mult, x_mult bits,
+    money, words drawn, the next getrandbits(32) of the stream, 0."""
+    o, mt = _score_hand_mt(cards, scoring, hand_type, name_style, level, jokers, hands_left, discards_left, deck_len, seed)
+    return [o.score, o.chips, o.mult, int(np.float64(o.x_mult).view(np.int64)), o.money, o.draws, int(lib().bo_mt_u32(C.byref(mt))), 0]
 
 
 def sim_evaluate(cards, four_fingers=False, shortcut=False):
@@ -272,8 +283,7 @@ def sim_evaluate(cards, four_fingers=False, shortcut=False):
     return int(ev.top), {t: (int(ev.nlists[t]), [int(ev.pos[t][i]) for i in range(ev.n0[t])]) for t in range(12)}
 
 
-def sim_score(cards, jokers, hands_left, discards_left, deck_len, seed):
-    """balatro_sim.py calculate_score after random.seed(seed); Four Fingers (18) / Shortcut (69) in `jokers` act on the evaluation."""
+def _sim_score_mt(cards, jokers, hands_left, discards_left, deck_len, seed):
     L = lib()
     ca = (SimCard * max(1, len(cards)))(*[SimCard(*c) for c in cards])
     ja = (C.c_int32 * max(1, len(jokers)))(*jokers)
@@ -281,4 +291,30 @@ def sim_score(cards, jokers, hands_left, discards_left, deck_len, seed):
     L.bo_mt_seed(C.byref(mt), seed)
     out = SimScoreOut()
     L.bo_sim_score(ca, len(cards), ja, len(jokers), hands_left, discards_left, deck_len, C.byref(mt), C.byref(out))
-    return out
+    return out, mt
+
+
+def sim_score(cards, jokers, hands_left, discards_left, deck_len, seed):
+    """balatro_sim.py calculate_score after random.seed(seed); Four Fingers (18) / Shortcut (69) in `jokers` act on the evaluation."""
+    return _sim_score_mt(cards, jokers, hands_left, discards_left, deck_len, seed)[0]
+
+
+def sim_score_words(cards, jokers, hands_left, discards_left, deck_len, seed):
+    """sim_score as the 8 int64 words of a bg_sim_score_batch result (include/balatro_mi355x.h): score, chips, added mult, x_mult bits,
+    money, words drawn, the next getrandbits(32) of the stream, top | nscoring << 8."""
+    o, mt = _sim_score_mt(cards, jokers, hands_left, discards_left, deck_len, seed)
+    return [o.score, o.chips, o.add_mult, int(np.float64(o.x_mult).view(np.int64)), o.money, o.draws, int(lib().bo_mt_u32(C.byref(mt))),
+            o.top | (o.nscoring << 8)]
+
+
+def sim_evaluate_bytes(cards, four_fingers=False, shortcut=False):
+    """sim_evaluate as a bg_sim_evaluate_batch row: a 128-byte int8 array, bytes 0..24 and 32..127 as the header documents them, bytes
+    25..31 (which the library leaves unwritten) 0."""
+    L = lib()
+    ca = (SimCard * max(1, len(cards)))(*[SimCard(*c) for c in cards])
+    ev = SimEval()
+    L.bo_sim_evaluate(ca, len(cards), int(four_fingers), int(shortcut), C.byref(ev))
+    raw = np.frombuffer(bytes(ev), np.int8)   # top, nlists[12], n0[12], pos[12][8]: 121 packed bytes
+    row = np.zeros(128, np.int8)
+    row[:25], row[32:] = raw[:25], raw[25:]
+    return row

@@ -148,3 +148,93 @@ def apply_sharded_workload(env, wl, lo, hi):
         env.inject_cards(wl["cards"][lo:hi], apply_now=True)
     if wl["consumables"] is not None:
         env.inject_consumables(wl["consumables"][lo:hi], apply_now=True)
+
+
+# ---------------------------------------------------------------------------------------------------------
+# The whole documented output of a step (include/balatro_mi355x.h bg_step / bg_info_ptrs), against the oracle
+# ---------------------------------------------------------------------------------------------------------
+POISON = 0xA5   # byte pattern the step tests fill every output buffer with before a call: a word the library never writes shows up
+BG_INFO_BOUGHT_JOKER, BG_INFO_SOLD_JOKER, BG_INFO_AUTORESET = 64, 128, 512
+
+
+def _np(x):
+    return x.cpu().numpy() if hasattr(x, "cpu") else np.asarray(x)
+
+
+def poison_(*tensors):
+    """Fill every byte of the given contiguous tensors with POISON; None entries are skipped."""
+    import torch
+    for t in tensors:
+        if t is not None:
+            assert t.is_contiguous(), "poison_ takes contiguous tensors"
+            t.view(torch.uint8).fill_(POISON)
+
+
+def poison_env_outputs(env):
+    """Poison what one step of `env` (a BalatroVecEnv) writes: the live observation (or its packed records), reward,
+    terminated, truncated and every info array."""
+    poison_(env.obs_flat, env.reward, env.terminated, env.truncated, *env.info.values())
+
+
+def assert_step_outputs(ctx, res, reward, terminated, truncated, info, obs=None, autoreset=False, want_obs=None):
+    """One step of N envs against the oracle: `res[i]` is what OracleEnv.step returned for env i, (obs, reward, terminated,
+    truncated, Info); reward / terminated / truncated / info (a dict of the 8 info arrays) / obs are what the library wrote,
+    torch tensors or arrays.  The documented contract, word by word:
+      reward bit patterns, terminated, truncated all 0; final_score, error, hand_type, cards_played, aux, reward_terms bits;
+      flags & 511 = the oracle's flags, flags & 512 (BG_INFO_AUTORESET) set exactly where terminated with autoreset on and
+      never without, no other bit; score_breakdown bits, all 8 columns: Info.breakdown on an accepted play, zeros elsewhere.
+    `obs` (optional) is compared key by key with `want_obs` (stacked per key) or, by default, with the oracle's observations.
+    Returns the oracle's flags (for tests that count what their workload reached)."""
+    n = len(res)
+    wr = np.array([r[1] for r in res], dtype=np.float64)
+    wt = np.array([r[2] for r in res], dtype=np.uint8)
+    inf = [r[4] for r in res]
+    g = _np(reward)
+    assert g.shape == (n,) and np.array_equal(g.view(np.uint64), wr.view(np.uint64)), f"{ctx}: reward {_first_diff(g.view(np.uint64), wr.view(np.uint64))}"
+    g = _np(terminated)
+    assert np.array_equal(g, wt), f"{ctx}: terminated {_first_diff(g, wt)}"
+    g = _np(truncated)
+    assert g.shape == (n,) and not g.any(), f"{ctx}: truncated {_first_diff(g, np.zeros_like(g))}"
+    wf = np.array([x.flags for x in inf], dtype=np.int32)
+    assert not (wf & ~511).any(), f"{ctx}: the oracle set a flag bit above BG_INFO_CURRICULUM (256)"
+    want = {
+        "final_score": np.array([x.final_score for x in inf], dtype=np.int64),
+        "error": np.array([x.error for x in inf], dtype=np.int32),
+        "aux": np.array([x.aux for x in inf], dtype=np.int32),
+        "hand_type": np.array([x.hand_type for x in inf], dtype=np.int8),
+        "cards_played": np.array([x.cards_played for x in inf], dtype=np.int8),
+        "reward_terms": np.array([list(x.reward_terms) for x in inf], dtype=np.float64).view(np.uint64),
+        "score_breakdown": np.array([list(x.breakdown) for x in inf], dtype=np.float64).view(np.uint64),
+    }
+    for k, w in want.items():
+        gk = _np(info[k])
+        if w.dtype == np.uint64:
+            gk = gk.view(np.uint64)
+        assert gk.shape == w.shape and np.array_equal(gk, w), f"{ctx}: info[{k}] {_first_diff(gk, w)}"
+    # (the loop above already holds the library's score_breakdown to Info.breakdown on every row: this pins the ORACLE side of the
+    #  documented contract -- zeros outside an accepted play, column 7 always 0 -- which the library then inherits)
+    played = want["hand_type"] >= 0
+    bd = _np(info["score_breakdown"])
+    assert not bd[~played].view(np.uint64).any() and not bd[:, 7].view(np.uint64).any(), f"{ctx}: score_breakdown outside an accepted play"
+    fl = _np(info["flags"])
+    assert np.array_equal(fl & 511, wf), f"{ctx}: info[flags] & 511 {_first_diff(fl & 511, wf)}"
+    wa = (wt.astype(np.int32) * BG_INFO_AUTORESET) if autoreset else np.zeros(n, np.int32)
+    assert np.array_equal(fl & BG_INFO_AUTORESET, wa), f"{ctx}: BG_INFO_AUTORESET (autoreset {autoreset}) {_first_diff(fl & BG_INFO_AUTORESET, wa)}"
+    assert not (fl & ~1023).any(), f"{ctx}: info[flags] has bits above BG_INFO_AUTORESET: {_first_diff(fl & ~1023, np.zeros(n, np.int32))}"
+    if obs is not None:
+        wobs = want_obs if want_obs is not None else {k: np.stack([r[0][k] for r in res]) for k in OBS_KEYS}
+        for k in OBS_KEYS:
+            gk, w = _np(obs[k]), wobs[k]
+            assert gk.shape == w.shape and np.array_equal(gk, w), f"{ctx}: obs[{k}] {_first_diff(gk.reshape(n, -1), w.reshape(n, -1))}"
+    return wf
+
+
+def _first_diff(g, w):
+    g, w = np.asarray(g), np.asarray(w)
+    if g.shape != w.shape:
+        return f"shape {g.shape} vs {w.shape}"
+    bad = np.argwhere(g != w)
+    if bad.size == 0:
+        return "(equal)"
+    i = tuple(bad[0])
+    return f"differs at {i} of {len(bad)} places: got {g[i[0]]} want {w[i[0]]}"

@@ -262,6 +262,84 @@ def test_rollout_refuses_per_step_outputs_without_per_step_buffers():
             BalatroVecEnv.rollout(fake, 8, **{kw: torch.zeros((8, 4), dtype=torch.int32)})
 
 
+def _fake_env(n=4):
+    """A stand-in for BalatroVecEnv's state: nothing behind it reaches the library (no handle, no `_L`), so a check that is missing shows up as
+    an AttributeError instead of the ValueError the tests below expect."""
+    import types
+    import torch
+    return types.SimpleNamespace(_obs=None, _rowbuf=None, num_envs=n, device=torch.device("cpu"))
+
+
+def test_step_refuses_actions_of_another_length():
+    """step() hands actions.data_ptr() to the kernel, which reads N of them: any other element count is refused (the tensors here are larger than
+    N, so even without the check nothing would be read out of bounds)."""
+    import torch
+    from balatro_gym_amd.vec_env import BalatroVecEnv
+    for bad in (torch.zeros(5, dtype=torch.int32), torch.zeros((2, 4), dtype=torch.int32), torch.zeros(8, dtype=torch.int64)):
+        with pytest.raises(ValueError, match="4 elements"):
+            BalatroVecEnv.step(_fake_env(4), bad)
+
+
+def _bad_outputs(rows, n):
+    """(name, tensor, message) triples the step_many / rollout wrappers must refuse for per-step outputs of `rows` steps ([rows, n]; rows None:
+    [n]).  Each tensor holds at least as many bytes as the right one, so none would be written out of bounds if a check were missing."""
+    import torch
+    lead = (rows, n) if rows else (n,)
+    wide = (rows, 2 * n) if rows else (2 * n,)
+    out = []
+    for name, dt, other in (("reward", torch.float64, torch.float32), ("terminated", torch.uint8, torch.int32), ("actions", torch.int32, torch.int16)):
+        out += [(name, torch.zeros(wide, dtype=other), "contiguous"),                                    # wrong dtype (as many bytes)
+                (name, torch.zeros(lead, dtype=dt, device="meta"), "contiguous"),                      # another device
+                (name, torch.zeros(lead + (2,), dtype=dt)[..., 0], "contiguous"),                      # not contiguous
+                (name, torch.zeros(wide, dtype=dt), "shape")]                                           # another size
+        if rows:
+            out.append((name, torch.zeros(rows * n, dtype=dt), "shape"))                                # flat [T * N]
+    return out
+
+
+def test_step_many_validates_caller_outputs():
+    """step_many hands reward / terminated to bg_step_many as [K, N] buffers: wrong dtype, another device, non-contiguous storage or a size other
+    than [>= K, N] are refused; without per-step obs_buffers reward / terminated are refused too (they would silently be left unwritten)."""
+    import types
+    import torch
+    from balatro_gym_amd.vec_env import BalatroVecEnv
+    n, K = 4, 3
+    acts = torch.zeros((K, n), dtype=torch.int32)
+    per_step = types.SimpleNamespace(steps=K)
+    for name, t, msg in _bad_outputs(K, n):
+        if name == "actions":
+            continue   # (step_many's actions are an INPUT: converted to int32 on the device, shape-checked)
+        with pytest.raises(ValueError, match=msg):
+            BalatroVecEnv.step_many(_fake_env(n), acts, obs_buffers=per_step, **{name: t})
+    for name, dt in (("reward", torch.float64), ("terminated", torch.uint8)):
+        with pytest.raises(ValueError, match="per-step obs_buffers"):
+            BalatroVecEnv.step_many(_fake_env(n), acts, **{name: torch.zeros((K, n), dtype=dt)})
+        with pytest.raises(ValueError, match="per-step obs_buffers"):
+            BalatroVecEnv.step_many(_fake_env(n), acts, **{name: torch.zeros(n, dtype=dt)})
+    with pytest.raises(ValueError, match=r"\[K, 4\]"):
+        BalatroVecEnv.step_many(_fake_env(n), torch.zeros(K * n, dtype=torch.int32))
+
+
+def test_rollout_validates_caller_outputs():
+    """rollout hands reward / terminated / actions to bg_rollout: float64 / uint8 / int32, on the env's device, contiguous, [>= T, N] with
+    per-step obs_buffers and [N] without -- anything else is refused before a pointer reaches the library.  A flat [T * N] tensor without
+    per-step buffers is refused like a [T, N] one (every step would overwrite its first N elements)."""
+    import types
+    import torch
+    from balatro_gym_amd.vec_env import BalatroVecEnv
+    n, T = 4, 3
+    per_step = types.SimpleNamespace(steps=T)
+    for name, t, msg in _bad_outputs(T, n):
+        with pytest.raises(ValueError, match=msg):
+            BalatroVecEnv.rollout(_fake_env(n), T, obs_buffers=per_step, **{name: t})
+    for name, t, msg in _bad_outputs(None, n):
+        with pytest.raises(ValueError, match=msg):
+            BalatroVecEnv.rollout(_fake_env(n), 1, **{name: t})
+    for name, dt in (("reward", torch.float64), ("terminated", torch.uint8), ("actions", torch.int32)):
+        with pytest.raises(ValueError, match="row 0"):
+            BalatroVecEnv.rollout(_fake_env(n), T, **{name: torch.zeros(T * n, dtype=dt)})
+
+
 def test_build_signature_is_reproducible(tmp_path):
     """The identity of the device code (`bg_build_signature`, what profiles/*_hbm_traffic.json are keyed on) must survive a rebuild of
     unchanged sources: the library reports the sha256 prefix of sources + flags (12 digits) and compiler (4 digits) it was built from, and

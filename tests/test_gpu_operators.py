@@ -13,7 +13,7 @@ from itertools import combinations
 import numpy as np
 import pytest
 
-from tests.helpers import GOLD, OBS_KEYS, forced_deck, forced_hand_script
+from tests.helpers import GOLD, POISON, assert_step_outputs, forced_deck, forced_hand_script, poison_env_outputs
 
 pytestmark = pytest.mark.gpu
 
@@ -153,8 +153,8 @@ def test_forced_rare_hands_vs_oracle(scorer):
     """Env-level: decks arranged so that the first play of every episode IS a chosen hand type (bg_inject_deck; a straight
     flush / four of a kind / flush ... at deck[0..k-1], classified on deck[position]), at antes 1..8 with and
     without jokers, small / big / boss blinds: reward shaping (hand quality, efficiency, strategy, synergy, the log10 score
-    term), final score and every observation key against the oracle, then 40 more steps of the counter-hash policy with the
-    highlights accumulating."""
+    term), final score, the score breakdown and every other output word against the oracle (tests/helpers.py assert_step_outputs,
+    into buffers poisoned before each call), then 40 more steps of the counter-hash policy with the highlights accumulating."""
     import torch
     from balatro_gym_amd import BalatroVecEnv
     from oracle import pyoracle as po
@@ -180,22 +180,12 @@ def test_forced_rare_hands_vs_oracle(scorer):
     for t in range(T):
         acts = np.array([scripts[i][t] if t < len(scripts[i]) else o.policy_action(0, 31, i, t) for i, o in enumerate(orc)], dtype=np.int32)
         res = [o.step(int(a)) for o, a in zip(orc, acts)]
-        _, reward, term, _, info = env.step(torch.from_numpy(acts).to(env.device))
+        poison_env_outputs(env)
+        ob, reward, term, trunc, info = env.step(torch.from_numpy(acts).to(env.device))
         ctx = f"scorer {scorer} t {t}"
-        wr = np.array([r[1] for r in res])
-        assert np.array_equal(reward.cpu().numpy().view(np.uint64), wr.view(np.uint64)), ctx
-        wt = np.array([r[2] for r in res], dtype=np.uint8)
-        assert np.array_equal(term.cpu().numpy(), wt), ctx
-        assert np.array_equal(info["final_score"].cpu().numpy(), np.array([r[4].final_score for r in res])), ctx
+        assert_step_outputs(ctx, res, reward, term, trunc, info, obs=ob)
         wh = np.array([r[4].hand_type for r in res], dtype=np.int8)
-        assert np.array_equal(info["hand_type"].cpu().numpy(), wh), ctx
-        assert np.array_equal(info["error"].cpu().numpy(), np.array([r[4].error for r in res], dtype=np.int32)), ctx
-        wterms = np.array([[r[4].reward_terms[q] for q in range(8)] for r in res])
-        assert np.array_equal(info["reward_terms"].cpu().numpy().view(np.uint64), wterms.view(np.uint64)), ctx
-        got = {k: v.cpu().numpy() for k, v in env.obs.items()}
-        for k in OBS_KEYS:
-            w = np.stack([r[0][k] for r in res])
-            assert np.array_equal(got[k], w), f"{ctx}: obs[{k}]"
+        wt = np.array([r[2] for r in res], dtype=np.uint8)
         for i in range(n):
             if t == len(scripts[i]) - 1 and wh[i] >= 0:
                 assert wh[i] == hts[i], (i, wh[i], hts[i])  # the forced play produced the intended type (boss rejections aside)
@@ -248,6 +238,202 @@ def test_sim_score_batch_golden():
     bad = np.nonzero((out[:M, 0] != g["s_score"]) | (out[:M, 4] != g["s_money"]) | (out[:M, 6] != g["s_probe"].astype(np.int64)))[0]
     assert bad.size == 0, f"case {bad[0]}: {rec[bad[0]].tolist()} got {out[bad[0]].tolist()} want {g['s_score'][bad[0]], g['s_money'][bad[0]], g['s_probe'][bad[0]]}"
     assert [int(x) for x in out[M:, 0]] == [k["score"] for k in kat]
+    # the words the fixture does not hold (chips, added mult, x_mult bits, words drawn, top | nscoring << 8) from the oracle, which
+    # tests/test_oracle_golden.py holds to the same fixture
+    want = np.array([_sim_words_of_rec(rec[i]) for i in range(len(rec))], dtype=np.int64)
+    bad = np.nonzero((out != want).any(axis=1))[0]
+    assert bad.size == 0, f"case {bad[0]}: {rec[bad[0]].tolist()} got {out[bad[0]].tolist()} want {want[bad[0]].tolist()}"
+
+
+def _sim_words_of_rec(c):
+    """pyoracle.sim_score_words of one bg_sim_score_batch case record."""
+    from oracle import pyoracle as po
+    n, nj = int(c[48]), int(c[49])
+    cards = [tuple(int(x) for x in c[6 * q:6 * q + 6]) for q in range(n)]
+    return po.sim_score_words(cards, [int(j) for j in c[50:50 + nj]], int(c[55]), int(c[56]), int(c[57]), int(np.uint32(c[58])))
+
+
+def _fresh_sim_cases(M, seed):
+    """M bg_sim_score_batch case records: 1-8 cards (every enhancement / edition / seal, duplicate cards), 0-5 jokers with repeats,
+    Four Fingers (18) and Shortcut (69) among them, hands_left / discards_left / deck length at their edges."""
+    from oracle.gen_golden import IMPLEMENTED, sim_random_hand
+    r = random.Random(seed)
+    rec = np.zeros((M, 64), np.int32)
+    for i in range(M):
+        cards = sim_random_hand(r, n=r.randint(1, 8))
+        if r.random() < 0.3:   # dense card modifiers
+            cards = [(rk, su, bv, r.randrange(9), r.randrange(5), r.randrange(5)) for rk, su, bv, _, _, _ in cards]
+        if r.random() < 0.15 and len(cards) < 8:   # an exact duplicate of a card
+            cards.insert(r.randrange(len(cards) + 1), r.choice(cards))
+        nj = r.randint(0, 5)
+        pool = IMPLEMENTED if r.random() < 0.8 else list(range(1, 151))
+        jokers = [r.choice(pool) for _ in range(nj)] if r.random() < 0.3 else r.sample(pool, nj)
+        for util in (18, 69):
+            if r.random() < 0.3 and len(jokers) < 5:
+                jokers.insert(r.randint(0, len(jokers)), util)
+        hl, dl = r.choice([0, 1, 1, 2, 4, 127]), r.choice([0, 0, 1, 3, 127])
+        deck_len = r.choice([0, 1, 8, 40, 52, 53, 127])
+        for q, cd in enumerate(cards):
+            rec[i, 6 * q:6 * q + 6] = cd
+        rec[i, 48], rec[i, 49] = len(cards), len(jokers)
+        rec[i, 50:50 + len(jokers)] = jokers
+        rec[i, 55:58] = (hl, dl, deck_len)
+        rec[i, 58] = np.uint32(r.choice([0, 1, 2 ** 32 - 1, r.randrange(2 ** 32)])).astype(np.int32)
+    return rec
+
+
+def test_sim_score_batch_vs_oracle_fresh_cases():
+    """balatro_sim.calculate_score: 20 000 fresh cases against pyoracle.sim_score, ALL 8 output words (score, chips, added mult, x_mult bits,
+    money, words drawn, the next getrandbits(32), top | nscoring << 8)."""
+    import torch
+    from balatro_gym_amd import sim_score_batch
+    rec = _fresh_sim_cases(20000, 31337)
+    want = np.array([_sim_words_of_rec(c) for c in rec], dtype=np.int64)
+    out = sim_score_batch(torch.from_numpy(rec).to("cuda:0")).cpu().numpy()
+    bad = np.nonzero((out != want).any(axis=1))[0]
+    assert bad.size == 0, f"{bad.size} cases differ; case {bad[0]}: {rec[bad[0]].tolist()} got {out[bad[0]].tolist()} want {want[bad[0]].tolist()}"
+    js = rec[:, 50:55]
+    assert ((js == 18).any(axis=1).sum() > 1000) and ((js == 69).any(axis=1).sum() > 1000)
+    assert len(np.unique(want[:, 7] & 0xff)) == 12   # every top hand type, Five of a Kind / Flush House / Flush Five included
+
+
+def _fresh_sim_hands(M, seed):
+    from oracle.gen_golden import sim_random_hand
+    r = random.Random(seed)
+    hands = np.zeros((M, 8, 6), np.int32)
+    n = np.zeros(M, np.int32)
+    flags = np.array([i % 4 for i in range(M)], np.int32)   # none, Four Fingers, Shortcut, both
+    for i in range(M):
+        cards = sim_random_hand(r, n=r.randint(1, 8))
+        n[i] = len(cards)
+        hands[i, :len(cards)] = cards
+    return hands, n, flags
+
+
+def _sim_eval_want(hands, n, flags):
+    from oracle import pyoracle as po
+    return np.stack([po.sim_evaluate_bytes([tuple(int(x) for x in c) for c in hands[i, :n[i]]], bool(flags[i] & 1), bool(flags[i] & 2))
+                     for i in range(len(n))])
+
+
+SIM_EVAL_DOCUMENTED = np.r_[0:25, 32:128]   # bytes of a bg_sim_evaluate_batch row the header defines (25..31 are left untouched)
+
+
+def test_sim_evaluate_batch_vs_oracle_fresh_hands():
+    """balatro_sim.evaluate_hand: 50 000 fresh hands (1-8 cards, duplicates, one-suit and run-heavy hands) with and without Four Fingers /
+    Shortcut against pyoracle.sim_evaluate: top, list counts, first-list lengths and positions of all 12 types."""
+    import torch
+    from balatro_gym_amd import sim_evaluate_batch
+    hands, n, flags = _fresh_sim_hands(50000, 2718)
+    want = _sim_eval_want(hands, n, flags)
+    dev = torch.device("cuda:0")
+    out = sim_evaluate_batch(torch.from_numpy(hands).to(dev), torch.from_numpy(n).to(dev), torch.from_numpy(flags).to(dev)).cpu().numpy()
+    g, w = out[:, SIM_EVAL_DOCUMENTED], want[:, SIM_EVAL_DOCUMENTED]
+    bad = np.nonzero((g != w).any(axis=1))[0]
+    assert bad.size == 0, f"{bad.size} hands differ; hand {bad[0]} flags {flags[bad[0]]}: {hands[bad[0], :n[bad[0]]].tolist()} got {g[bad[0]].tolist()} want {w[bad[0]].tolist()}"
+    assert (np.bincount(want[:, 0], minlength=12) > 0).all()
+
+
+# ---------------------------------------------------------------------------------------------------------
+# guard regions: inputs and outputs as views at an offset inside larger buffers filled with a byte pattern
+# ---------------------------------------------------------------------------------------------------------
+GUARD_M = [1, 7, 8, 9, 31, 32, 33, 63, 64, 65, 255, 256, 257, 1000]
+GUARD_BEFORE, GUARD_AFTER = 16, 256   # rows of pattern in front of row 0 and behind row m (a whole 256-lane block)
+
+
+class _Guarded:
+    """A POISON-filled device byte buffer of GUARD_BEFORE + m + GUARD_AFTER rows of `row_bytes`; `view` = rows [GUARD_BEFORE, +m) as `dtype`."""
+
+    def __init__(self, m, row_bytes, dtype, fill=None):
+        import torch
+        self.m, self.rb = m, row_bytes
+        self.buf = torch.full(((GUARD_BEFORE + m + GUARD_AFTER) * row_bytes,), POISON, dtype=torch.uint8, device="cuda:0")
+        self.view = self.buf[GUARD_BEFORE * row_bytes:(GUARD_BEFORE + m) * row_bytes].view(dtype)
+        if fill is not None:
+            self.view.copy_(torch.from_numpy(np.ascontiguousarray(fill)).view(dtype).reshape(-1).to("cuda:0"))
+
+    def ptr(self):
+        import ctypes as C
+        return C.c_void_p(self.view.data_ptr())
+
+    def rows(self):
+        return self.view.cpu().numpy().view(np.uint8).reshape(self.m, self.rb)
+
+    def assert_guards(self, ctx):
+        b = self.buf.cpu().numpy()
+        lo, hi = GUARD_BEFORE * self.rb, (GUARD_BEFORE + self.m) * self.rb
+        assert (b[:lo] == POISON).all(), f"{ctx}: the guard in front of row 0 was written"
+        assert (b[hi:] == POISON).all(), f"{ctx}: the guard behind row m was written (first at row {self.m + (np.argmax(b[hi:] != POISON) // self.rb)})"
+
+
+def _operator_call(rc, what):
+    from balatro_gym_amd import _native as nat
+    if rc != 0:
+        raise nat.NativeError(f"{what} failed ({rc}): {nat.load().bg_last_error(None).decode()}")
+
+
+def test_operator_guard_regions():
+    """All four operators -- both lane mappings of bg_classify_batch_ex / bg_score_hand_batch_ex -- through the C ABI for m in GUARD_M, inputs
+    and outputs as views inside larger buffers filled with a byte pattern: every documented output word of rows [0, m) equals the oracle's,
+    the pattern in front of row 0 and in the 256 rows behind row m is untouched (inputs' guards included), and what the header says of the
+    other output bytes holds -- bg_sim_evaluate_batch leaves bytes 25..31 of a row untouched, bg_score_hand_batch writes 0 into word 7."""
+    import ctypes as C
+    import torch
+    from balatro_gym_amd import _native as nat
+    from oracle import pyoracle as po
+    L = nat.load()
+    M = max(GUARD_M)
+    st = C.c_void_p(torch.cuda.current_stream(torch.device("cuda:0")).cuda_stream)
+    rr = random.Random(99)
+    # inputs of the largest m, oracle answers once; every m uses a prefix
+    cls_cards = np.zeros((M, 8), np.uint8)
+    cls_n = np.zeros(M, np.uint8)
+    for i in range(M):
+        k = rr.randint(0, 8)
+        cls_cards[i, :k] = rr.sample(range(52), k)
+        cls_n[i] = k
+    cls_want = np.array([po.classify([int(x) for x in cls_cards[i, :cls_n[i]]]) for i in range(M)], np.uint8)
+    cases, sh_rec = _score_cases()
+    sh_rec = sh_rec[:M]
+    sh_want = np.array([po.score_hand_words(c["cards"], c["cards"][:c["nscoring"]], c["hand_type"], c["style"], c["level"], c["jokers"],
+                                            c["hands_left"], c["discards_left"], c["deck_len"], c["gseed"]) for c in cases[:M]], np.int64)
+    hands, sn, sflags = _fresh_sim_hands(M, 4242)
+    se_want = _sim_eval_want(hands, sn, sflags)
+    ss_rec = _fresh_sim_cases(M, 777)
+    ss_want = np.array([_sim_words_of_rec(c) for c in ss_rec], np.int64)
+    for m in GUARD_M:
+        for lanes in (1, 8):
+            ctx = f"bg_classify_batch_ex m {m} lanes {lanes}"
+            ci, ni, out = _Guarded(m, 8, torch.uint8, cls_cards[:m]), _Guarded(m, 1, torch.uint8, cls_n[:m]), _Guarded(m, 1, torch.uint8)
+            _operator_call(L.bg_classify_batch_ex(ci.ptr(), ni.ptr(), out.ptr(), C.c_int64(m), lanes, None, st), ctx)
+            torch.cuda.synchronize()
+            assert np.array_equal(out.rows()[:, 0], cls_want[:m]), ctx
+            for b in (ci, ni, out):
+                b.assert_guards(ctx)
+            ctx = f"bg_score_hand_batch_ex m {m} lanes {lanes}"
+            ci, out = _Guarded(m, 160, torch.int32, sh_rec[:m]), _Guarded(m, 64, torch.int64)
+            _operator_call(L.bg_score_hand_batch_ex(ci.ptr(), out.ptr(), m, lanes, None, st), ctx)
+            got = out.rows().view(np.int64)
+            bad = np.nonzero((got != sh_want[:m]).any(axis=1))[0]
+            assert bad.size == 0, f"{ctx}: case {bad[0]} got {got[bad[0]].tolist()} want {sh_want[bad[0]].tolist()}"
+            ci.assert_guards(ctx); out.assert_guards(ctx)
+        ctx = f"bg_sim_evaluate_batch m {m}"
+        hi, ni, fi, out = (_Guarded(m, 192, torch.int32, hands[:m]), _Guarded(m, 4, torch.int32, sn[:m]), _Guarded(m, 4, torch.int32, sflags[:m]),
+                           _Guarded(m, 128, torch.int8))
+        _operator_call(L.bg_sim_evaluate_batch(hi.ptr(), ni.ptr(), fi.ptr(), out.ptr(), m, st), ctx)
+        torch.cuda.synchronize()
+        got = out.rows().view(np.int8)
+        assert np.array_equal(got[:, SIM_EVAL_DOCUMENTED], se_want[:m, SIM_EVAL_DOCUMENTED]), ctx
+        assert (got[:, 25:32].view(np.uint8) == POISON).all(), f"{ctx}: bytes 25..31 of a row were written"
+        for b in (hi, ni, fi, out):
+            b.assert_guards(ctx)
+        ctx = f"bg_sim_score_batch m {m}"
+        ci, out = _Guarded(m, 256, torch.int32, ss_rec[:m]), _Guarded(m, 64, torch.int64)
+        _operator_call(L.bg_sim_score_batch(ci.ptr(), out.ptr(), m, st), ctx)
+        got = out.rows().view(np.int64)
+        bad = np.nonzero((got != ss_want[:m]).any(axis=1))[0]
+        assert bad.size == 0, f"{ctx}: case {bad[0]} got {got[bad[0]].tolist()} want {ss_want[bad[0]].tolist()}"
+        ci.assert_guards(ctx); out.assert_guards(ctx)
 
 
 def test_cross_wave_state_handover_litmus():

@@ -9,7 +9,7 @@ import random
 import numpy as np
 import pytest
 
-from tests.helpers import OBS_KEYS, load_trace, trace_injection
+from tests.helpers import OBS_KEYS, assert_step_outputs, load_trace, poison_, poison_env_outputs, trace_injection
 
 HAND_TYPE_NAMES = ["High Card", "One Pair", "Two Pair", "Three Kind", "Straight", "Flush", "Full House", "Four Kind", "Straight Flush",
                    "Five Kind", "Flush House", "Flush Five"]
@@ -116,7 +116,9 @@ def _oracle_envs(n, seeds, scorer, max_ante, jokers=None):
 
 @pytest.mark.parametrize("policy,scorer", [(0, False), (2, False), (2, True), (0, True)])
 def test_step_vs_oracle_fresh_seeds(policy, scorer):
-    """512 fresh seeds x 250 steps in lockstep with the CPU oracle (actions from the oracle's counter-hash policy)."""
+    """512 fresh seeds x 250 steps in lockstep with the CPU oracle (actions from the oracle's counter-hash policy): every output word of
+    every step (tests/helpers.py assert_step_outputs), written into buffers poisoned before each call.  The uniform policy reaches the
+    shop, so the joker ids bought and sold in `aux` are compared too."""
     import torch
     from oracle import pyoracle as po
     from oracle.gen_golden import IMPLEMENTED
@@ -131,23 +133,15 @@ def test_step_vs_oracle_fresh_seeds(policy, scorer):
     orc = _oracle_envs(n, seeds, scorer, max_ante, jokers)
     want0 = [o.obs() for o in orc]
     _assert_obs(_obs_np(env), {k: np.stack([w[k] for w in want0]) for k in OBS_KEYS}, "initial")
+    flag_rows = np.zeros(10, np.int64)
     for t in range(T):
         acts = np.array([o.policy_action(policy, 99, i, t) for i, o in enumerate(orc)], dtype=np.int32)
         res = [o.step(int(a)) for o, a in zip(orc, acts)]
-        _, reward, term, _, info = env.step(torch.from_numpy(acts).to(env.device))
-        ctx = f"policy {policy} scorer {scorer} t {t}"
-        wr = np.array([r[1] for r in res])
-        assert np.array_equal(reward.cpu().numpy().view(np.uint64), wr.view(np.uint64)), ctx
+        poison_env_outputs(env)
+        ob, reward, term, trunc, info = env.step(torch.from_numpy(acts).to(env.device))
+        wf = assert_step_outputs(f"policy {policy} scorer {scorer} t {t}", res, reward, term, trunc, info, obs=ob)
+        flag_rows += [(wf >> b & 1).sum() for b in range(10)]
         wt = np.array([r[2] for r in res], dtype=np.uint8)
-        assert np.array_equal(term.cpu().numpy(), wt), ctx
-        assert np.array_equal(info["final_score"].cpu().numpy(), np.array([r[4].final_score for r in res])), ctx
-        assert np.array_equal(info["hand_type"].cpu().numpy(), np.array([r[4].hand_type for r in res], dtype=np.int8)), ctx
-        assert np.array_equal(info["cards_played"].cpu().numpy(), np.array([r[4].cards_played for r in res], dtype=np.int8)), ctx
-        assert np.array_equal(info["error"].cpu().numpy(), np.array([r[4].error for r in res], dtype=np.int32)), ctx
-        assert np.array_equal(info["flags"].cpu().numpy() & 511, np.array([r[4].flags for r in res], dtype=np.int32)), ctx
-        wterms = np.array([[r[4].reward_terms[i] for i in range(TERMS)] for r in res])
-        assert np.array_equal(info["reward_terms"].cpu().numpy().view(np.uint64), wterms.view(np.uint64)), ctx
-        _assert_obs(_obs_np(env), {k: np.stack([r[0][k] for r in res]) for k in OBS_KEYS}, ctx)
         if wt.any():
             for i in np.nonzero(wt)[0]:
                 orc[i].reset()
@@ -156,14 +150,82 @@ def test_step_vs_oracle_fresh_seeds(policy, scorer):
             env.reset(mask=torch.from_numpy(wt).to(env.device))
     env.check()
     env.close()
+    if policy == 0:   # the shop was reached: joker ids bought / sold were compared in aux hundreds of times
+        assert flag_rows[6] > 50 and flag_rows[7] > 50, flag_rows.tolist()
+
+
+class _StepBuffers:
+    """Every output bg_step_many writes, as caller buffers: with K > 1 (obs_stride_steps = 1) [K, N, ...] observation arrays and [K, N]
+    reward / terminated / truncated / info arrays, with K = 1 the [N, ...] ones (obs_stride_steps = 0).  `poison()` fills them all with
+    tests/helpers.POISON; `row(j)` is what call j wrote (obs, reward, terminated, truncated, info)."""
+
+    def __init__(self, n, device, K):
+        import torch
+        from balatro_gym_amd import _native as nat
+        from balatro_gym_amd.vec_env import ObsBuffers
+        dts = {"int8": torch.int8, "int32": torch.int32, "int64": torch.int64, "float64": torch.float64}
+        self.K, self.n = K, n
+        lead = (K, n) if K > 1 else (n,)
+        self.ob = ObsBuffers(n, device, steps=K)
+        self.reward = torch.empty(lead, dtype=torch.float64, device=device)
+        self.terminated = torch.empty(lead, dtype=torch.uint8, device=device)
+        self.truncated = torch.empty(lead, dtype=torch.uint8, device=device)
+        self.info = {k: torch.empty(lead + nat.INFO_SPEC[k][1], dtype=dts[nat.INFO_SPEC[k][0]], device=device) for k in nat.INFO_KEYS}
+        self.info_ptrs = nat.InfoPtrs(**{k: v.data_ptr() for k, v in self.info.items()})
+
+    def tensors(self):
+        return [self.ob.flat, self.reward, self.terminated, self.truncated, *self.info.values()]
+
+    def poison(self):
+        poison_(*self.tensors())
+
+    def row(self, j):
+        pick = (lambda v: v[j]) if self.K > 1 else (lambda v: v)
+        return ({k: pick(v) for k, v in self.ob.tensors.items()}, pick(self.reward), pick(self.terminated), pick(self.truncated),
+                {k: pick(v) for k, v in self.info.items()})
+
+    def step(self, env, acts, rows=None):
+        """One bg_step (rows None: the observation into these [N, ...] arrays) or bg_step_rows (into the [N, row_stride] byte tensor `rows`)."""
+        import ctypes as C
+        import torch
+        assert self.K == 1
+        a = torch.as_tensor(np.ascontiguousarray(acts, dtype=np.int32)).to(env.device)
+        outs = (C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.terminated.data_ptr()), C.c_void_p(self.truncated.data_ptr()),
+                C.byref(self.info_ptrs), env._stream())
+        if rows is None:
+            env._check(env._L.bg_step(env._h, C.c_void_p(a.data_ptr()), C.byref(self.ob.ptrs), *outs), "bg_step")
+        else:
+            env._check(env._L.bg_step_rows(env._h, C.c_void_p(a.data_ptr()), C.c_void_p(rows.data_ptr()), C.c_uint64(rows.shape[-1]), *outs),
+                       "bg_step_rows")
+
+    def step_many(self, env, acts):
+        """bg_step_many through the C ABI: K = len(acts) calls, every output into these buffers (per step when self.K > 1)."""
+        import ctypes as C
+        import torch
+        a = torch.as_tensor(np.ascontiguousarray(acts, dtype=np.int32)).to(env.device)
+        assert a.dim() == 2 and a.shape[1] == self.n and (self.K == 1 or a.shape[0] <= self.K)
+        rc = env._L.bg_step_many(env._h, int(a.shape[0]), C.c_void_p(a.data_ptr()), C.byref(self.ob.ptrs), 1 if self.K > 1 else 0,
+                                 C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.terminated.data_ptr()), C.c_void_p(self.truncated.data_ptr()),
+                                 C.byref(self.info_ptrs), env._stream())
+        env._check(rc, "bg_step_many")
+
+
+def _assert_poisoned(tensors, lo, ctx):
+    """Rows lo.. of every [K, N, ...] buffer still hold the poison: nothing was written past the steps of the call."""
+    import torch
+    from tests.helpers import POISON
+    for t in tensors:
+        rest = t[lo:]
+        assert bool((rest.contiguous().view(torch.uint8) == POISON).all()), f"{ctx}: a row past the call's last step was written"
 
 
 @pytest.mark.parametrize("many", [0, 40])
 def test_step_path_across_refill_periods_vs_oracle(many):
-    """900 steps through bg_step (one launch per step) and through bg_step_many (40 steps per call): more than two refill periods, so the look-ahead refill
-    runs BESIDE the step launches -- its scan behind the launch that asks for it, its dense kernels in pieces behind the following ones (round 5; a
-    synchronous refill on the stream before) -- with a masked reset and a state blob in between.  Observation, reward, termination and info of every
-    step against the oracle."""
+    """900 steps through bg_step (one launch per step) and through bg_step_many (up to 40 steps per call, every step's outputs kept): more than two
+    refill periods, so the look-ahead refill runs BESIDE the step launches -- its scan behind the launch that asks for it, its dense kernels in pieces
+    behind the following ones (round 5; a synchronous refill on the stream before) -- with a masked reset and a state blob in between.  Observation,
+    reward, terminated, truncated and every info array of EVERY step against the oracle (tests/helpers.py assert_step_outputs), in buffers poisoned
+    before each call; with bg_step_many the rows past a call's last step must keep the poison."""
     import torch
     from oracle.gen_golden import IMPLEMENTED
     n, T = 160, 900
@@ -174,10 +236,7 @@ def test_step_path_across_refill_periods_vs_oracle(many):
     env.observe()
     orc = _oracle_envs(n, seeds, True, 4, jokers)
     if many:
-        from balatro_gym_amd.vec_env import ObsBuffers
-        ob_k = ObsBuffers(n, env.device, steps=many)
-        reward_k = torch.zeros((many, n), dtype=torch.float64, device=env.device)
-        term_k = torch.zeros((many, n), dtype=torch.uint8, device=env.device)
+        bufs = _StepBuffers(n, env.device, many)
     t = 0
     while t < T:
         k = min(many, T - t) if many else 1
@@ -187,29 +246,24 @@ def test_step_path_across_refill_periods_vs_oracle(many):
             acts[j] = [o.policy_action(2, 77, i, t + j) for i, o in enumerate(orc)]
             res = [o.step(int(a)) for o, a in zip(orc, acts[j])]
             res_k.append(res)
-            for i, r in enumerate(res):   # autoreset off: the oracle side resets what terminated (the device side below, by mask, when stepping one by one)
+            for i, r in enumerate(res):   # autoreset off: the oracle side resets what terminated (the device side below, by mask)
                 if r[2]:
                     orc[i].reset(); orc[i].set_jokers(jokers[i])
             if many and any(r[2] for r in res):   # step_many stops nowhere: end the block at a termination so that both sides reset here
                 acts = acts[:j + 1]; k = j + 1
                 break
         if many:
-            env.step_many(torch.from_numpy(acts).to(env.device), obs_buffers=ob_k, reward=reward_k, terminated=term_k)
-            wr = np.array([[r[1] for r in res] for res in res_k])
-            assert np.array_equal(reward_k[:k].cpu().numpy().view(np.uint64), wr.view(np.uint64)), f"t {t}"
-            wt = np.array([[r[2] for r in res] for res in res_k], dtype=np.uint8)
-            assert np.array_equal(term_k[:k].cpu().numpy(), wt), f"t {t}"
-            for j in (0, k - 1):
-                _assert_obs({key: ob_k.tensors[key][j].cpu().numpy() for key in OBS_KEYS}, {key: np.stack([r[0][key] for r in res_k[j]]) for key in OBS_KEYS}, f"t {t} + {j}")
-            tm = wt[-1]
+            bufs.poison()
+            bufs.step_many(env, acts)
+            for j in range(k):
+                ob, rw, tm_j, tr, info = bufs.row(j)
+                assert_step_outputs(f"t {t} + {j}", res_k[j], rw, tm_j, tr, info, obs=ob)
+            _assert_poisoned(bufs.tensors()[1:] + list(bufs.ob.tensors.values()), k, f"t {t}, {k} steps")
         else:
-            _, reward, term, _, info = env.step(torch.from_numpy(acts[0]).to(env.device))
-            last = res_k[0]
-            assert np.array_equal(reward.cpu().numpy().view(np.uint64), np.array([r[1] for r in last]).view(np.uint64)), f"t {t}"
-            tm = np.array([r[2] for r in last], dtype=np.uint8)
-            assert np.array_equal(term.cpu().numpy(), tm), f"t {t}"
-            assert np.array_equal(info["error"].cpu().numpy(), np.array([r[4].error for r in last], dtype=np.int32)), f"t {t}"
-            _assert_obs(_obs_np(env), {key: np.stack([r[0][key] for r in last]) for key in OBS_KEYS}, f"t {t}")
+            poison_env_outputs(env)
+            ob, reward, term, trunc, info = env.step(torch.from_numpy(acts[0]).to(env.device))
+            assert_step_outputs(f"t {t}", res_k[0], reward, term, trunc, info, obs=ob)
+        tm = np.array([r[2] for r in res_k[-1]], dtype=np.uint8)
         if tm.any():
             env.reset(mask=torch.from_numpy(tm).to(env.device))
         t += k
@@ -1493,8 +1547,9 @@ def test_mt_streams_on_device():
 
 def test_step_rows_layout_vs_oracle():
     """`BalatroVecEnv(obs_layout="rows")`: bg_step_rows / bg_observe_rows -- the observation as one packed 384-byte record per env, written by
-    the copier waves, `obs[key]` strided views of it -- in lockstep with the oracle (every key, reward bits, terminated, the info arrays),
-    masked resets and an injection included; and against the "keys" layout of the same env."""
+    the copier waves, `obs[key]` strided views of it -- in lockstep with the oracle (every output word: tests/helpers.py assert_step_outputs,
+    into buffers poisoned before each call), masked resets and an injection included; and the "keys" layout of the same env, held to the
+    same oracle and to the same info bytes."""
     import torch
     from oracle import pyoracle as po
     from oracle.gen_golden import IMPLEMENTED
@@ -1509,23 +1564,24 @@ def test_step_rows_layout_vs_oracle():
     orc = _oracle_envs(n, seeds, True, 4, jokers)
     assert env.obs_rows.shape == (n, 384) and (env.obs_rows[:, 352:] == 0).all()
     _assert_obs(_obs_np(env), {k: np.stack([o.obs()[k] for o in orc]) for k in OBS_KEYS}, "initial")
+    flag_rows = np.zeros(10, np.int64)
     for t in range(T):
         acts = np.array([o.policy_action(0, 99, i, t) for i, o in enumerate(orc)], dtype=np.int32)
         res = [o.step(int(a)) for o, a in zip(orc, acts)]
         a = torch.from_numpy(acts).to(env.device)
-        _, reward, term, _, info = env.step(a)
-        _, reward2, term2, _, info2 = twin.step(a)
+        poison_env_outputs(env); poison_env_outputs(twin)
+        ob, reward, term, trunc, info = env.step(a)
+        ob2, reward2, term2, trunc2, info2 = twin.step(a)
         ctx = f"rows layout t {t}"
+        wf = assert_step_outputs(ctx, res, reward, term, trunc, info, obs=ob)
+        assert_step_outputs(ctx + " (keys twin)", res, reward2, term2, trunc2, info2, obs=ob2)
+        flag_rows += [(wf >> b & 1).sum() for b in range(10)]
         wr = np.array([r[1] for r in res])
-        assert np.array_equal(reward.cpu().numpy().view(np.uint64), wr.view(np.uint64)), ctx
         wt = np.array([r[2] for r in res], dtype=np.uint8)
-        assert np.array_equal(term.cpu().numpy(), wt), ctx
-        for k in ("final_score", "error", "hand_type", "cards_played", "aux"):
-            assert torch.equal(info[k], info2[k]), (ctx, k)
-        assert np.array_equal(info["error"].cpu().numpy(), np.array([r[4].error for r in res], dtype=np.int32)), ctx
-        assert torch.equal(info["reward_terms"].view(torch.int64), info2["reward_terms"].view(torch.int64)), ctx
-        _assert_obs(_obs_np(env), {k: np.stack([r[0][k] for r in res]) for k in OBS_KEYS}, ctx)
+        for k in info:
+            assert torch.equal(info[k].view(torch.uint8), info2[k].view(torch.uint8)), (ctx, k)
         rows = env.obs_rows.cpu().numpy()
+        assert not rows[:, 352:].any(), ctx   # the fast layout writes whole 128-byte lines: bytes 352..383 as zeros
         assert np.array_equal(rows[:, 136:144].copy().view(np.float64)[:, 0].view(np.uint64), wr.view(np.uint64)), ctx   # reward rides in the record
         assert np.array_equal(rows[:, 172:176].copy().view(np.int32)[:, 0], acts) and np.array_equal(rows[:, 342], wt), ctx
         if wt.any():
@@ -1534,6 +1590,200 @@ def test_step_rows_layout_vs_oracle():
                 orc[i].set_jokers(jokers[i])
             m = torch.from_numpy(wt).to(env.device)
             env.reset(mask=m); twin.reset(mask=m)
-            _assert_obs(_obs_np(env), {k: np.stack([o.obs()[k] for o in orc]) for k in OBS_KEYS}, ctx + " after reset")
+            after = [o.obs() for o in orc]
+            _assert_obs(_obs_np(env), {k: np.stack([w[k] for w in after]) for k in OBS_KEYS}, ctx + " after reset")
     env.check(); twin.check()
     env.close(); twin.close()
+    assert flag_rows[6] > 50 and flag_rows[7] > 50, flag_rows.tolist()   # joker ids bought / sold were compared in aux
+
+
+def _row_views(rows):
+    """Per-key views of a [N, row_stride] byte tensor of packed records (BG_ROW_* offsets)."""
+    from balatro_gym_amd import _native as nat
+    dts = {"int8": np.int8, "int16": np.int16, "int32": np.int32, "int64": np.int64, "float32": np.float32, "float64": np.float64}
+    r = rows.cpu().numpy()
+    out = {}
+    for k in OBS_KEYS:
+        dt, shape = nat.OBS_SPEC[k]
+        cnt = int(np.prod(shape, dtype=np.int64))
+        v = r[:, nat.ROW_OFFSETS[k]:nat.ROW_OFFSETS[k] + cnt * np.dtype(dts[dt]).itemsize].copy().view(dts[dt])
+        out[k] = v.reshape((len(r),) + tuple(shape))
+    return out
+
+
+def test_every_step_entry_point_writes_every_output_word():
+    """The output buffers of bg_reset(mask) / bg_observe / bg_step / bg_step_rows / bg_observe_rows -- the observation arrays or the packed
+    records, reward, terminated, truncated, all 8 info arrays -- filled with a byte pattern before EVERY call, the calls cycled on one handle
+    (the library keeps the state: no entry point reads an output buffer back): every documented word must come back equal to the oracle's.
+    bg_observe_rows leaves bytes 352.. of a record untouched and writes 0 into the record's reward / action / terminated; bg_step_rows on the
+    384-byte stride writes bytes 352..383 as zeros.  333 envs: a partial last workgroup."""
+    import ctypes as C
+    import torch
+    from balatro_gym_amd.vec_env import RowBuffers
+    from oracle.gen_golden import IMPLEMENTED
+    from tests.helpers import POISON
+    n, T = 333, 120
+    seeds = [741_000 + SEED_OFFSET + 3 * i for i in range(n)]
+    jokers = [random.Random(6100 + i).sample(IMPLEMENTED, i % 6) for i in range(n)]
+    env = _vec(n, seeds, scorer_jokers=True, autoreset=False, max_ante=4)
+    env.inject(jokers=jokers, apply_now=True)
+    orc = _oracle_envs(n, seeds, True, 4, jokers)
+    keys = _StepBuffers(n, env.device, 1)
+    rb = RowBuffers(n, env.device, steps=1, row_stride=384)
+    rows = rb.rows[0]
+    st = env._stream()
+
+    def want_obs():
+        obs = [o.obs() for o in orc]
+        return {k: np.stack([w[k] for w in obs]) for k in OBS_KEYS}
+
+    def observe(via_rows, ctx):
+        if via_rows:
+            poison_(rb.rows)
+            env._check(env._L.bg_observe_rows(env._h, C.c_void_p(rows.data_ptr()), C.c_uint64(384), st), "bg_observe_rows")
+            _assert_obs(_row_views(rows), want_obs(), ctx + " bg_observe_rows")
+            r = rows.cpu().numpy()
+            assert (r[:, 352:] == POISON).all(), f"{ctx}: bg_observe_rows wrote bytes 352.."
+            assert not r[:, 136:144].any() and not r[:, 172:176].any() and not r[:, 342].any(), f"{ctx}: record reward / action / terminated"
+        else:
+            poison_(keys.ob.flat)
+            env._check(env._L.bg_observe(env._h, C.byref(keys.ob.ptrs), st), "bg_observe")
+            _assert_obs(_obs_np_of(keys.ob.tensors), want_obs(), ctx + " bg_observe")
+
+    flag_rows = np.zeros(10, np.int64)
+    calls = np.zeros(5, np.int64)
+    for t in range(T):
+        via_rows = t % 2 == 1
+        acts = np.array([o.policy_action(0, 17, i, t) for i, o in enumerate(orc)], dtype=np.int32)
+        res = [o.step(int(a)) for o, a in zip(orc, acts)]
+        ctx = f"t {t} {'bg_step_rows' if via_rows else 'bg_step'}"
+        keys.poison(); poison_(rb.rows)
+        keys.step(env, acts, rows=rows if via_rows else None)
+        _, rw, tm, tr, info = keys.row(0)
+        if via_rows:
+            wf = assert_step_outputs(ctx, res, rw, tm, tr, info, obs=_row_views(rows))
+            r = rows.cpu().numpy()
+            assert not r[:, 352:].any() and np.array_equal(r[:, 172:176].copy().view(np.int32)[:, 0], acts), ctx
+            assert (keys.ob.flat.cpu().numpy() == POISON).all(), f"{ctx}: bg_step_rows wrote the per-key arrays"
+        else:
+            wf = assert_step_outputs(ctx, res, rw, tm, tr, info, obs=keys.ob.tensors)
+            assert (rb.rows.cpu().numpy() == POISON).all(), f"{ctx}: bg_step wrote the records"
+        calls[1 if via_rows else 0] += 1
+        flag_rows += [(wf >> b & 1).sum() for b in range(10)]
+        if t % 3 == 0:
+            observe(t % 6 == 3, ctx)
+            calls[3 if t % 6 == 3 else 2] += 1
+        wt = np.array([r[2] for r in res], dtype=np.uint8)
+        if wt.any():
+            for i in np.nonzero(wt)[0]:
+                orc[i].reset(); orc[i].set_jokers(jokers[i])
+            m = torch.from_numpy(wt).to(env.device)
+            if via_rows:   # bg_reset without observation arrays, then the records
+                env._check(env._L.bg_reset(env._h, C.c_void_p(m.data_ptr()), None, st), "bg_reset")
+                observe(True, ctx + " reset")
+            else:          # bg_reset writes the observation of EVERY env
+                poison_(keys.ob.flat)
+                env._check(env._L.bg_reset(env._h, C.c_void_p(m.data_ptr()), C.byref(keys.ob.ptrs), st), "bg_reset")
+                _assert_obs(_obs_np_of(keys.ob.tensors), want_obs(), ctx + " bg_reset")
+            calls[4] += 1
+    env.check()
+    env.close()
+    assert (calls > 3).all(), calls.tolist()
+    assert flag_rows[6] > 20 and flag_rows[7] > 20, flag_rows.tolist()
+
+
+def _obs_np_of(tensors):
+    return {k: v.cpu().numpy() for k, v in tensors.items()}
+
+
+def _step_many_vs_oracle(monkeypatch, autoreset, stride):
+    import torch
+    from oracle.gen_golden import IMPLEMENTED
+    monkeypatch.setenv("BG_KG", "4"); monkeypatch.setenv("BG_KS", "5"); monkeypatch.setenv("BG_KD", "4")
+    n, K, calls = 333, 48, 3
+    seeds = [752_000 + SEED_OFFSET + 7 * i for i in range(n)]
+    jokers = [random.Random(7300 + i).sample(IMPLEMENTED, i % 6) for i in range(n)]
+    env = _vec(n, seeds, scorer_jokers=True, autoreset=autoreset, max_ante=4)
+    env.inject(jokers=jokers, apply_now=True)
+    orc = _oracle_envs(n, seeds, True, 4, jokers)
+    bufs = _StepBuffers(n, env.device, K if stride else 1)
+    flag_rows = np.zeros(10, np.int64)
+    env.set_profiling(True)
+    for c in range(calls):
+        acts = np.zeros((K, n), np.int32)
+        res_k, want_k = [], []
+        for j in range(K):
+            t = c * K + j
+            acts[j] = [o.policy_action(0, 23, i, t) for i, o in enumerate(orc)]
+            res = [o.step(int(a)) for o, a in zip(orc, acts[j])]
+            if autoreset:   # SAME_STEP auto-reset: the env is reset inside the step that terminates it, the observation shows the new episode
+                for i, r in enumerate(res):
+                    if r[2]:
+                        orc[i].reset(); orc[i].set_jokers(jokers[i])
+            res_k.append(res)
+            obs = [o.obs() for o in orc] if autoreset else [r[0] for r in res]
+            want_k.append({k: np.stack([w[k] for w in obs]) for k in OBS_KEYS})
+        bufs.poison()
+        bufs.step_many(env, acts)
+        prof = env.get_profile()
+        ctx = f"autoreset {autoreset} stride {stride} call {c}"
+        assert prof["step_launches"] >= 3, (ctx, prof)   # shallow rings: the call runs as several launches with refills between them
+        rows = range(K) if stride else [K - 1]
+        for j in rows:
+            ob, rw, tm, tr, info = bufs.row(j if stride else 0)
+            wf = assert_step_outputs(f"{ctx} step {j}", res_k[j], rw, tm, tr, info, obs=ob, autoreset=autoreset, want_obs=want_k[j])
+            flag_rows += [(wf >> b & 1).sum() for b in range(10)]
+    env.check()
+    env.close()
+    return flag_rows
+
+
+@pytest.mark.parametrize("autoreset", [False, True], ids=["autoreset_off", "autoreset_on"])
+def test_step_many_per_step_outputs_vs_oracle(monkeypatch, autoreset):
+    """bg_step_many through the C ABI with obs_stride_steps = 1: EVERY output in [K, N, ...] caller buffers poisoned before the call -- all 31
+    observation keys, reward, terminated, truncated and the 8 info arrays -- and every row against the oracle (tests/helpers.py
+    assert_step_outputs).  Shallow rings make each 48-step call several launches with refills between them, so every launch after the first
+    writes at its own `done * N` rows (bg_step_impl's pointer advance, info included).  333 envs: a partial last workgroup.  With autoreset on
+    the oracle side resets an env in the step that terminates it, and BG_INFO_AUTORESET must be set exactly there."""
+    flag_rows = _step_many_vs_oracle(monkeypatch, autoreset, 1)
+    assert flag_rows[6] > 20 and flag_rows[7] > 20, flag_rows.tolist()   # joker ids bought / sold compared in aux
+    assert flag_rows[0] > 20 and flag_rows[1] > 20, flag_rows.tolist()
+
+
+@pytest.mark.parametrize("autoreset", [False, True], ids=["autoreset_off", "autoreset_on"])
+def test_step_many_last_step_outputs_vs_oracle(monkeypatch, autoreset):
+    """bg_step_many with obs_stride_steps = 0: the [N, ...] buffers (observation, reward, terminated, truncated, info) hold the LAST call's
+    values, every word of them, after several launches."""
+    _step_many_vs_oracle(monkeypatch, autoreset, 0)
+
+
+def test_step_many_wrapper_keeps_no_stale_info():
+    """BalatroVecEnv.step_many with per-step obs_buffers keeps per-step outputs only in per-step tensors: it returns None for truncated, info
+    and whichever of reward / terminated was not given, and writes nothing into the live [N] tensors (a [K, N] output there would run past
+    their end) -- they keep a byte pattern.  Without per-step buffers it refuses reward / terminated tensors (they would be ignored)."""
+    import torch
+    from balatro_gym_amd.vec_env import ObsBuffers
+    from tests.helpers import POISON
+    n, K = 64, 6
+    env = _vec(n, [5 + i for i in range(n)], autoreset=True)
+    acts = torch.full((K, n), 45, dtype=torch.int32, device=env.device)
+    ob = ObsBuffers(n, env.device, steps=K)
+    reward = torch.zeros((K, n), dtype=torch.float64, device=env.device)
+    term = torch.full((K, n), 7, dtype=torch.uint8, device=env.device)
+    live = [env.reward, env.terminated, env.truncated, *env.info.values()]
+    poison_(*live)
+    _, rw, tm, trunc, info = env.step_many(acts, obs_buffers=ob, reward=reward)
+    assert rw is reward and tm is None and trunc is None and info is None
+    _, rw, tm, trunc, info = env.step_many(acts, obs_buffers=ob, terminated=term)
+    assert rw is None and tm is term and trunc is None and info is None
+    _, rw, tm, trunc, info = env.step_many(acts, obs_buffers=ob)
+    assert rw is None and tm is None and trunc is None and info is None
+    torch.cuda.synchronize(env.device)
+    for t in live:
+        assert bool((t.view(torch.uint8) == POISON).all()), "step_many with per-step buffers wrote a live [N] tensor"
+    assert bool((reward[:, :] != 0).any()) and bool((term <= 1).all())   # the per-step tensors were written (action 45: reward, no ending)
+    with pytest.raises(ValueError, match="per-step obs_buffers"):
+        env.step_many(acts, reward=reward)
+    _, rw, tm, trunc, info = env.step_many(acts)
+    assert rw is env.reward and tm is env.terminated and trunc is env.truncated and info is env.info
+    env.close()
