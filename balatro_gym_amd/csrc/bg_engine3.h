@@ -37,6 +37,7 @@ constexpr bool kE3Tl = false;
 #define BG_E3_REC_STORE(v, p) __builtin_nontemporal_store(v, p)
 #define BG_E3_SPARSE 8u   // records finished in an owner iteration up to which the copy-out takes its one-group path
 #define BG_E3_SPARSE2 16u // ... its two-group path (a three-group tier: inside the noise, profiles/r05/sparse_copy_out.txt)
+#define BG_E3_ACTB 8      // ACT: actions per env fetched at a time (and owner iterations between two fetches)
 template <int NOW, int KS, int NSV>
 struct E3Lds {
   static constexpr int NE = NOW * KS * BG_BLOCK;
@@ -62,7 +63,17 @@ struct E3Lds {
 };
 // A workgroup = NE = 64 * NOW * KS envs: NOW owner waves (each owns KS slices of 64 envs, lane = env of a slice) + NSV service waves.  256 envs per
 // workgroup fill the chip at 65 536 envs; a small job takes 64 or 128 per workgroup and spreads over four or two times as many CUs.
-template <bool HASH, bool CARDS, int NOW, int KS, int NSV>
+// ACT (bg_step_many_rows): the action of every step is the CALLER's, a.actions_in[t * N + env] (any int32), instead of the counter-hash policy's, and
+// the launch may run with auto-reset off.  What that changes, all of it behind `if constexpr (ACT)` (the policy instantiations compile as before):
+//   * the lanes of an owner wave are at different t, so a load of the wave's next actions touches up to 64 lines 4 N bytes apart, and waiting for it is
+//     waiting for the vector-memory counter -- i.e. also for the record stores the copy-out issued before it, which the owner otherwise never waits
+//     for (one such wait per iteration: step phase 2.1 k -> 4.6 k cycles, profiles/step_many_rows_owner_phases.txt).  So every BG_E3_ACTB-th iteration
+//     every lane fetches the next BG_E3_ACTB actions of its env into LDS (a lane advances at most one step per iteration): one wait per eight iterations;
+//   * a request's queue word has 15 bits for the action, enough for a policy's 0..59: the owner leaves the caller's int32 in the action word of the env's
+//     image and the service wave takes it from there (32768 + 2 must not become a toggle, and the record carries the value as given);
+//   * without auto-reset an env stays above its curriculum cap, and every step of such an env -- a toggle, an invalid action -- reports terminated
+//     (CurriculumBalatroEnv.step, train_balatro_agent.py:146-152): the owner's `terminal` test includes the cap, so that these steps go to a service wave, which applies the rule.
+template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT = false>
 // (Round 5 measured reading the arguments THROUGH the kernarg segment pointer instead of as by-value parameters -- whose 16-register blocks the compiler
 //  spills to VGPR lanes and reloads whole, 12 % of the kernel's instructions being v_readlane / v_writelane / s_nop: SGPR spills 237 -> 61, 14 454 -> 13 114
 //  instructions, and 3.4 % SLOWER at both launch lengths: a scalar load per use waits longer than sixteen lane reads.  profiles/r05/play_path_ab.txt.)
@@ -75,6 +86,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
   auto& s_img = L.s_img; auto& s_c34 = L.s_c34; auto& s_mask = L.s_mask; auto& s_prod = L.s_prod; auto& s_ans = L.s_ans; auto& s_q = L.s_q;
   auto& s_ctl = L.s_ctl; auto& s_win = L.s_win; auto& s_list = L.s_list; auto& s_zero = L.s_zero; auto& s_owners_left = L.s_owners_left; auto& jt = L.jt;
   auto& s_nd = L.s_nd; auto& s_ndst = L.s_ndst;
+  __shared__ int s_actb[ACT ? BG_E3_ACTB : 1][ACT ? NE : 1];   // ACT: the next actions of every env (row j: step abase + j); not referenced, so not allocated, otherwise
   __builtin_amdgcn_s_setprio(2);
   const unsigned long long e3_k0 = kE3Tl ? wall_clock64() : 0ull;
   BG_PROBE_INIT();
@@ -154,11 +166,21 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
     uint64_t px[KS];
     size_t prow[KS];
     int pblind[KS];
+    // ACT: the step whose action is in row 0 of s_actb, and the ante above which the env is terminal (100, :619, or its cap)
+    uint32_t abase[KS];
+    uint32_t athr[KS];
 #pragma unroll
     for (int s = 0; s < KS; s++) {
       t[s] = 0; nreq[s] = 0; waiting[s] = false;
       const int l = (wave * KS + s) * BG_BLOCK + lane;
-      {
+      if constexpr (ACT) {
+        abase[s] = 0; athr[s] = 100u;
+        prow[s] = (size_t)(env0 + l);
+        if (l < n_live) {   // (the envs past N of the last workgroup have no state)
+          const uint32_t cap = (d.hot[(size_t)7 * N + (size_t)(env0 + l)].w >> 16) & 0xffu;   // Env::max_ante (bg_unpack), a constant of the launch
+          if (cap > 0u && cap < 100u) athr[s] = cap;
+        }
+      } else {
         const int env = env0 + l;
         const uint64_t gi0 = a.env_index0 + (uint64_t)env;
         px[s] = a.policy_seed + 0x9E3779B97F4A7C15ull * (gi0 + 1) + BG_POLICY_PSI * (a.t0 + 1);
@@ -167,10 +189,10 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
       }
       rc3[s] = s_c34[0][l]; rc4[s] = s_c34[1][l]; rmask[s] = s_mask[l];
       const lds_u32* im = (const lds_u32*)&s_img[l][0];
-      terminal[s] = bg_b(rc3[s].x, 0) > 100u || (int64_t)(((uint64_t)im[33] << 32) | im[32]) > 1000000000ll;   // :619-623
+      terminal[s] = bg_b(rc3[s].x, 0) > (ACT ? athr[s] : 100u) || (int64_t)(((uint64_t)im[33] << 32) | im[32]) > 1000000000ll;   // :619-623
     }
     uint64_t n_steps = 0, rbits = 0, ohash = 0;
-    uint32_t idle = 0;
+    uint32_t idle = 0, aiter = 0;
     // a ring deck on its way into LDS (requested when the answer of a step that reset the env is seen, stored at the end of the iteration,
     // behind the copy-out: the round trip runs beside it): per slice
     E3T_DECL();
@@ -184,6 +206,26 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
       for (int s = 0; s < KS; s++) busy = busy || ((wave * KS + s) * BG_BLOCK + lane < n_live && (t[s] < T || waiting[s]));
       if (__ballot(busy) == 0ull) break;
       E3T_CNT(4, 1);
+      if constexpr (ACT) {
+        if ((aiter++ & (BG_E3_ACTB - 1u)) == 0u) {
+#pragma unroll
+          for (int s = 0; s < KS; s++) {
+            const int l = (wave * KS + s) * BG_BLOCK + lane;
+            // the next step that needs its action: t, or t + 1 when step t is with a service wave.  Row T of the caller's tensor and the envs past N
+            // of the last workgroup do not exist.
+            const uint32_t nt = t[s] + (waiting[s] ? 1u : 0u);
+            abase[s] = nt;
+            int av[BG_E3_ACTB];
+#pragma unroll
+            for (int j = 0; j < BG_E3_ACTB; j++) {
+              av[j] = 0;
+              if (l < n_live && nt + (uint32_t)j < T) av[j] = a.actions_in[(size_t)(nt + (uint32_t)j) * N + (size_t)(env0 + l)];
+            }
+#pragma unroll
+            for (int j = 0; j < BG_E3_ACTB; j++) s_actb[j][l] = av[j];
+          }
+        }
+      }
       uint32_t nb = 0;   // records finished in this iteration (all slices): the copy-out list
       bool glast = false; // ... one of them is a last-step record of a launch whose current records are gathered (a.gworld)
 #pragma unroll
@@ -205,7 +247,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
             ndp[s] = true;
           }
           rc3[s] = s_c34[0][l]; rc4[s] = s_c34[1][l]; rmask[s] = s_mask[l];
-          terminal[s] = bg_b(rc3[s].x, 0) > 100u || (int64_t)(((uint64_t)img32[33] << 32) | img32[32]) > 1000000000ll;
+          terminal[s] = bg_b(rc3[s].x, 0) > (ACT ? athr[s] : 100u) || (int64_t)(((uint64_t)img32[33] << 32) | img32[32]) > 1000000000ll;
         }
         // ---- the cheap step of every ready env (bg_engine.h: cheap_step)
         else if (live && !waiting[s] && t[s] < T) {
@@ -213,7 +255,8 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           const uint4 c3 = rc3[s];
           const uint32_t phase = bg_b(c3.x, 2), discards_left = bg_b(c3.y, 0), nsel0 = bg_b(c3.y, 3);
           int action;
-          {
+          if constexpr (ACT) action = s_actb[(t[s] - abase[s]) & (BG_E3_ACTB - 1u)][l];   // (t - abase < BG_E3_ACTB: at most one step per iteration)
+          else {
             Env pe; pe.phase = (int)phase; // the policy only looks at the phase and the mask
             PolicyLane pl; pl.seed_env = 0; pl.blind = pblind[s];   // (bg_policy_action_fast reads the blind and x0 only)
             action = bg_policy_action_fast(pe, mask, a.policy, pl, px[s], (lds_JTables*)&jt);
@@ -254,6 +297,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           else {
             // a request: chunks 3 / 4 and the mask to LDS, then one queue word (the service waves poll the tails)
             s_c34[0][l] = rc3[s]; s_c34[1][l] = rc4[s]; s_mask[l] = mask;
+            if constexpr (ACT) img32[43] = (uint32_t)action;   // the whole int32, for the service wave (BG_ROW_ACTION: it writes the same value back)
             const int q = (!term && phase == 0u && action == 0) ? 0 : 1;
             const uint32_t slot = __hip_atomic_fetch_add(&s_ctl[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
             bg_lds_st(&s_q[q][slot & (NE - 1)], (uint32_t)l | (((slot >> LNE) & 0xffu) << 8) | (((uint32_t)action & 0x7fffu) << 16) | BG_ITEM_VALID);
@@ -273,7 +317,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           n_steps++;
           rbits ^= rb * (2 * (uint64_t)(a.t0 + t[s]) + 1);
           t[s]++;
-          px[s] += BG_POLICY_PSI;
+          if constexpr (!ACT) px[s] += BG_POLICY_PSI;
           if (a.obs_stride_steps) prow[s] += N;
         }
         const unsigned long long fms = __ballot(fin);
@@ -445,7 +489,8 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
         if ((item & (BG_ITEM_VALID | 0xff00u)) != want) atomicOr(d.err, BG_DEVERR_SPIN);
         else {
           const int l = (int)(item & 0xffu), env = env0 + l;
-          const int action = (int)((item >> 16) & 0x7fffu);
+          // (ACT: the caller's int32 as the owner left it in the image, in front of the queue word)
+          const int action = ACT ? (int)((const lds_u32*)&s_img[l][0])[43] : (int)((item >> 16) & 0x7fffu);
           uint64_t mask = s_mask[l];
           BG_PROBE_BEGIN();
           uint4 c[BG_NHOT];

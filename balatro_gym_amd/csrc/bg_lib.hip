@@ -1257,7 +1257,8 @@ static int bg_engine_waves(int T) {
 static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0, bool hash, bool info, hipStream_t st, hipEvent_t ev_a = nullptr, hipEvent_t ev_b = nullptr) {
   const bool cards = h->dev.cstate != nullptr;
   EngineArgs a = a0;
-  if (h->engine == 3 && a.obs.rows && !info && !a.actions_in && !a.reward && !a.term && !a.actions_out) { // packed-record rollouts: owner waves + service waves (bg_engine3.h)
+  // packed-record rollouts, with the policy's actions or the caller's (bg_step_many_rows): owner waves + service waves (bg_engine3.h)
+  if (h->engine == 3 && a.obs.rows && !info && !a.reward && !a.term && !a.actions_out) {
     // batch thresholds of the service waves: never by threshold and no waiting -- a free service wave takes the FULLER of the two queues at once
     // (measured at 372 steps: thresholds 32 / 48 / 64 with waits of 3 - 20 us all lose 1 - 8 %, and serving plays as soon as one is queued --
     // batches of a few lanes -- loses a third: profiles/r04_engine3/thresholds_ab.txt)
@@ -1276,13 +1277,15 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
       if (!h->e3_epw) { while (epw > 16 && (h->dev.N + epw - 1) / epw < 256) epw >>= 1; }
       a.epw = (uint32_t)epw;
     }
-#define BG_E3K(HV, CV, NOWV, KSV, NSVV) do { \
+#define BG_E3K(HV, CV, NOWV, KSV, NSVV, AV) do { \
       const dim3 g_((NOWV * KSV == 1) ? (h->dev.N + epw - 1) / epw : (h->dev.N + NOWV * KSV * 64 - 1) / (NOWV * KSV * 64)), b_((NOWV + NSVV) * BG_BLOCK); \
-      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
-      else hipLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV>), g_, b_, 0, st, dv, a); } while (0)
+      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
+      else hipLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV>), g_, b_, 0, st, dv, a); } while (0)
+    // (the caller's actions: bg_step_many_rows asks for no observation hash, so the action mode has no HASH variant)
 #define BG_E3(NOWV, KSV, NSVV) do { \
-      if (hash && cards) BG_E3K(true, true, NOWV, KSV, NSVV); else if (hash) BG_E3K(true, false, NOWV, KSV, NSVV); \
-      else if (cards) BG_E3K(false, true, NOWV, KSV, NSVV); else BG_E3K(false, false, NOWV, KSV, NSVV); } while (0)
+      if (a.actions_in) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true); } \
+      else if (hash && cards) BG_E3K(true, true, NOWV, KSV, NSVV, false); else if (hash) BG_E3K(true, false, NOWV, KSV, NSVV, false); \
+      else if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, false); else BG_E3K(false, false, NOWV, KSV, NSVV, false); } while (0)
     switch (cfg) {   // (other shapes were measured and dropped: profiles/r04_engine3/wave_split_ab.txt, small_jobs.txt, profiles/r05/scheduling_ab.txt)
       case 113: BG_E3(1, 1, 3); break;
       case 213: BG_E3(2, 1, 3); break;
@@ -1429,7 +1432,7 @@ int bg_observe(bg_handle* h, const bg_obs_ptrs* obs, void* stream) {
 static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed, uint64_t env_index0, uint64_t t0,
                            const bg_obs_ptrs* obs, uint8_t* rows_dev, size_t row_stride, int obs_stride_steps,
                            double* reward_dev, uint8_t* terminated_dev, int32_t* actions_out_dev,
-                           bg_rollout_stats* stats_dev, void* stream) {
+                           bg_rollout_stats* stats_dev, void* stream, const int32_t* actions_in_dev = nullptr, bool autoreset = true) {
   int rc = bg_require_seeded(h);
   if (rc) return rc;
   BG_GUARD(h);
@@ -1516,7 +1519,8 @@ static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed
       memset(&ea, 0, sizeof(ea));
       ea.T = chunk; ea.policy = pol; ea.policy_seed = policy_seed; ea.env_index0 = env_index0; ea.t0 = tt;
       ea.obs = o; ea.obs_stride_steps = obs_stride_steps; ea.reward = rw; ea.term = tm; ea.actions_out = ac; ea.stats = stats_dev;
-      bg_engine_queues(h, ea); ea.autoreset = 1;
+      bg_engine_queues(h, ea); ea.autoreset = autoreset ? 1u : 0u;
+      if (actions_in_dev) ea.actions_in = actions_in_dev + (size_t)done * (size_t)h->dev.N;   // (bg_step_many_rows: [T, N], whatever the rows' stride)
       if (h->gworld > 0 && rows_dev && h->engine == 3 && done + chunk == T) { // the call's LAST launch: its last step is every env's current record
         ea.gpeer = h->d_gpeer;
         ea.gworld = (uint32_t)h->gworld; ea.grank = (uint32_t)h->grank;
@@ -1604,6 +1608,18 @@ int bg_rollout_rows(bg_handle* h, int T, int policy, uint64_t policy_seed, uint6
   }
   return bg_rollout_impl(h, T, policy, policy_seed, env_index0, t0, nullptr, rows_dev, (size_t)row_stride_bytes,
                          rows_stride_steps, nullptr, nullptr, nullptr, stats_dev, stream);
+}
+
+int bg_step_many_rows(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                      int rows_stride_steps, bg_rollout_stats* stats_dev, void* stream) {
+  if (!h) return BG_E_ARG;
+  if (!actions_dev || K <= 0) { h->err = "bg_step_many_rows: actions_dev must be a device pointer to [K, N] int32 actions, K > 0"; return BG_E_ARG; }
+  if ((uint64_t)h->dev.N * (uint64_t)bg_max_fused_steps(h) > 0xffffffffull) { h->err = "bg_step_many_rows: more than 2**32 records per launch (envs x fused steps)"; return BG_E_ARG; }
+  if (const char* m = bg_rows_args(rows_dev, row_stride_bytes)) { h->err = std::string("bg_step_many_rows: ") + m; return BG_E_ARG; }
+  // bg_rollout_rows' host path (lazy overlapped refill in pieces, chunks of bg_max_fused_steps, profiling events, gather of the last step) with the
+  // caller's actions and the handle's auto-reset flag.  BG_ENGINE=1: bg_engine.h reads actions_in and writes records through its copier wave.
+  return bg_rollout_impl(h, K, 0, 0, 0, 0, nullptr, rows_dev, (size_t)row_stride_bytes, rows_stride_steps, nullptr, nullptr, nullptr, stats_dev,
+                         stream, actions_dev, (h->dev.flags & BG_FLAG_AUTORESET) != 0);
 }
 
 __global__ __launch_bounds__(BG_BLOCK) void bg_inject_cards_kernel(BgDev d, const uint16_t* __restrict__ cs, const uint8_t* __restrict__ mask_in, int apply_now) {

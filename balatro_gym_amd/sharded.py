@@ -125,6 +125,11 @@ class ShardedBalatroVecEnv:
     def step(self, actions_local: torch.Tensor):
         return self.local.step(actions_local)
 
+    def step_many(self, actions_local: torch.Tensor, **kw):
+        """K steps of this rank's shard with the caller's actions ([K, n_local]).  With a `RowBuffers` (bg_step_many_rows) and
+        `enable_peer_gather()`, the last step's records land in `peer_records` exactly as after `rollout`."""
+        return self.local.step_many(actions_local, **kw)
+
     def rollout(self, steps: int, **kw):
         kw.setdefault("env_index0", self.lo)
         return self.local.rollout(steps, **kw)

@@ -69,7 +69,7 @@ class ObsBuffers:
 
 
 class RowBuffers:
-    """[steps, N] packed records for `BalatroVecEnv.rollout` (bg_rollout_rows): one 352-byte record per (step, env),
+    """[steps, N] packed records for `BalatroVecEnv.rollout` (bg_rollout_rows) and `step_many` (bg_step_many_rows): one 352-byte record per (step, env),
     every observation key -- plus the step's reward / action / terminated -- a strided, correctly typed VIEW of the
     same byte tensor (`tensors[key]`, `reward`, `action`, `terminated`); `.contiguous()` gives the dense per-key array.
     """
@@ -283,12 +283,35 @@ class BalatroVecEnv:
         given; the returned truncated and info are None, and so is reward / terminated when no tensor was given for it: this call
         writes none of them (a per-step output never goes into the live [N] tensors; bg_step_many with per-step info buffers gives
         the info).  Otherwise the live tensors hold the last call's observation / reward / terminated / truncated / info, and
-        reward / terminated must not be given."""
+        reward / terminated must not be given.
+
+        A `RowBuffers` selects the packed-record engine (bg_step_many_rows: the rollout's kernel with the caller's actions, several times
+        the rate of the per-key path): every step's record is kept when it has at least K rows, a one-row `RowBuffers` holds the last
+        step's.  Returns (rb.tensors, rb.reward, rb.terminated, None, None) -- views of the records; `rb.action` holds the actions as
+        given.  This path produces no per-step truncated / info; reward / terminated tensors are refused (the records carry them)."""
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if actions.dim() != 2 or actions.shape[1] != self.num_envs:
             raise ValueError(f"actions must be [K, {self.num_envs}]")
         K = int(actions.shape[0])
+        if isinstance(obs_buffers, RowBuffers):
+            if K < 1:
+                raise ValueError(f"actions must be [K, {self.num_envs}] with K >= 1")
+            if obs_buffers.steps < K and obs_buffers.steps > 1:
+                raise ValueError("obs_buffers has fewer rows than steps")
+            if reward is not None or terminated is not None:
+                raise ValueError("packed records already carry reward / action / terminated")
+            if obs_buffers.n != self.num_envs or obs_buffers.rows.device != self.device:
+                raise ValueError(f"obs_buffers must hold records of {self.num_envs} envs on {self.device}")
+            self._stats.zero_()
+            rc = self._L.bg_step_many_rows(
+                self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
+                1 if obs_buffers.steps > 1 else 0, C.c_void_p(self._stats.data_ptr()), self._stream())
+            if rc != 0:
+                self._check(rc, "bg_step_many_rows")
+            if self._rowbuf is not None:
+                self.observe()   # (obs_layout "rows": the live records follow)
+            return obs_buffers.tensors, obs_buffers.reward, obs_buffers.terminated, None, None
         keep = obs_buffers is not None and obs_buffers.steps > 1
         if keep and obs_buffers.steps < K:
             raise ValueError("obs_buffers has fewer rows than steps")

@@ -263,6 +263,20 @@ int bg_rollout_rows(bg_handle* h, int T, int policy, uint64_t policy_seed, uint6
                     uint8_t* rows_dev, uint64_t row_stride_bytes, int rows_stride_steps, bg_rollout_stats* stats_dev,
                     void* stream);
 
+/* K consecutive step() calls per env with the CALLER's actions, on the packed-record engine of bg_rollout_rows (bg_engine3.h: owner waves +
+ * service waves per workgroup): what bg_step_many does, at the rollout's rate, for callers whose actions come from a network.
+ * Replaces: K calls of `BalatroEnv.step(action)` per env (balatro_env_2.py:616-637), every call's observation, reward and terminated kept.
+ * actions_dev: int32 [K, N] on the device (row t * N + env), any int32 value (out of range = invalid action: reward -1.0, state unchanged).
+ * rows_dev / row_stride_bytes: as bg_rollout_rows (16-byte aligned, stride a multiple of 16, >= BG_ROW_BYTES; 384 = whole lines).
+ * rows_stride_steps != 0: record of step t of env e at row t * N + e ([K, N] records); 0: row e, overwritten every step.
+ * The record is bg_rollout_rows': the 31 observation keys at the BG_ROW_* offsets plus the step's reward (f64), action (i32: the caller's value as
+ * given) and terminated byte.  There are NO per-step truncated / info arrays on this path: callers who need them keep bg_step_many.
+ * stats_dev: optional, as bg_rollout_rows (t0 = 0 at the call's first step).
+ * Auto-reset follows the HANDLE's BG_FLAG_AUTORESET (as bg_step / bg_step_many do), not "always on" as the rollouts.  With bg_set_gather_peers the
+ * call's last step lands in the gather buffers as after bg_rollout_rows.  BG_ENGINE=1 handles run it on bg_engine.h: same records. */
+int bg_step_many_rows(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                      int rows_stride_steps, bg_rollout_stats* stats_dev, void* stream);
+
 /* Sharded jobs (one process per GPU): the exchange of the design -- every rank sees the CURRENT record of every env -- without a collective
  * behind the launch.  bufs[r] is rank r's gather buffer, uint8 [world][N][BG_ROW_BYTES], as mapped into THIS process (own buffer: an ordinary device
  * pointer; peers': hipIpcOpenMemHandle / torch's CUDA IPC over xGMI); N = this handle's env count, the same on every rank.  From then on the LAST launch
