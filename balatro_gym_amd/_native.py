@@ -56,13 +56,45 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_step", "bg_observe", "bg_rollout", "bg_rollout_rows", "bg_inject", "bg_inject_cards", "bg_inject_consumables", "bg_state_blob_bytes", "bg_get_state", "bg_set_state",
            "bg_refill", "bg_check", "bg_set_profiling", "bg_get_profile", "bg_set_max_ante", "bg_inject_deck",
            "bg_classify_batch", "bg_score_hand_batch", "bg_classify_batch_ex", "bg_score_hand_batch_ex", "bg_bench_copy", "bg_bench_fill", "bg_step_many",
-           "bg_sim_evaluate_batch", "bg_sim_score_batch", "bg_create_ex", "bg_step_rows", "bg_observe_rows", "bg_step_many_rows"]
+           "bg_sim_evaluate_batch", "bg_sim_score_batch", "bg_create_ex", "bg_step_rows", "bg_observe_rows", "bg_step_many_rows",
+           "bg_encode_cols", "bg_encode_rows"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
 SHOP_SLOT_WORDS, SHOP_SLOT_SEED_WORD = 64, 62
 SCORE_CASE_WORDS, SCORE_OUT_WORDS = 40, 8
 SIM_EVAL_BYTES, SIM_CASE_WORDS = 128, 64
+
+# bg_encode_rows (include/balatro_mi355x.h BG_ENC_*; the column tables live in csrc/bg_encode.h, tests/test_encode_rows_host.py holds this copy to them)
+ENC_PRODUCED, ENC_FIXED, ENC_EXTRACTOR = 0, 1, 2
+ENC_F32, ENC_BF16 = 0, 1
+ENC_LAYOUTS = {"produced": ENC_PRODUCED, "fixed": ENC_FIXED, "extractor": ENC_EXTRACTOR}
+# the keys BalatroEnvFixed zero-fills (train_balatro_fixed.py:125-207), in the order of its observation space, with their element counts
+ENC_ZERO_KEYS = [("hand_one_hot", 416), ("hand_suits", 8), ("hand_ranks", 8), ("rank_counts", 13), ("suit_counts", 4), ("straight_potential", 1),
+                 ("flush_potential", 1), ("avg_score_per_hand", 1), ("hands_until_shop", 1), ("rounds_until_boss", 1), ("has_mult_jokers", 1),
+                 ("has_chip_jokers", 1), ("has_xmult_jokers", 1), ("has_economy_jokers", 1), ("hand_potential_scores", 12), ("joker_synergy_score", 1),
+                 ("risk_level", 1), ("economy_health", 1), ("blind_difficulty", 1), ("win_probability", 1)]
+# BalatroFeaturesExtractor.forward (train_balatro_agent.py:84-119): (name, source key, elements, divisor or None)
+ENC_EXTRACTOR_PARTS = [("hand_one_hot", "hand", 416, None), ("joker_ids", "joker_ids", 10, None), ("chips_scored", "chips_scored", 1, 1e6),
+                       ("chips_needed", "chips_needed", 1, 1e5), ("progress_ratio", "progress_ratio", 1, None), ("money", "money", 1, 100.0),
+                       ("ante", "ante", 1, 10.0), ("round", "round", 1, 3.0), ("hands_left", "hands_left", 1, 10.0),
+                       ("discards_left", "discards_left", 1, 5.0), ("hand_levels", "hand_levels", 12, 10.0), ("phase", "phase", 1, 3.0)]
+
+
+def _enc_columns():
+    def run(parts):
+        out, c = [], 0
+        for name, n in parts:
+            out.append((name, c, n))
+            c += n
+        return out
+    produced = [(k, 1 if OBS_SPEC[k][1] == () else OBS_SPEC[k][1][0]) for k in OBS_KEYS]
+    return {ENC_PRODUCED: run(produced), ENC_FIXED: run(produced + ENC_ZERO_KEYS), ENC_EXTRACTOR: run([(p[0], p[2]) for p in ENC_EXTRACTOR_PARTS])}
+
+
+# layout -> [(name, first column, columns)]: e.g. the 60 action_mask columns of a PRODUCED / FIXED matrix
+ENC_COLUMNS = _enc_columns()
+ENC_COLS = {layout: cols[-1][1] + cols[-1][2] for layout, cols in ENC_COLUMNS.items()}   # what bg_encode_cols returns
 
 
 class ObsPtrs(C.Structure):
@@ -197,5 +229,7 @@ def load(build_if_missing: bool = True):
     L.bg_sim_score_batch.argtypes = [vp, vp, i32, vp]
     L.bg_bench_copy.argtypes = [vp, vp, u64, i32, C.POINTER(C.c_double), vp]
     L.bg_bench_fill.argtypes = [vp, u64, i32, C.POINTER(C.c_double), vp]
+    L.bg_encode_cols.argtypes = [i32]
+    L.bg_encode_rows.argtypes = [vp, u64, i64, i32, i32, vp, u64, C.POINTER(C.c_float), vp]
     _lib = L
     return L

@@ -1,0 +1,326 @@
+// bg_encode.h -- bg_encode_rows: packed records (BG_ROW_*) -> the float matrix a policy network reads.
+//
+// Three layouts, all restatements of what the reference feeds its networks (include/balatro_mi355x.h has the citations):
+//   BG_ENC_PRODUCED  the 31 keys the env fills, in the reference's key order, every element as float        153 columns
+//   BG_ENC_FIXED     PRODUCED + the 20 declared-but-never-filled keys of BalatroEnvFixed as zeros           628 columns
+//   BG_ENC_EXTRACTOR what BalatroFeaturesExtractor.forward builds: hand one-hot, joker ids, 21 state features 447 columns
+//
+// ONE column table per layout, built at compile time from the X-macro lists below (key, record offset, source type, count [, divisor]):
+// the kernel, bg_encode_cols, the host build of tests/test_encode_rows_host.py and -- through that test -- _native.ENC_COLUMNS all
+// read these lists and nothing else.  The per-element conversion and the bf16 rounding are plain C++ behind BG_ENC_FN, so the text the
+// GPU runs compiles with g++ (define BG_ENC_HOST before including; the pattern of tests/test_seed_slot_host.py).
+#ifndef BG_ENCODE_H
+#define BG_ENCODE_H
+#include <stdint.h>
+
+#ifdef BG_ENC_HOST
+#define BG_ENC_FN static inline
+#define BG_ENC_TABLE static constexpr
+#else
+#define BG_ENC_FN __host__ __device__ __forceinline__
+#define BG_ENC_TABLE static __device__ constexpr
+#endif
+
+// source types of a record field
+#define BG_ENC_SRC_I8 0
+#define BG_ENC_SRC_I16 1
+#define BG_ENC_SRC_I32 2
+#define BG_ENC_SRC_I64 3
+#define BG_ENC_SRC_F32 4 /* copied bit for bit */
+// per-column rule
+#define BG_ENC_OP_NONE 0
+#define BG_ENC_OP_DIV 1    /* float32(value) / float32(divisor): an IEEE division, as numpy / torch-CPU compute `x.float() / c` */
+#define BG_ENC_OP_ONEHOT 2 /* 1.0 where the int8 field equals the column's card (a card is >= 0, so the -1 padding never matches) */
+#define BG_ENC_OP_ZERO 3   /* a never-produced key of the fixed space */
+
+// X(key, record offset, source type, elements): the keys `_get_observation()` fills, in the order of the reference's observation space
+// (balatro_env_2.py:388-468; _native.OBS_KEYS; tests/golden/sb3_fixed.npz `keys`[:31])
+#define BG_ENC_PRODUCED_KEYS(X)                                   \
+  X(hand, BG_ROW_HAND, BG_ENC_SRC_I8, 8)                              \
+  X(hand_size, BG_ROW_HAND_SIZE, BG_ENC_SRC_I8, 1)                    \
+  X(deck_size, BG_ROW_DECK_SIZE, BG_ENC_SRC_I8, 1)                    \
+  X(selected_cards, BG_ROW_SELECTED_CARDS, BG_ENC_SRC_I64, 8)         \
+  X(chips_scored, BG_ROW_CHIPS_SCORED, BG_ENC_SRC_I64, 1)             \
+  X(round_chips_scored, BG_ROW_ROUND_CHIPS_SCORED, BG_ENC_SRC_I32, 1) \
+  X(progress_ratio, BG_ROW_PROGRESS_RATIO, BG_ENC_SRC_F32, 1)         \
+  X(mult, BG_ROW_MULT, BG_ENC_SRC_I32, 1)                             \
+  X(chips_needed, BG_ROW_CHIPS_NEEDED, BG_ENC_SRC_I32, 1)             \
+  X(money, BG_ROW_MONEY, BG_ENC_SRC_I32, 1)                           \
+  X(ante, BG_ROW_ANTE, BG_ENC_SRC_I16, 1)                             \
+  X(round, BG_ROW_ROUND, BG_ENC_SRC_I8, 1)                            \
+  X(hands_left, BG_ROW_HANDS_LEFT, BG_ENC_SRC_I8, 1)                  \
+  X(discards_left, BG_ROW_DISCARDS_LEFT, BG_ENC_SRC_I8, 1)            \
+  X(joker_count, BG_ROW_JOKER_COUNT, BG_ENC_SRC_I8, 1)                \
+  X(joker_ids, BG_ROW_JOKER_IDS, BG_ENC_SRC_I16, 10)                  \
+  X(joker_slots, BG_ROW_JOKER_SLOTS, BG_ENC_SRC_I8, 1)                \
+  X(consumable_count, BG_ROW_CONSUMABLE_COUNT, BG_ENC_SRC_I8, 1)      \
+  X(consumables, BG_ROW_CONSUMABLES, BG_ENC_SRC_I16, 5)               \
+  X(consumable_slots, BG_ROW_CONSUMABLE_SLOTS, BG_ENC_SRC_I8, 1)      \
+  X(shop_items, BG_ROW_SHOP_ITEMS, BG_ENC_SRC_I16, 10)                \
+  X(shop_costs, BG_ROW_SHOP_COSTS, BG_ENC_SRC_I16, 10)                \
+  X(shop_rerolls, BG_ROW_SHOP_REROLLS, BG_ENC_SRC_I16, 1)             \
+  X(hand_levels, BG_ROW_HAND_LEVELS, BG_ENC_SRC_I8, 12)               \
+  X(phase, BG_ROW_PHASE, BG_ENC_SRC_I8, 1)                            \
+  X(action_mask, BG_ROW_ACTION_MASK, BG_ENC_SRC_I8, 60)               \
+  X(hands_played, BG_ROW_HANDS_PLAYED, BG_ENC_SRC_I32, 1)             \
+  X(best_hand_this_ante, BG_ROW_BEST_HAND_THIS_ANTE, BG_ENC_SRC_I32, 1) \
+  X(boss_blind_active, BG_ROW_BOSS_BLIND_ACTIVE, BG_ENC_SRC_I8, 1)    \
+  X(boss_blind_type, BG_ROW_BOSS_BLIND_TYPE, BG_ENC_SRC_I8, 1)        \
+  X(face_down_cards, BG_ROW_FACE_DOWN_CARDS, BG_ENC_SRC_I64, 8)
+// X(key, elements): the keys the env declares (balatro_env_2.py:386-470) and never fills; BalatroEnvFixed zero-fills them
+// (train_balatro_fixed.py:125-207), in the order of the fixed space (sb3_fixed.npz `keys`[31:])
+#define BG_ENC_ZERO_KEYS(X)      \
+  X(hand_one_hot, 416)           \
+  X(hand_suits, 8)               \
+  X(hand_ranks, 8)               \
+  X(rank_counts, 13)             \
+  X(suit_counts, 4)              \
+  X(straight_potential, 1)       \
+  X(flush_potential, 1)          \
+  X(avg_score_per_hand, 1)       \
+  X(hands_until_shop, 1)         \
+  X(rounds_until_boss, 1)        \
+  X(has_mult_jokers, 1)          \
+  X(has_chip_jokers, 1)          \
+  X(has_xmult_jokers, 1)         \
+  X(has_economy_jokers, 1)       \
+  X(hand_potential_scores, 12)   \
+  X(joker_synergy_score, 1)      \
+  X(risk_level, 1)               \
+  X(economy_health, 1)           \
+  X(blind_difficulty, 1)         \
+  X(win_probability, 1)
+// X(key, record offset, source type, elements, divisor index | -1): `game_features` of BalatroFeaturesExtractor.forward
+// (train_balatro_agent.py:102-113), behind the hand one-hot (:86-93) and `joker_ids.float()` (:98)
+#define BG_ENC_EXTRACTOR_STATE(X)                        \
+  X(chips_scored, BG_ROW_CHIPS_SCORED, BG_ENC_SRC_I64, 1, 0) \
+  X(chips_needed, BG_ROW_CHIPS_NEEDED, BG_ENC_SRC_I32, 1, 1) \
+  X(progress_ratio, BG_ROW_PROGRESS_RATIO, BG_ENC_SRC_F32, 1, -1) \
+  X(money, BG_ROW_MONEY, BG_ENC_SRC_I32, 1, 2)               \
+  X(ante, BG_ROW_ANTE, BG_ENC_SRC_I16, 1, 3)                 \
+  X(round, BG_ROW_ROUND, BG_ENC_SRC_I8, 1, 4)                \
+  X(hands_left, BG_ROW_HANDS_LEFT, BG_ENC_SRC_I8, 1, 3)      \
+  X(discards_left, BG_ROW_DISCARDS_LEFT, BG_ENC_SRC_I8, 1, 5) \
+  X(hand_levels, BG_ROW_HAND_LEVELS, BG_ENC_SRC_I8, 12, 3)   \
+  X(phase, BG_ROW_PHASE, BG_ENC_SRC_I8, 1, 4)
+
+#define BG_ENC_COUNT4(k, o, t, n) +(n)
+#define BG_ENC_COUNT2(k, n) +(n)
+#define BG_ENC_COUNT5(k, o, t, n, d) +(n)
+#define BG_ENC_PRODUCED_COLS (0 BG_ENC_PRODUCED_KEYS(BG_ENC_COUNT4))
+#define BG_ENC_FIXED_COLS (BG_ENC_PRODUCED_COLS BG_ENC_ZERO_KEYS(BG_ENC_COUNT2))
+#define BG_ENC_ONEHOT_COLS (8 * 52)
+#define BG_ENC_ONEHOT_SLOT(c) ((c) / 52) /* one-hot column c = slot * 52 + card */
+#define BG_ENC_ONEHOT_CARD(c) ((c) % 52)
+#define BG_ENC_JOKER_COLS 10
+#define BG_ENC_EXTRACTOR_COLS (BG_ENC_ONEHOT_COLS + BG_ENC_JOKER_COLS BG_ENC_EXTRACTOR_STATE(BG_ENC_COUNT5))
+#define BG_ENC_MAX_COLS BG_ENC_FIXED_COLS
+static_assert(BG_ENC_PRODUCED_COLS == 153 && BG_ENC_FIXED_COLS == 628 && BG_ENC_EXTRACTOR_COLS == 447, "layout widths of include/balatro_mi355x.h");
+
+constexpr int bg_enc_cols(int layout) {
+  return layout == BG_ENC_PRODUCED ? BG_ENC_PRODUCED_COLS : layout == BG_ENC_FIXED ? BG_ENC_FIXED_COLS : layout == BG_ENC_EXTRACTOR ? BG_ENC_EXTRACTOR_COLS : -1;
+}
+
+// A column: bits 0..8 byte offset of the element in the record, 9..11 source type, 12..13 rule, 14..19 the one-hot card / the divisor index
+constexpr uint32_t bg_enc_desc(uint32_t off, uint32_t type, uint32_t op, uint32_t par) { return off | type << 9 | op << 12 | par << 14; }
+#define BG_ENC_OFF(d) ((d) & 0x1ffu)
+#define BG_ENC_TYPE(d) (((d) >> 9) & 7u)
+#define BG_ENC_OP(d) (((d) >> 12) & 3u)
+#define BG_ENC_PAR(d) (((d) >> 14) & 0x3fu)
+constexpr uint32_t bg_enc_type_bytes(uint32_t t) { return t == BG_ENC_SRC_I8 ? 1u : t == BG_ENC_SRC_I16 ? 2u : t == BG_ENC_SRC_I64 ? 8u : 4u; }
+
+template <int LAYOUT>
+struct BgEncTable {
+  uint32_t d[BG_ENC_MAX_COLS] = {};
+  constexpr BgEncTable() {
+    int c = 0;
+    if (LAYOUT == BG_ENC_EXTRACTOR) {
+      for (; c < BG_ENC_ONEHOT_COLS; c++) d[c] = bg_enc_desc(BG_ROW_HAND + BG_ENC_ONEHOT_SLOT(c), BG_ENC_SRC_I8, BG_ENC_OP_ONEHOT, BG_ENC_ONEHOT_CARD(c));
+      for (int j = 0; j < BG_ENC_JOKER_COLS; j++) d[c++] = bg_enc_desc(BG_ROW_JOKER_IDS + 2 * j, BG_ENC_SRC_I16, BG_ENC_OP_NONE, 0);
+#define BG_ENC_X(k, o, t, n, dv) \
+  for (int i = 0; i < (n); i++) d[c++] = bg_enc_desc((o) + i * bg_enc_type_bytes(t), t, (dv) >= 0 ? BG_ENC_OP_DIV : BG_ENC_OP_NONE, (dv) >= 0 ? (dv) : 0);
+      BG_ENC_EXTRACTOR_STATE(BG_ENC_X)
+#undef BG_ENC_X
+    } else {
+#define BG_ENC_X(k, o, t, n) \
+  for (int i = 0; i < (n); i++) d[c++] = bg_enc_desc((o) + i * bg_enc_type_bytes(t), t, BG_ENC_OP_NONE, 0);
+      BG_ENC_PRODUCED_KEYS(BG_ENC_X)
+#undef BG_ENC_X
+      if (LAYOUT == BG_ENC_FIXED)
+        while (c < BG_ENC_FIXED_COLS) d[c++] = bg_enc_desc(0, BG_ENC_SRC_F32, BG_ENC_OP_ZERO, 0);
+    }
+  }
+};
+template <int LAYOUT>
+struct BgEncTab { BG_ENC_TABLE BgEncTable<LAYOUT> t{}; };
+
+// an aligned 32-bit word of a record (records are 16-byte aligned in HBM, in LDS and in the host build's buffers)
+BG_ENC_FN uint32_t bg_enc_word(const uint8_t* rec, uint32_t off) {
+  uint32_t w;
+  __builtin_memcpy(&w, __builtin_assume_aligned(rec + off, 4), 4);
+  return w;
+}
+BG_ENC_FN uint32_t bg_enc_float_bits(float f) { uint32_t u; __builtin_memcpy(&u, &f, 4); return u; }
+BG_ENC_FN uint32_t bg_enc_onehot(int32_t hand_value, int32_t card) { return hand_value == card ? 0x3f800000u : 0u; }   // float32 bits of 1.0 / 0.0
+BG_ENC_FN float bg_enc_divisor(uint32_t i) {
+  return i == 0 ? 1e6f : i == 1 ? 1e5f : i == 2 ? 100.f : i == 3 ? 10.f : i == 4 ? 3.f : 5.f;
+}
+
+// The float32 BIT PATTERN of one column of one record: numpy.float32(value) (round to nearest even from int32 / int64), a float field
+// bit for bit, then the column's rule.
+template <int LAYOUT>
+BG_ENC_FN uint32_t bg_enc_element(const uint8_t* rec, uint32_t d) {
+  const uint32_t off = BG_ENC_OFF(d), type = BG_ENC_TYPE(d), op = BG_ENC_OP(d);
+  if (LAYOUT == BG_ENC_FIXED && op == BG_ENC_OP_ZERO) return 0u;
+  const uint32_t lo = bg_enc_word(rec, off & ~3u);
+  if (type == BG_ENC_SRC_F32) return lo;
+  float f;
+  if (type == BG_ENC_SRC_I64) {
+    const uint32_t hi = bg_enc_word(rec, off + 4u);
+    f = (float)(int64_t)((uint64_t)hi << 32 | lo);
+  } else {
+    const uint32_t v = lo >> ((off & 3u) * 8u);
+    const int32_t s = type == BG_ENC_SRC_I8 ? (int32_t)(int8_t)v : type == BG_ENC_SRC_I16 ? (int32_t)(int16_t)v : (int32_t)v;
+    if (LAYOUT == BG_ENC_EXTRACTOR && op == BG_ENC_OP_ONEHOT) return bg_enc_onehot(s, (int32_t)BG_ENC_PAR(d));
+    f = (float)s;
+  }
+  if (LAYOUT == BG_ENC_EXTRACTOR && op == BG_ENC_OP_DIV) f = f / bg_enc_divisor(BG_ENC_PAR(d));
+  return bg_enc_float_bits(f);
+}
+
+// float32 bits -> bfloat16 bits, round to nearest even; a NaN becomes the canonical quiet NaN (what torch's float -> bfloat16 gives)
+BG_ENC_FN uint16_t bg_enc_bf16(uint32_t u) {
+  if ((u & 0x7fffffffu) > 0x7f800000u) return (uint16_t)0x7fc0u;
+  return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
+
+#ifndef BG_ENC_HOST
+// ---- the kernel ----
+// A workgroup of 256 lanes takes BG_ENC_RECS = 32 consecutive records, in three phases with a barrier between them:
+//   1  the records' 352 bytes are read from HBM once, 16 bytes per lane, into LDS (record pitch 356 bytes = 89 words: odd, so phase 2's lanes, one
+//      record each, read without bank conflicts);
+//   2  lane = (record, one of 8 column slices): the layout's DENSE columns -- the 153 produced ones; for EXTRACTOR the 31 behind the one-hot -- are
+//      converted with the column index a compile-time constant (the table folds away: one LDS read, a bit-field extract and a convert per column; the
+//      int64 and division sequences only where a column needs them) into a float32 tile in LDS (pitch 153 / 31 words: odd again);
+//   3  the lanes walk the output with consecutive lanes on consecutive 16-byte pieces, reading finished values from the tile:
+//        BG_ENC_ST_ROWS  out_dev and the row pitch are 16-byte aligned: a piece is 4 (f32) / 8 (bf16) columns of one row, the row's tail by element
+//        BG_ENC_ST_FLAT  rows are not 16-byte aligned but the matrix is dense (pitch == columns) and out_dev aligned: a workgroup's rows are ONE
+//                        aligned run of RECS * D elements, so pieces run across row ends (RECS * D * 2 bytes is a multiple of 16)
+//        BG_ENC_ST_ELEM  anything else: one element per lane
+//      FIXED's 475 zero columns touch neither LDS nor the table; EXTRACTOR's 416 one-hot columns are computed here from the record's hand bytes
+//      (bg_enc_onehot: a byte read and a compare per element).
+// LDS: 11 392 bytes of records + 19 584 (153-column tile) or 3 968 (EXTRACTOR) bytes: five / eight workgroups per CU.
+#define BG_ENC_BLOCK 256
+#define BG_ENC_RECS 32
+#define BG_ENC_SLICES (BG_ENC_BLOCK / BG_ENC_RECS)
+#define BG_ENC_CHUNKS (BG_ROW_BYTES / 16)
+#define BG_ENC_REC_PITCH (BG_ROW_BYTES + 4)
+#define BG_ENC_ST_ROWS 0
+#define BG_ENC_ST_FLAT 1
+#define BG_ENC_ST_ELEM 2
+static_assert(BG_ROW_BYTES % 16 == 0 && BG_ENC_RECS % 8 == 0, "records are staged in 16-byte pieces; a workgroup's dense output starts on a 16-byte boundary");
+static_assert((BG_ENC_REC_PITCH / 4) % 2 == 1 && BG_ENC_REC_PITCH % 4 == 0, "odd word pitch: lane = record reads are conflict-free");
+
+// the dense columns of a layout: [first, first + count) are staged in the tile
+constexpr int bg_enc_dense_first(int layout) { return layout == BG_ENC_EXTRACTOR ? BG_ENC_ONEHOT_COLS : 0; }
+constexpr int bg_enc_dense_cols(int layout) { return layout == BG_ENC_EXTRACTOR ? BG_ENC_EXTRACTOR_COLS - BG_ENC_ONEHOT_COLS : BG_ENC_PRODUCED_COLS; }
+
+template <int LAYOUT, int S>
+__device__ __forceinline__ void bg_enc_convert_slice(const uint8_t* rec, uint32_t* dst) {
+  constexpr int N = bg_enc_dense_cols(LAYOUT), C0 = bg_enc_dense_first(LAYOUT), CH = (N + BG_ENC_SLICES - 1) / BG_ENC_SLICES;
+#pragma unroll
+  for (int i = S * CH; i < (S + 1) * CH; i++)
+    if (i < N) dst[i] = bg_enc_element<LAYOUT>(rec, BgEncTab<LAYOUT>::t.d[C0 + i]);
+}
+
+// one finished element in phase 3 (k-th column `c` of record `r` of the workgroup)
+template <int LAYOUT>
+__device__ __forceinline__ uint32_t bg_enc_fetch(const uint8_t* recs, const uint32_t* tile, int r, int c) {
+  if (LAYOUT == BG_ENC_FIXED && c >= BG_ENC_PRODUCED_COLS) return 0u;
+  if (LAYOUT == BG_ENC_EXTRACTOR && c < BG_ENC_ONEHOT_COLS)   // the table's rule for these columns, without the table: one byte of the record's hand
+    return bg_enc_onehot((int8_t)recs[r * BG_ENC_REC_PITCH + BG_ROW_HAND + BG_ENC_ONEHOT_SLOT(c)], BG_ENC_ONEHOT_CARD(c));
+  return tile[r * bg_enc_dense_cols(LAYOUT) + c - bg_enc_dense_first(LAYOUT)];
+}
+
+template <int LAYOUT, int DT, int ST>
+__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out,
+                                                                 uint64_t pitch) {
+  __shared__ __attribute__((aligned(16))) uint32_t recs32[BG_ENC_RECS * BG_ENC_REC_PITCH / 4];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[BG_ENC_RECS * bg_enc_dense_cols(LAYOUT)];
+  const uint8_t* const recs = reinterpret_cast<const uint8_t*>(recs32);
+  constexpr int D = bg_enc_cols(LAYOUT);
+  constexpr int E = ST == BG_ENC_ST_ELEM ? 1 : DT == BG_ENC_F32 ? 4 : 8;   // elements of a 16-byte piece
+  const long long rec0 = (long long)blockIdx.x * BG_ENC_RECS;
+  const int nrec = (int)(m - rec0 < BG_ENC_RECS ? m - rec0 : BG_ENC_RECS);
+  for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
+    const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
+    const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
+    uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  }
+  __syncthreads();
+  {
+    const int r = threadIdx.x % BG_ENC_RECS;
+    if (r < nrec) {
+      const uint8_t* const rec = recs + r * BG_ENC_REC_PITCH;
+      uint32_t* const dst = tile + r * bg_enc_dense_cols(LAYOUT);
+      switch (threadIdx.x / BG_ENC_RECS) {
+        case 0: bg_enc_convert_slice<LAYOUT, 0>(rec, dst); break;
+        case 1: bg_enc_convert_slice<LAYOUT, 1>(rec, dst); break;
+        case 2: bg_enc_convert_slice<LAYOUT, 2>(rec, dst); break;
+        case 3: bg_enc_convert_slice<LAYOUT, 3>(rec, dst); break;
+        case 4: bg_enc_convert_slice<LAYOUT, 4>(rec, dst); break;
+        case 5: bg_enc_convert_slice<LAYOUT, 5>(rec, dst); break;
+        case 6: bg_enc_convert_slice<LAYOUT, 6>(rec, dst); break;
+        default: bg_enc_convert_slice<LAYOUT, 7>(rec, dst); break;
+      }
+    }
+  }
+  __syncthreads();
+  constexpr int U = (D + E - 1) / E;   // pieces of a row (BG_ENC_ST_ROWS)
+  const int nunits = ST == BG_ENC_ST_ROWS ? nrec * U : (nrec * D + E - 1) / E;
+  uint32_t* const o32 = reinterpret_cast<uint32_t*>(out);
+  uint16_t* const o16 = reinterpret_cast<uint16_t*>(out);
+  for (int u = threadIdx.x; u < nunits; u += BG_ENC_BLOCK) {
+    int r, c, nvalid;
+    size_t at;   // element index of the piece in `out`
+    if (ST == BG_ENC_ST_ROWS) { r = u / U; c = (u - r * U) * E; nvalid = D - c < E ? D - c : E; at = (size_t)(rec0 + r) * pitch + c; }
+    else if (ST == BG_ENC_ST_FLAT) { const int e0 = u * E; r = e0 / D; c = e0 - r * D; nvalid = nrec * D - e0 < E ? nrec * D - e0 : E; at = (size_t)rec0 * D + e0; }
+    else { r = u / D; c = u - r * D; nvalid = 1; at = (size_t)(rec0 + r) * pitch + c; }
+    uint32_t w[E];
+    if (LAYOUT == BG_ENC_FIXED && c >= BG_ENC_PRODUCED_COLS && c + E <= D) {
+#pragma unroll
+      for (int k = 0; k < E; k++) w[k] = 0u;
+    } else {
+#pragma unroll
+      for (int k = 0; k < E; k++) {
+        int rk = r, ck = c + k;
+        if (ST == BG_ENC_ST_FLAT && ck >= D) { ck -= D; rk++; }
+        w[k] = k < nvalid ? bg_enc_fetch<LAYOUT>(recs, tile, rk, ck) : 0u;
+      }
+    }
+    if (DT == BG_ENC_F32) {
+      if (E == 4 && nvalid == E) *reinterpret_cast<uint4*>(o32 + at) = make_uint4(w[0], w[E > 1 ? 1 : 0], w[E > 2 ? 2 : 0], w[E > 3 ? 3 : 0]);
+      else
+        for (int k = 0; k < nvalid; k++) o32[at + k] = w[k];
+    } else {
+      if (E == 8 && nvalid == E) {
+        uint32_t p[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) p[k] = (uint32_t)bg_enc_bf16(w[E > 1 ? 2 * k : 0]) | (uint32_t)bg_enc_bf16(w[E > 1 ? 2 * k + 1 : 0]) << 16;
+        *reinterpret_cast<uint4*>(o16 + at) = make_uint4(p[0], p[1], p[2], p[3]);
+      } else
+        for (int k = 0; k < nvalid; k++) o16[at + k] = bg_enc_bf16(w[k]);
+    }
+  }
+}
+
+// host side: the store path `st` is chosen from the alignment of the caller's matrix (bg_encode_rows)
+template <int LAYOUT, int DT>
+static void bg_encode_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, long long m, void* out, uint64_t pitch) {
+  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
+  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
+  else hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
+}
+#endif  // BG_ENC_HOST
+#endif

@@ -328,6 +328,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 
 #include "bg_ops.h" // operator-level batch kernels (classify / score_hand): need bg_mt_seed, bg_mt_twist
 #include "bg_sim.h" // balatro_sim.py evaluator / scorer (operator-level)
+#include "bg_encode.h" // packed records -> policy-network input (operator-level)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -2003,6 +2004,39 @@ int bg_classify_batch_ex(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t
 }
 int bg_classify_batch(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t* hand_type_dev, int64_t m, void* stream) {
   return bg_classify_batch_ex(cards_dev, n_dev, hand_type_dev, m, 1, nullptr, stream);
+}
+
+// packed records -> network input (bg_encode.h).  The store path follows the alignment of the caller's matrix.
+int bg_encode_cols(int layout) { const int d = bg_enc_cols(layout); return d > 0 ? d : BG_E_ARG; }
+
+int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m, int layout, int out_dtype, void* out_dev,
+                   uint64_t out_stride_elems, float* kernel_ms_out, void* stream) {
+  const int D = bg_enc_cols(layout);
+  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const char* bad = nullptr;
+  if (D < 0) bad = "layout must be BG_ENC_PRODUCED, BG_ENC_FIXED or BG_ENC_EXTRACTOR";
+  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (m < 0 || m > (int64_t)BG_ENC_RECS * 0x7fffffffll) bad = "m out of range";
+  else if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) bad = r;
+  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
+  else if (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= the layout's column count";
+  if (bad) { g_create_err = std::string("bg_encode_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (m == 0) return 0;
+  const bool base16 = ((uintptr_t)out_dev & 15) == 0;
+  const int st = base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
+  const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+#define BG_ENC_GO(L, T) bg_encode_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, (long long)m, out_dev, out_stride_elems)
+  if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_F32); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_F32); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_F32); }
+  else { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_BF16); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_BF16); }
+#undef BG_ENC_GO
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
 }
 
 static int bg_batch_dev(BgDev& d, int m, uint32_t** scratch_out);

@@ -96,7 +96,15 @@ class BalatroSB3VecEnv(_SB3VecEnv):
 
     def __init__(self, num_envs: int, seed: int = 0, *, device: int = 0, max_invalid_actions: int = 50,
                  max_episode_steps: int = 1000, max_ante: int = 0, scorer_jokers: bool = False, as_torch: bool = False,
-                 seeds: Optional[Sequence[int]] = None):
+                 seeds: Optional[Sequence[int]] = None, features: Optional[str] = None):
+        """features: None -- the 51-key dict of `FIXED_SPEC` (BalatroEnvFixed's space); "produced" / "fixed" / "extractor" -- ONE float32
+        [N, D] matrix per call instead, the layout of `vec_env.encode_rows` ("fixed" is what SB3's CombinedExtractor would concatenate from
+        the dict): the env keeps packed records (obs_layout="rows") and one bg_encode_rows launch turns them into the network's input;
+        `observation_space` is a float32 Box((D,)).  The wrapper logic, rewards, dones and info flags are those of the dict path;
+        `terminal_observation` is the encoded row of the record before the wrapper's reset (a second launch, on those steps only)."""
+        if features is not None and features not in nat.ENC_LAYOUTS:
+            raise ValueError(f"features must be None or one of {sorted(nat.ENC_LAYOUTS)} (got {features!r})")
+        self.features = features
         self.num_envs = int(num_envs)
         self.as_torch = bool(as_torch)
         self.max_invalid_actions = int(max_invalid_actions)
@@ -104,7 +112,8 @@ class BalatroSB3VecEnv(_SB3VecEnv):
         # make_env_fixed(seed, rank): BalatroEnvFixed(seed=seed + rank) (train_balatro_fixed.py:285-288)
         self.seeds = list(seeds) if seeds is not None else [seed + r for r in range(self.num_envs)]
         self.env = BalatroVecEnv(self.num_envs, self.seeds, device=device, scorer_jokers=scorer_jokers, autoreset=True,
-                                 max_ante=max_ante, fused_steps=32)  # a VecEnv steps once per call: shallow look-ahead rings
+                                 max_ante=max_ante, fused_steps=32,  # a VecEnv steps once per call: shallow look-ahead rings
+                                 obs_layout="rows" if features is not None else "keys")
         dev = self.env.device
         self.observation_spec = FIXED_SPEC
         self.num_actions = 60
@@ -116,6 +125,16 @@ class BalatroSB3VecEnv(_SB3VecEnv):
         self._make_spaces()
 
     def _make_spaces(self):
+        if self.features is not None:
+            D = nat.ENC_COLS[nat.ENC_LAYOUTS[self.features]]
+            try:
+                from gymnasium import spaces
+                self.observation_space = spaces.Box(low=-np.inf, high=np.inf, shape=(D,), dtype=np.float32)
+                self.action_space = spaces.Discrete(60)
+            except Exception:  # noqa: BLE001
+                self.observation_space = (np.dtype("float32"), (D,))
+                self.action_space = 60
+            return
         try:  # gymnasium is optional too
             from gymnasium import spaces
             d = {}
@@ -130,6 +149,9 @@ class BalatroSB3VecEnv(_SB3VecEnv):
 
     # ---- VecEnv calling convention ----------------------------------------------------------------------------
     def _out(self, obs: Dict[str, torch.Tensor]):
+        if self.features is not None:   # the live records, encoded by one launch into a fresh matrix
+            m = self.env.features(self.features)
+            return m if self.as_torch else m.cpu().numpy()
         fixed = fix_observation(obs, self._zeros)
         if self.as_torch:
             return {k: v.clone() for k, v in fixed.items()}
@@ -162,8 +184,11 @@ class BalatroSB3VecEnv(_SB3VecEnv):
         terminal_obs = None
         if bool(wrapper_end.any()):
             idx = wrapper_end.nonzero(as_tuple=False).flatten()
-            fixed_before = fix_observation(obs, self._zeros)
-            terminal_obs = (idx.cpu().numpy(), {k: v[idx].cpu().numpy() for k, v in fixed_before.items()})
+            if self.features is not None:
+                terminal_obs = (idx.cpu().numpy(), self.env.features(self.features)[idx].cpu().numpy())
+            else:
+                fixed_before = fix_observation(obs, self._zeros)
+                terminal_obs = (idx.cpu().numpy(), {k: v[idx].cpu().numpy() for k, v in fixed_before.items()})
             obs = self.env.reset(mask=wrapper_end)
         self._steps = torch.where(done, torch.zeros_like(self._steps), self._steps)
         self._invalid = torch.where(done, torch.zeros_like(self._invalid), self._invalid)
@@ -179,7 +204,7 @@ class BalatroSB3VecEnv(_SB3VecEnv):
         if terminal_obs is not None:
             rows, tob = terminal_obs
             for j, i in enumerate(rows):
-                infos[int(i)]["terminal_observation"] = {k: v[j] for k, v in tob.items()}
+                infos[int(i)]["terminal_observation"] = tob[j] if self.features is not None else {k: v[j] for k, v in tob.items()}
         out = self._out(obs)
         if self.as_torch:
             return out, reward.to(torch.float32), done, infos

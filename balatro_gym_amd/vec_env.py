@@ -91,6 +91,10 @@ class RowBuffers:
         self.action = self._view(nat.ROW_EXTRA["action"][0], "int32", ())
         self.terminated = self._view(nat.ROW_EXTRA["terminated"][0], "uint8", ())
 
+    def encode(self, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The records as ONE [steps, n, D] float matrix for a policy network (`encode_rows`: one launch over all steps * n records)."""
+        return encode_rows(self.rows, layout, dtype, out)
+
     def _view(self, off: int, dt: str, shape) -> torch.Tensor:
         item = np.dtype(dt).itemsize
         count = int(np.prod(shape, dtype=np.int64))
@@ -175,6 +179,12 @@ class BalatroVecEnv:
         if self._rowbuf is None:
             raise AttributeError("obs_rows exists with obs_layout='rows'")
         return self._rowbuf.rows[0]
+
+    def features(self, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """obs_layout "rows": the live records as the [N, D] float matrix a policy network reads (`encode_rows(env.obs_rows, ...)`)."""
+        if self._rowbuf is None:
+            raise ValueError("features() encodes the packed records of an obs_layout='rows' env")
+        return encode_rows(self._rowbuf.rows[0], layout, dtype, out)
 
     @property
     def obs_flat(self) -> torch.Tensor:
@@ -588,6 +598,61 @@ def classify_batch(cards: torch.Tensor, n: torch.Tensor, lanes_per_case: int = 1
     if rc != 0:
         raise nat.NativeError(f"bg_classify_batch failed ({rc}): {L.bg_last_error(None).decode()}")
     return (out, float(ms.value)) if timing else out
+
+
+def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
+                timing: bool = False):
+    """Packed records -> the float matrix a policy network reads, in one launch (bg_encode_rows).  rows: a contiguous uint8 device tensor
+    [..., stride] of records as `rollout` / `step_many` / an obs_layout="rows" env write them (`RowBuffers.rows`, `env.obs_rows`).
+    layout: "produced" -- the 31 observation keys in the reference's key order, every element as float (153 columns: what SB3's
+    CombinedExtractor concatenates); "fixed" -- those followed by the 475 zeros of BalatroEnvFixed's never-filled keys (628);
+    "extractor" -- what BalatroFeaturesExtractor.forward builds: hand one-hot, joker ids, 21 normalised state features (447).
+    `_native.ENC_COLUMNS[layout]` names the column ranges.  dtype: torch.float32 or torch.bfloat16 (round to nearest even).
+    out: optional [..., >= D] tensor of `dtype` on the same device with the same leading shape, last dimension contiguous and the leading
+    dimensions dense over its row pitch (e.g. a column slice of a wider matrix): columns beyond D are left untouched.
+    Returns the [..., D] matrix (a view of `out` when given); timing=True returns (matrix, kernel milliseconds)."""
+    if layout not in nat.ENC_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(nat.ENC_LAYOUTS)} (got {layout!r})")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 1 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous uint8 tensor [..., stride] of packed records")
+    stride = int(rows.shape[-1])
+    if stride < nat.ROW_BYTES or stride % 16:
+        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
+    D = nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]
+    lead = tuple(rows.shape[:-1])
+    m = int(np.prod(lead, dtype=np.int64))
+    if out is not None:
+        if out.dtype != dtype or out.device != rows.device:
+            raise ValueError(f"out must be a {dtype} tensor on {rows.device}")
+        if tuple(out.shape[:-1]) != lead or out.shape[-1] < D:
+            raise ValueError(f"out must have shape {lead + ('>= %d' % D,)} (got {tuple(out.shape)})")
+        pitch = int(out.stride(-2)) if out.dim() >= 2 else int(out.shape[-1])
+        dense = out.stride(-1) == 1 and pitch >= out.shape[-1]
+        for d in range(out.dim() - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
+            dense = dense and out.stride(d - 1) == out.stride(d) * out.shape[d]
+        if not dense:
+            raise ValueError("out must have a contiguous last dimension and leading dimensions that are dense over its row pitch")
+    if not rows.is_cuda:
+        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+    if rows.data_ptr() % 16:
+        raise ValueError("rows must be 16-byte aligned")
+    if out is None:
+        out = torch.empty(lead + (D,), dtype=dtype, device=rows.device)
+        pitch = D
+    if m == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
+        return (out[..., :D], 0.0) if timing else out[..., :D]
+    L = nat.load()
+    ms = C.c_float(0.0)
+    with torch.cuda.device(rows.device):
+        rc = L.bg_encode_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(m), nat.ENC_LAYOUTS[layout],
+                              nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(out.data_ptr()), C.c_uint64(pitch),
+                              C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+    if rc != 0:
+        raise nat.NativeError(f"bg_encode_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+    res = out[..., :D]
+    return (res, float(ms.value)) if timing else res
 
 
 def score_hand_batch(cases: torch.Tensor, lanes_per_case: int = 1, timing: bool = False):

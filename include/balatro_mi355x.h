@@ -401,6 +401,36 @@ int bg_sim_evaluate_batch(const int32_t* hands_dev, const int32_t* n_dev, const 
 #define BG_SIM_CASE_WORDS 64
 int bg_sim_score_batch(const int32_t* cases_dev, int64_t* out_dev, int m, void* stream);
 
+/* Packed records -> the float matrix a policy network reads, in ONE launch: the consumer of bg_rollout_rows / bg_step_rows /
+ * bg_step_many_rows.  Replaces the host glue between the env and the network's first layer:
+ *   BG_ENC_PRODUCED / BG_ENC_FIXED  SB3's `CombinedExtractor` under `MultiInputPolicy` over `BalatroEnvFixed` (hpc_train.py:77,
+ *     train_balatro_fixed.py:125-207,346): every key flattened, `.float()`ed and concatenated in the observation space's key order.
+ *     PRODUCED: the 31 keys `_get_observation()` fills (balatro_env_2.py:1488-1531; the order of bg_obs_ptrs), every element as
+ *     numpy.float32(value) -- round to nearest even above 2**24, `chips_scored` straight from int64 (`_fix_observation` does not narrow
+ *     it), `progress_ratio` bit for bit: 153 columns.  FIXED: PRODUCED followed by the 20 keys the env declares (balatro_env_2.py:386-470)
+ *     and never fills, which BalatroEnvFixed zero-fills: 475 zeros, 628 columns; its first 153 columns are PRODUCED.
+ *   BG_ENC_EXTRACTOR  the tensors `BalatroFeaturesExtractor.forward` builds (train_balatro_agent.py:84-119): columns [0, 416) the hand
+ *     one-hot, column slot * 52 + card = 1.0 where hand[slot] == card (:86-93; defined for hand values -1..51, what the env writes: the -1
+ *     padding sets nothing); [416, 426) `joker_ids.float()` (:98); [426, 447) chips_scored / 1e6, chips_needed / 1e5, progress_ratio,
+ *     money / 100, ante / 10, round / 3, hands_left / 10, discards_left / 5, hand_levels[0..11] / 10, phase / 3 (:102-113), each
+ *     numpy.float32(value) / numpy.float32(c): an IEEE float32 division, not a multiplication by a reciprocal.  (The reference's
+ *     constructor sizes its game-state layer for 32 inputs while its forward builds these 21: size a first layer from bg_encode_cols.)
+ * out_dtype BG_ENC_BF16: the float32 value rounded to nearest even (`tensor.to(torch.bfloat16)`; a NaN becomes 0x7fc0).
+ * rows_dev: m records as the row paths write them (16-byte aligned, row_stride_bytes a multiple of 16, >= BG_ROW_BYTES; a [K, N, stride]
+ * buffer is m = K * N).  out_dev: [m, out_stride_elems] elements of out_dtype (aligned to its element), out_stride_elems >= the column
+ * count; columns beyond the count are left untouched.  16-byte stores when out_dev and the row pitch are 16-byte aligned, or when out_dev
+ * is and the matrix is dense (out_stride_elems == columns); one element per lane otherwise.  The record's reward / action / terminated are
+ * in no layout.  kernel_ms_out as in bg_classify_batch_ex.  Runs on the current device; bg_last_error(NULL) has the text of a BG_E_ARG;
+ * m == 0 is a no-op. */
+#define BG_ENC_PRODUCED 0
+#define BG_ENC_FIXED 1
+#define BG_ENC_EXTRACTOR 2
+#define BG_ENC_F32 0
+#define BG_ENC_BF16 1
+int bg_encode_cols(int layout); /* number of columns, or BG_E_ARG */
+int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m, int layout, int out_dtype,
+                   void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
