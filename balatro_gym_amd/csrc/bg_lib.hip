@@ -329,6 +329,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_ops.h" // operator-level batch kernels (classify / score_hand): need bg_mt_seed, bg_mt_twist
 #include "bg_sim.h" // balatro_sim.py evaluator / scorer (operator-level)
 #include "bg_encode.h" // packed records -> policy-network input (operator-level)
+#include "bg_gae.h"    // packed records -> advantages / returns and episode statistics (operator-level)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -2034,6 +2035,57 @@ int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m
   if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_F32); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_F32); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_F32); }
   else { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_BF16); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_BF16); }
 #undef BG_ENC_GO
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+// packed records -> PPO's scans along K (bg_gae.h): advantages / returns, and per-episode reward sums / lengths with a per-env carry
+static const char* bg_scan_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N) {
+  if (K < 0 || N < 0 || N > (int64_t)BG_GAE_ENVS * 0x7fffffffll) return "K / N out of range";
+  return bg_rows_args(rows_dev, row_stride_bytes);
+}
+
+int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* values_dev, const float* last_values_dev,
+                double gamma, double gae_lambda, float* advantages_dev, float* returns_dev, float* kernel_ms_out, void* stream) {
+  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
+  if (!bad && (!values_dev || !last_values_dev || !advantages_dev)) bad = "values_dev, last_values_dev and advantages_dev must be device pointers";
+  else if (!bad && (((uintptr_t)values_dev | (uintptr_t)last_values_dev | (uintptr_t)advantages_dev | (uintptr_t)returns_dev) & 3)) bad = "float arrays must be 4-byte aligned";
+  else if (!bad && (advantages_dev == values_dev || returns_dev == values_dev || (returns_dev && returns_dev == advantages_dev))) bad = "advantages_dev / returns_dev must not be the same pointer as values_dev or as each other";
+  if (bad) { g_create_err = std::string("bg_gae_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (K == 0 || N == 0) return 0;
+  const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
+  const float g = bg_gae_g(gamma), gl = bg_gae_gl(gamma, gae_lambda);
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (returns_dev) hipLaunchKernelGGL((bg_gae_kernel<true>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, values_dev, last_values_dev, g, gl, advantages_dev, returns_dev);
+  else hipLaunchKernelGGL((bg_gae_kernel<false>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, values_dev, last_values_dev, g, gl, advantages_dev, returns_dev);
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double* ep_return_carry_dev, int32_t* ep_len_carry_dev,
+                          double* ep_return_dev, int32_t* ep_len_dev, float* kernel_ms_out, void* stream) {
+  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
+  if (!bad && (!ep_return_carry_dev || !ep_len_carry_dev)) bad = "ep_return_carry_dev and ep_len_carry_dev must be device pointers";
+  else if (!bad && ((((uintptr_t)ep_return_carry_dev | (uintptr_t)ep_return_dev) & 7) || (((uintptr_t)ep_len_carry_dev | (uintptr_t)ep_len_dev) & 3))) bad = "float64 arrays must be 8-byte aligned, int32 arrays 4-byte aligned";
+  else if (!bad && (ep_return_dev == ep_return_carry_dev || ep_len_dev == ep_len_carry_dev)) bad = "ep_return_dev / ep_len_dev must not be the same pointer as their carry";
+  if (bad) { g_create_err = std::string("bg_episode_stats_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (K == 0 || N == 0) return 0;
+  const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+#define BG_EPS_GO(R, L) hipLaunchKernelGGL((bg_episode_stats_kernel<R, L>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, ep_return_carry_dev, ep_len_carry_dev, ep_return_dev, ep_len_dev)
+  if (ep_return_dev) { if (ep_len_dev) BG_EPS_GO(true, true); else BG_EPS_GO(true, false); }
+  else { if (ep_len_dev) BG_EPS_GO(false, true); else BG_EPS_GO(false, false); }
+#undef BG_EPS_GO
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);

@@ -95,6 +95,15 @@ class RowBuffers:
         """The records as ONE [steps, n, D] float matrix for a policy network (`encode_rows`: one launch over all steps * n records)."""
         return encode_rows(self.rows, layout, dtype, out)
 
+    def gae(self, values: torch.Tensor, last_values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
+            advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False):
+        """(advantages, returns) float32 [steps, n] of these records (`gae_rows`: SB3's compute_returns_and_advantage in one launch)."""
+        return gae_rows(self.rows, values, last_values, gamma, gae_lambda, advantages, returns, timing)
+
+    def episode_stats(self, stats: "EpisodeStats"):
+        """(ep_return float64, ep_len int32) [steps, n] of these records, continuing the episodes `stats` carries (`EpisodeStats.update`)."""
+        return stats.update(self.rows)
+
     def _view(self, off: int, dt: str, shape) -> torch.Tensor:
         item = np.dtype(dt).itemsize
         count = int(np.prod(shape, dtype=np.int64))
@@ -653,6 +662,120 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
         raise nat.NativeError(f"bg_encode_rows failed ({rc}): {L.bg_last_error(None).decode()}")
     res = out[..., :D]
     return (res, float(ms.value)) if timing else res
+
+
+def _check_scan_rows(rows) -> tuple:
+    """rows of gae_rows / EpisodeStats.update: contiguous uint8 [K, N, stride] -> (K, N, stride)."""
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() != 3 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous uint8 tensor [K, N, stride] of packed records")
+    K, N, stride = (int(x) for x in rows.shape)
+    if stride < nat.ROW_BYTES or stride % 16:
+        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
+    return K, N, stride
+
+
+def _check_scan_tensor(name: str, t, dtype: torch.dtype, shape: tuple, device: torch.device):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)} on {device}")
+
+
+def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
+             advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False):
+    """Advantages and returns of a finished [K, N] rollout of packed records in one launch (bg_gae_rows): bit for bit SB3's
+    `RolloutBuffer.compute_returns_and_advantage` run in numpy on float32 buffers, with dones[t] = the record's terminated byte and the reward
+    rounded from the record's float64.  rows: contiguous uint8 device tensor [K, N, stride] (`RowBuffers.rows`); values float32 [K, N] (the value
+    network's output per step), last_values float32 [N] (its output on the observation after the last step).  advantages / returns: optional
+    float32 [K, N] tensors to write into; they must not share memory with values or with each other.
+    Returns (advantages, returns); timing=True returns (advantages, returns, kernel milliseconds)."""
+    K, N, stride = _check_scan_rows(rows)
+    dev = rows.device
+    _check_scan_tensor("values", values, torch.float32, (K, N), dev)
+    _check_scan_tensor("last_values", last_values, torch.float32, (N,), dev)
+    for name, t in (("advantages", advantages), ("returns", returns)):
+        if t is not None:
+            _check_scan_tensor(name, t, torch.float32, (K, N), dev)
+    gamma, gae_lambda = float(gamma), float(gae_lambda)
+    if not (np.isfinite(gamma) and np.isfinite(gae_lambda)):
+        raise ValueError("gamma and gae_lambda must be finite")
+    if not rows.is_cuda:
+        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+    if rows.data_ptr() % 16:
+        raise ValueError("rows must be 16-byte aligned")
+    if advantages is None:
+        advantages = torch.empty((K, N), dtype=torch.float32, device=dev)
+    if returns is None:
+        returns = torch.empty((K, N), dtype=torch.float32, device=dev)
+    ptrs = [values.data_ptr(), advantages.data_ptr(), returns.data_ptr()]
+    if K * N and len(set(ptrs)) != 3:
+        raise ValueError("advantages / returns must not share memory with values or with each other")
+    if K * N == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
+        return (advantages, returns, 0.0) if timing else (advantages, returns)
+    L = nat.load()
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        rc = L.bg_gae_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(values.data_ptr()),
+                           C.c_void_p(last_values.data_ptr()), C.c_double(gamma), C.c_double(gae_lambda), C.c_void_p(advantages.data_ptr()),
+                           C.c_void_p(returns.data_ptr()), C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise nat.NativeError(f"bg_gae_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+    return (advantages, returns, float(ms.value)) if timing else (advantages, returns)
+
+
+class EpisodeStats:
+    """What `Monitor` reports per finished episode, for N envs on the device (bg_episode_stats_rows): owns the running reward sum (float64, a plain
+    sum in step order) and step count (int32) of every env's current episode, across calls."""
+
+    def __init__(self, n: int, device):
+        if int(n) < 0:
+            raise ValueError("n must be >= 0")
+        self.n = int(n)
+        self.device = torch.device(device)
+        self.ep_return_carry = torch.zeros(self.n, dtype=torch.float64, device=self.device)
+        self.ep_len_carry = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Forget the running episodes (of the envs where `mask` is set): for callers who `env.reset()` by hand."""
+        if mask is None:
+            self.ep_return_carry.zero_()
+            self.ep_len_carry.zero_()
+            return
+        mask = torch.as_tensor(mask)
+        if tuple(mask.shape) != (self.n,):
+            raise ValueError(f"mask must have shape [{self.n}]")
+        mask = mask.to(device=self.device, dtype=torch.bool)
+        self.ep_return_carry.masked_fill_(mask, 0.0)
+        self.ep_len_carry.masked_fill_(mask, 0)
+
+    def update(self, rows: torch.Tensor, ep_return: Optional[torch.Tensor] = None, ep_len: Optional[torch.Tensor] = None, timing: bool = False):
+        """The next K steps of every env: rows contiguous uint8 [K, N, stride] on this device.  Returns (ep_return float64 [K, N], ep_len int32
+        [K, N]): on a terminated step the finished episode's reward sum and length, 0.0 / 0 elsewhere (`ep_len.nonzero()` lists the episodes);
+        timing=True appends the kernel milliseconds.  ep_return / ep_len: optional tensors to write into."""
+        K, N, stride = _check_scan_rows(rows)
+        if N != self.n or rows.device != self.device:
+            raise ValueError(f"rows must hold records of {self.n} envs on {self.device} (got {N} envs on {rows.device})")
+        if ep_return is not None:
+            _check_scan_tensor("ep_return", ep_return, torch.float64, (K, N), self.device)
+        if ep_len is not None:
+            _check_scan_tensor("ep_len", ep_len, torch.int32, (K, N), self.device)
+        if not rows.is_cuda:
+            raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+        if rows.data_ptr() % 16:
+            raise ValueError("rows must be 16-byte aligned")
+        if ep_return is None:
+            ep_return = torch.empty((K, N), dtype=torch.float64, device=self.device)
+        if ep_len is None:
+            ep_len = torch.empty((K, N), dtype=torch.int32, device=self.device)
+        if K * N == 0:
+            return (ep_return, ep_len, 0.0) if timing else (ep_return, ep_len)
+        L = nat.load()
+        ms = C.c_float(0.0)
+        with torch.cuda.device(self.device):
+            rc = L.bg_episode_stats_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(self.ep_return_carry.data_ptr()),
+                                         C.c_void_p(self.ep_len_carry.data_ptr()), C.c_void_p(ep_return.data_ptr()), C.c_void_p(ep_len.data_ptr()),
+                                         C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise nat.NativeError(f"bg_episode_stats_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+        return (ep_return, ep_len, float(ms.value)) if timing else (ep_return, ep_len)
 
 
 def score_hand_batch(cases: torch.Tensor, lanes_per_case: int = 1, timing: bool = False):

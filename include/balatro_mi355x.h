@@ -431,6 +431,39 @@ int bg_encode_cols(int layout); /* number of columns, or BG_E_ARG */
 int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m, int layout, int out_dtype,
                    void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream);
 
+/* PPO's two scans along K over a finished [K, N] rollout of packed records, on the device, in ONE launch each: the consumers of
+ * bg_rollout_rows / bg_step_many_rows beside bg_encode_rows.  Both read two fields of a record, BG_ROW_REWARD and BG_ROW_TERMINATED.
+ * Record (t, e) is at rows_dev + (t * N + e) * row_stride_bytes (the rows_stride_steps != 0 layout; a RowBuffers.rows tensor); rows_dev 16-byte
+ * aligned, row_stride_bytes a multiple of 16 and >= BG_ROW_BYTES.  Both run on the current device, need no handle, return BG_E_ARG (text in
+ * bg_last_error(NULL)) before launching anything, treat K == 0 or N == 0 as a no-op; kernel_ms_out as in bg_classify_batch_ex.
+ *
+ * bg_gae_rows replaces: SB3's `RolloutBuffer.compute_returns_and_advantage`, which every training script of the reference runs through
+ * `PPO(..., gamma=0.99, gae_lambda=0.95)` (hpc_train.py:77-86, train_balatro_fixed.py:346-355, train_balatro_agent.py:329-335,
+ * train_progressive.py:164-171, robust_training.py:143-149): a loop over the K steps, backwards, a handful of elementwise operations per step.
+ * The result is, bit for bit, that loop run in numpy on float32 buffers, with episode_starts[t + 1] = dones[t] = the record's terminated byte of
+ * step t (SAME_STEP auto-reset: the record of a terminated step already shows the next episode, so values[t + 1] belongs to it and is cut off):
+ *     g = float32(gamma);  gl = float32(gamma * gae_lambda)   (the product taken in float64 first);  last = 0
+ *     for t = K-1 .. 0:  r = float32(reward[t])  (round to nearest even);  nnt = 1 - float32(terminated[t] != 0)
+ *                        nv = t == K-1 ? last_values[e] : values[t+1][e]
+ *                        delta = (r + (g * nv) * nnt) - values[t][e];  last = delta + ((gl * nnt) * last)
+ *                        advantages[t][e] = last;  returns[t][e] = last + values[t][e]
+ * every operation rounded to float32, no fused multiply-add.  values_dev / advantages_dev / returns_dev are dense float32 [K, N], last_values_dev
+ * [N]; returns_dev may be NULL (not written).  Outputs must not alias inputs or each other.  Truncation bootstraps are out of scope: the rows
+ * path has no truncated flag.
+ *
+ * bg_episode_stats_rows replaces: `Monitor` (hpc_train.py:26, train_balatro_fixed.py:290), the source of ep_rew_mean / ep_len_mean, as
+ * info['episode']['r' / 'l'].  Per env, forwards: carry_return += reward[t] (a plain float64 sum in step order), carry_len += 1; on a set
+ * terminated byte ep_return[t][e] / ep_len[t][e] = the carries and the carries return to 0.0 / 0, otherwise the outputs are written as 0.0 / 0.
+ * The carries ([N], in / out) hold the running episode after the call, so 2 K steps give the same outputs in two calls of K as in one.  Monitor's own
+ * presentation (round(..., 6), CPython's compensated sum) is not promised to the last bit.  ep_return_dev / ep_len_dev: dense [K, N], each may be NULL;
+ * they must not alias the carries.  Wrapper-made endings (SafeBalatroEnv's invalid-action / step limits) do not exist on the rows path. */
+int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
+                const float* values_dev, const float* last_values_dev, double gamma, double gae_lambda,
+                float* advantages_dev, float* returns_dev, float* kernel_ms_out, void* stream);
+int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
+                          double* ep_return_carry_dev, int32_t* ep_len_carry_dev, double* ep_return_dev, int32_t* ep_len_dev,
+                          float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
