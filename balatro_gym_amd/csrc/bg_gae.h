@@ -74,11 +74,12 @@ BG_GAE_FN BgEpsStep bg_eps_step(double r, bool done, double carry_return, int32_
 #define BG_GAE_ENVS BG_GAE_BLOCK /* envs of a workgroup: the grid is ceil(N / BG_GAE_ENVS) */
 #define BG_GAE_BATCH 16
 
-// RET: returns_dev is written.  Batch at t0, slot j is step t = t0 - j.  K >= 1.
-template <bool RET>
+// RET: returns_dev is written.  RW: the step's reward is rewards[t][e] (dense float64, bg_gae_rows_ex) instead of the record's.  Batch at t0, slot j
+// is step t = t0 - j.  K >= 1.
+template <bool RET, bool RW>
 __global__ __launch_bounds__(BG_GAE_BLOCK) void bg_gae_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, int K, long long N,
                                                               const float* __restrict__ values, const float* __restrict__ last_values, float g, float gl,
-                                                              float* __restrict__ advantages, float* __restrict__ returns) {
+                                                              float* __restrict__ advantages, float* __restrict__ returns, const double* __restrict__ rewards) {
   const long long e = (long long)blockIdx.x * BG_GAE_BLOCK + threadIdx.x;
   if (e >= N) return;
   float last = 0.0f, nv = last_values[e];
@@ -93,7 +94,7 @@ __global__ __launch_bounds__(BG_GAE_BLOCK) void bg_gae_kernel(const uint8_t* __r
       if (t >= 0) {
         const size_t at = (size_t)t * (size_t)N + (size_t)e;
         const uint8_t* const rec = rows + at * row_stride;
-        r64[j] = bg_gae_reward64(rec);
+        r64[j] = RW ? rewards[at] : bg_gae_reward64(rec);
         dn[j] = rec[BG_ROW_TERMINATED];
         v[j] = values[at];
       }

@@ -330,6 +330,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_sim.h" // balatro_sim.py evaluator / scorer (operator-level)
 #include "bg_encode.h" // packed records -> policy-network input (operator-level)
 #include "bg_gae.h"    // packed records -> advantages / returns and episode statistics (operator-level)
+#include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -2046,13 +2047,16 @@ static const char* bg_scan_args(const uint8_t* rows_dev, uint64_t row_stride_byt
   return bg_rows_args(rows_dev, row_stride_bytes);
 }
 
-int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* values_dev, const float* last_values_dev,
-                double gamma, double gae_lambda, float* advantages_dev, float* returns_dev, float* kernel_ms_out, void* stream) {
+int bg_gae_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* values_dev, const float* last_values_dev,
+                   double gamma, double gae_lambda, float* advantages_dev, float* returns_dev, const double* rewards_dev, float* kernel_ms_out, void* stream) {
+  const char* const who = rewards_dev ? "bg_gae_rows_ex: " : "bg_gae_rows: ";
   const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
   if (!bad && (!values_dev || !last_values_dev || !advantages_dev)) bad = "values_dev, last_values_dev and advantages_dev must be device pointers";
   else if (!bad && (((uintptr_t)values_dev | (uintptr_t)last_values_dev | (uintptr_t)advantages_dev | (uintptr_t)returns_dev) & 3)) bad = "float arrays must be 4-byte aligned";
+  else if (!bad && ((uintptr_t)rewards_dev & 7)) bad = "rewards_dev must be 8-byte aligned";
   else if (!bad && (advantages_dev == values_dev || returns_dev == values_dev || (returns_dev && returns_dev == advantages_dev))) bad = "advantages_dev / returns_dev must not be the same pointer as values_dev or as each other";
-  if (bad) { g_create_err = std::string("bg_gae_rows: ") + bad; return BG_E_ARG; }
+  else if (!bad && rewards_dev && ((const void*)rewards_dev == (const void*)advantages_dev || (const void*)rewards_dev == (const void*)returns_dev)) bad = "advantages_dev / returns_dev must not be the same pointer as rewards_dev";
+  if (bad) { g_create_err = std::string(who) + bad; return BG_E_ARG; }
   if (kernel_ms_out) *kernel_ms_out = 0.f;
   if (K == 0 || N == 0) return 0;
   const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
@@ -2061,11 +2065,17 @@ int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64
   BgOpTimer tm;
   int rc = tm.begin(kernel_ms_out, s);
   if (rc) return rc;
-  if (returns_dev) hipLaunchKernelGGL((bg_gae_kernel<true>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, values_dev, last_values_dev, g, gl, advantages_dev, returns_dev);
-  else hipLaunchKernelGGL((bg_gae_kernel<false>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, values_dev, last_values_dev, g, gl, advantages_dev, returns_dev);
+#define BG_GAE_GO(R, W) hipLaunchKernelGGL((bg_gae_kernel<R, W>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, values_dev, last_values_dev, g, gl, advantages_dev, returns_dev, rewards_dev)
+  if (returns_dev) { if (rewards_dev) BG_GAE_GO(true, true); else BG_GAE_GO(true, false); }
+  else { if (rewards_dev) BG_GAE_GO(false, true); else BG_GAE_GO(false, false); }
+#undef BG_GAE_GO
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);
+}
+int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* values_dev, const float* last_values_dev,
+                double gamma, double gae_lambda, float* advantages_dev, float* returns_dev, float* kernel_ms_out, void* stream) {
+  return bg_gae_rows_ex(rows_dev, row_stride_bytes, K, N, values_dev, last_values_dev, gamma, gae_lambda, advantages_dev, returns_dev, nullptr, kernel_ms_out, stream);
 }
 
 int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double* ep_return_carry_dev, int32_t* ep_len_carry_dev,
@@ -2086,6 +2096,110 @@ int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, in
   if (ep_return_dev) { if (ep_len_dev) BG_EPS_GO(true, true); else BG_EPS_GO(true, false); }
   else { if (ep_len_dev) BG_EPS_GO(false, true); else BG_EPS_GO(false, false); }
 #undef BG_EPS_GO
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+// packed records -> VecNormalize (bg_norm.h).  Workspace, in doubles: [K * chunks * 306] partial (mean, M2) per (step, 256-env chunk), [K * 306] batch
+// moments (when the caller does not take them), [K * 306] (mean, sqrt(var + epsilon)) per step for the normalising pass.  The reward call's needs -- 2 per
+// (step, 64-env chunk), 2 + 1 per step -- are smaller at every shape.
+static uint64_t bg_norm_chunks(int64_t N) { return ((uint64_t)N + BG_NORM_CHUNK - 1) / BG_NORM_CHUNK; }
+static uint64_t bg_norm_rchunks(int64_t N) { return ((uint64_t)N + BG_NORM_RBLOCK - 1) / BG_NORM_RBLOCK; }
+uint64_t bg_norm_workspace_bytes(int K, int64_t N) {
+  if (K <= 0 || N <= 0) return 0;
+  return ((uint64_t)K * bg_norm_chunks(N) + 2u * (uint64_t)K) * (2u * BG_NORM_COLS) * sizeof(double);
+}
+static_assert(2 * (BG_NORM_CHUNK / BG_NORM_RBLOCK) + 3 <= 2 * BG_NORM_COLS, "the reward call fits the workspace of the observation call");
+
+int bg_norm_obs_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, int layout, int out_dtype, double* mean_dev, double* var_dev,
+                     double* count_dev, int update, double epsilon, double clip_obs, void* out_dev, uint64_t out_stride_elems, double* moments_dev,
+                     void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
+  const int D = layout == BG_ENC_PRODUCED || layout == BG_ENC_FIXED ? bg_enc_cols(layout) : -1;
+  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
+  if (bad) {}
+  else if (D < 0) bad = "layout must be BG_ENC_PRODUCED or BG_ENC_FIXED (VecNormalize wraps the env's keys, not the extractor's tensors)";
+  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if ((uint64_t)K * (uint64_t)N > (uint64_t)BG_ENC_RECS * 0x7fffffffull) bad = "K * N out of range";
+  else if (!mean_dev || !var_dev || !count_dev || (((uintptr_t)mean_dev | (uintptr_t)var_dev | (uintptr_t)count_dev | (uintptr_t)moments_dev) & 7)) bad = "mean_dev, var_dev and count_dev must be 8-byte aligned device pointers (moments_dev 8-byte aligned)";
+  else if (mean_dev == var_dev || mean_dev == count_dev || var_dev == count_dev) bad = "mean_dev, var_dev and count_dev must not be the same pointer";
+  else if (out_dev && ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be aligned to its element type";
+  else if (out_dev && (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull)) bad = "out_stride_elems must be >= the layout's column count";
+  else if (!update && moments_dev) bad = "moments_dev must be NULL when update == 0 (no batch moments are taken)";
+  else if (!update && !out_dev) bad = "update == 0 with out_dev NULL asks for nothing";
+  else if (!(epsilon == epsilon) || !(clip_obs == clip_obs)) bad = "epsilon and clip_obs must not be NaN";
+  else if (K > 0 && N > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_norm_workspace_bytes(K, N))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_norm_workspace_bytes(K, N) bytes";
+  else if (out_dev && ((void*)mean_dev == out_dev || (void*)var_dev == out_dev || (void*)moments_dev == out_dev || workspace_dev == out_dev || (const void*)rows_dev == out_dev)) bad = "out_dev must not be the same pointer as an input or another output";
+  if (bad) { g_create_err = std::string("bg_norm_obs_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (K == 0 || N == 0) return 0;
+  const uint64_t chunks = bg_norm_chunks(N);
+  double* const part = (double*)workspace_dev;
+  double* const mom_ws = part + (uint64_t)K * chunks * (2 * BG_NORM_COLS);
+  double* const stat = mom_ws + (uint64_t)K * (2 * BG_NORM_COLS);
+  double* const mom = moments_dev ? moments_dev : mom_ws;
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (update) {
+    hipLaunchKernelGGL(bg_norm_obs_partials, dim3((unsigned)(chunks * (uint64_t)K)), dim3(BG_NORM_PBLOCK), 0, s, rows_dev, row_stride_bytes, (long long)N, (long long)chunks, part);
+    hipLaunchKernelGGL(bg_norm_obs_combine, dim3((unsigned)K), dim3(BG_NORM_PBLOCK), 0, s, part, (long long)N, (long long)chunks, mom);
+    hipLaunchKernelGGL((bg_norm_obs_chain<true>), dim3(1), dim3(BG_NORM_PBLOCK), 0, s, mom, K, (double)N, epsilon, mean_dev, var_dev, count_dev, stat);
+  } else if (out_dev)
+    hipLaunchKernelGGL((bg_norm_obs_chain<false>), dim3(1), dim3(BG_NORM_PBLOCK), 0, s, mom, K, (double)N, epsilon, mean_dev, var_dev, count_dev, stat);
+  if (out_dev) {
+    const long long m = (long long)K * (long long)N;
+    const bool base16 = ((uintptr_t)out_dev & 15) == 0;
+    const int st = base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
+    const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
+    const size_t sstride = update ? 2 * BG_NORM_COLS : 0;
+#define BG_NORM_GO(L, T) bg_norm_obs_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, m, (long long)N, stat, sstride, clip_obs, out_dev, out_stride_elems)
+    if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_F32); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_F32); }
+    else { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_BF16); }
+#undef BG_NORM_GO
+  }
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double* returns_carry_dev, double* ret_stats_dev, int update,
+                        double gamma, double epsilon, double clip_reward, double* rewards_dev, double* moments_dev, void* workspace_dev,
+                        uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
+  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
+  if (bad) {}
+  else if ((uint64_t)K * (uint64_t)N > 256ull * 0x7fffffffull) bad = "K * N out of range";
+  else if (!ret_stats_dev || (update && !returns_carry_dev)) bad = "ret_stats_dev (and, with update != 0, returns_carry_dev) must be device pointers";
+  else if (((uintptr_t)returns_carry_dev | (uintptr_t)ret_stats_dev | (uintptr_t)rewards_dev | (uintptr_t)moments_dev) & 7) bad = "float64 arrays must be 8-byte aligned";
+  else if (!update && moments_dev) bad = "moments_dev must be NULL when update == 0 (no batch moments are taken)";
+  else if (!update && !rewards_dev) bad = "update == 0 with rewards_dev NULL asks for nothing";
+  else if (!(gamma == gamma) || !(epsilon == epsilon) || !(clip_reward == clip_reward)) bad = "gamma, epsilon and clip_reward must not be NaN";
+  else if (K > 0 && N > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_norm_workspace_bytes(K, N))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_norm_workspace_bytes(K, N) bytes";
+  else if (rewards_dev && (rewards_dev == returns_carry_dev || rewards_dev == ret_stats_dev || rewards_dev == moments_dev || (void*)rewards_dev == workspace_dev || returns_carry_dev == ret_stats_dev)) bad = "outputs must not be the same pointer as an input or as each other";
+  if (bad) { g_create_err = std::string("bg_norm_reward_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (K == 0 || N == 0) return 0;
+  const uint64_t chunks = bg_norm_rchunks(N);
+  double* const part = (double*)workspace_dev;
+  double* const mom_ws = part + (uint64_t)K * chunks * 2;
+  double* const denom = mom_ws + (uint64_t)K * 2;
+  double* const mom = moments_dev ? moments_dev : mom_ws;
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (update) {
+    hipLaunchKernelGGL(bg_norm_ret_partials, dim3((unsigned)chunks), dim3(BG_NORM_RBLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, (long long)chunks, gamma, returns_carry_dev, part);
+    hipLaunchKernelGGL(bg_norm_ret_combine, dim3((unsigned)K), dim3(BG_NORM_RBLOCK), 0, s, part, (long long)N, (long long)chunks, mom);
+    hipLaunchKernelGGL((bg_norm_ret_chain<true>), dim3(1), dim3(64), 0, s, mom, K, (double)N, epsilon, ret_stats_dev, denom);
+  } else
+    hipLaunchKernelGGL((bg_norm_ret_chain<false>), dim3(1), dim3(64), 0, s, mom, K, (double)N, epsilon, ret_stats_dev, denom);
+  if (rewards_dev) {
+    const long long m = (long long)K * (long long)N;
+    hipLaunchKernelGGL(bg_norm_reward_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, rows_dev, row_stride_bytes, m, (long long)N, denom, update ? 1 : 0, clip_reward, rewards_dev);
+  }
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);

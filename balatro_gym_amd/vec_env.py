@@ -96,9 +96,18 @@ class RowBuffers:
         return encode_rows(self.rows, layout, dtype, out)
 
     def gae(self, values: torch.Tensor, last_values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
-            advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False):
+            advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False,
+            rewards: Optional[torch.Tensor] = None):
         """(advantages, returns) float32 [steps, n] of these records (`gae_rows`: SB3's compute_returns_and_advantage in one launch)."""
-        return gae_rows(self.rows, values, last_values, gamma, gae_lambda, advantages, returns, timing)
+        return gae_rows(self.rows, values, last_values, gamma, gae_lambda, advantages, returns, timing, rewards)
+
+    def normalize(self, norm: "RowNormalizer", layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The records as VecNormalize would hand them to the network, [steps, n, D] (`RowNormalizer.normalize_obs`)."""
+        return norm.normalize_obs(self.rows, layout, dtype, out)
+
+    def normalize_reward(self, norm: "RowNormalizer", out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The records' rewards as VecNormalize would hand them to the learner, float64 [steps, n] (`RowNormalizer.normalize_reward`)."""
+        return norm.normalize_reward(self.rows, out)
 
     def episode_stats(self, stats: "EpisodeStats"):
         """(ep_return float64, ep_len int32) [steps, n] of these records, continuing the episodes `stats` carries (`EpisodeStats.update`)."""
@@ -680,12 +689,14 @@ def _check_scan_tensor(name: str, t, dtype: torch.dtype, shape: tuple, device: t
 
 
 def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
-             advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False):
+             advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False,
+             rewards: Optional[torch.Tensor] = None):
     """Advantages and returns of a finished [K, N] rollout of packed records in one launch (bg_gae_rows): bit for bit SB3's
     `RolloutBuffer.compute_returns_and_advantage` run in numpy on float32 buffers, with dones[t] = the record's terminated byte and the reward
     rounded from the record's float64.  rows: contiguous uint8 device tensor [K, N, stride] (`RowBuffers.rows`); values float32 [K, N] (the value
     network's output per step), last_values float32 [N] (its output on the observation after the last step).  advantages / returns: optional
-    float32 [K, N] tensors to write into; they must not share memory with values or with each other.
+    float32 [K, N] tensors to write into; they must not share memory with values or with each other.  rewards: optional float64 [K, N] device tensor
+    to take the rewards from instead of the records (bg_gae_rows_ex; `RowNormalizer.normalize_reward`'s output), each rounded to float32 like the record's.
     Returns (advantages, returns); timing=True returns (advantages, returns, kernel milliseconds)."""
     K, N, stride = _check_scan_rows(rows)
     dev = rows.device
@@ -694,6 +705,8 @@ def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor
     for name, t in (("advantages", advantages), ("returns", returns)):
         if t is not None:
             _check_scan_tensor(name, t, torch.float32, (K, N), dev)
+    if rewards is not None:
+        _check_scan_tensor("rewards", rewards, torch.float64, (K, N), dev)
     gamma, gae_lambda = float(gamma), float(gae_lambda)
     if not (np.isfinite(gamma) and np.isfinite(gae_lambda)):
         raise ValueError("gamma and gae_lambda must be finite")
@@ -713,9 +726,11 @@ def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor
     L = nat.load()
     ms = C.c_float(0.0)
     with torch.cuda.device(dev):
-        rc = L.bg_gae_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(values.data_ptr()),
-                           C.c_void_p(last_values.data_ptr()), C.c_double(gamma), C.c_double(gae_lambda), C.c_void_p(advantages.data_ptr()),
-                           C.c_void_p(returns.data_ptr()), C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        args = (C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(values.data_ptr()),
+                C.c_void_p(last_values.data_ptr()), C.c_double(gamma), C.c_double(gae_lambda), C.c_void_p(advantages.data_ptr()),
+                C.c_void_p(returns.data_ptr()))
+        tail = (C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        rc = L.bg_gae_rows(*args, *tail) if rewards is None else L.bg_gae_rows_ex(*args, C.c_void_p(rewards.data_ptr()), *tail)
     if rc != 0:
         raise nat.NativeError(f"bg_gae_rows failed ({rc}): {L.bg_last_error(None).decode()}")
     return (advantages, returns, float(ms.value)) if timing else (advantages, returns)
@@ -776,6 +791,153 @@ class EpisodeStats:
         if rc != 0:
             raise nat.NativeError(f"bg_episode_stats_rows failed ({rc}): {L.bg_last_error(None).decode()}")
         return (ep_return, ep_len, float(ms.value)) if timing else (ep_return, ep_len)
+
+
+def _norm_rows(rows) -> torch.Tensor:
+    """rows of RowNormalizer: [N, stride] (one step) or [K, N, stride] -> the [K, N, stride] view."""
+    if isinstance(rows, torch.Tensor) and rows.dim() == 2:
+        rows = rows.unsqueeze(0)
+    return rows
+
+
+class RowNormalizer:
+    """SB3's `VecNormalize(norm_obs, norm_reward)` for N envs over packed records, on the device (bg_norm_obs_rows / bg_norm_reward_rows).  Owns what
+    VecNormalize pickles -- one RunningMeanStd (mean, var float64 [153], one count) over the columns of the "produced" layout, the return statistics
+    `ret_stats` (mean, var, count) -- plus the per-env discounted return `returns` (float64 [N]) and a cached workspace, all device tensors.
+    Each of the K steps of a call is one VecNormalize step: update the statistics with the batch of N envs, then normalise with the updated statistics.
+    training=False (or `.training = False` later) freezes the statistics: only the normalisation runs.  With norm_obs / norm_reward unset the matching
+    call refuses: encode the records / read `RowBuffers.reward` instead."""
+
+    def __init__(self, n: int, device, *, gamma: float = 0.99, epsilon: float = 1e-8, clip_obs: float = 10.0, clip_reward: float = 10.0,
+                 norm_obs: bool = True, norm_reward: bool = True, training: bool = True):
+        if int(n) < 0:
+            raise ValueError("n must be >= 0")
+        for name, v in (("gamma", gamma), ("epsilon", epsilon), ("clip_obs", clip_obs), ("clip_reward", clip_reward)):
+            if not np.isfinite(float(v)):
+                raise ValueError(f"{name} must be finite")
+        self.n = int(n)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:   # "cuda" is the current device: tensors report it with its index
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.gamma, self.epsilon, self.clip_obs, self.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
+        self.norm_obs, self.norm_reward, self.training = bool(norm_obs), bool(norm_reward), bool(training)
+        f64 = dict(dtype=torch.float64, device=self.device)
+        self.obs_mean = torch.zeros(nat.NORM_COLS, **f64)        # RunningMeanStd(epsilon=1e-4): mean 0, var 1, count 1e-4
+        self.obs_var = torch.ones(nat.NORM_COLS, **f64)
+        self.obs_count = torch.full((1,), 1e-4, **f64)
+        self.ret_stats = torch.tensor([0.0, 1.0, 1e-4], **f64)   # mean, var, count
+        self.returns = torch.zeros(self.n, **f64)
+        self._workspace: Optional[torch.Tensor] = None
+
+    def reset_returns(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Zero the discounted returns (of the envs where `mask` is set): VecNormalize.reset() does so for all envs."""
+        if mask is None:
+            self.returns.zero_()
+            return
+        mask = torch.as_tensor(mask)
+        if tuple(mask.shape) != (self.n,):
+            raise ValueError(f"mask must have shape [{self.n}]")
+        self.returns.masked_fill_(mask.to(device=self.device, dtype=torch.bool), 0.0)
+
+    def state_dict(self) -> dict:
+        """Host copies of everything the next call depends on: the counterpart of VecNormalize's pickle.  `load_state_dict` restores it exactly."""
+        return {"obs_mean": self.obs_mean.cpu().clone(), "obs_var": self.obs_var.cpu().clone(), "obs_count": self.obs_count.cpu().clone(),
+                "ret_stats": self.ret_stats.cpu().clone(), "returns": self.returns.cpu().clone(),
+                "gamma": self.gamma, "epsilon": self.epsilon, "clip_obs": self.clip_obs, "clip_reward": self.clip_reward,
+                "norm_obs": self.norm_obs, "norm_reward": self.norm_reward, "training": self.training}
+
+    def load_state_dict(self, state: dict) -> None:
+        for name in ("obs_mean", "obs_var", "obs_count", "ret_stats", "returns"):
+            mine, t = getattr(self, name), torch.as_tensor(state[name])
+            if t.dtype != torch.float64 or tuple(t.shape) != tuple(mine.shape):
+                raise ValueError(f"{name} must be a torch.float64 tensor of shape {list(mine.shape)}")
+        for name in ("obs_mean", "obs_var", "obs_count", "ret_stats", "returns"):
+            getattr(self, name).copy_(torch.as_tensor(state[name]))
+        for name in ("gamma", "epsilon", "clip_obs", "clip_reward"):
+            if name in state:
+                setattr(self, name, float(state[name]))
+        for name in ("norm_obs", "norm_reward", "training"):
+            if name in state:
+                setattr(self, name, bool(state[name]))
+
+    def _check_rows(self, rows) -> tuple:
+        K, N, stride = _check_scan_rows(_norm_rows(rows))
+        if N != self.n or rows.device != self.device:
+            raise ValueError(f"rows must hold records of {self.n} envs on {self.device} (got {N} envs on {rows.device})")
+        return K, N, stride
+
+    def _ready(self, L, K, N) -> torch.Tensor:
+        need = int(L.bg_norm_workspace_bytes(K, C.c_int64(N)))
+        if self._workspace is None or self._workspace.numel() < need:
+            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
+        return self._workspace
+
+    def normalize_obs(self, rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
+                      timing: bool = False):
+        """K VecNormalize steps over the observations of rows (contiguous uint8 [K, N, stride], or [N, stride] = one step): returns the normalised
+        [K, N, D] (or [N, D]) matrix of `layout` ("produced" 153 columns, "fixed" 628: the never-filled columns are 0.0) in `dtype` (torch.float32 or
+        torch.bfloat16).  out: optional contiguous tensor of that shape and dtype to write into.  timing=True appends the kernel milliseconds."""
+        if not self.norm_obs:
+            raise ValueError("this RowNormalizer was made with norm_obs=False: use encode_rows")
+        if layout not in ("produced", "fixed"):
+            raise ValueError(f"layout must be 'produced' or 'fixed' (got {layout!r}): VecNormalize wraps the env's keys, not the extractor's tensors")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        K, N, stride = self._check_rows(rows)
+        D = nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]
+        shape = (K, N, D) if rows.dim() == 3 else (N, D)
+        if out is not None:
+            _check_scan_tensor("out", out, dtype, shape, self.device)
+        if not rows.is_cuda:
+            raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+        if rows.data_ptr() % 16:
+            raise ValueError("rows must be 16-byte aligned")
+        if out is None:
+            out = torch.empty(shape, dtype=dtype, device=self.device)
+        if K * N == 0:
+            return (out, 0.0) if timing else out
+        L = nat.load()
+        ms = C.c_float(0.0)
+        with torch.cuda.device(self.device):
+            ws = self._ready(L, K, N)
+            rc = L.bg_norm_obs_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), nat.ENC_LAYOUTS[layout],
+                                    nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(self.obs_mean.data_ptr()),
+                                    C.c_void_p(self.obs_var.data_ptr()), C.c_void_p(self.obs_count.data_ptr()), 1 if self.training else 0,
+                                    C.c_double(self.epsilon), C.c_double(self.clip_obs), C.c_void_p(out.data_ptr()), C.c_uint64(D), None,
+                                    C.c_void_p(ws.data_ptr()), C.c_uint64(ws.numel()), C.byref(ms) if timing else None,
+                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise nat.NativeError(f"bg_norm_obs_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+        return (out, float(ms.value)) if timing else out
+
+    def normalize_reward(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None, timing: bool = False):
+        """K VecNormalize steps over the rewards of rows: returns the normalised rewards, float64 [K, N] (or [N] for [N, stride] rows), what
+        `gae_rows(..., rewards=)` takes.  out: optional contiguous float64 tensor of that shape.  timing=True appends the kernel milliseconds."""
+        if not self.norm_reward:
+            raise ValueError("this RowNormalizer was made with norm_reward=False: the records' own rewards are `RowBuffers.reward`")
+        K, N, stride = self._check_rows(rows)
+        shape = (K, N) if rows.dim() == 3 else (N,)
+        if out is not None:
+            _check_scan_tensor("out", out, torch.float64, shape, self.device)
+        if not rows.is_cuda:
+            raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+        if rows.data_ptr() % 16:
+            raise ValueError("rows must be 16-byte aligned")
+        if out is None:
+            out = torch.empty(shape, dtype=torch.float64, device=self.device)
+        if K * N == 0:
+            return (out, 0.0) if timing else out
+        L = nat.load()
+        ms = C.c_float(0.0)
+        with torch.cuda.device(self.device):
+            ws = self._ready(L, K, N)
+            rc = L.bg_norm_reward_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(self.returns.data_ptr()),
+                                       C.c_void_p(self.ret_stats.data_ptr()), 1 if self.training else 0, C.c_double(self.gamma), C.c_double(self.epsilon),
+                                       C.c_double(self.clip_reward), C.c_void_p(out.data_ptr()), None, C.c_void_p(ws.data_ptr()), C.c_uint64(ws.numel()),
+                                       C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
+        if rc != 0:
+            raise nat.NativeError(f"bg_norm_reward_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+        return (out, float(ms.value)) if timing else out
 
 
 def score_hand_batch(cases: torch.Tensor, lanes_per_case: int = 1, timing: bool = False):

@@ -464,6 +464,59 @@ int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, in
                           double* ep_return_carry_dev, int32_t* ep_len_carry_dev, double* ep_return_dev, int32_t* ep_len_dev,
                           float* kernel_ms_out, void* stream);
 
+/* bg_gae_rows with the rewards taken from a dense float64 [K, N] array instead of the records (rewards_dev; NULL = the record's reward: then it IS
+ * bg_gae_rows): how the normalised rewards of bg_norm_reward_rows reach the advantage scan.  Each value is converted to float32 as the record's reward
+ * is (round to nearest even); the terminated byte still comes from the record.  rewards_dev is 8-byte aligned and must not alias an output. */
+int bg_gae_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
+                   const float* values_dev, const float* last_values_dev, double gamma, double gae_lambda,
+                   float* advantages_dev, float* returns_dev, const double* rewards_dev, float* kernel_ms_out, void* stream);
+
+/* SB3's VecNormalize over [K, N] packed records, on the device: the last wrapper between the env and the network in the reference's training scripts.
+ * Replaces: `VecNormalize(env, norm_obs=True, norm_reward=True, clip_obs=10.0)` (hpc_train.py:68,72; train_balatro_agent.py:319,323), whose pickle is
+ * saved beside every checkpoint (hpc_train.py:101-107,151-152): per step a numpy mean / var over the envs of every key, a RunningMeanStd merge, a
+ * subtract / divide / clip, and the same for the discounted-return statistics of the reward.
+ * Records, K, N, alignment: as bg_gae_rows (record (t, e) at rows_dev + (t * N + e) * row_stride_bytes; 16-byte aligned; stride a multiple of 16, >=
+ * BG_ROW_BYTES).  Both calls run on the current device, need no handle, return BG_E_ARG (text in bg_last_error(NULL)) before launching anything, treat
+ * K == 0 or N == 0 as a no-op, never synchronise the host (several launches on `stream`); kernel_ms_out as in bg_classify_batch_ex.
+ * workspace_dev: 16-byte aligned scratch of >= bg_norm_workspace_bytes(K, N) bytes (the per-workgroup partial moments of either call).
+ *
+ * RunningMeanStd (float64; a fresh one is mean 0, var 1, count 1e-4) is updated with a batch's mean bm, population variance bv and size n by
+ *     delta = bm - mean;  tot = count + n;  new_mean = mean + delta * n / tot;  m_a = var * count;  m_b = bv * n
+ *     m_2 = m_a + m_b + square(delta) * count * n / (count + n);  new_var = m_2 / (count + n);  new_count = n + count
+ * evaluated left to right, every operation rounded on its own (no fused multiply-add), `/` and sqrt IEEE operations.
+ *
+ * bg_norm_obs_rows: step t is the batch of the N records (t, 0..N-1).  The statistics are one (mean, var) per column of the BG_ENC_PRODUCED layout
+ * (153 columns: one RunningMeanStd per key, of the key's shape) and one shared count.  update != 0: per step, in order, the statistics are updated
+ * with the step's batch moments and row t is normalised with the statistics AFTER its own update,
+ *     out[t][e][c] = float32(clip((float64(x) - mean[c]) / sqrt(var[c] + epsilon), -clip_obs, clip_obs))
+ * (x converted from the key's own dtype); after the call mean_dev / var_dev / count_dev hold the state behind step K-1.  update == 0: every row is
+ * normalised with the statistics as given, which are not written; moments_dev must be NULL.  layout BG_ENC_PRODUCED or BG_ENC_FIXED (its columns
+ * 153..627 are written as 0.0 and carry no statistics: (0 - 0) / sqrt(var + epsilon)); BG_ENC_EXTRACTOR is a BG_E_ARG.  out_dtype BG_ENC_BF16: the
+ * float32 result rounded to nearest even.  out_dev: [K * N, out_stride_elems], columns beyond the layout's count left untouched, 16-byte stores
+ * under bg_encode_rows' rule; NULL = statistics only.  moments_dev: [K, 2, 153], the batch mean and batch variance of every step, or NULL.
+ *
+ * bg_norm_reward_rows, per step t: ret[e] = ret[e] * gamma + reward[t][e]; ret_stats (mean, var, count of a RunningMeanStd of shape ()) is updated with
+ * the batch moments of ret over e; rewards[t][e] = clip(reward[t][e] / sqrt(var + epsilon), -clip_reward, clip_reward) (float64, dense [K, N], may be
+ * NULL); ret[e] = 0 where the record's terminated byte is set.  returns_carry_dev [N] holds ret across calls: 2 K steps give the same bits in two
+ * calls of K as in one.  update == 0: only the normalisation, with ret_stats as given; neither ret_stats nor the carry is written.  moments_dev: [K, 2].
+ *
+ * What is numpy's to the bit and what is bounded: the batch moments are the mean and population variance of float64(x) over the N envs, reduced as
+ * (n, mean, M2) triples merged in a fixed tree -- deterministic (no atomics; the same inputs give the same bits on every call), exactly 0.0 variance
+ * for a column that is constant over the batch, and within summation error of numpy.mean / numpy.var(x.astype(float64), axis=0), whose own order of
+ * additions is an implementation detail.  (For the float32 key `progress_ratio` this is more accurate than SB3, which sums that key in float32.)
+ * Everything behind the reduction -- the merge chain, the normalisation, the return recurrence -- is bit for bit the float64 expressions above.
+ * Outputs must not alias inputs or each other.  Truncation, the extractor layout and terminal observations are out of scope. */
+#define BG_NORM_COLS 153
+uint64_t bg_norm_workspace_bytes(int K, int64_t N);
+int bg_norm_obs_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, int layout, int out_dtype,
+                     double* mean_dev, double* var_dev, double* count_dev, int update, double epsilon, double clip_obs,
+                     void* out_dev, uint64_t out_stride_elems, double* moments_dev,
+                     void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
+                        double* returns_carry_dev, double* ret_stats_dev, int update, double gamma, double epsilon, double clip_reward,
+                        double* rewards_dev, double* moments_dev,
+                        void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,209 @@
+"""Numpy restatement of SB3's VecNormalize (stable_baselines3/common/vec_env/vec_normalize.py, running_mean_std.py) over packed records, shared by
+tests/test_norm_rows_host.py and tests/test_norm_rows.py.  No SB3 is needed: RunningMeanStd and the VecNormalize step are written out from their
+definitions, in float64, in their order of evaluation.
+
+The observation of a record is the `produced` matrix of tests/encode_ref.py BEFORE its float32 conversion: every key of the same record bytes in its
+own dtype, converted to float64 (`produced64`).  Two entry points:
+  vecnormalize(records, state, ...)           the batch moments are numpy's own mean / var of the float64-converted batch
+  from_moments(records, moments, state, ...)  the batch moments are taken as given; everything behind them is the same code
+Everything is compared as bit patterns."""
+import numpy as np
+
+from tests import encode_ref, gae_ref
+from tests.helpers import OBS_KEYS
+
+COLS = 153
+FIXED_COLS = 628
+DEFAULTS = dict(gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0)
+
+
+# ---- RunningMeanStd(epsilon=1e-4, shape) ----
+def new_state(n):
+    """A fresh VecNormalize for n envs: obs_rms of 153 columns with one shared count, ret_rms of shape (), returns = zeros(n)."""
+    return {"obs_mean": np.zeros(COLS, np.float64), "obs_var": np.ones(COLS, np.float64), "obs_count": np.float64(1e-4),
+            "ret_mean": np.float64(0.0), "ret_var": np.float64(1.0), "ret_count": np.float64(1e-4), "returns": np.zeros(n, np.float64)}
+
+
+def copy_state(s):
+    return {k: np.array(v, dtype=np.float64, copy=True) if np.ndim(v) else np.float64(v) for k, v in s.items()}
+
+
+def update_from_moments(mean, var, count, batch_mean, batch_var, batch_count):
+    """RunningMeanStd.update_from_moments, verbatim."""
+    delta = batch_mean - mean
+    tot_count = count + batch_count
+    new_mean = mean + delta * batch_count / tot_count
+    m_a = var * count
+    m_b = batch_var * batch_count
+    m_2 = m_a + m_b + np.square(delta) * count * batch_count / (count + batch_count)
+    new_var = m_2 / (count + batch_count)
+    new_count = batch_count + count
+    return new_mean, new_var, new_count
+
+
+# ---- records ----
+def produced64(rows):
+    """uint8 [K, N, stride] records -> float64 [K, N, 153]: every key in its own dtype (encode_ref.unpack_records), `.astype(float64)`, in key order."""
+    rows = np.ascontiguousarray(rows)
+    K, N, stride = rows.shape
+    obs = encode_ref.unpack_records(rows.reshape(K * N, stride))
+    x = np.concatenate([np.asarray(obs[k]).astype(np.float64).reshape(K * N, -1) for k in OBS_KEYS], axis=1)
+    assert x.shape == (K * N, COLS)
+    return x.reshape(K, N, COLS)
+
+
+def numpy_moments(rows, state=None, gamma=0.99):
+    """What numpy itself gives: {"obs": [K, 2, 153], "ret": [K, 2]} = mean / population variance of the float64 batch of every step (the returns follow
+    the recurrence from state["returns"], zeros when no state is given)."""
+    rows = np.ascontiguousarray(rows)
+    K, N, _ = rows.shape
+    x = produced64(rows)
+    reward, done = gae_ref.unpack_records(rows)
+    ret = np.zeros(N, np.float64) if state is None else np.array(state["returns"], np.float64)
+    mo, mr = np.zeros((K, 2, COLS), np.float64), np.zeros((K, 2), np.float64)
+    for t in range(K):
+        mo[t, 0], mo[t, 1] = np.mean(x[t], axis=0), np.var(x[t], axis=0)
+        ret = ret * gamma + reward[t]
+        mr[t, 0], mr[t, 1] = np.mean(ret), np.var(ret)
+        ret[done[t]] = 0
+    return {"obs": mo, "ret": mr}
+
+
+def _run(rows, state, moments, gamma, epsilon, clip_obs, clip_reward, training):
+    rows = np.ascontiguousarray(rows)
+    K, N, _ = rows.shape
+    s = copy_state(state)
+    x = produced64(rows)
+    reward, done = gae_ref.unpack_records(rows)
+    obs_n = np.zeros((K, N, COLS), np.float32)
+    rew_n = np.zeros((K, N), np.float64)
+    with np.errstate(all="ignore"):
+        for t in range(K):
+            obs = x[t]
+            if training:   # obs_rms[key].update(obs[key]) for every key: one (mean, var) per column, one count
+                s["obs_mean"], s["obs_var"], s["obs_count"] = update_from_moments(s["obs_mean"], s["obs_var"], s["obs_count"], moments["obs"][t, 0], moments["obs"][t, 1], N)
+            obs_n[t] = np.clip((obs - s["obs_mean"]) / np.sqrt(s["obs_var"] + epsilon), -clip_obs, clip_obs).astype(np.float32)
+            if training:   # _update_reward
+                s["returns"] = s["returns"] * gamma + reward[t]
+                s["ret_mean"], s["ret_var"], s["ret_count"] = update_from_moments(s["ret_mean"], s["ret_var"], s["ret_count"], moments["ret"][t, 0], moments["ret"][t, 1], N)
+            rew_n[t] = np.clip(reward[t] / np.sqrt(s["ret_var"] + epsilon), -clip_reward, clip_reward)
+            if training:
+                s["returns"][done[t]] = 0
+    return {"obs": obs_n, "reward": rew_n, "state": s}
+
+
+def vecnormalize(rows, state, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0, training=True):
+    """K VecNormalize steps over uint8 [K, N, stride] records with numpy's own batch moments -> {"obs" float32 [K, N, 153], "reward" float64 [K, N],
+    "state"}.  `state` is not modified."""
+    return _run(rows, state, numpy_moments(rows, state, gamma) if training else None, gamma, epsilon, clip_obs, clip_reward, training)
+
+
+def from_moments(rows, moments, state, gamma=0.99, epsilon=1e-8, clip_obs=10.0, clip_reward=10.0, training=True):
+    """The same with the batch moments as given: moments = {"obs": float64 [K, 2, 153], "ret": float64 [K, 2]} (ignored when not training)."""
+    return _run(rows, state, moments, gamma, epsilon, clip_obs, clip_reward, training)
+
+
+def obs_bits(obs_n, layout="produced", dtype="float32"):
+    """The normalised float32 [..., 153] matrix as the bit patterns of `layout` / `dtype`: uint32 or (bfloat16) uint16 [..., D]."""
+    b = np.ascontiguousarray(obs_n, np.float32).view(np.uint32)
+    if layout == "fixed":
+        b = np.concatenate([b, np.zeros(b.shape[:-1] + (FIXED_COLS - COLS,), np.uint32)], axis=-1)
+    return encode_ref.bf16_bits(b) if dtype == "bfloat16" else b
+
+
+# ---- the bound on the batch moments (the issue's: 4 N 2**-53 relative to mean(|x|) and to the variance; exactly 0.0 for a constant column) ----
+def moment_bounds(x):
+    """x float64 [N, C] -> (mean bound [C], var bound [C], constant [C])."""
+    N = x.shape[0]
+    f = 4.0 * N * 2.0 ** -53
+    return f * np.mean(np.abs(x), axis=0), f * np.var(x, axis=0), np.all(x == x[0], axis=0)
+
+
+def check_moments(got_mean, got_var, x, what):
+    """Prints the worst ratios to the bound, then asserts.  x float64 [N, C] (or [N] for the returns)."""
+    x = np.asarray(x, np.float64)
+    x = x.reshape(x.shape[0], -1)
+    got_mean, got_var = np.asarray(got_mean, np.float64).reshape(-1), np.asarray(got_var, np.float64).reshape(-1)
+    bm, bv, const = moment_bounds(x)
+    dm, dv = np.abs(got_mean - np.mean(x, axis=0)), np.abs(got_var - np.var(x, axis=0))
+    assert np.all(got_var[const] == 0.0), f"{what}: a constant column has batch variance {got_var[const][got_var[const] != 0.0][:3]}"
+    assert np.all(got_mean[const] == x[0][const]), f"{what}: a constant column's batch mean is not that constant"
+    with np.errstate(all="ignore"):
+        rm, rv = np.where(dm > 0, dm / bm, 0.0), np.where(dv > 0, dv / bv, 0.0)
+    assert np.all(dm <= bm), f"{what}: batch mean off by {rm.max():.3f} of the bound (column {int(rm.argmax())})"
+    assert np.all(dv <= bv), f"{what}: batch variance off by {rv.max():.3f} of the bound (column {int(rv.argmax())})"
+    return float(rm.max()), float(rv.max())
+
+
+# ---- synthetic records ----
+def synthetic_rows(K, N, stride, seed):
+    """uint8 [K, N, stride] records no game writes, every value exactly representable in float64:
+    constant columns (mult = 1, joker_slots = 5, chips_needed = 2**31 - 1, deck_size = -128: batch variance exactly 0); money mostly -60..60 with a rare
+    +-10**6 (clips on both sides once the statistics have settled; negative money); chips_scored just above 2**24, up to +-(2**53 - 1), and small;
+    round_chips_scored over all of int32; hand with -1 padding; progress_ratio float32 in [0, 2) with exact zeros; flags in the int64 keys; rewards of
+    both signs with a rare +-10**7 (clip on both sides); terminated bytes of any nonzero value on about a sixth of the steps."""
+    from balatro_gym_amd import _native as nat
+    rng = np.random.default_rng(seed)
+    m = K * N
+    obs = {}
+    for k in OBS_KEYS:
+        dt, shape = nat.OBS_SPEC[k]
+        if dt == "float32":
+            a = rng.uniform(0.0, 2.0, (m,) + shape).astype(np.float32)
+            a[rng.integers(0, 5, (m,) + shape) == 0] = 0.0
+        elif dt == "int64":
+            a = rng.integers(0, 2, (m,) + shape).astype(np.int64)
+        else:
+            ii = np.iinfo(np.dtype(dt))
+            lo, hi = max(ii.min, -30000), min(ii.max, 30000)
+            a = rng.integers(lo, hi, (m,) + shape, endpoint=True).astype(np.dtype(dt))
+        obs[k] = a
+    obs["hand"] = rng.integers(-1, 52, obs["hand"].shape).astype(np.int8)
+    obs["hand"][rng.integers(0, 3, m) == 0, 5:] = -1
+    obs["mult"][:] = 1
+    obs["joker_slots"][:] = 5
+    obs["chips_needed"][:] = 2 ** 31 - 1
+    obs["deck_size"][:] = -128
+    money = rng.integers(-60, 61, m).astype(np.int32)
+    big = rng.integers(0, 500, m)
+    money[big == 0], money[big == 1] = 10 ** 6, -10 ** 6
+    obs["money"] = money.reshape(obs["money"].shape)
+    kind = rng.integers(0, 4, m)
+    chips = rng.integers(-(2 ** 53) + 1, 2 ** 53, m)
+    chips = np.where(kind == 0, 2 ** 24 + 1 + 2 * rng.integers(0, 1000, m), chips)
+    chips = np.where(kind == 1, rng.integers(0, 300, m), chips)
+    chips = np.where(kind == 2, (2 ** 53 - 1) * rng.choice([-1, 1], m), chips)
+    obs["chips_scored"] = chips.astype(np.int64).reshape(obs["chips_scored"].shape)
+    obs["round_chips_scored"] = rng.integers(-2 ** 31, 2 ** 31, obs["round_chips_scored"].shape).astype(np.int32)
+    rows = encode_ref.pack_records(obs, stride).reshape(K, N, stride).copy()
+    rows[:, :, gae_ref.ROW_BYTES:] = 0xa5
+    reward = rng.uniform(-50.0, 100.0, (K, N))
+    big = rng.integers(0, 500, (K, N))
+    reward[big == 0], reward[big == 1] = 1e7, -1e7
+    reward[rng.integers(0, 10, (K, N)) == 0] = -1.0
+    done = (rng.integers(0, 6, (K, N)) == 0).astype(np.uint8) * rng.integers(1, 256, (K, N)).astype(np.uint8)
+    rows[:, :, gae_ref.ROW_REWARD:gae_ref.ROW_REWARD + 8] = np.ascontiguousarray(reward).view(np.uint8).reshape(K, N, 8)
+    rows[:, :, gae_ref.ROW_TERMINATED] = done
+    return rows
+
+
+SYN_N = (1, 2, 63, 65, 300)
+SYN_K = (1, 17, 33)
+
+
+def synthetic_cases():
+    """(K, N, stride, seed): every N with every K, the strides alternating so that each goes with each N and each K."""
+    out, i = [], 0
+    for K in SYN_K:
+        for N in SYN_N:
+            out.append((K, N, (352, 384)[i % 2], 7000 + i))
+            i += 1
+    return out
+
+
+def bits32(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def bits64(a):
+    return np.ascontiguousarray(a, dtype=np.float64).view(np.uint64)
