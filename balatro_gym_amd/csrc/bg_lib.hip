@@ -331,6 +331,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_encode.h" // packed records -> policy-network input (operator-level)
 #include "bg_gae.h"    // packed records -> advantages / returns and episode statistics (operator-level)
 #include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
+#include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -2203,6 +2204,64 @@ int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int 
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);
+}
+
+// logits + action masks -> the policy head (bg_head.h).  The load paths follow the alignment of the caller's matrices.
+static int bg_head_call(const char* who, int mode, const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev,
+                        uint64_t mask_stride_bytes, int64_t m, uint64_t seed, uint64_t index0, uint64_t t, const int32_t* actions_in, int32_t* actions_out,
+                        float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream) {
+  const bool bf16 = logits_dtype == BG_HEAD_BF16;
+  const uint64_t es = bf16 ? 2u : 4u;
+  const void* const act = mode == BG_HEAD_EVALUATE ? (const void*)actions_in : (const void*)actions_out;
+  const char* bad = nullptr;
+  if (logits_dtype != BG_HEAD_F32 && logits_dtype != BG_HEAD_BF16) bad = "logits_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
+  else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
+  else if (!logits_dev || ((uintptr_t)logits_dev & (es - 1))) bad = "logits_dev must be a device pointer aligned to its element type";
+  else if (logits_stride_elems < BG_HEAD_ACTIONS || logits_stride_elems > 0xffffffffull) bad = "logits_stride_elems must be >= 60";
+  else if (mask_dev && (((uintptr_t)mask_dev & 3) || mask_stride_bytes < BG_HEAD_ACTIONS || (mask_stride_bytes & 3) || mask_stride_bytes > 0xffffffffull)) bad = "mask_dev must be 4-byte aligned and mask_stride_bytes a multiple of 4, >= 60";
+  else if (!act || ((uintptr_t)act & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
+  else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "log_prob_dev / entropy_dev must be 4-byte aligned";
+  else if ((log_prob_dev && log_prob_dev == entropy_dev) || (const void*)log_prob_dev == act || (const void*)entropy_dev == act) bad = "actions_dev, log_prob_dev and entropy_dev must not be the same pointer";
+  else if (act == logits_dev || act == (const void*)mask_dev || (log_prob_dev && ((const void*)log_prob_dev == logits_dev || (const void*)log_prob_dev == (const void*)mask_dev)) ||
+           (entropy_dev && ((const void*)entropy_dev == logits_dev || (const void*)entropy_dev == (const void*)mask_dev))) bad = "outputs must not alias the logits or the masks";
+  if (bad) { g_create_err = std::string(who) + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (m == 0) return 0;
+  const bool l16 = ((uintptr_t)logits_dev & 15) == 0;
+  int lld;
+  if (l16 && (logits_stride_elems * es) % 16 == 0) lld = BG_HEAD_LD_ROWS16;
+  else if (bf16 && l16 && logits_stride_elems == BG_HEAD_ACTIONS) lld = BG_HEAD_LD_FLAT16;
+  else if (!bf16 || (((uintptr_t)logits_dev & 3) == 0 && logits_stride_elems % 2 == 0)) lld = BG_HEAD_LD_WORD;
+  else lld = BG_HEAD_LD_HALF;
+  int mld = BG_HEAD_LD_NONE;
+  if (mask_dev) {
+    const bool m16 = ((uintptr_t)mask_dev & 15) == 0;
+    mld = m16 && mask_stride_bytes % 16 == 0 ? BG_HEAD_LD_ROWS16 : m16 && mask_stride_bytes == BG_HEAD_ACTIONS ? BG_HEAD_LD_FLAT16 : BG_HEAD_LD_WORD;
+  }
+  const unsigned grid = (unsigned)((m + BG_HEAD_ROWS - 1) / BG_HEAD_ROWS);
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+#define BG_HEAD_GO(M) hipLaunchKernelGGL((bg_head_kernel<M>), dim3(grid), dim3(BG_HEAD_BLOCK), 0, s, logits_dev, bf16 ? 1 : 0, lld, logits_stride_elems, mask_dev, mld, mask_stride_bytes, (long long)m, seed, index0, t, actions_in, actions_out, log_prob_dev, entropy_dev)
+  if (mode == BG_HEAD_SAMPLE) BG_HEAD_GO(BG_HEAD_SAMPLE); else if (mode == BG_HEAD_ARGMAX) BG_HEAD_GO(BG_HEAD_ARGMAX); else BG_HEAD_GO(BG_HEAD_EVALUATE);
+#undef BG_HEAD_GO
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+int bg_sample_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
+                      uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, int32_t* actions_dev, float* log_prob_dev, float* entropy_dev,
+                      float* kernel_ms_out, void* stream) {
+  if (flags & ~BG_HEAD_DETERMINISTIC) { g_create_err = "bg_sample_actions: flags must be 0 or BG_HEAD_DETERMINISTIC"; return BG_E_ARG; }
+  return bg_head_call("bg_sample_actions: ", flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE, logits_dev, logits_dtype, logits_stride_elems, mask_dev,
+                      mask_stride_bytes, m, seed, index0, t, nullptr, actions_dev, log_prob_dev, entropy_dev, kernel_ms_out, stream);
+}
+int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
+                        const int32_t* actions_dev, float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream) {
+  return bg_head_call("bg_evaluate_actions: ", BG_HEAD_EVALUATE, logits_dev, logits_dtype, logits_stride_elems, mask_dev, mask_stride_bytes, m, 0, 0, 0, actions_dev,
+                      nullptr, log_prob_dev, entropy_dev, kernel_ms_out, stream);
 }
 
 static int bg_batch_dev(BgDev& d, int m, uint32_t** scratch_out);

@@ -109,6 +109,11 @@ class RowBuffers:
         """The records' rewards as VecNormalize would hand them to the learner, float64 [steps, n] (`RowNormalizer.normalize_reward`)."""
         return norm.normalize_reward(self.rows, out)
 
+    def sample(self, logits: torch.Tensor, step: int = -1, **kwargs):
+        """(actions, log_prob, entropy) drawn from `logits` [n, 60] under the action mask of record row `step` (`sample_actions`; seed= and t= are
+        required): the mask a record carries is the one after its step, i.e. the mask of the action to take next."""
+        return sample_actions(logits, self.rows[step], **kwargs)
+
     def episode_stats(self, stats: "EpisodeStats"):
         """(ep_return float64, ep_len int32) [steps, n] of these records, continuing the episodes `stats` carries (`EpisodeStats.update`)."""
         return stats.update(self.rows)
@@ -203,6 +208,14 @@ class BalatroVecEnv:
         if self._rowbuf is None:
             raise ValueError("features() encodes the packed records of an obs_layout='rows' env")
         return encode_rows(self._rowbuf.rows[0], layout, dtype, out)
+
+    def act(self, logits: torch.Tensor, *, seed: int, t: int, deterministic: bool = False, log_prob: Optional[torch.Tensor] = None,
+            entropy: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [N] actions for `step()`, drawn from `logits` [N, 60] under the CURRENT action mask (`sample_actions` with index0 = 0: the live records
+        of an obs_layout="rows" env, `obs["action_mask"]` otherwise), so no env takes an invalid action.  log_prob / entropy: float32 [N] tensors that
+        receive what PPO stores."""
+        mask = self._rowbuf.rows[0] if self._rowbuf is not None else self._obs.tensors["action_mask"]
+        return sample_actions(logits, mask, seed=seed, t=t, deterministic=deterministic, log_prob=log_prob, entropy=entropy)[0]
 
     @property
     def obs_flat(self) -> torch.Tensor:
@@ -671,6 +684,120 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
         raise nat.NativeError(f"bg_encode_rows failed ({rc}): {L.bg_last_error(None).decode()}")
     res = out[..., :D]
     return (res, float(ms.value)) if timing else res
+
+
+
+def _head_logits(logits) -> tuple:
+    """logits of sample_actions / evaluate_actions: float32 / bfloat16 [..., 60] with a contiguous last dimension and leading dimensions dense over the
+    row pitch (e.g. 60 columns of a wider matrix) -> (leading shape, m, row pitch in elements)."""
+    if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16) or logits.dim() < 1 or logits.shape[-1] != 60:
+        raise ValueError("logits must be a float32 or bfloat16 tensor [..., 60]")
+    pitch = int(logits.stride(-2)) if logits.dim() >= 2 else 60
+    dense = logits.stride(-1) == 1 and pitch >= 60
+    for d in range(logits.dim() - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
+        dense = dense and logits.stride(d - 1) == logits.stride(d) * logits.shape[d]
+    if not dense:
+        raise ValueError("logits must have a contiguous last dimension and leading dimensions that are dense over its row pitch")
+    lead = tuple(logits.shape[:-1])
+    return lead, int(np.prod(lead, dtype=np.int64)), pitch
+
+
+def _head_mask(mask, lead: tuple, device: torch.device) -> tuple:
+    """mask of sample_actions / evaluate_actions -> (tensor to keep alive, byte offset of the first row's mask, row pitch in bytes): packed records
+    (a contiguous uint8 tensor [..., stride], recognised as encode_rows recognises them), an int8 [..., 60] matrix, or None."""
+    if mask is None:
+        return None, 0, 0
+    if not isinstance(mask, torch.Tensor) or mask.dim() < 1:
+        raise ValueError("mask must be a uint8 tensor [..., stride] of packed records, an int8 tensor [..., 60] or None")
+    if mask.dtype == torch.uint8:
+        stride = int(mask.shape[-1])
+        if not mask.is_contiguous() or stride < nat.ROW_BYTES or stride % 16:
+            raise ValueError(f"a uint8 mask is a contiguous tensor [..., stride] of packed records: stride a multiple of 16, >= {nat.ROW_BYTES}")
+        off = nat.ROW_OFFSETS["action_mask"]
+    elif mask.dtype == torch.int8 and mask.shape[-1] == 60:
+        stride = int(mask.stride(-2)) if mask.dim() >= 2 else 60
+        dense = mask.stride(-1) == 1 and stride >= 60
+        for d in range(mask.dim() - 2, 0, -1):
+            dense = dense and mask.stride(d - 1) == mask.stride(d) * mask.shape[d]
+        if not dense or stride % 4:
+            raise ValueError("an int8 mask must have a contiguous last dimension and leading dimensions dense over a row pitch that is a multiple of 4")
+        off = 0
+    else:
+        raise ValueError("mask must be a uint8 tensor [..., stride] of packed records, an int8 tensor [..., 60] or None")
+    if tuple(mask.shape[:-1]) != lead:
+        raise ValueError(f"mask must have the leading shape of logits {list(lead)} (got {list(mask.shape[:-1])})")
+    if mask.device != device:
+        raise ValueError(f"mask must be on {device}")
+    return mask, off, stride
+
+
+def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: int, t: int, actions, log_prob, entropy, timing: bool):
+    lead, m, pitch = _head_logits(logits)
+    dev = logits.device
+    mask, moff, mstride = _head_mask(mask, lead, dev)
+    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"{what} must be an integer in [0, 2**64)")
+    if given is not None:
+        _check_scan_tensor("actions", given, torch.int32, lead, dev)
+    for what, tt, dt in (("actions", actions, torch.int32), ("log_prob", log_prob, torch.float32), ("entropy", entropy, torch.float32)):
+        if tt is not None:
+            _check_scan_tensor(what, tt, dt, lead, dev)
+    if not logits.is_cuda:
+        raise ValueError("logits must be a device tensor (there is no CPU fallback)")
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+    if given is None and actions is None:
+        actions = torch.empty(lead, dtype=torch.int32, device=dev)
+    if log_prob is None:
+        log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
+    if entropy is None:
+        entropy = torch.empty(lead, dtype=torch.float32, device=dev)
+    res = (log_prob, entropy) if given is not None else (actions, log_prob, entropy)
+    if m == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
+        return res + (0.0,) if timing else res
+    outs = [x.data_ptr() for x in res]
+    ins = [logits.data_ptr()] + ([mask.data_ptr()] if mask is not None else []) + ([given.data_ptr()] if given is not None else [])
+    if len(set(outs)) != len(outs) or set(outs) & set(ins):
+        raise ValueError("outputs must not share memory with the inputs or with each other")
+    L = nat.load()
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        head = (C.c_void_p(logits.data_ptr()), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
+                C.c_void_p(mask.data_ptr() + moff) if mask is not None else None, C.c_uint64(mstride), C.c_int64(m))
+        tail = (C.c_void_p(log_prob.data_ptr()), C.c_void_p(entropy.data_ptr()), C.byref(ms) if timing else None,
+                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if given is None:
+            rc = L.bg_sample_actions(*head, C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)),
+                                     C.c_void_p(actions.data_ptr()), *tail)
+        else:
+            rc = L.bg_evaluate_actions(*head, C.c_void_p(given.data_ptr()), *tail)
+    if rc != 0:
+        raise nat.NativeError(f"{name} failed ({rc}): {L.bg_last_error(None).decode()}")
+    return res + (float(ms.value),) if timing else res
+
+
+def sample_actions(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, *, seed: int, t: int, index0: int = 0, deterministic: bool = False,
+                   actions: Optional[torch.Tensor] = None, log_prob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
+                   timing: bool = False):
+    """The masked categorical policy head in one launch (bg_sample_actions): logits float32 / bfloat16 [..., 60] -> (actions int32, log_prob float32,
+    entropy float32), each [...].  mask: packed records (a contiguous uint8 tensor [..., stride]: `RowBuffers.rows[t]`, `env.obs_rows` -- their
+    action_mask field is read in place), an int8 [..., 60] matrix (`obs["action_mask"]`) or None (every action valid).  A masked action is never
+    drawn; a row with no valid action (or a NaN / +inf valid logit) gives action -1 and NaN.  Row i draws with the counter hash of (seed, index0 + i,
+    t), the rollout's: the same arguments give the same bits, whatever the batch shape or sharding (a shard passes its first global env as index0).
+    deterministic=True takes the first valid maximum instead (SB3's `mode()`).  A record's mask is the mask AFTER its step: it goes with the logits
+    computed from that record.  actions / log_prob / entropy: optional contiguous tensors to write into.  timing=True appends kernel milliseconds."""
+    return _head_call("bg_sample_actions", logits, mask, None, nat.HEAD_DETERMINISTIC if deterministic else 0, seed, index0, t, actions, log_prob,
+                      entropy, timing)
+
+
+def evaluate_actions(logits: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None, *, log_prob: Optional[torch.Tensor] = None,
+                     entropy: Optional[torch.Tensor] = None, timing: bool = False):
+    """(log_prob, entropy) float32 [...] of given int32 actions [...] under the masked distribution of `sample_actions` (bg_evaluate_actions; forward
+    only, no autograd): bit for bit what the sampler returned for the actions it drew.  A masked action has log_prob -inf, one outside [0, 60) NaN."""
+    if not isinstance(actions, torch.Tensor):
+        raise ValueError("actions must be an int32 tensor with the leading shape of logits")
+    return _head_call("bg_evaluate_actions", logits, mask, actions, 0, 0, 0, 0, None, log_prob, entropy, timing)
 
 
 def _check_scan_rows(rows) -> tuple:

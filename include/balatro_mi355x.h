@@ -517,6 +517,49 @@ int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int 
                         double* rewards_dev, double* moments_dev,
                         void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* The masked categorical policy head: [m, 60] logits -> the int32 actions bg_step_rows / bg_step_many_rows take, with the log-probability and the
+ * entropy PPO stores, in ONE launch; bg_evaluate_actions is the forward pass for given actions.  The arithmetic is csrc/bg_head.h.
+ * Replaces: with mask_dev == NULL, SB3's `CategoricalDistribution.sample / log_prob / entropy / mode` as `PPO("MultiInputPolicy", ...)` runs them on
+ * every step (hpc_train.py:77-86); with a mask, the discipline of the reference's own driver loop, which draws only from `action_mask`
+ * (balatro_env_2.py:1841-1849) -- an invalid action costs reward -1.0 and a wasted step (balatro_env_2.py:625-627), and the training scripts, which
+ * ignore the mask, end an episode with -50 after 50 of them (SafeBalatroEnv, train_balatro_fixed.py:228-283).
+ *
+ * A row is 60 logits l[j] (BG_HEAD_F32, or BG_HEAD_BF16 widened exactly: bits << 16) and 60 mask bytes (non-zero = valid; mask_dev == NULL = all
+ * valid); V = the valid j.  All arithmetic is float32, every operation rounded on its own (no fused multiply-add):
+ *     m = max over V of l[j];  d[j] = l[j] - m;  e[j] = expf(d[j]);  P[j] = running sum of e over the valid j in index order 0..59;  S = P[59]
+ *     A = running sum, same order, of e[j] * d[j] over the valid j with e[j] > 0
+ *     sample:         h = bg_policy_hash(seed, index0 + i, t)  (the rollout's splitmix64 counter hash, high 32 bits);  u = float(h >> 8) * 2^-24;
+ *                     action = the smallest valid j with P[j] > u * S  (else the largest valid j with e[j] > 0: never taken for finite inputs)
+ *     deterministic:  action = the smallest valid j with l[j] == m                                                (flags & BG_HEAD_DETERMINISTIC)
+ *     log_prob = d[action] - logf(S);  entropy = logf(S) - A / S
+ *     evaluate:       the action is given; in range but masked -> log_prob = -inf; outside [0, 60) -> log_prob = NaN; the entropy is unchanged
+ * A DEGENERATE row -- V empty, a valid logit NaN or +inf, or every valid logit -inf -- gives action = -1 (an invalid action to the step entry points)
+ * and log_prob = entropy = quiet NaN (0x7fc00000) in every mode; a valid -inf logit beside finite ones has probability 0.  So a masked action and an
+ * action of probability 0 are never returned, and row i is a pure function of (its logits, its mask, seed, index0 + i, t): independent of m, of the
+ * launch shape and of sharding (index0 / t mirror bg_rollout's env_index0 / t0: a sharded job passes its shard's first global env).  expf / logf are the
+ * device library's accurate functions: the same inputs give the same bits on every call; they are bounded against float64, not promised glibc's bits.
+ *
+ * logits_dev: row i starts at element i * logits_stride_elems (>= 60), the pointer aligned to the element.  mask_dev: the first row's 60 mask bytes,
+ * row i at + i * mask_stride_bytes (>= 60, a multiple of 4), the pointer 4-byte aligned; the mask of records is rows_dev + BG_ROW_ACTION_MASK with
+ * the row stride (offset 176 is 16-byte aligned), the per-key layout's [N, 60] int8 array passes stride 60.  16-byte loads when pointer and row
+ * pitch are 16-byte aligned or the pointer is and the matrix is dense; 4- or 2-byte loads per lane otherwise.  ALIGNMENT IN TIME: a record's mask is
+ * the mask AFTER that record's step, so it belongs to the NEXT action (record t's mask goes with the logits computed from record t).
+ * actions_dev int32 [m]; log_prob_dev / entropy_dev float32 [m], each may be NULL.  Outputs must not alias inputs or each other.  Both calls run on the
+ * current device, need no handle, return BG_E_ARG (text in bg_last_error(NULL)) before launching anything, treat m == 0 as a no-op and never
+ * synchronise unless timing is asked for; kernel_ms_out as in bg_classify_batch_ex.  Gradients, temperature and truncation are out of scope. */
+#define BG_HEAD_F32 0
+#define BG_HEAD_BF16 1
+#define BG_HEAD_DETERMINISTIC 1u /* flags */
+int bg_sample_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems,
+                      const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m, uint32_t flags,
+                      uint64_t seed, uint64_t index0, uint64_t t,
+                      int32_t* actions_dev, float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+                      float* kernel_ms_out, void* stream);
+int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems,
+                        const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
+                        const int32_t* actions_dev, float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+                        float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
