@@ -332,6 +332,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_gae.h"    // packed records -> advantages / returns and episode statistics (operator-level)
 #include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
 #include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
+#include "bg_ppo.h"    // logits + stored rollout arrays -> PPO's clipped loss, its diagnostics and its gradient (operator-level)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -2262,6 +2263,92 @@ int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logit
                         const int32_t* actions_dev, float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream) {
   return bg_head_call("bg_evaluate_actions: ", BG_HEAD_EVALUATE, logits_dev, logits_dtype, logits_stride_elems, mask_dev, mask_stride_bytes, m, 0, 0, 0, actions_dev,
                       nullptr, log_prob_dev, entropy_dev, kernel_ms_out, stream);
+}
+
+// logits + the stored arrays of a rollout -> PPO's loss, diagnostics and gradient (bg_ppo.h).  Workspace: BG_PPO_WS_HEAD bytes (mean, std, apply), one
+// (n, mean, M2) triple per 256 rows, six float64 sums per 64 rows.
+uint64_t bg_ppo_loss_workspace_bytes(int64_t m) {
+  if (m <= 0) return 0;
+  return BG_PPO_WS_HEAD + bg_ppo_stat_parts(m) * sizeof(BgPpoMoments) + bg_ppo_row_parts(m) * (BG_PPO_SUMS * sizeof(double));
+}
+
+int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes,
+                const int32_t* actions_dev, const float* old_log_prob_dev, const float* advantages_dev, const float* values_dev, const float* returns_dev,
+                const int32_t* index_dev, int64_t store_rows, int64_t m, float clip_range, float ent_coef, float vf_coef, uint32_t flags, void* dlogits_dev,
+                uint64_t dlogits_stride_elems, float* dvalues_dev, float* log_prob_dev, float* entropy_dev, float* stats_dev, void* workspace_dev,
+                uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
+  const bool bf16 = logits_dtype == BG_HEAD_BF16;
+  const uint64_t es = bf16 ? 2u : 4u;
+  const void* const ins[] = {logits_dev, mask_dev, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev};
+  const void* const outs[] = {dlogits_dev, dvalues_dev, log_prob_dev, entropy_dev, stats_dev, workspace_dev};
+  bool alias = false;
+  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
+    if (!outs[o]) continue;
+    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
+    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
+  }
+  const char* bad = nullptr;
+  if (logits_dtype != BG_HEAD_F32 && logits_dtype != BG_HEAD_BF16) bad = "logits_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
+  else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
+  else if (flags & ~BG_PPO_NORMALIZE_ADV) bad = "flags must be 0 or BG_PPO_NORMALIZE_ADV";
+  else if (!(clip_range > 0.0f && clip_range < 1.0f)) bad = "clip_range must be in (0, 1)";
+  else if (!bg_ppo_finite(ent_coef) || !bg_ppo_finite(vf_coef)) bad = "ent_coef and vf_coef must be finite";
+  else if (!logits_dev || ((uintptr_t)logits_dev & (es - 1))) bad = "logits_dev must be a device pointer aligned to its element type";
+  else if (logits_stride_elems < BG_HEAD_ACTIONS || logits_stride_elems > 0xffffffffull) bad = "logits_stride_elems must be >= 60";
+  else if (!dlogits_dev || ((uintptr_t)dlogits_dev & (es - 1))) bad = "dlogits_dev must be a device pointer aligned to its element type";
+  else if (dlogits_stride_elems < BG_HEAD_ACTIONS || dlogits_stride_elems > 0xffffffffull) bad = "dlogits_stride_elems must be >= 60";
+  else if (mask_dev && (((uintptr_t)mask_dev & 3) || mask_stride_bytes < BG_HEAD_ACTIONS || (mask_stride_bytes & 3) || mask_stride_bytes > 0xffffffffull)) bad = "mask_dev must be 4-byte aligned and mask_stride_bytes a multiple of 4, >= 60";
+  else if (!actions_dev || !old_log_prob_dev || !advantages_dev || (((uintptr_t)actions_dev | (uintptr_t)old_log_prob_dev | (uintptr_t)advantages_dev) & 3)) bad = "actions_dev, old_log_prob_dev and advantages_dev must be 4-byte aligned device pointers";
+  else if ((values_dev == nullptr) != (returns_dev == nullptr)) bad = "values_dev and returns_dev go together: both or neither";
+  else if (((uintptr_t)values_dev | (uintptr_t)returns_dev | (uintptr_t)index_dev | (uintptr_t)dvalues_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "values_dev, returns_dev, index_dev, dvalues_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
+  else if (dvalues_dev && !values_dev) bad = "dvalues_dev needs values_dev and returns_dev";
+  else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
+  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_PPO_STATS floats";
+  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_ppo_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_ppo_loss_workspace_bytes(m) bytes";
+  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  if (bad) { g_create_err = std::string("bg_ppo_loss: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  hipStream_t s = (hipStream_t)stream;
+  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_PPO_STATS * sizeof(float), s)); return 0; }
+  BgPpoArgs A;
+  A.logits = logits_dev; A.lstride = logits_stride_elems;
+  const bool l16 = ((uintptr_t)logits_dev & 15) == 0;
+  if (l16 && (logits_stride_elems * es) % 16 == 0) A.lld = BG_HEAD_LD_ROWS16;
+  else if (bf16 && l16 && logits_stride_elems == BG_HEAD_ACTIONS) A.lld = BG_HEAD_LD_FLAT16;
+  else if (!bf16 || (((uintptr_t)logits_dev & 3) == 0 && logits_stride_elems % 2 == 0)) A.lld = BG_HEAD_LD_WORD;
+  else A.lld = BG_HEAD_LD_HALF;
+  const bool d16 = ((uintptr_t)dlogits_dev & 15) == 0;
+  if (d16 && (dlogits_stride_elems * es) % 16 == 0) A.dst = BG_HEAD_LD_ROWS16;
+  else if (bf16 && d16 && dlogits_stride_elems == BG_HEAD_ACTIONS) A.dst = BG_HEAD_LD_FLAT16;
+  else if (!bf16 || (((uintptr_t)dlogits_dev & 3) == 0 && dlogits_stride_elems % 2 == 0)) A.dst = BG_HEAD_LD_WORD;
+  else A.dst = BG_HEAD_LD_HALF;
+  A.mask = mask_dev; A.mstride = mask_stride_bytes; A.mld = BG_HEAD_LD_NONE;
+  if (mask_dev) {
+    const bool m16 = ((uintptr_t)mask_dev & 15) == 0;
+    A.mld = m16 && mask_stride_bytes % 16 == 0 ? BG_HEAD_LD_ROWS16 : !index_dev && m16 && mask_stride_bytes == BG_HEAD_ACTIONS ? BG_HEAD_LD_FLAT16 : BG_HEAD_LD_WORD;
+  }
+  A.actions = actions_dev; A.old_lp = old_log_prob_dev; A.adv = advantages_dev; A.values = values_dev; A.returns = returns_dev;
+  A.index = index_dev; A.store_rows = (long long)store_rows; A.m = (long long)m;
+  A.c.clip = clip_range; A.c.lo = 1.0f - clip_range; A.c.hi = 1.0f + clip_range; A.c.ent_coef = ent_coef; A.c.vf_coef = vf_coef; A.c.fm = (float)m;
+  A.normalize = flags & BG_PPO_NORMALIZE_ADV ? 1 : 0;
+  A.dlogits = dlogits_dev; A.dstride = dlogits_stride_elems; A.dvalues = dvalues_dev; A.log_prob = log_prob_dev; A.entropy = entropy_dev;
+  float* const head = (float*)workspace_dev;
+  BgPpoMoments* const mom = (BgPpoMoments*)((uint8_t*)workspace_dev + BG_PPO_WS_HEAD);
+  const uint64_t SP = bg_ppo_stat_parts(m), RP = bg_ppo_row_parts(m);
+  A.head = head; A.partials = (double*)(mom + SP);
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (A.normalize) {
+    hipLaunchKernelGGL(bg_ppo_adv_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, advantages_dev, index_dev, (long long)store_rows, (long long)m, mom);
+    hipLaunchKernelGGL(bg_ppo_adv_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, mom, (long long)SP, head);
+  }
+  if (bf16) hipLaunchKernelGGL((bg_ppo_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+  else hipLaunchKernelGGL((bg_ppo_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+  hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
 }
 
 static int bg_batch_dev(BgDev& d, int m, uint32_t** scratch_out);

@@ -793,11 +793,126 @@ def sample_actions(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
 
 def evaluate_actions(logits: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None, *, log_prob: Optional[torch.Tensor] = None,
                      entropy: Optional[torch.Tensor] = None, timing: bool = False):
-    """(log_prob, entropy) float32 [...] of given int32 actions [...] under the masked distribution of `sample_actions` (bg_evaluate_actions; forward
-    only, no autograd): bit for bit what the sampler returned for the actions it drew.  A masked action has log_prob -inf, one outside [0, 60) NaN."""
+    """(log_prob, entropy) float32 [...] of given int32 actions [...] under the masked distribution of `sample_actions` (bg_evaluate_actions; a
+    forward pass -- `ppo_loss` is the call that takes part in autograd): bit for bit what the sampler returned for the actions it drew.  A masked
+    action has log_prob -inf, one outside [0, 60) NaN."""
     if not isinstance(actions, torch.Tensor):
         raise ValueError("actions must be an int32 tensor with the leading shape of logits")
     return _head_call("bg_evaluate_actions", logits, mask, actions, 0, 0, 0, 0, None, log_prob, entropy, timing)
+
+
+class PpoStats:
+    """What `ppo_loss` returns beside the loss: the scalars of `_native.PPO_STATS` as 0-dim float32 device tensors (views of `raw`, no host
+    synchronisation), `log_prob` / `entropy` [...] of the minibatch rows (bit for bit `evaluate_actions`'), and the gradient the call produced --
+    `dlogits` [..., 60] in the dtype of the logits, `dvalues` [...] or None.  `kernel_ms` with timing=True."""
+
+    def __init__(self, raw, log_prob, entropy, dlogits, dvalues, kernel_ms=None):
+        self.raw, self.log_prob, self.entropy, self.dlogits, self.dvalues, self.kernel_ms = raw, log_prob, entropy, dlogits, dvalues, kernel_ms
+        for k, name in enumerate(nat.PPO_STATS):
+            setattr(self, name, raw[k])
+
+    def __repr__(self):
+        return "PpoStats(" + ", ".join(nat.PPO_STATS) + ", log_prob, entropy, dlogits, dvalues)"
+
+
+class _PpoLossGrad(torch.autograd.Function):
+    """The node `ppo_loss` hangs on its loss: the forward pass already produced the gradient, the backward is one multiplication."""
+
+    @staticmethod
+    def forward(ctx, loss, dlogits, dvalues, logits, values):
+        ctx.save_for_backward(dlogits, dvalues if dvalues is not None else dlogits.new_empty(0))
+        ctx.has_values = dvalues is not None
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        dlogits, dvalues = ctx.saved_tensors
+        gl = (dlogits * grad).to(dlogits.dtype) if ctx.needs_input_grad[3] else None
+        gv = dvalues * grad if ctx.has_values and ctx.needs_input_grad[4] else None
+        return None, None, None, gl, gv
+
+
+_ppo_workspaces: dict = {}
+
+
+def _ppo_workspace(L, dev: torch.device, m: int) -> torch.Tensor:
+    need = int(L.bg_ppo_loss_workspace_bytes(C.c_int64(m)))
+    key = (dev, need)
+    if key not in _ppo_workspaces:
+        _ppo_workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return _ppo_workspaces[key]
+
+
+def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Tensor, advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+             values: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None,
+             clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5, normalize_advantage: bool = True, timing: bool = False):
+    """SB3's `PPO.train` loss over the masked head of `sample_actions`, its diagnostics and its gradient, in one pass over the logits (bg_ppo_loss):
+    -> (loss, stats).  loss: 0-dim float32; when `logits` (or `values`) require grad it carries an autograd node whose backward is
+    grad_output * stats.dlogits (and * stats.dvalues) -- `loss.backward()` drives the network's own backward with nothing recomputed.  stats: `PpoStats`.
+    logits float32 / bfloat16 [..., 60] and values float32 [...] are the network's outputs for the minibatch.  Without `index`, actions int32,
+    old_log_prob / advantages / returns float32 and the mask (forms of `sample_actions`) have the leading shape of logits.  With `index` (int32 [...],
+    SB3's `RolloutBuffer.get` permutation) they are the STORED arrays of the whole rollout, one common shape, read at row index[i]: the minibatch is
+    gathered inside the launch, a record's mask in place.  A row that cannot take part (degenerate mask, masked or out-of-range action, non-finite
+    input, index out of range) is excluded: zero gradient, counted in stats.excluded, the divisor stays m.  values / returns: both or neither."""
+    lead, m, pitch = _head_logits(logits)
+    dev = logits.device
+    if index is not None:
+        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != lead or not index.is_contiguous() or index.device != dev:
+            raise ValueError(f"index must be a contiguous torch.int32 tensor of shape {list(lead)} on {dev}")
+        if not isinstance(actions, torch.Tensor):
+            raise ValueError("actions must be an int32 tensor")
+        store = tuple(actions.shape)
+    else:
+        store = lead
+    store_rows = int(np.prod(store, dtype=np.int64))
+    if store_rows >= 2 ** 31:
+        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
+    mask, moff, mstride = _head_mask(mask, store, dev)
+    _check_scan_tensor("actions", actions, torch.int32, store, dev)
+    _check_scan_tensor("old_log_prob", old_log_prob, torch.float32, store, dev)
+    _check_scan_tensor("advantages", advantages, torch.float32, store, dev)
+    if (values is None) != (returns is None):
+        raise ValueError("values and returns go together: both or neither")
+    if values is not None:
+        _check_scan_tensor("values", values, torch.float32, lead, dev)
+        _check_scan_tensor("returns", returns, torch.float32, store, dev)
+    for what, v in (("clip_range", clip_range), ("ent_coef", ent_coef), ("vf_coef", vf_coef)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{what} must be a finite number")
+    if not 0.0 < float(np.float32(clip_range)) < 1.0:
+        raise ValueError("clip_range must be in (0, 1)")
+    if not logits.is_cuda:
+        raise ValueError("logits must be a device tensor (there is no CPU fallback)")
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+    lg = logits.detach()
+    vals = values.detach() if values is not None else None
+    raw = torch.zeros(len(nat.PPO_STATS), dtype=torch.float32, device=dev)
+    dlogits = torch.empty(lead + (60,), dtype=logits.dtype, device=dev)
+    dvalues = torch.empty(lead, dtype=torch.float32, device=dev) if values is not None else None
+    log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
+    entropy = torch.empty(lead, dtype=torch.float32, device=dev)
+    ms = C.c_float(0.0)
+    if m > 0:
+        L = nat.load()
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(dev):
+            ws = _ppo_workspace(L, dev, m)
+            rc = L.bg_ppo_loss(ptr(lg), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
+                               C.c_void_p(mask.data_ptr() + moff) if mask is not None else None, C.c_uint64(mstride), ptr(actions), ptr(old_log_prob),
+                               ptr(advantages), ptr(vals), ptr(returns), ptr(index), C.c_int64(store_rows), C.c_int64(m), C.c_float(clip_range),
+                               C.c_float(ent_coef), C.c_float(vf_coef), C.c_uint32(nat.PPO_NORMALIZE_ADV if normalize_advantage else 0), ptr(dlogits),
+                               C.c_uint64(60), ptr(dvalues), ptr(log_prob), ptr(entropy), ptr(raw), ptr(ws), C.c_uint64(ws.numel()),
+                               C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise nat.NativeError(f"bg_ppo_loss failed ({rc}): {L.bg_last_error(None).decode()}")
+    stats = PpoStats(raw, log_prob, entropy, dlogits, dvalues, float(ms.value) if timing else None)
+    loss = raw[0]
+    if torch.is_grad_enabled() and (logits.requires_grad or (values is not None and values.requires_grad)):
+        loss = _PpoLossGrad.apply(loss, dlogits, dvalues, logits, values)
+    return loss, stats
 
 
 def _check_scan_rows(rows) -> tuple:

@@ -546,7 +546,8 @@ int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int 
  * the mask AFTER that record's step, so it belongs to the NEXT action (record t's mask goes with the logits computed from record t).
  * actions_dev int32 [m]; log_prob_dev / entropy_dev float32 [m], each may be NULL.  Outputs must not alias inputs or each other.  Both calls run on the
  * current device, need no handle, return BG_E_ARG (text in bg_last_error(NULL)) before launching anything, treat m == 0 as a no-op and never
- * synchronise unless timing is asked for; kernel_ms_out as in bg_classify_batch_ex.  Gradients, temperature and truncation are out of scope. */
+ * synchronise unless timing is asked for; kernel_ms_out as in bg_classify_batch_ex.  Both are forward passes: the gradient through this head is bg_ppo_loss
+ * (below).  Temperature and truncation are out of scope. */
 #define BG_HEAD_F32 0
 #define BG_HEAD_BF16 1
 #define BG_HEAD_DETERMINISTIC 1u /* flags */
@@ -559,6 +560,54 @@ int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logit
                         const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
                         const int32_t* actions_dev, float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
                         float* kernel_ms_out, void* stream);
+
+/* PPO's clipped loss over the masked head above, its diagnostics, and its gradient with respect to the logits and the values, in one pass over the
+ * logits: what a learner needs to train through the head that collected its data.  The arithmetic and the order of every operation are csrc/bg_ppo.h.
+ * Replaces: the loss of SB3's `PPO.train` (masked_fill -> log_softmax -> gather -> exp -> clamp -> min -> mean, the entropy and value terms) and its
+ * autograd backward, which every training script of the reference runs n_epochs = 10 times over each rollout (hpc_train.py:77-88,
+ * train_balatro_fixed.py:346-357, train_balatro_agent.py:326-337, robust_training.py:140-151: clip_range 0.2, ent_coef 0.01, vf_coef 0.5;
+ * train_progressive.py:161-176: 0.3 / 0.02).
+ *
+ * Row i of the minibatch reads its logits and value at i.  With index_dev (SB3's RolloutBuffer.get permutation, int32 [m]) the STORED arrays -- mask,
+ * actions, old_log_prob, advantages, returns -- are read at row index[i] of store_rows rows, so the minibatch is gathered inside the launch and a
+ * record's mask is read in place (rows_dev + BG_ROW_ACTION_MASK, the row stride); without it they are read at i.  All arithmetic is float32, every
+ * operation rounded on its own; the sums across rows are float64.  m_, d[j], e[j], S, A, logS are bg_head_row's, so log_prob and entropy H are bit for
+ * bit what bg_evaluate_actions returns for the row.
+ *     adv'  = adv, or with BG_PPO_NORMALIZE_ADV and n > 1: (adv - mean) / (std + 1e-8f); mean / std: float64 mean and unbiased standard deviation of the
+ *             call's n advantages (n = m less the rows whose index is out of range), rounded to float32 -- SB3's rule, its `len > 1` included
+ *     lr = log_prob - old_log_prob;  ratio = expf(lr);  lo = 1 - clip;  hi = 1 + clip;  rc = min(max(ratio, lo), hi);  s1 = adv' * ratio;  s2 = adv' * rc
+ *     policy term = -min(s1, s2);  g = adv' * ratio if (lo <= ratio <= hi) or s1 < s2, else 0   (torch's min / clamp backward, ties included)
+ *     kl term = (ratio - 1) - lr;  clipped = |ratio - 1| > clip
+ *     with values_dev / returns_dev (both or neither):  dv = v - ret;  value term = dv * dv;  dvalues[i] = ((vf_coef * 2) * dv) / float(m)
+ *     p = e[j] / S;  valid j with e[j] > 0:  dlogits[i, j] = ((ent_coef * p) * ((d[j] - logS) + H) - g * (1[j == a] - p)) / float(m)
+ *     valid j with e[j] == 0: (0 - g) / float(m) if j == a, else +0.0;  invalid j: +0.0;  padding columns of a strided dlogits are not written
+ *     policy_loss = sum policy / m;  value_loss = sum value / m;  entropy_loss = -(sum H) / m;  approx_kl = sum kl / m;  clip_fraction = sum clipped / m
+ *     loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss        (float64 from the float64 sums, each scalar rounded to float32 once)
+ * An EXCLUDED row -- degenerate for the head, action outside [0, 60) or masked, old_log_prob / adv / adv' / value / return not finite, index outside
+ * [0, store_rows) (nothing is read for it; log_prob = entropy = quiet NaN) -- adds nothing to any sum, has dlogits row and dvalue +0.0, is counted, and
+ * the divisor stays m.  The sums take a fixed order (64 rows per workgroup by a tree, the workgroups' partials from workspace_dev in index order by
+ * slices and a tree, in a one-workgroup kernel; no floating-point atomics), so two calls give the same bits.
+ * stats_dev, float32 [BG_PPO_STATS]: loss, policy_loss, value_loss, entropy_loss, approx_kl, clip_fraction, adv_mean, adv_std (0 without the flag),
+ * excluded rows, m.  dlogits_dev has the dtype of the logits (bfloat16: the float32 value rounded to nearest even) and its own row stride (>= 60).
+ * dvalues_dev, log_prob_dev, entropy_dev may be NULL.  Alignment rules and load paths as above; the gradient tile leaves by the mirror of those paths
+ * (16-byte pieces, words or halves by the alignment of dlogits_dev).  workspace_dev: 16-byte aligned, bg_ppo_loss_workspace_bytes(m) bytes.
+ * BG_E_ARG (text "bg_ppo_loss: ..." in bg_last_error(NULL)) before anything is launched for: wrong alignment, a stride < 60, an output that is the same
+ * pointer as an input or another output, values without returns, clip_range outside (0, 1), a non-finite coefficient, a workspace too small, unknown
+ * flags.  m == 0 writes zeros to stats_dev and launches nothing else.  Never synchronises unless timing is asked for.
+ * Out of scope: clip_range_vf, temperature, target_kl early stopping (read approx_kl), gradient clipping, the optimiser. */
+#define BG_PPO_STATS 10
+#define BG_PPO_NORMALIZE_ADV 1u /* flags */
+uint64_t bg_ppo_loss_workspace_bytes(int64_t m);
+int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems,
+                const int8_t* mask_dev /*nullable*/, uint64_t mask_stride_bytes,
+                const int32_t* actions_dev, const float* old_log_prob_dev, const float* advantages_dev,
+                const float* values_dev /*nullable*/, const float* returns_dev /*nullable*/,
+                const int32_t* index_dev /*nullable*/, int64_t store_rows, int64_t m,
+                float clip_range, float ent_coef, float vf_coef, uint32_t flags,
+                void* dlogits_dev, uint64_t dlogits_stride_elems, float* dvalues_dev /*nullable*/,
+                float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+                float* stats_dev /* float32[BG_PPO_STATS = 10] */,
+                void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
 #ifdef __cplusplus
 }
