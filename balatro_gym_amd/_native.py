@@ -59,7 +59,7 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_sim_evaluate_batch", "bg_sim_score_batch", "bg_create_ex", "bg_step_rows", "bg_observe_rows", "bg_step_many_rows",
            "bg_encode_cols", "bg_encode_rows", "bg_gae_rows", "bg_episode_stats_rows",
            "bg_gae_rows_ex", "bg_norm_workspace_bytes", "bg_norm_obs_rows", "bg_norm_reward_rows",
-           "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes"]
+           "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -238,6 +238,7 @@ def load(build_if_missing: bool = True):
     L.bg_bench_fill.argtypes = [vp, u64, i32, C.POINTER(C.c_double), vp]
     L.bg_encode_cols.argtypes = [i32]
     L.bg_encode_rows.argtypes = [vp, u64, i64, i32, i32, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_encode_rows_ex.argtypes = [vp, u64, i64, vp, i64, i32, i32, vp, vp, C.c_double, C.c_double, vp, u64, C.POINTER(C.c_float), vp]
     L.bg_gae_rows.argtypes = [vp, u64, i32, i64, vp, vp, C.c_double, C.c_double, vp, vp, C.POINTER(C.c_float), vp]
     L.bg_episode_stats_rows.argtypes = [vp, u64, i32, i64, vp, vp, vp, vp, C.POINTER(C.c_float), vp]
     L.bg_gae_rows_ex.argtypes = [vp, u64, i32, i64, vp, vp, C.c_double, C.c_double, vp, vp, vp, C.POINTER(C.c_float), vp]

@@ -194,6 +194,10 @@ BG_ENC_FN uint16_t bg_enc_bf16(uint32_t u) {
   return (uint16_t)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
 }
 
+// bg_encode_rows_ex's index: the record an index value names, or -1 ("none": the output row is zeros and nothing is read) when it is outside
+// [0, store_rows) -- the rule by which bg_ppo_loss excludes a row, so the two calls agree on a minibatch
+BG_ENC_FN int64_t bg_enc_source_row(int32_t index, int64_t store_rows) { return index >= 0 && (int64_t)index < store_rows ? (int64_t)index : (int64_t)-1; }
+
 #ifndef BG_ENC_HOST
 // ---- the kernel ----
 // A workgroup of 256 lanes takes BG_ENC_RECS = 32 consecutive records, in three phases with a barrier between them:
@@ -210,6 +214,11 @@ BG_ENC_FN uint16_t bg_enc_bf16(uint32_t u) {
 //      FIXED's 475 zero columns touch neither LDS nor the table; EXTRACTOR's 416 one-hot columns are computed here from the record's hand bytes
 //      (bg_enc_onehot: a byte read and a compare per element).
 // LDS: 11 392 bytes of records + 19 584 (153-column tile) or 3 968 (EXTRACTOR) bytes: five / eight workgroups per CU.
+// GATHER (bg_encode_rows_ex; a compile-time variant, the contiguous instantiations are the code above and nothing else): phase 1 first resolves the
+// workgroup's 32 indices once (bg_enc_source_row) into LDS, a barrier, then the 22 pieces of record r come from rows + src[r] * stride -- still
+// consecutive lanes on consecutive 16-byte pieces of a record, so a record of stride 384 is fetched as its three lines.  A record with no source is not
+// read: its LDS image is filled with 0xff (a hand of -1: phase 3's one-hot columns come out 0.0) and phase 2 writes zeros into its tile row, so phase 3
+// is the same code.  index == NULL is the identity (the norm variant without an index).
 #define BG_ENC_BLOCK 256
 #define BG_ENC_RECS 32
 #define BG_ENC_SLICES (BG_ENC_BLOCK / BG_ENC_RECS)
@@ -233,6 +242,27 @@ __device__ __forceinline__ void bg_enc_convert_slice(const uint8_t* rec, uint32_
     if (i < N) dst[i] = bg_enc_element<LAYOUT>(rec, BgEncTab<LAYOUT>::t.d[C0 + i]);
 }
 
+// the tile row of a record without a source (GATHER): slice `s` of its N dense columns as +0.0
+template <int N>
+__device__ __forceinline__ void bg_enc_zero_slice(int s, uint32_t* dst) {
+  constexpr int CH = (N + BG_ENC_SLICES - 1) / BG_ENC_SLICES;
+  for (int i = s * CH; i < (s + 1) * CH && i < N; i++) dst[i] = 0u;
+}
+
+// phase 1 of the GATHER variants: the workgroup's sources into LDS (one barrier), then the records; -1 = no source, the image is 0xff and nothing is read
+__device__ __forceinline__ void bg_enc_stage_gather(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index, long long store_rows,
+                                                    long long rec0, int nrec, long long* src, uint32_t* recs32) {
+  if ((int)threadIdx.x < nrec) src[threadIdx.x] = index ? bg_enc_source_row(index[rec0 + threadIdx.x], store_rows) : rec0 + threadIdx.x;
+  __syncthreads();
+  for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
+    const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
+    const long long from = src[r];
+    const uint4 v = from >= 0 ? *reinterpret_cast<const uint4*>(rows + (size_t)from * row_stride + p * 16) : make_uint4(~0u, ~0u, ~0u, ~0u);
+    uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  }
+}
+
 // one finished element in phase 3 (k-th column `c` of record `r` of the workgroup)
 template <int LAYOUT>
 __device__ __forceinline__ uint32_t bg_enc_fetch(const uint8_t* recs, const uint32_t* tile, int r, int c) {
@@ -242,29 +272,33 @@ __device__ __forceinline__ uint32_t bg_enc_fetch(const uint8_t* recs, const uint
   return tile[r * bg_enc_dense_cols(LAYOUT) + c - bg_enc_dense_first(LAYOUT)];
 }
 
-template <int LAYOUT, int DT, int ST>
-__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out,
-                                                                 uint64_t pitch) {
+template <int LAYOUT, int DT, int ST, bool GATHER>
+__device__ __forceinline__ void bg_encode_body(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out, uint64_t pitch,
+                                               const int32_t* __restrict__ index, long long store_rows) {
   __shared__ __attribute__((aligned(16))) uint32_t recs32[BG_ENC_RECS * BG_ENC_REC_PITCH / 4];
   __shared__ __attribute__((aligned(16))) uint32_t tile[BG_ENC_RECS * bg_enc_dense_cols(LAYOUT)];
+  __shared__ long long src[GATHER ? BG_ENC_RECS : 1];
   const uint8_t* const recs = reinterpret_cast<const uint8_t*>(recs32);
   constexpr int D = bg_enc_cols(LAYOUT);
   constexpr int E = ST == BG_ENC_ST_ELEM ? 1 : DT == BG_ENC_F32 ? 4 : 8;   // elements of a 16-byte piece
   const long long rec0 = (long long)blockIdx.x * BG_ENC_RECS;
   const int nrec = (int)(m - rec0 < BG_ENC_RECS ? m - rec0 : BG_ENC_RECS);
-  for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
-    const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
-    const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
-    uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  }
+  if (GATHER) bg_enc_stage_gather(rows, row_stride, index, store_rows, rec0, nrec, src, recs32);
+  else
+    for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
+      const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
+      const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
+      uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
   __syncthreads();
   {
     const int r = threadIdx.x % BG_ENC_RECS;
     if (r < nrec) {
       const uint8_t* const rec = recs + r * BG_ENC_REC_PITCH;
       uint32_t* const dst = tile + r * bg_enc_dense_cols(LAYOUT);
-      switch (threadIdx.x / BG_ENC_RECS) {
+      if (GATHER && src[r] < 0) bg_enc_zero_slice<bg_enc_dense_cols(LAYOUT)>(threadIdx.x / BG_ENC_RECS, dst);
+      else switch (threadIdx.x / BG_ENC_RECS) {
         case 0: bg_enc_convert_slice<LAYOUT, 0>(rec, dst); break;
         case 1: bg_enc_convert_slice<LAYOUT, 1>(rec, dst); break;
         case 2: bg_enc_convert_slice<LAYOUT, 2>(rec, dst); break;
@@ -315,12 +349,31 @@ __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_kernel(const uint8_t* 
   }
 }
 
+template <int LAYOUT, int DT, int ST>
+__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out,
+                                                                 uint64_t pitch) {
+  bg_encode_body<LAYOUT, DT, ST, false>(rows, row_stride, m, out, pitch, nullptr, 0);
+}
+// output row i from record index[i] of the store_rows records at `rows` (bg_encode_rows_ex)
+template <int LAYOUT, int DT, int ST>
+__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_gather_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index,
+                                                                        long long store_rows, long long m, void* __restrict__ out, uint64_t pitch) {
+  bg_encode_body<LAYOUT, DT, ST, true>(rows, row_stride, m, out, pitch, index, store_rows);
+}
+
 // host side: the store path `st` is chosen from the alignment of the caller's matrix (bg_encode_rows)
 template <int LAYOUT, int DT>
 static void bg_encode_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, long long m, void* out, uint64_t pitch) {
   if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
   else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
   else hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
+}
+template <int LAYOUT, int DT>
+static void bg_encode_gather_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, const int32_t* index, long long store_rows,
+                                    long long m, void* out, uint64_t pitch) {
+  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_encode_gather_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, out, pitch);
+  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_encode_gather_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, out, pitch);
+  else hipLaunchKernelGGL((bg_encode_gather_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, out, pitch);
 }
 #endif  // BG_ENC_HOST
 #endif

@@ -2167,6 +2167,59 @@ int bg_norm_obs_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, 
   return tm.end(kernel_ms_out);
 }
 
+// bg_encode_rows / frozen bg_norm_obs_rows for the rows a minibatch names: the GATHER variants of their kernels (bg_encode.h, bg_norm.h).  Without an
+// index and without statistics it IS bg_encode_rows; statistics without an index run the GATHER variant with the identity (no workspace to hold
+// sqrt(var + epsilon): the workgroups take the roots themselves).
+int bg_encode_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout, int out_dtype,
+                      const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, void* out_dev, uint64_t out_stride_elems,
+                      float* kernel_ms_out, void* stream) {
+  const int D = bg_enc_cols(layout);
+  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const bool norm = mean_dev || var_dev;
+  const char* bad = nullptr;
+  if (D < 0) bad = "layout must be BG_ENC_PRODUCED, BG_ENC_FIXED or BG_ENC_EXTRACTOR";
+  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (m < 0 || m > (int64_t)BG_ENC_RECS * 0x7fffffffll) bad = "m out of range";
+  else if (store_rows < 0) bad = "store_rows must be >= 0";
+  else if (index_dev && store_rows > 0x7fffffffll) bad = "store_rows must be in [0, 2**31) when index_dev is given";
+  else if (!index_dev && m > store_rows) bad = "m must be <= store_rows when index_dev is NULL";
+  else if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) bad = r;
+  else if ((uintptr_t)index_dev & 3) bad = "index_dev must be 4-byte aligned";
+  else if (norm && (!mean_dev || !var_dev)) bad = "mean_dev and var_dev go together: both or neither";
+  else if (norm && layout == BG_ENC_EXTRACTOR) bad = "statistics need layout BG_ENC_PRODUCED or BG_ENC_FIXED (VecNormalize wraps the env's keys, not the extractor's tensors)";
+  else if (norm && (((uintptr_t)mean_dev | (uintptr_t)var_dev) & 7)) bad = "mean_dev and var_dev must be 8-byte aligned";
+  else if (norm && mean_dev == var_dev) bad = "mean_dev and var_dev must not be the same pointer";
+  else if (norm && !(epsilon >= 0.0 && epsilon <= 1.7976931348623157e308 && clip_obs >= 0.0 && clip_obs <= 1.7976931348623157e308)) bad = "epsilon and clip_obs must be finite and >= 0 when statistics are given";
+  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
+  else if (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= the layout's column count";
+  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev) bad = "out_dev must not be the same pointer as an input";
+  if (bad) { g_create_err = std::string("bg_encode_rows_ex: ") + bad; return BG_E_ARG; }
+  if (!index_dev && !norm) return bg_encode_rows(rows_dev, row_stride_bytes, m, layout, out_dtype, out_dev, out_stride_elems, kernel_ms_out, stream);
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (m == 0) return 0;
+  const bool base16 = ((uintptr_t)out_dev & 15) == 0;
+  const int st = base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
+  const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (norm) {
+#define BG_NORM_GO(L, T) bg_norm_obs_gather_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, out_dev, out_stride_elems)
+    if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_F32); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_F32); }
+    else { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_BF16); }
+#undef BG_NORM_GO
+  } else {
+#define BG_ENC_GO(L, T) bg_encode_gather_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, out_dev, out_stride_elems)
+    if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_F32); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_F32); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_F32); }
+    else { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_BF16); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_BF16); }
+#undef BG_ENC_GO
+  }
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
 int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double* returns_carry_dev, double* ret_stats_dev, int update,
                         double gamma, double epsilon, double clip_reward, double* rewards_dev, double* moments_dev, void* workspace_dev,
                         uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {

@@ -205,32 +205,43 @@ __global__ __launch_bounds__(BG_NORM_PBLOCK) void bg_norm_obs_chain(const double
   if (c == 0) count_io[0] = s.count;
 }
 
-template <int S>
-__device__ __forceinline__ void bg_norm_convert_slice(const uint8_t* rec, const double* __restrict__ st, double clip, uint32_t* dst) {
+// st: the 153 means followed by the 153 sqrt(var + epsilon) the record is normalised with; SPLIT (the GATHER variant): the roots are at dn instead
+template <int S, bool SPLIT>
+__device__ __forceinline__ void bg_norm_convert_slice(const uint8_t* rec, const double* __restrict__ st, const double* __restrict__ dn, double clip, uint32_t* dst) {
   constexpr int CH = (BG_NORM_COLS + BG_ENC_SLICES - 1) / BG_ENC_SLICES;
 #pragma unroll
   for (int i = S * CH; i < (S + 1) * CH; i++)
-    if (i < BG_NORM_COLS) dst[i] = bg_norm_obs_bits(bg_norm_value64(rec, BgEncTab<BG_ENC_PRODUCED>::t.d[i]), st[i], st[BG_NORM_COLS + i], clip);
+    if (i < BG_NORM_COLS) dst[i] = bg_norm_obs_bits(bg_norm_value64(rec, BgEncTab<BG_ENC_PRODUCED>::t.d[i]), st[i], SPLIT ? dn[i] : st[BG_NORM_COLS + i], clip);
 }
 
 // LAYOUT BG_ENC_PRODUCED | BG_ENC_FIXED; DT / ST as bg_encode_kernel.  Record i of the call belongs to step i / N; stat_step_stride is 0 for frozen statistics.
-template <int LAYOUT, int DT, int ST>
-__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, long long N,
-                                                                   const double* __restrict__ stat, size_t stat_step_stride, double clip, void* __restrict__ out,
-                                                                   uint64_t pitch) {
+// GATHER (bg_encode_rows_ex with statistics; bg_encode_kernel's compile-time variant, the contiguous instantiations are untouched by it): the call has
+// no workspace, so `stat` is the caller's 153 means and `var` its 153 variances: lane c < 153 takes sqrt(var[c] + epsilon) -- the expression and the
+// bits of bg_norm_obs_chain<false> -- into LDS once per workgroup (1 224 bytes: still five workgroups per CU); phase 1 is bg_enc_stage_gather and a
+// record without a source becomes a row of +0.0, not of normalised zeros.
+template <int LAYOUT, int DT, int ST, bool GATHER>
+__device__ __forceinline__ void bg_norm_obs_body(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, long long N, const double* __restrict__ stat,
+                                                 size_t stat_step_stride, double clip, void* __restrict__ out, uint64_t pitch, const int32_t* __restrict__ index,
+                                                 long long store_rows, const double* __restrict__ var, double epsilon) {
   __shared__ __attribute__((aligned(16))) uint32_t recs32[BG_ENC_RECS * BG_ENC_REC_PITCH / 4];
   __shared__ __attribute__((aligned(16))) uint32_t tile[BG_ENC_RECS * BG_NORM_COLS];
+  __shared__ long long src[GATHER ? BG_ENC_RECS : 1];
+  __shared__ double denom[GATHER ? BG_NORM_COLS : 1];
   const uint8_t* const recs = reinterpret_cast<const uint8_t*>(recs32);
   constexpr int D = bg_enc_cols(LAYOUT);
   constexpr int E = ST == BG_ENC_ST_ELEM ? 1 : DT == BG_ENC_F32 ? 4 : 8;
   const long long rec0 = (long long)blockIdx.x * BG_ENC_RECS;
   const int nrec = (int)(m - rec0 < BG_ENC_RECS ? m - rec0 : BG_ENC_RECS);
-  for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
-    const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
-    const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
-    uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-  }
+  if (GATHER) {
+    if (threadIdx.x < BG_NORM_COLS) denom[threadIdx.x] = bg_norm_denom(var[threadIdx.x], epsilon);
+    bg_enc_stage_gather(rows, row_stride, index, store_rows, rec0, nrec, src, recs32);
+  } else
+    for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
+      const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
+      const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
+      uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
+      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+    }
   __syncthreads();
   {
     const int r = threadIdx.x % BG_ENC_RECS;
@@ -238,15 +249,17 @@ __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_kernel(const uint8_t
       const uint8_t* const rec = recs + r * BG_ENC_REC_PITCH;
       uint32_t* const dst = tile + r * BG_NORM_COLS;
       const double* const st = stat + (size_t)((rec0 + r) / N) * stat_step_stride;
-      switch (threadIdx.x / BG_ENC_RECS) {
-        case 0: bg_norm_convert_slice<0>(rec, st, clip, dst); break;
-        case 1: bg_norm_convert_slice<1>(rec, st, clip, dst); break;
-        case 2: bg_norm_convert_slice<2>(rec, st, clip, dst); break;
-        case 3: bg_norm_convert_slice<3>(rec, st, clip, dst); break;
-        case 4: bg_norm_convert_slice<4>(rec, st, clip, dst); break;
-        case 5: bg_norm_convert_slice<5>(rec, st, clip, dst); break;
-        case 6: bg_norm_convert_slice<6>(rec, st, clip, dst); break;
-        default: bg_norm_convert_slice<7>(rec, st, clip, dst); break;
+      const double* const dn = GATHER ? denom : nullptr;
+      if (GATHER && src[r] < 0) bg_enc_zero_slice<BG_NORM_COLS>(threadIdx.x / BG_ENC_RECS, dst);
+      else switch (threadIdx.x / BG_ENC_RECS) {
+        case 0: bg_norm_convert_slice<0, GATHER>(rec, st, dn, clip, dst); break;
+        case 1: bg_norm_convert_slice<1, GATHER>(rec, st, dn, clip, dst); break;
+        case 2: bg_norm_convert_slice<2, GATHER>(rec, st, dn, clip, dst); break;
+        case 3: bg_norm_convert_slice<3, GATHER>(rec, st, dn, clip, dst); break;
+        case 4: bg_norm_convert_slice<4, GATHER>(rec, st, dn, clip, dst); break;
+        case 5: bg_norm_convert_slice<5, GATHER>(rec, st, dn, clip, dst); break;
+        case 6: bg_norm_convert_slice<6, GATHER>(rec, st, dn, clip, dst); break;
+        default: bg_norm_convert_slice<7, GATHER>(rec, st, dn, clip, dst); break;
       }
     }
   }
@@ -284,12 +297,35 @@ __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_kernel(const uint8_t
   }
 }
 
+template <int LAYOUT, int DT, int ST>
+__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, long long N,
+                                                                   const double* __restrict__ stat, size_t stat_step_stride, double clip, void* __restrict__ out,
+                                                                   uint64_t pitch) {
+  bg_norm_obs_body<LAYOUT, DT, ST, false>(rows, row_stride, m, N, stat, stat_step_stride, clip, out, pitch, nullptr, 0, nullptr, 0.0);
+}
+// output row i from record index[i] (NULL: record i), normalised with the frozen statistics mean / var (bg_encode_rows_ex)
+template <int LAYOUT, int DT, int ST>
+__global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_gather_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index,
+                                                                          long long store_rows, long long m, const double* __restrict__ mean,
+                                                                          const double* __restrict__ var, double epsilon, double clip, void* __restrict__ out,
+                                                                          uint64_t pitch) {
+  bg_norm_obs_body<LAYOUT, DT, ST, true>(rows, row_stride, m, 1, mean, 0, clip, out, pitch, index, store_rows, var, epsilon);
+}
+
 template <int LAYOUT, int DT>
 static void bg_norm_obs_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, long long m, long long N, const double* stat,
                                size_t stat_step_stride, double clip, void* out, uint64_t pitch) {
   if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_norm_obs_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, N, stat, stat_step_stride, clip, out, pitch);
   else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_norm_obs_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, N, stat, stat_step_stride, clip, out, pitch);
   else hipLaunchKernelGGL((bg_norm_obs_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, N, stat, stat_step_stride, clip, out, pitch);
+}
+
+template <int LAYOUT, int DT>
+static void bg_norm_obs_gather_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, const int32_t* index, long long store_rows,
+                                      long long m, const double* mean, const double* var, double epsilon, double clip, void* out, uint64_t pitch) {
+  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_norm_obs_gather_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, mean, var, epsilon, clip, out, pitch);
+  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_norm_obs_gather_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, mean, var, epsilon, clip, out, pitch);
+  else hipLaunchKernelGGL((bg_norm_obs_gather_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, mean, var, epsilon, clip, out, pitch);
 }
 
 // Reward call, update != 0, four launches:

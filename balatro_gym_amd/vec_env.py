@@ -91,9 +91,29 @@ class RowBuffers:
         self.action = self._view(nat.ROW_EXTRA["action"][0], "int32", ())
         self.terminated = self._view(nat.ROW_EXTRA["terminated"][0], "uint8", ())
 
-    def encode(self, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The records as ONE [steps, n, D] float matrix for a policy network (`encode_rows`: one launch over all steps * n records)."""
-        return encode_rows(self.rows, layout, dtype, out)
+    def encode(self, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None, *,
+               index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The records as ONE [steps, n, D] float matrix for a policy network (`encode_rows`: one launch over all steps * n records); with `index`
+        (int32 [m], one tensor of `minibatches`) the [m, D] matrix of those records, gathered inside the launch."""
+        return encode_rows(self.rows, layout, dtype, out, index=index)
+
+    def minibatches(self, batch_size: int, *, generator: Optional[torch.Generator] = None, drop_last: bool = False):
+        """SB3's `RolloutBuffer.get(batch_size)`: yields int32 [<= batch_size] tensors on the records' device, consecutive slices of ONE
+        torch.randperm(steps * n) (drawn on `generator`'s device, or the records' without one).  Index t * n + e names record (t, e), the order in
+        which `ppo_loss(index=)` reads dense [steps, n] stored arrays: one tensor serves `encode(index=)`, `normalize(index=)` and `ppo_loss(index=)`.
+        The last tensor is shorter when steps * n is no multiple of batch_size; drop_last=True leaves it out."""
+        batch_size = int(batch_size)
+        if batch_size < 1:
+            raise ValueError("batch_size must be >= 1")
+        total = self.steps * self.n
+        if total >= 2 ** 31:
+            raise ValueError("the stored records hold at most 2**31 - 1 rows")
+        dev = self.rows.device
+        perm = torch.randperm(total, generator=generator, device=generator.device if generator is not None else dev).to(device=dev, dtype=torch.int32)
+        for start in range(0, total, batch_size):
+            if drop_last and start + batch_size > total:
+                return
+            yield perm[start:start + batch_size]
 
     def gae(self, values: torch.Tensor, last_values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
             advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False,
@@ -101,9 +121,11 @@ class RowBuffers:
         """(advantages, returns) float32 [steps, n] of these records (`gae_rows`: SB3's compute_returns_and_advantage in one launch)."""
         return gae_rows(self.rows, values, last_values, gamma, gae_lambda, advantages, returns, timing, rewards)
 
-    def normalize(self, norm: "RowNormalizer", layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """The records as VecNormalize would hand them to the network, [steps, n, D] (`RowNormalizer.normalize_obs`)."""
-        return norm.normalize_obs(self.rows, layout, dtype, out)
+    def normalize(self, norm: "RowNormalizer", layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None, *,
+                  index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The records as VecNormalize would hand them to the network, [steps, n, D] (`RowNormalizer.normalize_obs`); with `index` (int32 [m]) the
+        [m, D] matrix of those records under the statistics as they stand (frozen)."""
+        return norm.normalize_obs(self.rows, layout, dtype, out, index=index)
 
     def normalize_reward(self, norm: "RowNormalizer", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The records' rewards as VecNormalize would hand them to the learner, float64 [steps, n] (`RowNormalizer.normalize_reward`)."""
@@ -631,8 +653,15 @@ def classify_batch(cards: torch.Tensor, n: torch.Tensor, lanes_per_case: int = 1
     return (out, float(ms.value)) if timing else out
 
 
+def _check_index(index, shape: Optional[tuple], device: torch.device) -> None:
+    """The `index=` of ppo_loss and encode_rows (SB3's `RolloutBuffer.get` permutation): contiguous int32 on `device`, of `shape` (None: any [m])."""
+    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or (tuple(index.shape) != shape if shape is not None else index.dim() != 1) \
+            or not index.is_contiguous() or index.device != device:
+        raise ValueError(f"index must be a contiguous torch.int32 tensor of shape {list(shape) if shape is not None else '[m]'} on {device}")
+
+
 def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
-                timing: bool = False):
+                timing: bool = False, *, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None):
     """Packed records -> the float matrix a policy network reads, in one launch (bg_encode_rows).  rows: a contiguous uint8 device tensor
     [..., stride] of records as `rollout` / `step_many` / an obs_layout="rows" env write them (`RowBuffers.rows`, `env.obs_rows`).
     layout: "produced" -- the 31 observation keys in the reference's key order, every element as float (153 columns: what SB3's
@@ -641,7 +670,11 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
     `_native.ENC_COLUMNS[layout]` names the column ranges.  dtype: torch.float32 or torch.bfloat16 (round to nearest even).
     out: optional [..., >= D] tensor of `dtype` on the same device with the same leading shape, last dimension contiguous and the leading
     dimensions dense over its row pitch (e.g. a column slice of a wider matrix): columns beyond D are left untouched.
-    Returns the [..., D] matrix (a view of `out` when given); timing=True returns (matrix, kernel milliseconds)."""
+    Returns the [..., D] matrix (a view of `out` when given); timing=True returns (matrix, kernel milliseconds).
+    index: int32 [m] on the rows' device -- the tensor `ppo_loss(index=)` takes (`RowBuffers.minibatches`): the result (and `out`) is [m, D], row i
+    made from record index[i] of the flattened rows (t * N + e names record (t, e)), gathered inside the launch (bg_encode_rows_ex); a row whose index
+    is out of range is zeros, the row `ppo_loss` excludes.  norm: a `RowNormalizer`: the rows as its `normalize_obs` gives them with the statistics
+    frozen ("produced" / "fixed"); its statistics, epsilon and clip_obs are read, never updated.  Without index and norm the call is bg_encode_rows."""
     if layout not in nat.ENC_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(nat.ENC_LAYOUTS)} (got {layout!r})")
     if dtype not in (torch.float32, torch.bfloat16):
@@ -653,9 +686,26 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
         raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
     D = nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]
     lead = tuple(rows.shape[:-1])
+    store_rows = int(np.prod(lead, dtype=np.int64))
+    if index is not None:
+        _check_index(index, None, rows.device)
+        if store_rows >= 2 ** 31:
+            raise ValueError("the stored records hold at most 2**31 - 1 rows")
+        lead = (int(index.shape[0]),)
+    if norm is not None:
+        if not isinstance(norm, RowNormalizer):
+            raise ValueError("norm must be a RowNormalizer")
+        if not norm.norm_obs:
+            raise ValueError("this RowNormalizer was made with norm_obs=False: use encode_rows without norm")
+        if layout not in ("produced", "fixed"):
+            raise ValueError(f"layout must be 'produced' or 'fixed' with norm (got {layout!r}): VecNormalize wraps the env's keys, not the extractor's tensors")
+        if norm.device != rows.device:
+            raise ValueError(f"norm holds its statistics on {norm.device}, rows are on {rows.device}")
+        if not (np.isfinite(norm.epsilon) and norm.epsilon >= 0.0 and np.isfinite(norm.clip_obs) and norm.clip_obs >= 0.0):
+            raise ValueError("norm.epsilon and norm.clip_obs must be finite and >= 0")
     m = int(np.prod(lead, dtype=np.int64))
     if out is not None:
-        if out.dtype != dtype or out.device != rows.device:
+        if not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != rows.device:
             raise ValueError(f"out must be a {dtype} tensor on {rows.device}")
         if tuple(out.shape[:-1]) != lead or out.shape[-1] < D:
             raise ValueError(f"out must have shape {lead + ('>= %d' % D,)} (got {tuple(out.shape)})")
@@ -676,15 +726,23 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
         return (out[..., :D], 0.0) if timing else out[..., :D]
     L = nat.load()
     ms = C.c_float(0.0)
+    odt = nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16
+    tail = (C.c_void_p(out.data_ptr()), C.c_uint64(pitch), C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
     with torch.cuda.device(rows.device):
-        rc = L.bg_encode_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(m), nat.ENC_LAYOUTS[layout],
-                              nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(out.data_ptr()), C.c_uint64(pitch),
-                              C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+        if index is None and norm is None:
+            name = "bg_encode_rows"
+            rc = L.bg_encode_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(m), nat.ENC_LAYOUTS[layout], odt, *tail)
+        else:
+            name = "bg_encode_rows_ex"
+            rc = L.bg_encode_rows_ex(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(store_rows),
+                                     C.c_void_p(index.data_ptr()) if index is not None else None, C.c_int64(m), nat.ENC_LAYOUTS[layout], odt,
+                                     C.c_void_p(norm.obs_mean.data_ptr()) if norm is not None else None,
+                                     C.c_void_p(norm.obs_var.data_ptr()) if norm is not None else None,
+                                     C.c_double(norm.epsilon if norm is not None else 0.0), C.c_double(norm.clip_obs if norm is not None else 0.0), *tail)
     if rc != 0:
-        raise nat.NativeError(f"bg_encode_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+        raise nat.NativeError(f"{name} failed ({rc}): {L.bg_last_error(None).decode()}")
     res = out[..., :D]
     return (res, float(ms.value)) if timing else res
-
 
 
 def _head_logits(logits) -> tuple:
@@ -857,8 +915,7 @@ def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Te
     lead, m, pitch = _head_logits(logits)
     dev = logits.device
     if index is not None:
-        if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or tuple(index.shape) != lead or not index.is_contiguous() or index.device != dev:
-            raise ValueError(f"index must be a contiguous torch.int32 tensor of shape {list(lead)} on {dev}")
+        _check_index(index, lead, dev)
         if not isinstance(actions, torch.Tensor):
             raise ValueError("actions must be an int32 tensor")
         store = tuple(actions.shape)
@@ -1115,10 +1172,18 @@ class RowNormalizer:
         return self._workspace
 
     def normalize_obs(self, rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
-                      timing: bool = False):
+                      timing: bool = False, *, index: Optional[torch.Tensor] = None, update: Optional[bool] = None):
         """K VecNormalize steps over the observations of rows (contiguous uint8 [K, N, stride], or [N, stride] = one step): returns the normalised
         [K, N, D] (or [N, D]) matrix of `layout` ("produced" 153 columns, "fixed" 628: the never-filled columns are 0.0) in `dtype` (torch.float32 or
-        torch.bfloat16).  out: optional contiguous tensor of that shape and dtype to write into.  timing=True appends the kernel milliseconds."""
+        torch.bfloat16).  out: optional contiguous tensor of that shape and dtype to write into.  timing=True appends the kernel milliseconds.
+        update: None = `self.training`; False normalises with the statistics as they stand.  index: int32 [m] (`RowBuffers.minibatches`): the
+        [m, D] matrix of records index[i], gathered inside the launch with the statistics FROZEN (`encode_rows(index=, norm=)`); a statistics update is
+        defined per step over all N envs, not over a minibatch, so update=True with an index is refused."""
+        if index is not None:
+            if update:
+                raise ValueError("update=True with an index: a statistics update is defined per step over all N envs, not over a minibatch")
+            self._check_rows(rows)
+            return encode_rows(rows, layout, dtype, out, index=index, norm=self, timing=timing)
         if not self.norm_obs:
             raise ValueError("this RowNormalizer was made with norm_obs=False: use encode_rows")
         if layout not in ("produced", "fixed"):
@@ -1144,7 +1209,7 @@ class RowNormalizer:
             ws = self._ready(L, K, N)
             rc = L.bg_norm_obs_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), nat.ENC_LAYOUTS[layout],
                                     nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(self.obs_mean.data_ptr()),
-                                    C.c_void_p(self.obs_var.data_ptr()), C.c_void_p(self.obs_count.data_ptr()), 1 if self.training else 0,
+                                    C.c_void_p(self.obs_var.data_ptr()), C.c_void_p(self.obs_count.data_ptr()), 1 if (self.training if update is None else update) else 0,
                                     C.c_double(self.epsilon), C.c_double(self.clip_obs), C.c_void_p(out.data_ptr()), C.c_uint64(D), None,
                                     C.c_void_p(ws.data_ptr()), C.c_uint64(ws.numel()), C.byref(ms) if timing else None,
                                     C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))

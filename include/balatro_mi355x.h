@@ -517,6 +517,35 @@ int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int 
                         double* rewards_dev, double* moments_dev,
                         void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* One minibatch's network input straight from the stored records, in ONE launch: bg_encode_rows, or bg_norm_obs_rows with frozen statistics, for the
+ * rows an index names.  The other half of bg_ppo_loss' index_dev: the logits that call consumes come from the features of the same rows index[i].
+ * Replaces: SB3's `RolloutBuffer.get`, which `PPO.train` runs n_epochs (10 in hpc_train.py:77-86) times per rollout: `observations[key][indices]`
+ * for every key of a random permutation's slice, on top of a rollout stored as floats.  Here the rollout stays the 352-byte records; neither the
+ * [K * N, columns] feature matrix nor a gathered copy of the records exists.
+ * rows_dev: store_rows records under bg_encode_rows' rules (16-byte aligned, row_stride_bytes a multiple of 16, >= BG_ROW_BYTES).  index_dev: int32
+ * [m], 4-byte aligned -- the convention of bg_ppo_loss' index_dev / store_rows, so ONE tensor serves both calls (index t * N + e names record
+ * (t, e)); output row i is made from record index_dev[i]; repeats are allowed; an index outside [0, store_rows) reads nothing and row i is written
+ * as +0.0 in every column of the layout (bg_ppo_loss excludes and counts such a row).  index_dev == NULL: row i from record i, m <= store_rows.
+ * mean_dev == var_dev == NULL: row i is, bit for bit, the row bg_encode_rows writes for that record alone (any layout).  Both given: double[153]
+ * each, 8-byte aligned, the statistics of bg_norm_obs_rows; row i is, bit for bit, the row bg_norm_obs_rows(update = 0) writes for that record with
+ * these statistics, epsilon and clip_obs (BG_ENC_FIXED's columns 153..627: 0.0); layout BG_ENC_PRODUCED or BG_ENC_FIXED.  The statistics are only
+ * read; there is no count and no workspace.
+ * out_dev, out_dtype, out_stride_elems, the untouched columns beyond the count, the 16-byte store rule, kernel_ms_out: as bg_encode_rows; rows at or
+ * beyond m are not touched.  Runs on the current device, needs no handle, never synchronises the host unless kernel_ms_out is given; m == 0 is a
+ * no-op.  BG_E_ARG (text "bg_encode_rows_ex: ..." in bg_last_error(NULL)) before anything is launched: a misaligned pointer, a stride below
+ * BG_ROW_BYTES or no multiple of 16, out_stride_elems below the column count, an unknown layout or dtype, store_rows < 0, store_rows > INT32_MAX
+ * with an index, m > store_rows without one, only one of mean_dev / var_dev, statistics with BG_ENC_EXTRACTOR, epsilon or clip_obs negative or not
+ * finite when statistics are given, out_dev equal to an input pointer.
+ * Out of scope: statistics updates over a minibatch (an update is defined per step over all N envs: bg_norm_obs_rows); the extractor layout with
+ * statistics; int64 indices; a gathered bg_norm_reward_rows (normalised rewards are stored dense and bg_ppo_loss gathers what follows from them);
+ * shifting an index from a step to the record before it -- a record's observation and mask belong to the NEXT action (the head's note on alignment
+ * in time), and that bookkeeping stays with the caller. */
+int bg_encode_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                      const int32_t* index_dev /*nullable*/, int64_t m, int layout, int out_dtype,
+                      const double* mean_dev /*nullable*/, const double* var_dev /*nullable*/,
+                      double epsilon, double clip_obs,
+                      void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream);
+
 /* The masked categorical policy head: [m, 60] logits -> the int32 actions bg_step_rows / bg_step_many_rows take, with the log-probability and the
  * entropy PPO stores, in ONE launch; bg_evaluate_actions is the forward pass for given actions.  The arithmetic is csrc/bg_head.h.
  * Replaces: with mask_dev == NULL, SB3's `CategoricalDistribution.sample / log_prob / entropy / mode` as `PPO("MultiInputPolicy", ...)` runs them on
