@@ -100,8 +100,11 @@ class RowBuffers:
     def minibatches(self, batch_size: int, *, generator: Optional[torch.Generator] = None, drop_last: bool = False):
         """SB3's `RolloutBuffer.get(batch_size)`: yields int32 [<= batch_size] tensors on the records' device, consecutive slices of ONE
         torch.randperm(steps * n) (drawn on `generator`'s device, or the records' without one).  Index t * n + e names record (t, e), the order in
-        which `ppo_loss(index=)` reads dense [steps, n] stored arrays: one tensor serves `encode(index=)`, `normalize(index=)` and `ppo_loss(index=)`.
-        The last tensor is shorter when steps * n is no multiple of batch_size; drop_last=True leaves it out."""
+        which `ppo_loss(index=)` reads dense [steps, n] stored arrays: one tensor serves `encode_rows(index=)`, `normalize_obs(index=)` and
+        `ppo_loss(index=)` over the OBSERVATION records -- the record each action was drawn from, one step BEFORE the record that carries its reward.  A
+        `RowBuffers` filled by `step_many` / `rollout` holds the records AFTER each action (what `gae` reads): with the record before the call in front
+        they make the [steps + 1, n] store whose first `steps` rows are the observation records ("One PPO iteration over records"); the
+        index itself depends on steps * n alone.  The last tensor is shorter when steps * n is no multiple of batch_size; drop_last=True leaves it out."""
         batch_size = int(batch_size)
         if batch_size < 1:
             raise ValueError("batch_size must be >= 1")

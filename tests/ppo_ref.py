@@ -335,3 +335,47 @@ def torch_statement(c: Case, clip: float, ent_coef: float, vf_coef: float, norma
         return scal, loss
     loss.backward()
     return scal, logits.grad.numpy(), None if values is None else values.grad.numpy()
+
+
+def mlp_gradient_bounds(B, D, W1, W2, x, slack=2.0 ** -14, forward_abs=False):
+    """Carries the output-gradient bounds of a two-layer MLP  x -> tanh(x W1^T + b1) -> h W2^T + b2  (60 logits + 1 value) into the bounds of its parameter
+    gradients.  B float64 [m, 61]: the bound of every dlogits / dvalues element (ClosedForm.grad_bound and 2**-22 |dvalues| + 1e-45); D [m, 61]: |dout|,
+    the reference's absolute output gradient; W1: the float64 twin's (W1, b1), W2 its second weight matrix; x float64 [m, cols].
+    The bound goes through the absolute Jacobian (|h|, |W2|, |1 - h^2|, |x|); `slack` of the sum of absolute terms of each gradient element pays for the
+    float32 passes of the network itself (the forward activations carry at most (153 + 64) * 2**-24 < 2**-16, the backward dots over 256 rows 2**-16, tanh
+    and its derivative a few ulp: below 2**-14 together.  tests/test_ppo_iteration.py calls this with 1000-row minibatches, where a strictly sequential
+    float32 dot could reach 1000 * 2**-24 = 2**-14.03 on its own; a rounding error that grows like sqrt(m) stays near 2**-19, and the test prints its share).
+    forward_abs: `slack` takes the float32 error of h to be RELATIVE to |h|.  It is not: the pre-activation z = x W1^T + b1 carries an ABSOLUTE error of up to
+    EZ = (cols + 1) * 2**-24 * (|x| |W1|^T + |b1|), and tanh' <= 1 hands it to h whatever |h| is.  Where a logit column has a gradient on one or two rows
+    and |h| there is 1e-5, slack * |dout| |h| allows nothing while the error is |dout| EZ (a float32 network on the CPU fed the exactly rounded closed-form
+    gradient misses the relative bound by two orders of magnitude on such an element).  With forward_abs=True the bounds also hold |dout|^T EZ (W2.grad)
+    and, through 1 - h^2 (off by at most 2 |h| EZ), (|dout| |W2| * 2 |h| EZ)^T |x| (W1.grad) and its column sums (b1.grad).  The default is the bound as
+    test_mlp_takes_one_sgd_step_through_ppo_loss has always used it, on features squashed into (-1, 1).
+    -> [bound of W1.grad, b1.grad, W2.grad, b2.grad]"""
+    W1, b1 = W1
+    h = np.tanh(x @ W1.T + b1)
+    bW2 = B.T @ np.abs(h) + slack * (D.T @ np.abs(h))
+    bb2 = B.sum(0) + slack * D.sum(0)
+    Bh, Dh = (B @ np.abs(W2)) * np.abs(1 - h * h), (D @ np.abs(W2)) * np.abs(1 - h * h)
+    bW1 = Bh.T @ np.abs(x) + slack * (Dh.T @ np.abs(x))
+    bb1 = Bh.sum(0) + slack * Dh.sum(0)
+    if forward_abs:
+        EZ = (x.shape[1] + 1) * 2.0 ** -24 * (np.abs(x) @ np.abs(W1).T + np.abs(b1))
+        Eh = (D @ np.abs(W2)) * 2.0 * np.abs(h) * EZ
+        bW2 = bW2 + D.T @ EZ
+        bW1 = bW1 + Eh.T @ np.abs(x)
+        bb1 = bb1 + Eh.sum(0)
+    return [bW1, bb1, bW2, bb2]
+
+
+def check_mlp_gradients(grads, want, bounds, what: str = "") -> float:
+    """The parameter gradients [W1, b1, W2, b2] (float64 copies of the device's) against the twin's within `bounds`; an element whose bound is 0 must be
+    exact.  Returns the largest share of a bound."""
+    worst = 0.0
+    for name, g, w, b in zip(("W1", "b1", "W2", "b2"), grads, want, bounds):
+        err, live = np.abs(g - w), b > 0.0
+        assert (err[~live] == 0.0).all(), f"{what}{name}: an element whose bound is 0 (a feature column that is 0 on every row) must be exact"
+        share = float((err[live] / b[live]).max())
+        worst = max(worst, share)
+        assert share <= 1.0, f"{what}{name}: parameter gradient off by {share:.3f} of its propagated bound"
+    return worst

@@ -436,22 +436,8 @@ def test_mlp_takes_one_sgd_step_through_ppo_loss():
     want = [p.grad.numpy() for p in twin.parameters()]
     # the propagated bounds
     W1, b1, W2, b2 = (p.detach().numpy() for p in twin.parameters())
-    xa = x64.numpy()
-    h = np.tanh(xa @ W1.T + b1)
     B = np.concatenate([cf.grad_bound(cf.g, dl), (2.0 ** -22 * np.abs(cf.dvalues) + 1e-45)[:, None]], axis=1)          # [m, 61]
     D = np.abs(np.concatenate([cf.dlogits, cf.dvalues[:, None]], axis=1))                                              # |dout|
-    slack = 2.0 ** -14
-    bW2 = B.T @ np.abs(h) + slack * (D.T @ np.abs(h))
-    bb2 = B.sum(0) + slack * D.sum(0)
-    Bh, Dh = (B @ np.abs(W2)) * np.abs(1 - h * h), (D @ np.abs(W2)) * np.abs(1 - h * h)
-    bW1 = Bh.T @ np.abs(xa) + slack * (Dh.T @ np.abs(xa))
-    bb1 = Bh.sum(0) + slack * Dh.sum(0)
-    worst = 0.0
-    for name, g, w, b in (("W1", grads[0], want[0], bW1), ("b1", grads[1], want[1], bb1), ("W2", grads[2], want[2], bW2), ("b2", grads[3], want[3], bb2)):
-        err, live = np.abs(g - w), b > 0.0
-        assert (err[~live] == 0.0).all(), f"{name}: an element whose bound is 0 (a feature column that is 0 on every row) must be exact"
-        share = float((err[live] / b[live]).max())
-        worst = max(worst, share)
-        assert share <= 1.0, f"{name}: parameter gradient off by {share:.3f} of its propagated bound"
+    worst = ppo_ref.check_mlp_gradients(grads, want, ppo_ref.mlp_gradient_bounds(B, D, (W1, b1), W2, x64.numpy()))
     assert abs(scal["loss"] - float(loss.detach())) <= cf.stat_bounds["loss"]
     print(f"mlp: largest share of a propagated bound {worst:.3f}; dlogits share {sh['dlogits']:.3f}")
