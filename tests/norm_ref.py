@@ -201,6 +201,144 @@ def synthetic_cases():
     return out
 
 
+# ---- the normaliser's fixed tree (csrc/bg_norm.h), stated in float64 numpy: one IEEE operation per numpy call, vectorised over columns, tiles, chunks,
+# waves and any leading axes.  A triple is (n, mean, m2) of arrays that broadcast against each other. ----
+BIG_CASES = ((2, 4097, 352, 7100), (3, 8519, 384, 7101), (17, 4160, 352, 7102), (1, 65536, 384, 7103))   # (K, N, stride, seed): past one reduction level
+TREE_TILE, TREE_CHUNK, TREE_WAVE = 32, 256, 64
+
+
+def tree_merge(a, b):
+    """bg_norm_merge: `a` is the LEFT operand; b.n == 0 gives a, then a.n == 0 gives b."""
+    an, am, a2 = a
+    bn, bm, b2 = b
+    with np.errstate(all="ignore"):
+        n = an + bn
+        delta = bm - am
+        mean = am + delta * bn / n
+        m2 = a2 + b2 + delta * delta * an * bn / n
+    keep_a, keep_b = bn == 0.0, an == 0.0
+    if not (keep_a.any() or keep_b.any()):
+        return n, mean, m2
+    pick = lambda x, y, z: np.where(keep_a, x, np.where(keep_b, y, z))   # noqa: E731
+    return pick(an, bn, n), pick(am, bm, mean), pick(a2, b2, m2)
+
+
+def _tree_tiles(v, n):
+    """bg_norm_tile over v [..., T, 32, C] with n [T] live values per tile (1 <= n <= 32; the dead ones are never added)."""
+    p = v[..., 0, :]
+    nn = n[:, None].astype(np.float64)
+    s = np.zeros_like(p)
+    for i in range(TREE_TILE):
+        s = np.where((i < n)[:, None], s + (v[..., i, :] - p), s)
+    md = s / nn
+    m2 = np.zeros_like(p)
+    for i in range(TREE_TILE):
+        d = (v[..., i, :] - p) - md
+        m2 = np.where((i < n)[:, None], m2 + d * d, m2)
+    return nn, p + md, m2
+
+
+def tree_moments_obs(x):
+    """x float64 [..., N, C] -> (batch mean [..., C], batch population variance [..., C]) with bg_norm_obs_partials / bg_norm_obs_combine's order of
+    merging: tiles of 32 (bg_norm_tile), the tiles of a chunk of 256 left to right, the chunks left to right."""
+    x = np.asarray(x, np.float64)
+    N, Cn = x.shape[-2:]
+    lead = x.shape[:-2]
+    tpc = TREE_CHUNK // TREE_TILE
+    nchunks = -(-N // TREE_CHUNK)
+    T = nchunks * tpc
+    v = np.zeros(lead + (T * TREE_TILE, Cn), np.float64)
+    v[..., :N, :] = x
+    n = np.clip(N - np.arange(T) * TREE_TILE, 0, TREE_TILE)
+    live = np.maximum(n, 1)   # an absent tile is computed on zeros and then replaced by the empty triple
+    tn, tm, t2 = _tree_tiles(v.reshape(lead + (T, TREE_TILE, Cn)), live)
+    gone = (n == 0)[:, None]
+    tn, tm, t2 = np.where(gone, 0.0, tn), np.where(gone, 0.0, tm), np.where(gone, 0.0, t2)
+    shape = lead + (nchunks, tpc, Cn)
+    tn, tm, t2 = np.broadcast_to(tn, lead + (T, Cn)).reshape(shape), tm.reshape(shape), t2.reshape(shape)
+    zero = np.zeros(lead + (nchunks, Cn), np.float64)
+    acc = (zero, zero, zero)
+    for j in range(tpc):
+        acc = tree_merge(acc, (tn[..., j, :], tm[..., j, :], t2[..., j, :]))
+    step = (zero[..., 0, :], zero[..., 0, :], zero[..., 0, :])
+    for k in range(nchunks):
+        step = tree_merge(step, (acc[0][..., k, :], acc[1][..., k, :], acc[2][..., k, :]))
+    return step[1], step[2] / step[0]
+
+
+def _tree_wave(a):
+    """bg_norm_wave_tree over triples [..., 64] -> lane 0's triple.  Lane i takes lane i + off as its RIGHT operand, off = 1, 2, .., 32, and no lane there
+    is the empty triple.  Lane 0's result depends on the lanes that are multiples of 2 off only, so only those are computed: level by level the even
+    survivor merges the odd one to its right -- the same operands on the same sides as the shuffles give lane 0."""
+    while a[0].shape[-1] > 1:
+        a = tree_merge(tuple(c[..., 0::2] for c in a), tuple(c[..., 1::2] for c in a))
+    return tuple(c[..., 0] for c in a)
+
+
+def tree_moments_ret(ret):
+    """ret float64 [..., N] -> (batch mean [...], batch population variance [...]) with bg_norm_ret_partials / bg_norm_ret_combine's order of merging:
+    the shuffle tree over each wave of 64 envs, lane i of the finishing wave merges parts [i per, (i + 1) per) left to right, the same tree."""
+    ret = np.asarray(ret, np.float64)
+    N = ret.shape[-1]
+    lead = ret.shape[:-1]
+    nw = -(-N // TREE_WAVE)
+    per = -(-nw // TREE_WAVE)
+    v = np.zeros(lead + (nw * TREE_WAVE,), np.float64)
+    v[..., :N] = ret
+    n1 = (np.arange(nw * TREE_WAVE) < N).astype(np.float64)
+    shape = lead + (nw, TREE_WAVE)
+    _, pm, p2 = _tree_wave((np.broadcast_to(n1, v.shape).reshape(shape), v.reshape(shape), np.zeros(shape, np.float64)))
+    pn = np.clip(N - np.arange(nw) * TREE_WAVE, 0, TREE_WAVE).astype(np.float64)   # the combine takes a part's n from its index
+    pad = TREE_WAVE * per - nw
+    grid = lambda c: np.concatenate([np.broadcast_to(c, lead + (nw,)), np.zeros(lead + (pad,), np.float64)], axis=-1).reshape(lead + (TREE_WAVE, per))   # noqa: E731
+    gn, gm, g2 = grid(pn), grid(pm), grid(p2)
+    zero = np.zeros(lead + (TREE_WAVE,), np.float64)
+    acc = (zero, zero, zero)
+    for j in range(per):
+        acc = tree_merge(acc, (gn[..., j], gm[..., j], g2[..., j]))
+    n, mean, m2 = _tree_wave(acc)
+    return mean, m2 / n
+
+
+def returns_of(reward, done, carry, gamma=0.99):
+    """The returns every step's moments are taken over: float64 [K, N] (before the step's reset), and the carry behind the last step."""
+    ret = np.array(carry, np.float64)
+    out = np.empty(reward.shape, np.float64)
+    for t in range(reward.shape[0]):
+        ret = ret * gamma + reward[t]
+        out[t] = ret
+        ret = np.where(done[t], 0.0, ret)
+    return out, ret
+
+
+def tree_moments(rows, state=None, gamma=0.99):
+    """numpy_moments' shape with the fixed tree's values: {"obs": [K, 2, 153], "ret": [K, 2]}."""
+    rows = np.ascontiguousarray(rows)
+    K, N, _ = rows.shape
+    x = produced64(rows)
+    mo = np.stack([np.stack(tree_moments_obs(x[t])) for t in range(K)])
+    reward, done = gae_ref.unpack_records(rows)
+    rets, _ = returns_of(reward, done, np.zeros(N) if state is None else state["returns"], gamma)
+    return {"obs": mo, "ret": np.stack(tree_moments_ret(rets), axis=-1)}
+
+
+def reward_from_moments(reward, done, moments_ret, state, gamma=0.99, epsilon=1e-8, clip_reward=10.0, training=True):
+    """from_moments' reward half alone, on unpacked float64 [K, N] rewards and bool [K, N] terminated flags: -> {"reward" float64 [K, N], "state"} (the
+    observation statistics of `state` pass through untouched)."""
+    s = copy_state(state)
+    K, N = reward.shape
+    rew_n = np.zeros((K, N), np.float64)
+    with np.errstate(all="ignore"):
+        for t in range(K):
+            if training:
+                s["returns"] = s["returns"] * gamma + reward[t]
+                s["ret_mean"], s["ret_var"], s["ret_count"] = update_from_moments(s["ret_mean"], s["ret_var"], s["ret_count"], moments_ret[t, 0], moments_ret[t, 1], N)
+            rew_n[t] = np.clip(reward[t] / np.sqrt(s["ret_var"] + epsilon), -clip_reward, clip_reward)
+            if training:
+                s["returns"][done[t]] = 0
+    return {"reward": rew_n, "state": s}
+
+
 def bits32(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 

@@ -4,7 +4,11 @@ there (never with torch arithmetic on the GPU):
   1  the device's batch moments against numpy.mean / numpy.var(x.astype(float64), axis=0): |dmean| <= 4 N 2**-53 mean(|x|), |dvar| <= 4 N 2**-53 var,
      exactly 0.0 for a constant column -- every case, every step, every column and the returns;
   2  everything behind the reduction bit for bit: tests/norm_ref.py's `from_moments` on the host copy of the records and the device's own moments.
-Also: the carry across calls, determinism, update = 0, guards and arguments, gae_rows(rewards=), RowNormalizer."""
+Also: the carry across calls, determinism, update = 0, guards and arguments, gae_rows(rewards=), RowNormalizer.
+  9  past one reduction level (tests/norm_ref.py's BIG_CASES: 4 097, 8 519, 4 160 and 65 536 envs): 1 and 2, and both entry points' moments_out bit for bit
+     the numpy statement of the fixed tree (norm_ref.tree_moments_obs / tree_moments_ret).
+
+Largest observed shares of bound 1 on the MI355X at the shapes of 9: mean 0.0002, variance 0.062 (N = 65 536; 0.047 at the three smaller ones)."""
 import ctypes as C
 
 import numpy as np
@@ -198,6 +202,43 @@ def test_synthetic(K):
         again = d.obs(rows, "produced", "float32")[:2] + d.rew(rows)[:2]
         for a, b, name in zip(again, f, ("obs", "obs moments", "reward", "return moments")):
             _same(ref.bits64(a) if a.dtype == np.float64 else a, ref.bits64(b) if b.dtype == np.float64 else b, what + f": a second identical call differs ({name})")
+
+
+@pytest.mark.parametrize("case", ref.BIG_CASES, ids=lambda c: f"K{c[0]}-N{c[1]}")
+def test_past_one_reduction_level(case):
+    """9: N > 4 096, where bg_norm_ret_combine's lanes fold per >= 2 wave partials each before the tree (per = 2 with one part on lane 32 and none above;
+    per = 3 with a ragged last lane and a last wave of 7; per = 2 across the 16-step batch; per = 16 at 65 536 envs) and bg_norm_obs_combine walks 17,
+    34 and 256 chunks (a last chunk of one record, of two tiles and 7 records, full ones).  Checks 1 and 2 as everywhere, and the fixed tree itself: both
+    entry points' moments_out are tests/norm_ref.py's numpy statement of the merge order BIT FOR BIT -- a merge with its operands swapped, or one part
+    folded twice in place of its neighbour, can stay inside the bound of 1.  The same call twice gives the same bits; K split over two calls gives
+    the bits of one call."""
+    torch = _torch()
+    K, N, stride, seed = case
+    rows_host = ref.synthetic_rows(K, N, stride, seed)
+    rows = torch.from_numpy(rows_host).cuda()
+    s0 = ref.new_state(N)
+    what = f"K {K} N {N} stride {stride}"
+    w, f = _check_call(rows, s0, what, layouts=(("produced", "float32"), ("fixed", "bfloat16")))
+    tree = ref.tree_moments(rows_host, s0, KW["gamma"])
+    _same(ref.bits64(f[1]), ref.bits64(tree["obs"]), what + ": observation moments_out against the numpy statement of the fixed tree")
+    _same(ref.bits64(f[3]), ref.bits64(tree["ret"]), what + ": return moments_out against the numpy statement of the fixed tree")
+    d = Dev(s0, N)
+    again = d.obs(rows, "produced", "float32")[:2] + d.rew(rows)[:2]
+    names = ("obs", "obs moments", "reward", "return moments")
+    for a, b, name in zip(again, f, names):
+        _same(ref.bits64(a) if a.dtype == np.float64 else a, ref.bits64(b) if b.dtype == np.float64 else b, what + f": a second identical call differs ({name})")
+    if K > 1 and N < 10000:
+        k1 = K // 2
+        d = Dev(s0, N)
+        p1 = d.obs(rows[:k1], "produced", "float32")[:2] + d.rew(rows[:k1])[:2]
+        p2 = d.obs(rows[k1:], "produced", "float32")[:2] + d.rew(rows[k1:])[:2]
+        assert d.guards()
+        for a1, a2, b, name in zip(p1, p2, f, names):
+            a = np.concatenate([a1, a2])
+            _same(ref.bits64(a) if a.dtype == np.float64 else a, ref.bits64(b) if b.dtype == np.float64 else b, what + f": two calls differ from one ({name})")
+        got_state = d.state_bits()
+        for k, v in _want_state_bits(w["state"]).items():
+            _same(got_state[k], v, what + f": final {k} of two calls")
 
 
 @pytest.fixture(scope="module")

@@ -9,7 +9,10 @@ Then autograd: logits.grad is dlogits, a scaled loss scales it, and a two-layer 
 
 Largest observed shares of the bounds on the MI355X (the device library's expf / logf): dlogits 0.12, dvalues 0.49, policy_loss 0.011, approx_kl 0.001,
 entropy_loss 0.034, value_loss 0.19, loss 0.043, adv_mean 0.43, adv_std 0.40, log_prob 0.12, entropy 0.08, clip_fraction 0.48 (its bound on a set without
-undecidable rows is the final rounding alone)."""
+undecidable rows is the final rounding alone).
+At m = 65 793 (BIG2: two advantage triples per lane of bg_ppo_adv_combine, five row partials per lane of bg_ppo_finish): dlogits 0.12, dvalues 0.49,
+policy_loss 0.0006, approx_kl 0.00004, entropy_loss 0.010, value_loss 0.089, loss 0.0014, adv_mean 0.24, adv_std 0.28, log_prob 0.12, entropy 0.066,
+clip_fraction 0.071."""
 import ctypes as C
 
 import numpy as np
@@ -217,6 +220,22 @@ def test_more_partials_than_the_finishing_workgroup_has_lanes(layout):
         cf, (dl, dv, lp, en, st) = _check_one(layout, mkind, ikind, BIG, twice=True)
         assert st[9] == BIG and st[8] == cf.excluded.sum() > 0
     print(f"{layout}: largest shares so far {_shares}")
+
+
+BIG2 = 256 * 256 + 256 + 1   # 258 advantage triples: bg_ppo_adv_combine's lanes fold two each; 1 029 row partials: bg_ppo_finish's lanes fold five, lane 205 four
+BIG2_CASES = (("dense", "perm", True), (None, None, True), ("rec384", "repeat", True), ("dense", "perm", False))
+
+
+@pytest.mark.parametrize("mkind,ikind,normalize", BIG2_CASES, ids=["dense-perm", "none", "rec384-repeat", "dense-perm-raw-adv"])
+@pytest.mark.parametrize("layout", ["f32", "bf16"])
+def test_more_advantage_triples_than_the_statistics_workgroup_has_lanes(layout, mkind, ikind, normalize):
+    """m = 65 793: per = 2 in bg_ppo_adv_combine (m > 65 536; 258 triples of 256 rows, the last of one row) and per = 5 in bg_ppo_finish.  The record
+    masks are the product's 4 133 records read with repetition.  Twice, equal bits."""
+    assert -(-BIG2 // 256) == 258 and -(-258 // 256) == 2 and -(-BIG2 // 64) == 1029 and -(-1029 // 256) == 5 and 1029 - 205 * 5 == 4
+    cf, (dl, dv, lp, en, st) = _check_one(layout, mkind, ikind, BIG2, normalize=normalize, twice=True)
+    assert st[9] == BIG2 and st[8] == cf.excluded.sum() > 0
+    assert cf.apply == normalize
+    print(f"{layout} {mkind} {ikind}: largest shares so far {_shares}")
 
 
 def test_output_layout_is_independent_of_the_input_layout():

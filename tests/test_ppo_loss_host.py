@@ -6,7 +6,9 @@ masked and unmasked, with and without normalisation, value term and index; the h
 Also: the header's declaration, the exports, build.DEPS, and the argument checks of the Python wrapper.
 
 Largest observed shares of the bounds with g++ and glibc's expf / logf: dlogits 0.38, dvalues 0.25, policy_loss 0.0005, approx_kl 0.00002, entropy_loss
-0.02, value_loss 0.10, loss 0.002, adv_mean 0.45, adv_std 0.40, log_prob 0.11, entropy 0.08; undecidable rows at most 0.06 % of a set."""
+0.02, value_loss 0.10, loss 0.002, adv_mean 0.45, adv_std 0.40, log_prob 0.11, entropy 0.08; undecidable rows at most 0.06 % of a set.
+At m = 16 449 and 65 793 (the twin's folds with per > 1): dlogits 0.051, dvalues 0.50, policy_loss 0.0005, approx_kl 0.00001, entropy_loss 0.004,
+value_loss 0.079, loss 0.0013, adv_mean 0.43, adv_std 0.32, log_prob 0.094, entropy 0.048, clip_fraction 0.063; undecidable rows at most 0.033 %."""
 import ctypes as C
 import os
 import re
@@ -212,6 +214,27 @@ def test_synthetic_sets_hold_the_bounds(host, sigma, masked):
         hlp, hen = host.head(c.logits, mk, a)
         assert np.array_equal(_bits(lp)[ok], _bits(hlp)[ok]) and np.array_equal(_bits(en)[ok], _bits(hen)[ok])
     print(f"sigma {sigma} masked {masked}: largest shares so far {_shares}")
+
+
+@pytest.mark.parametrize("masked,index,normalize", [(True, "perm", True), (False, None, True), (True, "repeat", True), (True, "perm", False)],
+                         ids=["masked-perm", "unmasked", "masked-repeat", "masked-perm-raw-adv"])
+@pytest.mark.parametrize("m", [256 * 64 + 64 + 1, 256 * 256 + 256 + 1])
+def test_the_twins_second_level_folds(host, m, masked, index, normalize):
+    """per > 1 in the twin's own SLICES-THEN-TREE loops: m = 16 449 gives 258 row partials (per = 2 in the finish), m = 65 793 gives 258 advantage
+    triples (per = 2 in the moments) and 1 029 row partials (per = 5, lane 205 folds four, the lanes above none).  The sets are held to the cap."""
+    c = ppo_ref.synthetic(m % 1000 + 2 * masked + (5 if index else 0), m, 1.0, masked, index=index)
+    what = f"m {m} masked {masked} index {index} norm {normalize}"
+    cf = ppo_ref.ClosedForm(c, 0.2, 0.01, 0.5, normalize)
+    first = host.run(c, 0.2, 0.01, 0.5, normalize)
+    dl, dv, lp, en, st = first
+    _note(cf.check(dl, dv, lp, en, st, what, cap=True))
+    assert st[9] == m and st[8] == cf.excluded.sum() > 0 and cf.apply == normalize
+    for x, y in zip(first, host.run(c, 0.2, 0.01, 0.5, normalize, keep=True)):
+        assert np.array_equal(_bits(x), _bits(y)), what + ": two calls differ"
+    ok, mk, a, _, _, _ = c.gathered()
+    hlp, hen = host.head(c.logits, mk, a)
+    assert np.array_equal(_bits(lp)[ok], _bits(hlp)[ok]) and np.array_equal(_bits(en)[ok], _bits(hen)[ok])
+    print(f"{what}: undecidable {(~cf.decidable).mean():.5f}; largest shares so far {_shares}")
 
 
 def test_hand_made_rows(host):
