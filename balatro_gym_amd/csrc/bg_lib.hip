@@ -105,12 +105,28 @@ struct BgGenrandTab {
 static_assert(BG_MT_N % 16 == 0, "624 = 39 blocks of 16");
 static constexpr BgGenrandTab BG_GENRAND{};
 
+// One 16-byte group of a slot as ONE store instruction: on the device through the native vector type (assigned member by member, a uint4 whose
+// words are partly constants or arrive at different times is stored in two or three pieces); plain C++ on the host, where this text is compiled too
+// (tests/test_seed_slot*_host.py).
+#if defined(__HIP_DEVICE_COMPILE__)
+typedef uint32_t bg_u32x4v __attribute__((ext_vector_type(4)));
+__device__ __forceinline__ void bg_store16(uint4* dst, uint32_t x, uint32_t y, uint32_t z, uint32_t w) { bg_u32x4v v; v.x = x; v.y = y; v.z = z; v.w = w; *(bg_u32x4v*)dst = v; }
+#else
+__device__ __forceinline__ void bg_store16(uint4* dst, uint32_t x, uint32_t y, uint32_t z, uint32_t w) { *dst = make_uint4(x, y, z, w); }
+#endif
+
 // SLOT = false: the whole seeded state (156 16-byte stores).  SLOT = true: a shop-stream ring slot -- the first BG_SW_T OUTPUT words of
 // the stream, tempered, then the TOP BYTES of output words 0..23 packed into six words (BG_SW_PK: all a fresh inventory looks at, bg_shop_inventory --
-// two 16-byte pieces of ONE line instead of six of two), then the seed (bg_device.h): output word k = temper(S[k+397] ^ twist(S[k], S[k+1])).  The pass produces S in index
-// order, so the near words S[2..63] are parked RAW in the slot as they appear (blocks 0..3) and, when S[k+397] appears (blocks 24..28),
-// read back (they are this lane's own stores of ~20 000 cycles ago), combined, tempered and written over S[k] -- which nothing needs any
-// more.  S[1] is the last word the seeding produces, so outputs 0 and 1 (and the group they share with 2 and 3) are written at the end.
+// two 16-byte pieces of ONE line instead of six of two), then the seed (bg_device.h): output word k = temper(S[k+397] ^ twist(S[k], S[k+1])).
+// The slot is built ENTIRELY IN REGISTERS, every one of its sixteen 16-byte groups is stored exactly once, and the slot is never read here.  The pass
+// produces S in index order, so S[k] and S[k+1] are long gone when S[k+397] appears (blocks 24..28) -- they come AGAIN, from a second, delayed copy
+// of the two recurrences: it starts at index 2 when the chain reaches index 398 (its start values, the pass-1 word of index 1 and a1w, are known
+// when pass 2 begins; its init_genrand words have compile-time indexes) and runs in lockstep, one word ahead of k, so S[k], S[k+1] and S[k+397]
+// meet in registers: 55 extra chain steps on 1 870.  (The near words used to be parked raw in the slot and read back: 35 more memory instructions
+// per lane, each of them 64 separate lines, on the vector-memory path the step engine's service waves wait on.)  S[1] is the last word the
+// seeding produces, so outputs 0 and 1 -- and with them group 0 and the group of packed words 0..3 -- are stored at the end.  The stores are
+// PLAIN ones: the L2 puts a lane's sixteen pieces together into the slot's two lines; stored non-temporally they reach HBM piece by piece, the
+// kernel takes twice as long and the step engine beside it 20 % longer (profiles/refill_footprint.txt).
 template <bool SLOT>
 __device__ __forceinline__ void bg_mt_seed_impl(uint32_t* p, uint32_t key) {
   constexpr int NB = BG_MT_N / 16;
@@ -137,74 +153,88 @@ __device__ __forceinline__ void bg_mt_seed_impl(uint32_t* p, uint32_t key) {
   a = BG_GENRAND.blk[0].v[0];
   a = (BG_GENRAND.blk[0].v[1] ^ ((a ^ (a >> 30)) * 1664525u)) + key; // pass-1 mt[1] (before the wrap)
   uint32_t bprev = a1w, w2 = 0, w3 = 0;
-  uint32_t far0 = 0, far1 = 0, out2 = 0, out3 = 0;   // SLOT: S[397], S[398]; output words 2 and 3 (group 0 is written last)
-  uint32_t acc = 0;   // SLOT: the packed word under construction -- top byte of output word k -> byte k & 3 of slot word BG_SW_PK + (k >> 2), k < 24
+  // SLOT: the delayed copy of both recurrences (da: pass 1, db: pass 2 = S[index]); S[397], S[398]; output words 2 and 3 (group 0 is stored last); the
+  // output group and the packed word under construction (top byte of output word k -> byte k & 3 of slot word BG_SW_PK + (k >> 2), k < 24); the packed
+  // words 1..4 that wait for their group (1..3 for packed word 0 at the end, 4 for packed word 5)
+  uint32_t da = 0, db = 0, far0 = 0, far1 = 0, out2 = 0, out3 = 0, acc = 0;
+  uint32_t og[4] = {0, 0, 0, 0}, pk[5] = {0, 0, 0, 0, 0};
+  static_assert(BG_SW_T == 56 && BG_SW_PK == 56 && BG_SW_SEED == 62 && BG_SLOT_WORDS == 64, "slot layout: 14 groups of outputs, packed words 0..3, packed words 4 5 + seed + padding");
   {
     BgG16 cur = BG_GENRAND.blk[0];
+    // SLOT, blocks 24..28: the chain's words 16 B + c = S[k + 397] for k = 16 B - 397 + c (k = -13.., 3.., 19.., 35.., 51..), each met by the delayed copy's
+    // S[k], S[k+1].  B is a compile-time constant (b is uniform: each block is its own copy of the loop), so every k, group and packed-word index below
+    // is one too and all of it stays in registers.  (Six packed words kept to the end cost the kernel its fourth wave beside the step engine -- 69
+    // registers --, and indexed by a run-time k they went to scratch memory: the kernel ran 40 % longer.)
+    auto slot_block = [&](auto bc) {
+      constexpr int B = decltype(bc)::value;
+#pragma unroll
+      for (int c = 0; c < 16; c++) {
+        a = (cur.v[c] ^ ((a ^ (a >> 30)) * 1664525u)) + key;
+        bprev = (a ^ ((bprev ^ (bprev >> 30)) * 1566083941u)) - (uint32_t)(16 * B + c);
+        const int k = 16 * B + c - BG_MT_M;
+        if (k == 0) far0 = bprev;
+        if (k == 1) { // S[398]; the delayed copy starts: pass-1 word of index 1, S[1] as pass 2 saw it
+          far1 = bprev;
+          da = BG_GENRAND.blk[0].v[0];
+          da = (BG_GENRAND.blk[0].v[1] ^ ((da ^ (da >> 30)) * 1664525u)) + key;
+          db = a1w;
+        }
+        if (k >= 1 && k < BG_SW_T) {
+          const int i = k + 1;   // the delayed copy's index: 2..56
+          const uint32_t sk = db;
+          da = (BG_GENRAND.blk[i / 16].v[i % 16] ^ ((da ^ (da >> 30)) * 1664525u)) + key;
+          db = (da ^ ((db ^ (db >> 30)) * 1566083941u)) - (uint32_t)i;
+          if (k == 1) w2 = db;
+          else {
+            const uint32_t o = bg_temper(bg_twist(sk, db, bprev));   // output word k: S[k], S[k+1], S[k+397]
+            if (k == 2) out2 = o;
+            else if (k == 3) out3 = o;
+            else {
+              og[k & 3] = o;
+              if ((k & 3) == 3) bg_store16(p4 + (k >> 2), og[0], og[1], og[2], og[3]);
+              if (k < 24) {
+                acc |= (o >> 24) << (8 * (k & 3));
+                if ((k & 3) == 3) {
+                  // packed word 5 completes the slot's last group: packed words 4 and 5, the seed, padding
+                  if ((k >> 2) == 5) bg_store16(p4 + BG_SLOT_WORDS / 4 - 1, pk[4], acc, key, 0u);
+                  else pk[k >> 2] = acc;
+                  acc = 0u;
+                }
+              }
+            }
+          }
+        }
+      }
+    };
 #pragma unroll 1
     for (int b = 0; b < NB; b++) {
       const BgG16 nxt = BG_GENRAND.blk[b + 1 < NB ? b + 1 : NB - 1];
-      uint32_t v[16];
-#pragma unroll
-      for (int c = 0; c < 16; c++) {
-        v[c] = 0;
-        if (b > 0 || c >= 2) {
-          a = (cur.v[c] ^ ((a ^ (a >> 30)) * 1664525u)) + key;
-          bprev = (a ^ ((bprev ^ (bprev >> 30)) * 1566083941u)) - (uint32_t)(16 * b + c);
-          v[c] = bprev;
-        }
-      }
-      if (b == 0) { w2 = v[2]; w3 = v[3]; }
-      if constexpr (!SLOT) {
-#pragma unroll
-        for (int k = 0; k < 4; k++) {
-          const int q = 4 * b + k; // 16-byte group of the state
-          if (q == 0) continue;
-          p4[q] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-        }
+      bool slot_blk = false;
+      if constexpr (SLOT) slot_blk = b >= 24 && b <= 28;
+      if (slot_blk) {
+        if (b == 24) slot_block(std::integral_constant<int, 24>{});
+        else if (b == 25) slot_block(std::integral_constant<int, 25>{});
+        else if (b == 26) slot_block(std::integral_constant<int, 26>{});
+        else if (b == 27) slot_block(std::integral_constant<int, 27>{});
+        else slot_block(std::integral_constant<int, 28>{});
       } else {
-        if (b < 4) { // park S[4..63] raw in the slot (group 0 holds S[0..3]: S[2], S[3] stay in registers)
+        uint32_t v[16];
 #pragma unroll
-          for (int k = 0; k < 4; k++) if (4 * b + k > 0) p4[4 * b + k] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
-        } else if (b >= 24 && b <= 28) {
-          // words 16 b .. 16 b + 15 = S[k + 397] for k = 16 b - 397 + c
-          const int kb = 16 * b - BG_MT_M;                 // k of c = 0: -13, 3, 19, 35, 51
-          if (b == 24) { far0 = v[13]; far1 = v[14]; out2 = bg_temper(bg_twist(w2, w3, v[15])); }
-          else {
-            // near words S[kb .. kb + 16] back from the slot: five 16-byte groups starting at the group that holds word kb
-            const int g0 = kb >> 2;                        // 0, 4, 8, 12 (kb = 3, 19, 35, 51 -> the word is the group's fourth)
-            uint32_t nr[20];
+        for (int c = 0; c < 16; c++) {
+          v[c] = 0;
+          if (b > 0 || c >= 2) {
+            a = (cur.v[c] ^ ((a ^ (a >> 30)) * 1664525u)) + key;
+            bprev = (a ^ ((bprev ^ (bprev >> 30)) * 1566083941u)) - (uint32_t)(16 * b + c);
+            v[c] = bprev;
+          }
+        }
+        if constexpr (!SLOT) {
+          if (b == 0) { w2 = v[2]; w3 = v[3]; }
 #pragma unroll
-            for (int g = 0; g < 5; g++) {
-              uint4 t = make_uint4(0u, 0u, 0u, 0u);
-              if (g0 + g > 0 && g0 + g < BG_SLOT_WORDS / 4) t = p4[g0 + g];   // (not restrict-qualified reads of this lane's own earlier stores)
-              nr[4 * g] = t.x; nr[4 * g + 1] = t.y; nr[4 * g + 2] = t.z; nr[4 * g + 3] = t.w;
-            }
-            if (b == 25) nr[3] = w3;                       // (group 0 is not in memory: S[3])
-            // output words kb .. kb + 15 (its near words are nr[3 + c], nr[4 + c]); S[k] is dead: its place takes the output word.  Blocks 25 and 26 also
-            // collect the top bytes of words 4..23 into the packed words 1..5, each stored as soon as it is whole (slot words 57..61: the raw S[57..61]
-            // parked there are needed by nobody -- block 28 only looks at S[56] of that group); word 0 waits for outputs 0..2 at the end.  b is uniform, so
-            // each block is its own copy of the loop with COMPILE-TIME k.  (Six packed words kept to the end cost the kernel its fourth wave beside the
-            // step engine -- 69 registers --, and indexed by a run-time k they went to scratch memory: the kernel ran 40 % longer.)
-            auto outputs = [&](auto kbc) {
-              constexpr int KB = decltype(kbc)::value;
-#pragma unroll
-              for (int c = 0; c < 16; c++) {
-                const int k = KB + c;
-                if (k < BG_SW_T) {
-                  const uint32_t o = bg_temper(bg_twist(nr[3 + c], nr[4 + c], v[c]));
-                  if (k == 3) out3 = o; else p[k] = o;
-                  if (k >= 4 && k < 24) {
-                    acc |= (o >> 24) << (8 * (k & 3));
-                    if ((k & 3) == 3) { p[BG_SW_PK + (k >> 2)] = acc; acc = 0u; }
-                  }
-                }
-              }
-            };
-            if (b == 25) outputs(std::integral_constant<int, 16 * 25 - BG_MT_M>{});
-            else if (b == 26) outputs(std::integral_constant<int, 16 * 26 - BG_MT_M>{});
-            else if (b == 27) outputs(std::integral_constant<int, 16 * 27 - BG_MT_M>{});
-            else outputs(std::integral_constant<int, 16 * 28 - BG_MT_M>{});
+          for (int k = 0; k < 4; k++) {
+            const int q = 4 * b + k; // 16-byte group of the state
+            if (q == 0) continue;
+            p4[q] = make_uint4(v[4 * k], v[4 * k + 1], v[4 * k + 2], v[4 * k + 3]);
           }
         }
       }
@@ -215,11 +245,8 @@ __device__ __forceinline__ void bg_mt_seed_impl(uint32_t* p, uint32_t key) {
   if constexpr (!SLOT) p4[0] = make_uint4(0x80000000u, w1, w2, w3);
   else {
     const uint32_t out0 = bg_temper(bg_twist(0x80000000u, w1, far0)), out1 = bg_temper(bg_twist(w1, w2, far1));
-    p4[0] = make_uint4(out0, out1, out2, out3);
-    // the slot's tail: packed word 0 (the raw S[56] parked in its place has been read back by block 28), seed, padding
-    static_assert(BG_SW_PK == 56 && BG_SW_SEED == 62 && BG_SLOT_WORDS == 64, "slot tail layout");
-    p[BG_SW_PK] = (out0 >> 24) | ((out1 >> 24) << 8) | ((out2 >> 24) << 16) | (out3 & 0xff000000u);
-    *(uint2*)(p + BG_SW_SEED) = make_uint2(key, 0u);
+    bg_store16(p4, out0, out1, out2, out3);
+    bg_store16(p4 + BG_SW_PK / 4, (out0 >> 24) | ((out1 >> 24) << 8) | ((out2 >> 24) << 16) | (out3 & 0xff000000u), pk[1], pk[2], pk[3]);
   }
 }
 __device__ void bg_mt_seed(uint32_t* __restrict__ p, uint32_t key) { bg_mt_seed_impl<false>(p, key); }
@@ -447,6 +474,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_refill_scan_kernel(BgDev d) {
   if (g_valid > 0 && g_valid < d.KG) { uint32_t i = atomicAdd(&d.wl_count[2], 1u); d.wl[2 * N + i] = (uint32_t)env; }
 }
 
+typedef uint32_t bg_cp_u32x4 __attribute__((ext_vector_type(4)));   // a 16-byte piece as the non-temporal builtins take it
 // Lane = an env that is short of pre-shuffled decks; rounds of one shuffle each.  An env needs a deck per blind it started (~18 per
 // 372-step launch under a uniform policy: 1.2 M shuffles per refill at 65 536 envs) and its shuffles are serial (one stream), so a wave
 // that kept its 64 envs until the last of them was full ran max-over-lanes rounds: a lane whose env is full takes the NEXT env of the
@@ -511,7 +539,9 @@ __global__ __launch_bounds__(BG_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
         uint32_t wv[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int b = 0; b < 16; b++) { int i2 = k * 16 + b; if (i2 < 52) wv[b >> 2] |= (uint32_t)sdeck[i2][tid] << (8 * (b & 3)); }
-        d.ndeck[((size_t)slot * BG_NDECK + k) * N + env] = make_uint4(wv[0], wv[1], wv[2], wv[3]);
+        // non-temporal, as the global blocks: a ring deck is read a launch later, and its four pieces lie N x 16 bytes apart -- nothing for the L2 to combine
+        bg_cp_u32x4 nv; nv.x = wv[0]; nv.y = wv[1]; nv.z = wv[2]; nv.w = wv[3];
+        __builtin_nontemporal_store(nv, (bg_cp_u32x4*)&d.ndeck[((size_t)slot * BG_NDECK + k) * N + env]);
       }
       d_ready++; made++;
       need = d_ready < d.KD && made < cap;
@@ -560,8 +590,8 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_refill_seedring_kernel(BgDev d, B
 __global__ __launch_bounds__(BG_BLOCK, 8) void bg_refill_shop_kernel(BgDev d, BgPart pt) {
   const uint32_t count0 = d.wl_count[3], lo = bg_part_lo(count0, pt), count = bg_part_hi(count0, pt);
   for (uint32_t item = lo + blockIdx.x * BG_BLOCK + threadIdx.x; item < count; item += gridDim.x * BG_BLOCK) {
-    uint32_t es = d.wl_shop[2 * (size_t)item], seed = d.wl_shop[2 * (size_t)item + 1];
-    bg_mt_seed_slot(bg_sblock(d, (int)(es & 0xffffffu), (int)(es >> 24)), seed);
+    const uint2 it = ((const uint2*)d.wl_shop)[item];   // env | slot << 24, shop seed: one 8-byte load
+    bg_mt_seed_slot(bg_sblock(d, (int)(it.x & 0xffffffu), (int)(it.x >> 24)), it.y);
   }
 }
 // Next 624-word block(s) of the per-env global stream, ONE WAVE PER ENV: lane l holds words l, l + 64, ... of the block (ten
@@ -1924,7 +1954,6 @@ int bg_set_max_ante(bg_handle* h, int max_ante, const int32_t* per_env_host, con
 // Shape from a sweep on the MI355X (tools/micro/copybw.hip, profiles/r03_copybw.txt): ONE pass per workgroup (no grid-stride loop), four
 // 16-byte pieces per lane, non-temporal loads and stores: 6.5 TB/s read + written at 1 GiB (the guide's float4 copy: 6.29; the
 // grid-stride kernel of rounds 1-2: 5.1-5.6).  A plain one-pass fill writes 6.8 TB/s.
-typedef uint32_t bg_cp_u32x4 __attribute__((ext_vector_type(4)));
 __global__ __launch_bounds__(256) void bg_stream_copy_kernel(const bg_cp_u32x4* __restrict__ src, bg_cp_u32x4* __restrict__ dst, size_t n16) {
   const size_t i = (size_t)blockIdx.x * 256 * 4 + threadIdx.x;
   bg_cp_u32x4 v[4];
