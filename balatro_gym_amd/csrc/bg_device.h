@@ -1,13 +1,18 @@
 // bg_device.h -- HBM data layout + per-env device functions of the MI355X Balatro step path (gfx950 only).
 //
-// Execution model: ONE LANE = ONE ENV (a wave64 steps 64 independent games in lockstep).  Every per-env array is
-// structure-of-arrays with the env index fastest, so a wave's access to any field is one coalesced request:
+// Execution model of the per-key kernels: ONE LANE = ONE ENV (a wave64 steps 64 independent games in lockstep).  The per-env state arrays
+// are structure-of-arrays with the env index fastest, so such a wave's access to any field is one coalesced request:
 //   hot   uint4[BG_NHOT ][N]   packed game state, 16 B "chunks" (global_load_dwordx4 per lane = 1 KiB per wave)
-//   deck  uint4[4       ][N]   52 card codes ((rank-2)*4+suit, cards.py:103-104), 12 B pad
 //   cold  uint4[BG_NCOLD][N]   hand_play_counts + shop inventory (touched only by the lanes that need them)
 //   tmpl  uint4[2       ][N]   reset template (harness injection: jokers / money / ante / hand levels)
-//   ndeck uint4[KD][4][N]      ring of pre-shuffled decks (DeterministicRNG 'deck_shuffle' look-ahead)
-// MT19937 state is the exception: a stream is produced AND consumed by one lane walking consecutive words, so each env
+// The decks are array-of-structures: whoever touches a deck is a SPARSE lane (a service lane of bg_engine3.h that resets its env, an owner lane
+// fetching its env's next ring deck, a lane of bg_refill_deck_kernel with whichever env it took from the work list) and moves all four chunks,
+// so a deck is one aligned 64-byte sector instead of 16 bytes in each of four lines:
+//   deck  uint4[N][4]          52 card codes ((rank-2)*4+suit, cards.py:103-104), 12 B pad
+//   ndeck uint4[N][KD][4]      ring of pre-shuffled decks (DeterministicRNG 'deck_shuffle' look-ahead); two consecutive slots share a line
+// Every address of these five arrays comes from the accessors below (bg_hot / bg_cold / bg_deck / bg_tmpl / bg_ndeck), host and device.
+// (hot / cold / tmpl per env -- one 128-byte line each -- were measured too and did not gain: DESIGN.md section 3, profiles/state_lines.txt.)
+// MT19937 state likewise: a stream is produced AND consumed by one lane walking consecutive words, so each env
 // owns contiguous 2560-byte blocks (array-of-structures; sparse lanes then write whole lines instead of 4 bytes/line):
 //   gblk  u32[N][KG][640]      per-env "global random" stream: ring of consecutive raw MT19937 blocks (624 words used)
 //   sblk  u32[N][KS][640]      ring of pre-seeded shop streams (first block of random.Random(shop_seed))
@@ -30,6 +35,23 @@
 #define BG_MT_M 397
 #define BG_MTS 640 // words per stored MT block (624 + index word, padded to 20 x 128 B)
 #define BG_BLOCK 64 // threads per block = one wave64
+#define BG_HD __host__ __device__ __forceinline__
+
+// ---- per-env array layout ------------------------------------------------------------------------------------------
+// Index, in 16-byte chunks, of chunk k of an env (ring slot `slot` for ndeck) and the chunks each array is allocated with.  Plain
+// C++ (a test compiles this block on the host by itself): the allocations, the state blob's slices (bg_slices), the host
+// mirror of the reset template and every kernel go through these, so a layout is stated here and nowhere else.
+BG_HD size_t bg_hot_at(size_t N, size_t env, int k) { return (size_t)k * N + env; }
+BG_HD size_t bg_hot_chunks(size_t N) { return N * BG_NHOT; }
+BG_HD size_t bg_cold_at(size_t N, size_t env, int k) { return (size_t)k * N + env; }
+BG_HD size_t bg_cold_chunks(size_t N) { return N * BG_NCOLD; }
+BG_HD size_t bg_tmpl_at(size_t N, size_t env, int k) { return (size_t)k * N + env; }
+BG_HD size_t bg_tmpl_chunks(size_t N) { return N * BG_NTMPL; }
+BG_HD size_t bg_deck_at(size_t N, size_t env, int k) { (void)N; return env * BG_NDECK + (size_t)k; }
+BG_HD size_t bg_ndeck_at(size_t N, size_t KD, size_t env, size_t slot, int k) { (void)N; return (env * KD + slot) * BG_NDECK + (size_t)k; }
+BG_HD size_t bg_deck_chunks(size_t N) { return N * BG_NDECK; }
+BG_HD size_t bg_ndeck_chunks(size_t N, size_t KD) { return N * KD * BG_NDECK; }
+// ---- end of the per-env array layout -------------------------------------------------------------------------------
 
 // device error word bits (sticky; checked by the host, which then fails loudly)
 #define BG_DEVERR_GSTREAM 1u  // global-stream ring underflow
@@ -87,6 +109,12 @@ struct BgDev {
   uint32_t* sealmt;  // u32[N][640], lazy MT19937 of stream 13 'seal_applications' (purple seals)
   const uint32_t* jtab; // the JTables of bg_step.h, built once per handle (bg_tables_build_kernel): the engine kernel copies them to LDS
 };
+
+__device__ __forceinline__ uint4* bg_hot(const BgDev& d, int env, int k) { return d.hot + bg_hot_at((size_t)d.N, (size_t)env, k); }
+__device__ __forceinline__ uint4* bg_cold(const BgDev& d, int env, int k) { return d.cold + bg_cold_at((size_t)d.N, (size_t)env, k); }
+__device__ __forceinline__ uint4* bg_deck(const BgDev& d, int env, int k) { return d.deck + bg_deck_at((size_t)d.N, (size_t)env, k); }
+__device__ __forceinline__ uint4* bg_tmpl(const BgDev& d, int env, int k) { return d.tmpl + bg_tmpl_at((size_t)d.N, (size_t)env, k); }
+__device__ __forceinline__ uint4* bg_ndeck(const BgDev& d, int env, int slot, int k) { return d.ndeck + bg_ndeck_at((size_t)d.N, (size_t)d.KD, (size_t)env, (size_t)slot, k); }
 
 // ---------------------------------------------------------------------------------------------------------
 // Unpacked per-env state (lives in registers for the duration of a step)
@@ -185,7 +213,7 @@ __device__ __forceinline__ void bg_derive_ready(Env& e, uint32_t prod) {
 __device__ __forceinline__ void bg_load_env(const BgDev& d, int env, Env& e) {
   uint4 c[BG_NHOT];
 #pragma unroll
-  for (int k = 0; k < BG_NHOT; k++) c[k] = d.hot[(size_t)k * d.N + env];
+  for (int k = 0; k < BG_NHOT; k++) c[k] = *bg_hot(d, env, k);
   bg_unpack(c, e);
   bg_derive_ready(e, d.prod_view ? d.prod_view[env] : 0u);
 }
@@ -193,7 +221,7 @@ __device__ __forceinline__ void bg_store_env(const BgDev& d, int env, const Env&
   uint4 c[BG_NHOT];
   bg_pack(e, c);
 #pragma unroll
-  for (int k = 0; k < BG_NHOT; k++) d.hot[(size_t)k * d.N + env] = c[k];
+  for (int k = 0; k < BG_NHOT; k++) *bg_hot(d, env, k) = c[k];
 }
 
 // byte i of a packed 8-byte list
@@ -292,7 +320,7 @@ __device__ __forceinline__ uint32_t bg_cstate(const BgDev& d, int env, int ci) {
   return (uint32_t)((const uint16_t*)&d.cstate[(size_t)(ci >> 3) * d.N + env])[ci & 7];
 }
 __device__ __forceinline__ Deck0 bg_load_deck0(const BgDev& d, int env) {
-  uint4 c = d.deck[env];
+  uint4 c = *bg_deck(d, env, 0);
   Deck0 r;
   r.lo = ((uint64_t)c.y << 32) | c.x;
   r.hi = ((uint64_t)c.w << 32) | c.z;
@@ -307,7 +335,7 @@ __device__ __forceinline__ void bg_deck_set(DeckLds& dk, int k, uint4 c) {
 }
 __device__ __forceinline__ int bg_card(const BgDev& d, int env, const Deck0& k, int idx) {
   if (idx < 16) return (int)(((idx < 8 ? k.lo : k.hi) >> (8 * (idx & 7))) & 0xffull);
-  const uint32_t* p = (const uint32_t*)&d.deck[(size_t)(idx >> 4) * d.N + env];   // (rare: past the L1, see bg_ld4a)
+  const uint32_t* p = (const uint32_t*)bg_deck(d, env, idx >> 4);   // (rare: past the L1, see bg_ld4a)
   return (int)((bg_ld4a(p + ((idx & 15) >> 2)) >> (8 * (idx & 3))) & 0xffu);
 }
 // workgroup decks with the row stride as a parameter (bg_engine_kernel: 256 envs per workgroup)

@@ -175,9 +175,9 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
     int act0 = 0;
     if (mine) {
 #pragma unroll
-      for (int k = 0; k < BG_NHOT; k++) c[k] = d.hot[(size_t)k * N + envp];
+      for (int k = 0; k < BG_NHOT; k++) c[k] = *bg_hot(d, envp, k);
 #pragma unroll
-      for (int k = 0; k < BG_NDECK; k++) dw[k] = d.deck[(size_t)k * N + envp];
+      for (int k = 0; k < BG_NDECK; k++) dw[k] = *bg_deck(d, envp, k);
       prod = d.prod_view ? d.prod_view[envp] : 0u;
       if (a.actions_in) act0 = a.actions_in[envp];   // (step 0 of the launch)
     }
@@ -220,7 +220,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
       __builtin_amdgcn_s_setprio(1);
       uint4 c[BG_NHOT];
 #pragma unroll
-      for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) c[k] = d.hot[(size_t)k * N + envp];
+      for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) c[k] = *bg_hot(d, envp, k);
       c[3] = s_c34[0][l0]; c[4] = s_c34[1][l0];
       Env pe;
       ShopRegs psr; psr.valid = false;
@@ -573,7 +573,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         BG_PROBE_BEGIN();
         uint4 c[BG_NHOT];
 #pragma unroll
-        for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) c[k] = d.hot[(size_t)k * N + env];
+        for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) c[k] = *bg_hot(d, env, k);
         c[3] = s_c34[0][l]; c[4] = s_c34[1][l];
         Env e;
         bg_unpack(c, e);
@@ -601,7 +601,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         BG_PROBE(26);
         bg_pack(e, c);
 #pragma unroll
-        for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) d.hot[(size_t)k * N + env] = c[k];
+        for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) *bg_hot(d, env, k) = c[k];
         s_c34[0][l] = c[3]; s_c34[1][l] = c[4];
         s_mask[l] = mask;
         BG_PROBE(27);
@@ -649,8 +649,8 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
   __syncthreads();
   if (tid == 0) BG_TL(12);
   if (tid < n_live) {
-    d.hot[(size_t)3 * N + env0 + tid] = s_c34[0][tid];
-    d.hot[(size_t)4 * N + env0 + tid] = s_c34[1][tid];
+    *bg_hot(d, env0 + tid, 3) = s_c34[0][tid];
+    *bg_hot(d, env0 + tid, 4) = s_c34[1][tid];
     if (keys_at_end) bg_emit_keys_from_image((const lds_u4*)&s_img[tid][0], a.obs, (size_t)(env0 + tid));
   }
   if (a.stats) {   // (bg_step.h: one set of global atomics per workgroup, not per wave)

@@ -112,7 +112,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
     if (l < n_live) {
       uint4 c[BG_NHOT];
 #pragma unroll
-      for (int k = 0; k < BG_NHOT; k++) c[k] = d.hot[(size_t)k * N + env];
+      for (int k = 0; k < BG_NHOT; k++) c[k] = *bg_hot(d, env, k);
       s_c34[0][l] = c[3]; s_c34[1][l] = c[4];
       DeckT dk; static_cast<Deck0&>(dk) = bg_load_deck0(d, env);
       const uint32_t prod = d.prod_view ? d.prod_view[env] : 0u;
@@ -123,7 +123,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
       s_ndst[l] = e.d_ready > 0 ? 1u : 0u;
       if (e.d_ready > 0) {
 #pragma unroll
-        for (int k = 0; k < BG_NDECK; k++) s_nd[k][l] = d.ndeck[((size_t)e.d_head * BG_NDECK + k) * N + env];
+        for (int k = 0; k < BG_NDECK; k++) s_nd[k][l] = *bg_ndeck(d, env, e.d_head, k);
       }
       ShopRegs sr; sr.valid = false;
       const uint64_t mask = bg_action_mask(d, env, e, sr);
@@ -177,7 +177,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
         abase[s] = 0; athr[s] = 100u;
         prow[s] = (size_t)(env0 + l);
         if (l < n_live) {   // (the envs past N of the last workgroup have no state)
-          const uint32_t cap = (d.hot[(size_t)7 * N + (size_t)(env0 + l)].w >> 16) & 0xffu;   // Env::max_ante (bg_unpack), a constant of the launch
+          const uint32_t cap = (bg_hot(d, env0 + l, 7)->w >> 16) & 0xffu;   // Env::max_ante (bg_unpack), a constant of the launch
           if (cap > 0u && cap < 100u) athr[s] = cap;
         }
       } else {
@@ -242,7 +242,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           const uint32_t nds = bg_lds_ld(&s_ndst[l]);
           if ((nds & 0xffu) == 2u) {   // the step reset the env and consumed its LDS deck: fetch the next ring slot
 #pragma unroll
-            for (int k = 0; k < BG_NDECK; k++) ndv[s][k] = *(const __attribute__((address_space(1))) bg_u32x4*)&d.ndeck[((size_t)(nds >> 8) * BG_NDECK + k) * N + env];
+            for (int k = 0; k < BG_NDECK; k++) ndv[s][k] = *(const __attribute__((address_space(1))) bg_u32x4*)bg_ndeck(d, env, (int)(nds >> 8), k);
             bg_lds_st(&s_ndst[l], 0u);   // (not here until it has landed: a reset in between reads the ring itself)
             ndp[s] = true;
           }
@@ -495,7 +495,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           BG_PROBE_BEGIN();
           uint4 c[BG_NHOT];
 #pragma unroll
-          for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) c[k] = d.hot[(size_t)k * N + env];
+          for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) c[k] = *bg_hot(d, env, k);
           c[3] = s_c34[0][l]; c[4] = s_c34[1][l];
           DeckT dk; static_cast<Deck0&>(dk) = bg_load_deck0(d, env);
           RngWin w;
@@ -529,7 +529,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           BG_PROBE(26);
           bg_pack(e, c);
 #pragma unroll
-          for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) d.hot[(size_t)k * N + env] = c[k];
+          for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) *bg_hot(d, env, k) = c[k];
           s_c34[0][l] = c[3]; s_c34[1][l] = c[4];
           s_mask[l] = mask;
           if (o.hand_type >= 0) { n_plays++; ssum += o.final_score; }
@@ -548,8 +548,8 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
   BG_PROBE_FLUSH(d);
   __syncthreads();
   for (int l = tid; l < n_live; l += (NOW + NSV) * BG_BLOCK) {
-    d.hot[(size_t)3 * N + env0 + l] = s_c34[0][l];
-    d.hot[(size_t)4 * N + env0 + l] = s_c34[1][l];
+    *bg_hot(d, env0 + l, 3) = s_c34[0][l];
+    *bg_hot(d, env0 + l, 4) = s_c34[1][l];
   }
   if (a.stats) bg_stats_flush(a.stats, L.s_stats, tid);
   if constexpr (kE3Tl) if (tid == 0 && d.dbg) atomicAdd(&d.dbg[31], wall_clock64() - e3_k0);   // workgroup end

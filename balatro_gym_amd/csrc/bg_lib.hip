@@ -436,9 +436,9 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_refill_scan_kernel(BgDev d) {
   size_t N = d.N;
   // consumer counters (written by step / rollout kernels; each group sits in one 32-bit word, so a concurrent writer can
   // only make this kernel see a NEWER consumer state, which just frees more slots)
-  uint32_t w5 = ((const uint32_t*)&d.hot[(size_t)5 * N + env])[3];
-  uint32_t w6 = ((const uint32_t*)&d.hot[(size_t)6 * N + env])[3];
-  uint2 w7 = *((const uint2*)&d.hot[(size_t)7 * N + env]);
+  uint32_t w5 = ((const uint32_t*)bg_hot(d, env, 5))[3];
+  uint32_t w6 = ((const uint32_t*)bg_hot(d, env, 6))[3];
+  uint2 w7 = *((const uint2*)bg_hot(d, env, 7));
   uint32_t prod = d.prod_in[env];
   int d_cons = bg_b(w5, 3), g_cons = bg_b(w6, 3), s_cur = bg_b(w7.y, 0), s_cons = bg_b(w7.y, 1);
   int d_ready = (int)((prod - (uint32_t)d_cons) & 0xffu);
@@ -508,7 +508,7 @@ __global__ __launch_bounds__(BG_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
         if (!have && my < count) {
           env = (int)d.wl[my];
           mt = bg_deckmt(d, env);
-          const uint32_t w5 = ((const uint32_t*)&d.hot[(size_t)5 * N + env])[3];
+          const uint32_t w5 = ((const uint32_t*)bg_hot(d, env, 5))[3];
           prod = d.prod_out[env];
           d_head = bg_b(w5, 2);
           d_ready = (int)((prod - (uint32_t)bg_b(w5, 3)) & 0xffu);
@@ -539,9 +539,10 @@ __global__ __launch_bounds__(BG_BLOCK) __attribute__((amdgpu_waves_per_eu(4, 4))
         uint32_t wv[4] = {0, 0, 0, 0};
 #pragma unroll
         for (int b = 0; b < 16; b++) { int i2 = k * 16 + b; if (i2 < 52) wv[b >> 2] |= (uint32_t)sdeck[i2][tid] << (8 * (b & 3)); }
-        // non-temporal, as the global blocks: a ring deck is read a launch later, and its four pieces lie N x 16 bytes apart -- nothing for the L2 to combine
+        // four back-to-back 16-byte stores into the slot's one aligned 64-byte sector (bg_ndeck); non-temporal, as the global blocks: a ring deck is
+        // read a launch later (plain stores measured the same: profiles/state_lines.txt)
         bg_cp_u32x4 nv; nv.x = wv[0]; nv.y = wv[1]; nv.z = wv[2]; nv.w = wv[3];
-        __builtin_nontemporal_store(nv, (bg_cp_u32x4*)&d.ndeck[((size_t)slot * BG_NDECK + k) * N + env]);
+        __builtin_nontemporal_store(nv, (bg_cp_u32x4*)bg_ndeck(d, env, slot, k));
       }
       d_ready++; made++;
       need = d_ready < d.KD && made < cap;
@@ -606,7 +607,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_refill_gblk_kernel(BgDev d, BgPar
   constexpr int NR = (BG_MT_N + 63) / 64; // 10 rows, the last one 48 words
   for (uint32_t item = lo + blockIdx.x; item < count; item += gridDim.x) {
     const int env = (int)d.wl[2 * N + item];
-    const uint32_t w6 = ((const uint32_t*)&d.hot[(size_t)6 * N + env])[3];
+    const uint32_t w6 = ((const uint32_t*)bg_hot(d, env, 6))[3];
     const uint32_t prod = d.prod_out[env];
     const int g_cur = bg_b(w6, 2), g_cons = bg_b(w6, 3);
     int g_valid = (int)(((prod >> 16) - (uint32_t)g_cons) & 0xffu);
@@ -668,7 +669,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_inject_kernel(BgDev d, const uint
   if (mask_in && !mask_in[env]) return;
   Env e;
   bg_load_env(d, env, e);
-  uint4 t0 = d.tmpl[env], t1 = d.tmpl[(size_t)d.N + env];
+  uint4 t0 = *bg_tmpl(d, env, 0), t1 = *bg_tmpl(d, env, 1);
   if (t0.y & 0x80000000u) { e.njokers = (int)bg_b(t0.y, 1); e.jokers = (uint64_t)t0.x | ((uint64_t)(t0.y & 0xffu) << 32); }
   if (t0.y & 0x40000000u) e.money = (int32_t)t0.z;
   if (t0.y & 0x20000000u) e.ante = (int)bg_b(t0.y, 2);
@@ -692,13 +693,13 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_inject_deck_kernel(BgDev d, const
   if (env >= d.N) return;
   if (mask_in && !mask_in[env]) return;
 #pragma unroll
-  for (int k = 0; k < BG_NDECK; k++) d.deck[(size_t)k * d.N + env] = decks[(size_t)env * BG_NDECK + k];
+  for (int k = 0; k < BG_NDECK; k++) *bg_deck(d, env, k) = decks[(size_t)env * BG_NDECK + k];
 }
 __global__ __launch_bounds__(BG_BLOCK) void bg_set_cap_kernel(BgDev d, const int32_t* __restrict__ caps, int scalar, const uint8_t* __restrict__ mask_in) {
   int env = blockIdx.x * BG_BLOCK + threadIdx.x;
   if (env >= d.N) return;
   if (mask_in && !mask_in[env]) return;
-  uint32_t* w = ((uint32_t*)&d.hot[(size_t)7 * d.N + env]) + 3; // chunk 7, word 3: excess (low half) | cap << 16
+  uint32_t* w = ((uint32_t*)bg_hot(d, env, 7)) + 3; // chunk 7, word 3: excess (low half) | cap << 16
   const int cap = caps ? caps[env] : scalar;
   *w = (*w & 0xffffu) | ((uint32_t)(cap & 0xff) << 16);
 }
@@ -957,11 +958,11 @@ int bg_create_ex(int n_envs, int device_id, uint32_t flags, int max_ante, int fu
   size_t N = (size_t)n_envs;
   BG_GUARD(h); // the caller's current device is restored on return
   hipError_t e = hipSuccess;
-  if (e == hipSuccess) e = bg_alloc(h, &d.hot, BG_NHOT * N);
-  if (e == hipSuccess) e = bg_alloc(h, &d.deck, BG_NDECK * N);
-  if (e == hipSuccess) e = bg_alloc(h, &d.cold, BG_NCOLD * N);
-  if (e == hipSuccess) e = bg_alloc(h, &d.tmpl, BG_NTMPL * N);
-  if (e == hipSuccess) e = bg_alloc(h, &d.ndeck, (size_t)d.KD * BG_NDECK * N);
+  if (e == hipSuccess) e = bg_alloc(h, &d.hot, bg_hot_chunks(N));
+  if (e == hipSuccess) e = bg_alloc(h, &d.deck, bg_deck_chunks(N));
+  if (e == hipSuccess) e = bg_alloc(h, &d.cold, bg_cold_chunks(N));
+  if (e == hipSuccess) e = bg_alloc(h, &d.tmpl, bg_tmpl_chunks(N));
+  if (e == hipSuccess) e = bg_alloc(h, &d.ndeck, bg_ndeck_chunks(N, (size_t)d.KD));
   if (e == hipSuccess) e = bg_alloc(h, &d.gblk, (size_t)d.KG * BG_MTS * N);
   if (e == hipSuccess) e = bg_alloc(h, &d.sblk, (size_t)d.KS * BG_SLOT_WORDS * N);
   if (e == hipSuccess) e = bg_alloc(h, &d.sovf, (size_t)BG_MTS * N);
@@ -1003,7 +1004,7 @@ int bg_create_ex(int n_envs, int device_id, uint32_t flags, int max_ante, int fu
   d.jtab = h->d_jtab;
   hipLaunchKernelGGL(bg_tables_build_kernel, dim3(1), dim3(256), 0, 0, h->d_jtab);
   if (hipGetLastError() != hipSuccess || hipDeviceSynchronize() != hipSuccess) { g_create_err = "bg_create: table kernel failed"; bg_destroy(h); return BG_E_HIP; }
-  h->h_tmpl.assign(BG_NTMPL * N, make_uint4(0, 0, 0, 0));
+  h->h_tmpl.assign(bg_tmpl_chunks(N), make_uint4(0, 0, 0, 0));
   h->h_cap.assign(N, (uint8_t)(max_ante > 0 && max_ante < 256 ? max_ante : 0));
   if (max_ante < 0 || max_ante > 255) { g_create_err = "bg_create: max_ante must be in [0, 255]"; bg_destroy(h); return BG_E_ARG; }
   if (max_ante > 0) { // the cap lives in each env's state (bg_set_max_ante changes it later: a rising curriculum)
@@ -1704,8 +1705,8 @@ int bg_inject(bg_handle* h, const int32_t* jokers_host, const int32_t* njokers_h
   size_t N = h->dev.N;
   for (size_t i = 0; i < N; i++) {
     if (mask_host && !mask_host[i]) continue;
-    uint4& t0 = h->h_tmpl[i];
-    uint4& t1 = h->h_tmpl[N + i];
+    uint4& t0 = h->h_tmpl[bg_tmpl_at(N, i, 0)];
+    uint4& t1 = h->h_tmpl[bg_tmpl_at(N, i, 1)];
     uint32_t fl = t0.y >> 24;
     uint32_t j4 = t0.y & 0xffu, nj = (t0.y >> 8) & 0xffu, an = (t0.y >> 16) & 0xffu;
     if (jokers_host && njokers_host) {
@@ -1733,7 +1734,7 @@ int bg_inject(bg_handle* h, const int32_t* jokers_host, const int32_t* njokers_h
     }
     t0.y = j4 | (nj << 8) | (an << 16) | (fl << 24);
   }
-  BG_HIP(hipMemcpyAsync(h->dev.tmpl, h->h_tmpl.data(), BG_NTMPL * N * sizeof(uint4), hipMemcpyHostToDevice, s));
+  BG_HIP(hipMemcpyAsync(h->dev.tmpl, h->h_tmpl.data(), h->h_tmpl.size() * sizeof(uint4), hipMemcpyHostToDevice, s));
   if (apply_now) {
     if (mask_host) BG_HIP(hipMemcpyAsync(h->d_mask, mask_host, N, hipMemcpyHostToDevice, s));
     { const int rcw = bg_wait_refill(h, s, 0); if (rcw) return rcw; }
@@ -1754,7 +1755,7 @@ int bg_inject_consumables(bg_handle* h, const int32_t* ids_host, const int32_t* 
   for (size_t i = 0; i < N; i++) {
     if (mask_host && !mask_host[i]) continue;
     int n = n_host[i];
-    if (n < 0) { h->h_tmpl[N + i].z = 0; continue; } // back to the reset default (no consumables)
+    if (n < 0) { h->h_tmpl[bg_tmpl_at(N, i, 1)].z = 0; continue; } // back to the reset default (no consumables)
     if (n > 2) { h->err = "bg_inject_consumables: an env holds at most consumable_slots = 2"; return BG_E_ARG; }
     uint32_t v = 0x80000000u | (uint32_t)n;
     for (int k = 0; k < n; k++) {
@@ -1764,9 +1765,9 @@ int bg_inject_consumables(bg_handle* h, const int32_t* ids_host, const int32_t* 
       if (other && !h->dev.cstate) { h->err = "bg_inject_consumables: tarot / spectral cards need BG_FLAG_CARD_STATES"; return BG_E_ARG; }
       v |= (uint32_t)id << (8 * (k + 1));
     }
-    h->h_tmpl[N + i].z = v;
+    h->h_tmpl[bg_tmpl_at(N, i, 1)].z = v;
   }
-  BG_HIP(hipMemcpyAsync(h->dev.tmpl, h->h_tmpl.data(), BG_NTMPL * N * sizeof(uint4), hipMemcpyHostToDevice, s));
+  BG_HIP(hipMemcpyAsync(h->dev.tmpl, h->h_tmpl.data(), h->h_tmpl.size() * sizeof(uint4), hipMemcpyHostToDevice, s));
   if (apply_now) {
     if (mask_host) BG_HIP(hipMemcpyAsync(h->d_mask, mask_host, N, hipMemcpyHostToDevice, s));
     { const int rcw = bg_wait_refill(h, s, 0); if (rcw) return rcw; }
@@ -1779,17 +1780,28 @@ int bg_inject_consumables(bg_handle* h, const int32_t* ids_host, const int32_t* 
 }
 
 // ---- save_state / load_state: raw per-env slices of every array, in a fixed order ----
-struct BgSlice { void* base; size_t rows; size_t elem; };
+// A slice is `rows` pieces of `elem` bytes per env: row r of env i lies at base + i * env_stride + r * row_stride on the device (the strides are the
+// array's layout, bg_device.h) and at r * elem in the blob, whatever the layout
+struct BgSlice { void* base; size_t rows; size_t elem; size_t env_stride, row_stride; };
+static BgSlice bg_slice1(void* base, size_t bytes) { return {base, 1, bytes, bytes, bytes}; }   // one contiguous piece per env
 static void bg_slices(bg_handle* h, std::vector<BgSlice>& v) {
   BgDev& d = h->dev;
-  v.push_back({d.hot, BG_NHOT, 16}); v.push_back({d.deck, BG_NDECK, 16}); v.push_back({d.cold, BG_NCOLD, 16});
-  v.push_back({d.tmpl, BG_NTMPL, 16}); v.push_back({d.ndeck, (size_t)d.KD * BG_NDECK, 16});
+  const size_t N = (size_t)d.N, KD = (size_t)d.KD;
+  // the chunked arrays: row r = chunk r (ring decks: chunk r & 3 of slot r >> 2), 16 bytes each, strides from the accessors
+  v.push_back({d.hot, BG_NHOT, 16, 16 * (bg_hot_at(N, 1, 0) - bg_hot_at(N, 0, 0)), 16 * (bg_hot_at(N, 0, 1) - bg_hot_at(N, 0, 0))});
+  v.push_back({d.deck, BG_NDECK, 16, 16 * (bg_deck_at(N, 1, 0) - bg_deck_at(N, 0, 0)), 16 * (bg_deck_at(N, 0, 1) - bg_deck_at(N, 0, 0))});
+  v.push_back({d.cold, BG_NCOLD, 16, 16 * (bg_cold_at(N, 1, 0) - bg_cold_at(N, 0, 0)), 16 * (bg_cold_at(N, 0, 1) - bg_cold_at(N, 0, 0))});
+  v.push_back({d.tmpl, BG_NTMPL, 16, 16 * (bg_tmpl_at(N, 1, 0) - bg_tmpl_at(N, 0, 0)), 16 * (bg_tmpl_at(N, 0, 1) - bg_tmpl_at(N, 0, 0))});
+  v.push_back({d.ndeck, KD * BG_NDECK, 16, 16 * (bg_ndeck_at(N, KD, 1, 0, 0) - bg_ndeck_at(N, KD, 0, 0, 0)), 16 * (bg_ndeck_at(N, KD, 0, 0, 1) - bg_ndeck_at(N, KD, 0, 0, 0))});
   // per-env contiguous MT blocks: one "row" of KG*2560 / KS*2560 / 2560 bytes at base + env * elem
-  v.push_back({d.gblk, 1, (size_t)d.KG * BG_MTS * 4}); v.push_back({d.sblk, 1, (size_t)d.KS * BG_SLOT_WORDS * 4}); v.push_back({d.sovf, 1, (size_t)BG_MTS * 4});
-  v.push_back({d.deckmt, 1, (size_t)BG_MTS * 4}); v.push_back({d.shopgenmt, 1, (size_t)BG_MTS * 4});
-  v.push_back({d.sseed, 1, BG_SSEED * 4}); v.push_back({d.smeta, 1, 4});
-  v.push_back({bg_prod_latest(h), 1, 4});
-  if (d.cstate) { v.push_back({d.cstate, BG_NCST, 16}); v.push_back({d.ctmpl, BG_NCST, 16}); v.push_back({d.cardmt, 1, (size_t)BG_MTS * 4}); v.push_back({d.sealmt, 1, (size_t)BG_MTS * 4}); }
+  v.push_back(bg_slice1(d.gblk, (size_t)d.KG * BG_MTS * 4)); v.push_back(bg_slice1(d.sblk, (size_t)d.KS * BG_SLOT_WORDS * 4)); v.push_back(bg_slice1(d.sovf, (size_t)BG_MTS * 4));
+  v.push_back(bg_slice1(d.deckmt, (size_t)BG_MTS * 4)); v.push_back(bg_slice1(d.shopgenmt, (size_t)BG_MTS * 4));
+  v.push_back(bg_slice1(d.sseed, BG_SSEED * 4)); v.push_back(bg_slice1(d.smeta, 4));
+  v.push_back(bg_slice1(bg_prod_latest(h), 4));
+  if (d.cstate) { // uint4[7][N]
+    v.push_back({d.cstate, BG_NCST, 16, 16, 16 * N}); v.push_back({d.ctmpl, BG_NCST, 16, 16, 16 * N});
+    v.push_back(bg_slice1(d.cardmt, (size_t)BG_MTS * 4)); v.push_back(bg_slice1(d.sealmt, (size_t)BG_MTS * 4));
+  }
 }
 uint64_t bg_state_blob_bytes(const bg_handle* h) {
   if (!h) return 0;
@@ -1831,7 +1843,7 @@ int bg_get_state(bg_handle* h, int env_index, void* blob_host, uint64_t blob_byt
   bg_slices(h, v);
   size_t N = h->dev.N;
   for (auto& s : v) {
-    BG_HIP(hipMemcpy2D(out, s.elem, (uint8_t*)s.base + (size_t)env_index * s.elem, N * s.elem, s.elem, s.rows, hipMemcpyDeviceToHost));
+    BG_HIP(hipMemcpy2D(out, s.elem, (uint8_t*)s.base + (size_t)env_index * s.env_stride, s.row_stride, s.elem, s.rows, hipMemcpyDeviceToHost));
     out += s.rows * s.elem;
   }
   return 0;
@@ -1860,9 +1872,9 @@ int bg_set_state(bg_handle* h, int env_index, const void* blob_host, uint64_t bl
   bg_slices(h, v);
   size_t N = h->dev.N;
   for (auto& s : v) {
-    BG_HIP(hipMemcpy2D((uint8_t*)s.base + (size_t)env_index * s.elem, N * s.elem, in, s.elem, s.elem, s.rows, hipMemcpyHostToDevice));
+    BG_HIP(hipMemcpy2D((uint8_t*)s.base + (size_t)env_index * s.env_stride, s.row_stride, in, s.elem, s.elem, s.rows, hipMemcpyHostToDevice));
     if (s.base == (void*)h->dev.tmpl) // the host mirror of the reset template follows (later bg_inject calls upload the whole mirror)
-      for (size_t r = 0; r < s.rows; r++) memcpy(&h->h_tmpl[r * N + (size_t)env_index], in + r * s.elem, sizeof(uint4));
+      for (size_t r = 0; r < s.rows; r++) memcpy(&h->h_tmpl[bg_tmpl_at(N, (size_t)env_index, (int)r)], in + r * s.elem, sizeof(uint4));
     if (s.base == (void*)h->dev.hot) { uint4 c7; memcpy(&c7, in + 7 * s.elem, sizeof(uint4)); h->h_cap[env_index] = (uint8_t)((c7.w >> 16) & 0xffu); } // the cap travels in the blob
     in += s.rows * s.elem;
   }
@@ -1920,7 +1932,7 @@ int bg_set_max_ante(bg_handle* h, int max_ante, const int32_t* per_env_host, con
     if (c < 0 || c > 255) { h->err = "bg_set_max_ante: every cap must be in [0, 255] (0 = none)"; return BG_E_ARG; }
     // an env whose reset template puts it ABOVE its cap would end every episode on its first step: one pre-shuffled deck per step,
     // three times what the look-ahead rings are budgeted for (bg_chunk_limit) -- refused here as in bg_inject
-    const uint32_t ty = h->h_tmpl[i].y;
+    const uint32_t ty = h->h_tmpl[bg_tmpl_at(N, i, 0)].y;
     if (c > 0 && ((ty >> 24) & 0x20u) && (int)((ty >> 16) & 0xffu) > c) { h->err = "bg_set_max_ante: a cap below the env's template ante (bg_inject)"; return BG_E_ARG; }
   }
   for (size_t i = 0; i < N; i++)

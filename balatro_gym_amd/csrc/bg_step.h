@@ -27,13 +27,11 @@ struct StepOut {
 struct ShopRegs { uint4 c3, c4, c5, c6; bool valid; };
 __device__ __forceinline__ void bg_shop_load(const BgDev& d, int env, ShopRegs& sr) {
   if (sr.valid) return;
-  size_t N = d.N;
-  sr.c3 = bg_ld16a(&d.cold[3 * N + env]); sr.c4 = bg_ld16a(&d.cold[4 * N + env]); sr.c5 = bg_ld16a(&d.cold[5 * N + env]); sr.c6 = bg_ld16a(&d.cold[6 * N + env]); // (past the L1: bg_ld16a)
+  sr.c3 = bg_ld16a(bg_cold(d, env, 3)); sr.c4 = bg_ld16a(bg_cold(d, env, 4)); sr.c5 = bg_ld16a(bg_cold(d, env, 5)); sr.c6 = bg_ld16a(bg_cold(d, env, 6)); // (past the L1: bg_ld16a)
   sr.valid = true;
 }
 __device__ __forceinline__ void bg_shop_store(const BgDev& d, int env, const ShopRegs& sr) {
-  size_t N = d.N;
-  d.cold[3 * N + env] = sr.c3; d.cold[4 * N + env] = sr.c4; d.cold[5 * N + env] = sr.c5; d.cold[6 * N + env] = sr.c6;
+  *bg_cold(d, env, 3) = sr.c3; *bg_cold(d, env, 4) = sr.c4; *bg_cold(d, env, 5) = sr.c5; *bg_cold(d, env, 6) = sr.c6;
 }
 __device__ __forceinline__ void bg_shop_unpack(const ShopRegs& sr, int32_t cost[9], uint32_t tp[9]) {
   cost[0] = sr.c3.x; cost[1] = sr.c3.y; cost[2] = sr.c3.z; cost[3] = sr.c3.w;
@@ -89,7 +87,7 @@ template <class DK>
 __device__ __forceinline__ void bg_env_reset(const BgDev& d, int env, Env& e, DK& dk, const uint4* pre = nullptr, lds_cu4* pv = nullptr, int pv_stride = 0) {
   // the reset template (applied at the end) is requested FIRST: its HBM round trip then runs beside the cold stores and the deck copy instead of
   // behind them (the compiler cannot move a load above stores through other pointers)
-  const uint4 t0 = d.tmpl[env], t1 = d.tmpl[(size_t)d.N + env];
+  const uint4 t0 = *bg_tmpl(d, env, 0), t1 = *bg_tmpl(d, env, 1);
   e.ante = 1; e.round = 1; e.phase = 2; e.chips_needed = 300; e.chips_scored = 0; e.round_chips = 0; e.money = 4;
   e.hand = 0; e.nhand = 0; e.sel = 0; e.nsel = 0; e.hands_left = 4; e.discards_left = 3; e.hand_size = 8;
   e.njokers = 0; e.jokers = 0; e.ncons = 0; e.cons0 = 0; e.cons1 = 0; e.n_magic = 0; e.n_minim = 0;
@@ -102,7 +100,7 @@ __device__ __forceinline__ void bg_env_reset(const BgDev& d, int env, Env& e, DK
   e.excess = 0;
   // hand_play_counts = 0 (cold chunks 0..2)
 #pragma unroll
-  for (int k = 0; k < 3; k++) d.cold[(size_t)k * d.N + env] = make_uint4(0, 0, 0, 0);
+  for (int k = 0; k < 3; k++) *bg_cold(d, env, k) = make_uint4(0, 0, 0, 0);
   // consume one pre-shuffled deck
   if (e.d_ready <= 0) atomicOr(d.err, BG_DEVERR_DECKRING);
   else {
@@ -110,8 +108,8 @@ __device__ __forceinline__ void bg_env_reset(const BgDev& d, int env, Env& e, DK
     for (int k = 0; k < BG_NDECK; k++) {
       uint4 c;
       if (pv) { const bg_pv_u32x4 v = pv[k * pv_stride]; c = make_uint4(v.x, v.y, v.z, v.w); }   // (bg_engine3.h: the env's next deck waits in LDS; chunk by chunk, so that only one is in registers at a time)
-      else c = pre ? pre[k] : d.ndeck[((size_t)e.d_head * BG_NDECK + k) * d.N + env];
-      d.deck[(size_t)k * d.N + env] = c;
+      else c = pre ? pre[k] : *bg_ndeck(d, env, e.d_head, k);
+      *bg_deck(d, env, k) = c;
       bg_deck_set(dk, k, c);
     }
     e.d_head = (e.d_head + 1 == d.KD) ? 0 : e.d_head + 1;
@@ -894,7 +892,7 @@ __device__ __forceinline__ void bg_step_play_hand(const BgDev& d, int env, Env& 
   e.hp_total++; e.hp_ante++;
   if (final_score > e.best_hand) e.best_hand = final_score;
   // engine.hand_play_counts[hand_type] += 1 (write-only statistic: a no-return atomic keeps it off the wait path)
-  atomicAdd(((uint32_t*)&d.cold[(size_t)(ht >> 2) * d.N + env]) + (ht & 3), 1u);
+  atomicAdd(((uint32_t*)bg_cold(d, env, ht >> 2)) + (ht & 3), 1u);
   // :789-794 boss on_hand_scored (boss_blinds.py:480-507); Tooth/Serpent mutate a throw-away dict
   if (e.boss_type) {
     e.boss_types |= 1u << ht;
@@ -1317,7 +1315,7 @@ __device__ __forceinline__ void bg_use_consumable(const BgDev& d, int env, Env& 
 #pragma unroll
         for (int k = 0; k < BG_NDECK; k++) {
           const uint4 c4 = make_uint4(w.lds[(4 * k) * BG_BLOCK], w.lds[(4 * k + 1) * BG_BLOCK], w.lds[(4 * k + 2) * BG_BLOCK], w.lds[(4 * k + 3) * BG_BLOCK]);
-          d.deck[(size_t)k * d.N + env] = c4;
+          *bg_deck(d, env, k) = c4;
           bg_deck_set(mdk, k, c4);
         }
         e.boss_cards = played;
