@@ -42,7 +42,11 @@ ROW_OFFSETS = {
     "discards_left": 334, "joker_count": 335, "joker_slots": 336, "consumable_count": 337, "consumable_slots": 338,
     "phase": 339, "boss_blind_active": 340, "boss_blind_type": 341,
 }
-ROW_EXTRA = {"reward": (136, "float64"), "action": (172, "int32"), "terminated": (342, "uint8")}
+# (end_flags: byte BG_ROW_END_FLAGS, written by bg_step_many_rows_ex with limits -- its BG_END_* bits are below -- and 0 on every other path)
+ROW_EXTRA = {"reward": (136, "float64"), "action": (172, "int32"), "terminated": (342, "uint8"), "end_flags": (343, "uint8")}
+ROW_END_FLAGS = ROW_EXTRA["end_flags"][0]
+END_GAME, END_INVALID, END_MAX_STEPS = 1, 2, 4
+SAFE_MIN_LIMIT = 3
 INFO_KEYS = ["final_score", "error", "flags", "aux", "hand_type", "cards_played", "reward_terms", "score_breakdown"]
 INFO_SPEC = {"final_score": ("int64", ()), "error": ("int32", ()), "flags": ("int32", ()), "aux": ("int32", ()),
              "hand_type": ("int8", ()), "cards_played": ("int8", ()), "reward_terms": ("float64", (8,)), "score_breakdown": ("float64", (8,))}
@@ -59,7 +63,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_sim_evaluate_batch", "bg_sim_score_batch", "bg_create_ex", "bg_step_rows", "bg_observe_rows", "bg_step_many_rows",
            "bg_encode_cols", "bg_encode_rows", "bg_gae_rows", "bg_episode_stats_rows",
            "bg_gae_rows_ex", "bg_norm_workspace_bytes", "bg_norm_obs_rows", "bg_norm_reward_rows",
-           "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex"]
+           "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex",
+           "bg_step_many_rows_ex", "bg_safe_terminal_slots"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -115,6 +120,13 @@ class InfoPtrs(C.Structure):
 class RolloutStats(C.Structure):
     _fields_ = [("steps", C.c_uint64), ("episodes", C.c_uint64), ("plays", C.c_uint64), ("score_sum", C.c_int64),
                 ("reward_bits", C.c_uint64), ("obs_hash", C.c_uint64)]
+
+
+class SafeLimits(C.Structure):
+    """bg_safe_limits (include/balatro_mi355x.h)."""
+    _fields_ = [("max_invalid_actions", C.c_int32), ("max_episode_steps", C.c_int32), ("counters_dev", C.c_void_p),
+                ("terminal_rows_dev", C.c_void_p), ("terminal_stride_bytes", C.c_uint64), ("terminal_step_dev", C.c_void_p),
+                ("terminal_slots", C.c_int32)]
 
 
 class NativeError(RuntimeError):
@@ -214,6 +226,8 @@ def load(build_if_missing: bool = True):
     L.bg_rollout.argtypes = [vp, i32, i32, u64, u64, u64, C.POINTER(ObsPtrs), i32, vp, vp, vp, vp, vp]
     L.bg_rollout_rows.argtypes = [vp, i32, i32, u64, u64, u64, vp, u64, i32, vp, vp]
     L.bg_step_many_rows.argtypes = [vp, i32, vp, vp, u64, i32, vp, vp]
+    L.bg_step_many_rows_ex.argtypes = [vp, i32, vp, vp, u64, i32, C.POINTER(SafeLimits), vp, vp]
+    L.bg_safe_terminal_slots.argtypes = [i32, i32, i32]
     L.bg_set_gather_peers.argtypes = [vp, vp, i32, i32]
     L.bg_inject.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.bg_inject_cards.argtypes = [vp, vp, vp, vp, vp, i32, vp]

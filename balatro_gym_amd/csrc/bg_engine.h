@@ -46,6 +46,15 @@ static_assert(BG_ENG_LNE == 8, "only 256 envs per workgroup are supported: items
 #define BG_ENG_NSV 4    // of them, how many own an RNG window and may run service batches
 #define BG_ENG_SMASK_DEFAULT (((1u << BG_ENG_NSV) - 1u) << (BG_ENG_NW - BG_ENG_NSV)) // which: the last NSV waves (BG_ENG_SMASK)
 
+// bg_step_many_rows_ex's limits as a SAFE launch of bg_engine3.h reads them (bg_safe_limits, checked by the host)
+struct SafeArgs {
+  int32_t* counters;           // int32 [N, 4]: episode_steps, consecutive_invalid, wrapper endings so far in this call, 0
+  uint8_t* term_rows;          // [slots, N] records of term_stride bytes, or null
+  int32_t* term_step;          // int32 [slots, N]
+  uint32_t term_stride, slots;
+  int32_t max_invalid, max_steps;
+};
+static_assert(sizeof(SafeArgs) <= sizeof(InfoPtrs), "SafeArgs rides in the bytes of EngineArgs::info");
 struct EngineArgs {
   int T;                       // steps per env in this launch
   int policy;                  // BG_POLICY_* (ignored when actions_in is set)
@@ -54,7 +63,12 @@ struct EngineArgs {
   int obs_stride_steps;        // != 0: row = env + t * N ([T, N] buffers); 0: row = env (overwritten every step)
   double* reward; uint8_t* term; uint8_t* trunc; int32_t* actions_out;
   const int32_t* actions_in;   // [T, N] actions (row t * N + env) or null = counter-hash policy on device
-  InfoPtrs info;               // bg_step's info arrays (null pointers are skipped)
+  // bg_engine3.h's SAFE launches (bg_step_many_rows_ex with limits) write no info arrays and read their arguments from the same bytes: the
+  // layout of the kernel arguments, and with it the code of every other instantiation, is what it was before SAFE existed
+  union {
+    InfoPtrs info;             // bg_step's info arrays (null pointers are skipped)
+    SafeArgs safe;
+  };
   bg_rollout_stats* stats;
   uint32_t th_run, th_play, th_other; // a queue is served once it holds this many items ...
   uint32_t th_part;            // ... or, while other waves are busy (their envs will come back soon), this many; anything when no wave is busy

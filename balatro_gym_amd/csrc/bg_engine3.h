@@ -45,7 +45,7 @@ struct E3Lds {
   uint4 s_c34[2][NE];              // hot chunks 3 and 4
   unsigned long long s_mask[NE];
   uint32_t s_prod[NE];
-  uint16_t s_ans[NE];              // service steps completed for this env in this launch, mod 2**16 (the owner counts its requests; a launch fuses < 2**16 steps)
+  uint16_t s_ans[NE];              // service steps completed for this env in this launch, mod 2**16 (the owner counts its requests; a launch fuses < 2**16 steps -- SAFE: a step the wrapper ends is two requests, and a launch fuses < 2**15 steps)
   uint32_t s_q[2][NE];             // request rings: env lane | generation of the ring position << 8 | action << 16 | VALID
   __attribute__((aligned(16))) uint32_t s_ctl[8];   // [0..1] requests ever queued per class, [4..5] ever claimed
   uint32_t s_win[NSV][BG_WIN][BG_BLOCK];
@@ -73,12 +73,26 @@ struct E3Lds {
 //     image and the service wave takes it from there (32768 + 2 must not become a toggle, and the record carries the value as given);
 //   * without auto-reset an env stays above its curriculum cap, and every step of such an env -- a toggle, an invalid action -- reports terminated
 //     (CurriculumBalatroEnv.step, train_balatro_agent.py:146-152): the owner's `terminal` test includes the cap, so that these steps go to a service wave, which applies the rule.
-template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT = false>
+// SAFE (bg_step_many_rows_ex with limits; implies ACT): SafeBalatroEnv's two episode limits (bg_safe.h) inside the launch, all of it behind
+// `if constexpr (SAFE)` (the other instantiations compile to what they were):
+//   * the owner lane keeps its env's counters -- steps of the episode, consecutive -1.0 rewards, wrapper endings of this call -- in registers: one
+//     16-byte load in the prologue, one store behind the loop; launches of one call and successive calls hand over through a.safe.counters;
+//   * when a record is finished -- a cheap step, or a service wave's answer -- the owner applies bg_safe_step to the reward and the terminated byte in
+//     the env's image and writes bytes 342 / 343 (and -50.0 on a kill).  Unless the WRAPPER ended the episode, that is all;
+//   * a wrapper-made ending (at most one step in min(limits)): the lane writes the image as it stands to its terminal slot itself (22 or 24 16-byte
+//     stores, not coalesced), does NOT count the step finished, and posts a RESET-ONLY request to the "other" queue: the queue word's 15 action bits,
+//     unused in ACT mode (the service wave reads the action from the image), are all ones in such a request and zero in every other.  The service
+//     wave skips guards and dispatch, resets the env exactly as a game over does (ring deck, templates, the LDS deck hand-over through s_ndst), and
+//     writes the new episode's mask and observation into the image around the step's reward, action and ending bytes, which it read there first.
+//     The owner waits for the answer like for any other (`waiting`, s_ans, the same BG_SPIN_LIMIT bounds), then counts the step and lists the record;
+//   * such a step counts TWO requests in s_ans (mod 2**16; a launch fuses far fewer than 2**15 steps).
+template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT = false, bool SAFE = false>
 // (Round 5 measured reading the arguments THROUGH the kernarg segment pointer instead of as by-value parameters -- whose 16-register blocks the compiler
 //  spills to VGPR lanes and reloads whole, 12 % of the kernel's instructions being v_readlane / v_writelane / s_nop: SGPR spills 237 -> 61, 14 454 -> 13 114
 //  instructions, and 3.4 % SLOWER at both launch lengths: a scalar load per use waits longer than sixteen lane reads.  profiles/r05/play_path_ab.txt.)
 __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(BgDev d, EngineArgs a) {
   constexpr int NE = NOW * KS * BG_BLOCK, LNE = NE == 256 ? 8 : (NE == 128 ? 7 : 6);
+  static_assert(ACT || !SAFE, "the limits exist on the caller's-actions path");
   static_assert(NE == 64 || NE == 128 || NE == 256, "envs per workgroup (a request carries the env's lane in 8 bits)");
   // (static LDS: the compiler then pads the register allocation to the 256 VGPRs that two waves per SIMD leave each -- which this kernel needs
   //  anyway: with dynamic LDS and the same cap it compiles to 256 VGPRs plus a spilled one)
@@ -169,6 +183,9 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
     // ACT: the step whose action is in row 0 of s_actb, and the ante above which the env is terminal (100, :619, or its cap)
     uint32_t abase[KS];
     uint32_t athr[KS];
+    // SAFE: the env's counters (bg_safe.h), its wrapper endings so far in this call (= its next terminal slot), and "the request I wait for is a reset-only one"
+    int32_t csteps[KS], cinv[KS], cwrap[KS];
+    bool rwait[KS];
 #pragma unroll
     for (int s = 0; s < KS; s++) {
       t[s] = 0; nreq[s] = 0; waiting[s] = false;
@@ -186,6 +203,13 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
         px[s] = a.policy_seed + 0x9E3779B97F4A7C15ull * (gi0 + 1) + BG_POLICY_PSI * (a.t0 + 1);
         prow[s] = (size_t)env;
         pblind[s] = a.policy == 2 ? 45 + (int)((bmod3 + (uint32_t)env % 3u) % 3u) : 45;
+      }
+      if constexpr (SAFE) {
+        csteps[s] = 0; cinv[s] = 0; cwrap[s] = 0; rwait[s] = false;
+        if (l < n_live) {
+          const int4 cv = *(const int4*)(a.safe.counters + 4 * (size_t)(env0 + l));
+          csteps[s] = cv.x; cinv[s] = cv.y; cwrap[s] = cv.z;
+        }
       }
       rc3[s] = s_c34[0][l]; rc4[s] = s_c34[1][l]; rmask[s] = s_mask[l];
       const lds_u32* im = (const lds_u32*)&s_img[l][0];
@@ -300,7 +324,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
             if constexpr (ACT) img32[43] = (uint32_t)action;   // the whole int32, for the service wave (BG_ROW_ACTION: it writes the same value back)
             const int q = (!term && phase == 0u && action == 0) ? 0 : 1;
             const uint32_t slot = __hip_atomic_fetch_add(&s_ctl[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            bg_lds_st(&s_q[q][slot & (NE - 1)], (uint32_t)l | (((slot >> LNE) & 0xffu) << 8) | (((uint32_t)action & 0x7fffu) << 16) | BG_ITEM_VALID);
+            bg_lds_st(&s_q[q][slot & (NE - 1)], (uint32_t)l | (((slot >> LNE) & 0xffu) << 8) | ((SAFE ? 0u : ((uint32_t)action & 0x7fffu)) << 16) | BG_ITEM_VALID);
             nreq[s]++;
             waiting[s] = true;
           }
@@ -308,6 +332,41 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
             *(__attribute__((address_space(3))) double*)&img32[34] = reward;  // BG_ROW_REWARD
             img32[43] = (uint32_t)action;                                      // BG_ROW_ACTION
             img8[BG_ROW_TERMINATED] = 0;
+          }
+        }
+        // ---- SAFE: the wrapper's rule on the finished record (bg_safe.h); the answer of a reset-only request is a record the rule has already seen
+        if constexpr (SAFE) {
+          if (fin && rwait[s]) rwait[s] = false;
+          else if (fin) {
+            const bool env_term = img8[BG_ROW_TERMINATED] != 0;
+            const BgSafeStep so = bg_safe_step(*(__attribute__((address_space(3))) const double*)&img32[34], env_term, csteps[s], cinv[s], a.safe.max_invalid, a.safe.max_steps);
+            csteps[s] = so.episode_steps; cinv[s] = so.consecutive_invalid;
+            if (so.flags & BG_SAFE_END_INVALID) *(__attribute__((address_space(3))) double*)&img32[34] = so.reward;
+            // bytes 342 (SB3's done) and 343 (why), every step: the image keeps the bytes of the env's last ending
+            *(__attribute__((address_space(3))) uint16_t*)&img8[BG_ROW_TERMINATED] = (uint16_t)(so.flags ? (1u | (so.flags << 8)) : 0u);
+            if (bg_safe_wrapper_ending(so.flags)) {
+              // the record as it stands is SB3's terminal_observation: to this env's next slot of the call (the host has checked the slot count; a
+              // slot past it is not written)
+              if (a.safe.term_rows && (uint32_t)cwrap[s] < a.safe.slots) {
+                const size_t slot = (size_t)cwrap[s] * N + (size_t)env;
+                uint8_t* const dst = a.safe.term_rows + slot * (size_t)a.safe.term_stride;
+#pragma unroll 2
+                for (int k = 0; k < 22; k++) *(__attribute__((address_space(1))) bg_u32x4*)(dst + 16 * k) = s_img[l][k];
+                if (a.safe.term_stride == 384u) {   // whole lines, as the records of a 384-byte stride
+                  *(__attribute__((address_space(1))) bg_u32x4*)(dst + 352) = bg_u32x4{0u, 0u, 0u, 0u};
+                  *(__attribute__((address_space(1))) bg_u32x4*)(dst + 368) = bg_u32x4{0u, 0u, 0u, 0u};
+                }
+                a.safe.term_step[slot] = (int32_t)((uint32_t)a.t0 + t[s]);
+              }
+              cwrap[s]++;
+              // the reset-only request: chunks 3 / 4 and the mask to LDS as for any request; the step is finished when its answer is seen
+              s_c34[0][l] = rc3[s]; s_c34[1][l] = rc4[s]; s_mask[l] = rmask[s];
+              const uint32_t slot = __hip_atomic_fetch_add(&s_ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+              bg_lds_st(&s_q[1][slot & (NE - 1)], (uint32_t)l | (((slot >> LNE) & 0xffu) << 8) | (0x7fffu << 16) | BG_ITEM_VALID);
+              nreq[s]++;
+              waiting[s] = true; rwait[s] = true;
+              fin = false;
+            }
           }
         }
         // ---- accounting of every record finished in this iteration (cheap or served), and its place in the copy-out list
@@ -430,6 +489,13 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
     if constexpr (kE3Tl) if (lane == 0 && d.dbg) atomicAdd(&d.dbg[29], wall_clock64() - e3_k0);   // owner loop end, summed over owner waves
 #pragma unroll
     for (int s = 0; s < KS; s++) { const int l = (wave * KS + s) * BG_BLOCK + lane; s_c34[0][l] = rc3[s]; s_c34[1][l] = rc4[s]; }   // (the epilogue stores them)
+    if constexpr (SAFE) {
+#pragma unroll
+      for (int s = 0; s < KS; s++) {
+        const int l = (wave * KS + s) * BG_BLOCK + lane;
+        if (l < n_live) *(int4*)(a.safe.counters + 4 * (size_t)(env0 + l)) = make_int4(csteps[s], cinv[s], cwrap[s], 0);
+      }
+    }
     if (lane == 0) __hip_atomic_fetch_sub(&s_owners_left, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     if (a.stats) bg_stats_wave(L.s_stats, n_steps, 0, 0, 0, rbits, ohash);
   } else {
@@ -491,6 +557,9 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           const int l = (int)(item & 0xffu), env = env0 + l;
           // (ACT: the caller's int32 as the owner left it in the image, in front of the queue word)
           const int action = ACT ? (int)((const lds_u32*)&s_img[l][0])[43] : (int)((item >> 16) & 0x7fffu);
+          // SAFE: a reset-only request (the wrapper ended the episode): the step's reward and ending bytes stay what the owner left in the image
+          const bool ronly = SAFE && ((item >> 16) & 0x7fffu) == 0x7fffu;
+          const uint32_t endb = SAFE ? (uint32_t)((const lds_u8*)&s_img[l][0])[BG_ROW_END_FLAGS] : 0u;
           uint64_t mask = s_mask[l];
           BG_PROBE_BEGIN();
           uint4 c[BG_NHOT];
@@ -508,9 +577,12 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           StepOut o;
           bg_step_init(o);
           o.bd_dst = nullptr;
+          if (SAFE && ronly) { o.terminated = true; o.reward = *(__attribute__((address_space(3))) const double*)&((const lds_u32*)&s_img[l][0])[34]; }
+          else {
           if (bg_step_guards(e, mask, action, o)) bg_env_dispatch(d, env, e, w, sr, dk, action, o);
           BG_PROBE(cls == 0 ? 20 : 21);
           if (e.max_ante > 0 && e.ante > e.max_ante) { o.terminated = true; o.flags |= 256; }
+          }
           if (o.terminated) n_eps++;
           if (o.terminated && a.autoreset) {
             const bool have = bg_lds_ld(&s_ndst[l]) == 1u;
@@ -526,6 +598,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           //  compiler cannot know to be set -- the per-key writer's 31 pointers stayed live in scalar registers through the whole service step.)
           const ObsPtrs none{};
           bg_write_obs_impl<false, 3>(d, env, 0, e, dk, none, mask, sr, RowExtra{o.reward, action, o.terminated ? 1u : 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
+          if constexpr (SAFE) if (ronly) ((lds_u8*)&s_img[l][0])[BG_ROW_END_FLAGS] = (uint8_t)endb;
           BG_PROBE(26);
           bg_pack(e, c);
 #pragma unroll

@@ -51,6 +51,7 @@ __device__ __forceinline__ void bg_emit_info(size_t row, const StepOut& o, uint8
   }
 }
 
+#include "bg_safe.h"   // SafeBalatroEnv's episode limits: the rule of one step (bg_engine3.h's SAFE launches, bg_step_many_rows_ex)
 #include "bg_engine.h" // the step engine: one kernel behind bg_step / bg_step_many / bg_rollout / bg_rollout_rows
 #include "bg_engine3.h" // owner waves + service waves in ONE workgroup (packed-record rollouts)
 
@@ -1313,13 +1314,15 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
       if (!h->e3_epw) { while (epw > 16 && (h->dev.N + epw - 1) / epw < 256) epw >>= 1; }
       a.epw = (uint32_t)epw;
     }
-#define BG_E3K(HV, CV, NOWV, KSV, NSVV, AV) do { \
+#define BG_E3K(HV, CV, NOWV, KSV, NSVV, AV, ...) do { \
       const dim3 g_((NOWV * KSV == 1) ? (h->dev.N + epw - 1) / epw : (h->dev.N + NOWV * KSV * 64 - 1) / (NOWV * KSV * 64)), b_((NOWV + NSVV) * BG_BLOCK); \
-      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
-      else hipLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV>), g_, b_, 0, st, dv, a); } while (0)
-    // (the caller's actions: bg_step_many_rows asks for no observation hash, so the action mode has no HASH variant)
+      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV, ##__VA_ARGS__>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
+      else hipLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV, ##__VA_ARGS__>), g_, b_, 0, st, dv, a); } while (0)
+    // (the caller's actions: bg_step_many_rows asks for no observation hash, so the action mode has no HASH variant; with bg_step_many_rows_ex's
+    //  limits -- a.safe, which shares the bytes of the info pointers no launch of this branch has -- the SAFE instantiation of the same shape)
 #define BG_E3(NOWV, KSV, NSVV) do { \
-      if (a.actions_in) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true); } \
+      if (a.actions_in && a.safe.counters) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true, true); } \
+      else if (a.actions_in) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true); } \
       else if (hash && cards) BG_E3K(true, true, NOWV, KSV, NSVV, false); else if (hash) BG_E3K(true, false, NOWV, KSV, NSVV, false); \
       else if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, false); else BG_E3K(false, false, NOWV, KSV, NSVV, false); } while (0)
     switch (cfg) {   // (other shapes were measured and dropped: profiles/r04_engine3/wave_split_ab.txt, small_jobs.txt, profiles/r05/scheduling_ab.txt)
@@ -1468,7 +1471,8 @@ int bg_observe(bg_handle* h, const bg_obs_ptrs* obs, void* stream) {
 static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed, uint64_t env_index0, uint64_t t0,
                            const bg_obs_ptrs* obs, uint8_t* rows_dev, size_t row_stride, int obs_stride_steps,
                            double* reward_dev, uint8_t* terminated_dev, int32_t* actions_out_dev,
-                           bg_rollout_stats* stats_dev, void* stream, const int32_t* actions_in_dev = nullptr, bool autoreset = true) {
+                           bg_rollout_stats* stats_dev, void* stream, const int32_t* actions_in_dev = nullptr, bool autoreset = true,
+                           const SafeArgs* safe = nullptr) {
   int rc = bg_require_seeded(h);
   if (rc) return rc;
   BG_GUARD(h);
@@ -1557,6 +1561,7 @@ static int bg_rollout_impl(bg_handle* h, int T, int policy, uint64_t policy_seed
       ea.obs = o; ea.obs_stride_steps = obs_stride_steps; ea.reward = rw; ea.term = tm; ea.actions_out = ac; ea.stats = stats_dev;
       bg_engine_queues(h, ea); ea.autoreset = autoreset ? 1u : 0u;
       if (actions_in_dev) ea.actions_in = actions_in_dev + (size_t)done * (size_t)h->dev.N;   // (bg_step_many_rows: [T, N], whatever the rows' stride)
+      if (safe) ea.safe = *safe;   // (bg_step_many_rows_ex: engine 3 only, t0 = 0, so ea.t0 is the step of the call a launch starts at)
       if (h->gworld > 0 && rows_dev && h->engine == 3 && done + chunk == T) { // the call's LAST launch: its last step is every env's current record
         ea.gpeer = h->d_gpeer;
         ea.gworld = (uint32_t)h->gworld; ea.grank = (uint32_t)h->grank;
@@ -1656,6 +1661,56 @@ int bg_step_many_rows(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* 
   // caller's actions and the handle's auto-reset flag.  BG_ENGINE=1: bg_engine.h reads actions_in and writes records through its copier wave.
   return bg_rollout_impl(h, K, 0, 0, 0, 0, nullptr, rows_dev, (size_t)row_stride_bytes, rows_stride_steps, nullptr, nullptr, nullptr, stats_dev,
                          stream, actions_dev, (h->dev.flags & BG_FLAG_AUTORESET) != 0);
+}
+
+static_assert(BG_SAFE_END_GAME == BG_END_GAME && BG_SAFE_END_INVALID == BG_END_INVALID && BG_SAFE_END_MAX_STEPS == BG_END_MAX_STEPS,
+              "bg_safe.h's ending bits are include/balatro_mi355x.h's");
+int bg_safe_terminal_slots(int K, int max_invalid_actions, int max_episode_steps) {
+  if (K < 0 || max_invalid_actions < BG_SAFE_MIN_LIMIT || max_episode_steps < BG_SAFE_MIN_LIMIT) return BG_E_ARG;
+  return bg_safe_slots(K, max_invalid_actions, max_episode_steps);
+}
+
+int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                         int rows_stride_steps, const bg_safe_limits* limits, bg_rollout_stats* stats_dev, void* stream) {
+  if (!limits) return bg_step_many_rows(h, K, actions_dev, rows_dev, row_stride_bytes, rows_stride_steps, stats_dev, stream);
+  if (!h) return BG_E_ARG;
+  const char* bad = nullptr;
+  if (!actions_dev || K <= 0) bad = "actions_dev must be a device pointer to [K, N] int32 actions, K > 0";
+  else if ((uint64_t)h->dev.N * (uint64_t)bg_max_fused_steps(h) > 0xffffffffull) bad = "more than 2**32 records per launch (envs x fused steps)";
+  else if (const char* m = bg_rows_args(rows_dev, row_stride_bytes)) bad = m;
+  // Both limits >= 3: bg_chunk_limit sizes a launch on "an env consumes at most one pre-shuffled deck per 3 steps" (the shortest episode the game
+  // itself allows: reset -> blind -> select -> failing play).  A wrapper ending consumes a ring deck like a game over does; with both limits >= 3
+  // every episode still lasts at least 3 steps however it ends, so the ring arithmetic stands as it is.
+  else if (limits->max_invalid_actions < BG_SAFE_MIN_LIMIT || limits->max_episode_steps < BG_SAFE_MIN_LIMIT)
+    bad = "max_invalid_actions and max_episode_steps must be >= 3 (an episode of fewer steps would outrun the look-ahead rings)";
+  else if (!(h->dev.flags & BG_FLAG_AUTORESET)) bad = "limits need a handle with BG_FLAG_AUTORESET (an ended episode is reset inside the step)";
+  else if (h->engine != 3) bad = "limits exist on bg_engine3.h only (BG_ENGINE=3)";
+  else if (!limits->counters_dev || ((uintptr_t)limits->counters_dev & 15)) bad = "counters_dev must be a 16-byte aligned device pointer to int32 [N, 4]";
+  else if ((limits->terminal_rows_dev == nullptr) != (limits->terminal_step_dev == nullptr)) bad = "terminal_rows_dev and terminal_step_dev must both be set or both be NULL";
+  else if (limits->terminal_rows_dev) {
+    if (bg_rows_args(limits->terminal_rows_dev, limits->terminal_stride_bytes)) bad = "terminal_rows_dev must be 16-byte aligned and terminal_stride_bytes a multiple of 16, >= BG_ROW_BYTES";
+    else if ((uintptr_t)limits->terminal_step_dev & 3) bad = "terminal_step_dev must be a 4-byte aligned device pointer to int32 [terminal_slots, N]";
+    else if (limits->terminal_slots < bg_safe_slots(K, limits->max_invalid_actions, limits->max_episode_steps)) bad = "terminal_slots must be >= bg_safe_terminal_slots(K, limits)";
+  }
+  if (bad) { h->err = std::string("bg_step_many_rows_ex: ") + bad; return BG_E_ARG; }
+  // (bg_rollout_impl's own refusals, in front of the memsets below: nothing of the caller's is written by a call that returns an error code for its arguments)
+  { const int rcs = bg_require_seeded(h); if (rcs) return rcs; }
+  BG_GUARD(h);
+  hipStream_t st = (hipStream_t)stream;
+  // the call's own state, in front of its launches: no wrapper ending yet (word 2 of every env's counters), no terminal slot used
+  BG_HIP(hipMemset2DAsync(limits->counters_dev + 2, 16, 0, 4, (size_t)h->dev.N, st));
+  SafeArgs sa;
+  memset(&sa, 0, sizeof(sa));
+  sa.counters = limits->counters_dev;
+  sa.max_invalid = limits->max_invalid_actions; sa.max_steps = limits->max_episode_steps;
+  if (limits->terminal_rows_dev) {
+    BG_HIP(hipMemsetAsync(limits->terminal_step_dev, 0xff, (size_t)limits->terminal_slots * (size_t)h->dev.N * sizeof(int32_t), st));
+    sa.term_rows = limits->terminal_rows_dev; sa.term_step = limits->terminal_step_dev;
+    sa.term_stride = (uint32_t)limits->terminal_stride_bytes;   // (bg_rows_args above refuses a stride past 2**32 - 1)
+    sa.slots = (uint32_t)limits->terminal_slots;
+  }
+  return bg_rollout_impl(h, K, 0, 0, 0, 0, nullptr, rows_dev, (size_t)row_stride_bytes, rows_stride_steps, nullptr, nullptr, nullptr, stats_dev,
+                         stream, actions_dev, true, &sa);
 }
 
 __global__ __launch_bounds__(BG_BLOCK) void bg_inject_cards_kernel(BgDev d, const uint16_t* __restrict__ cs, const uint8_t* __restrict__ mask_in, int apply_now) {

@@ -90,6 +90,8 @@ class RowBuffers:
         self.reward = self._view(nat.ROW_EXTRA["reward"][0], "float64", ())
         self.action = self._view(nat.ROW_EXTRA["action"][0], "int32", ())
         self.terminated = self._view(nat.ROW_EXTRA["terminated"][0], "uint8", ())
+        # byte BG_ROW_END_FLAGS: why a step ended its episode (END_GAME | END_INVALID | END_MAX_STEPS), written by `step_many(..., limits=)`; 0 otherwise
+        self.end_flags = self._view(nat.ROW_EXTRA["end_flags"][0], "uint8", ())
 
     def encode(self, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None, *,
                index: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -138,6 +140,30 @@ class RowBuffers:
         """(actions, log_prob, entropy) drawn from `logits` [n, 60] under the action mask of record row `step` (`sample_actions`; seed= and t= are
         required): the mask a record carries is the one after its step, i.e. the mask of the action to take next."""
         return sample_actions(logits, self.rows[step], **kwargs)
+
+    def bootstrap_rewards(self, limits: "EpisodeLimits", terminal_values: torch.Tensor, gamma: float = 0.99,
+                          rewards: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """float64 [steps, n] rewards for `gae(..., rewards=)` with SB3's time-limit bootstrap (`collect_rollouts`: rewards[idx] += gamma *
+        terminal_value where the episode was truncated and not terminated): the records' rewards, or the given ones (float64 [steps, n], e.g.
+        `normalize_reward`'s output; not modified), plus gamma * terminal_values[i] at entry `limits.terminal()[0][i]` wherever that step's
+        `end_flags` are exactly END_MAX_STEPS.  terminal_values: float [M], the value network's output on the M records of `limits.terminal()`
+        (all of them, in that order), after the `step_many(..., limits=)` call that filled these records."""
+        if limits.n != self.n or limits.steps > self.steps:
+            raise ValueError("limits.terminal() names steps these records do not hold (limits of other envs, or of longer calls)")
+        index, _ = limits.terminal()
+        if rewards is None:
+            out = self.reward.clone(memory_format=torch.contiguous_format)   # (one copy of the strided view)
+        else:
+            _check_scan_tensor("rewards", rewards, torch.float64, (self.steps, self.n), self.rows.device)
+            out = rewards.clone()
+        terminal_values = torch.as_tensor(terminal_values, device=self.rows.device)
+        if tuple(terminal_values.shape) != (int(index.numel()),):
+            raise ValueError(f"terminal_values must have shape [{int(index.numel())}], one value per record of limits.terminal()")
+        if index.numel():   # (index < limits.steps * n <= steps * n: checked above on the shapes, without reading the device)
+            idx = index.long()
+            only = self.end_flags.reshape(-1)[idx] == nat.END_MAX_STEPS
+            out.view(-1)[idx[only]] += float(gamma) * terminal_values[only].to(torch.float64)
+        return out
 
     def episode_stats(self, stats: "EpisodeStats"):
         """(ep_return float64, ep_len int32) [steps, n] of these records, continuing the episodes `stats` carries (`EpisodeStats.update`)."""
@@ -343,7 +369,7 @@ class BalatroVecEnv:
         return self._obs.tensors, self.reward, self.terminated, self.truncated, self.info
 
     def step_many(self, actions: torch.Tensor, obs_buffers: Optional["ObsBuffers"] = None, reward: Optional[torch.Tensor] = None,
-                  terminated: Optional[torch.Tensor] = None):
+                  terminated: Optional[torch.Tensor] = None, limits: Optional["EpisodeLimits"] = None):
         """K consecutive `step()` calls in one launch (bg_step_many): actions int32 [K, N].  With `obs_buffers` of at least K rows
         every call's observation is kept, and so are its reward / terminated when float64 / uint8 [>= K, N] tensors on this device are
         given; the returned truncated and info are None, and so is reward / terminated when no tensor was given for it: this call
@@ -354,7 +380,11 @@ class BalatroVecEnv:
         A `RowBuffers` selects the packed-record engine (bg_step_many_rows: the rollout's kernel with the caller's actions, several times
         the rate of the per-key path): every step's record is kept when it has at least K rows, a one-row `RowBuffers` holds the last
         step's.  Returns (rb.tensors, rb.reward, rb.terminated, None, None) -- views of the records; `rb.action` holds the actions as
-        given.  This path produces no per-step truncated / info; reward / terminated tensors are refused (the records carry them)."""
+        given.  This path produces no per-step truncated / info; reward / terminated tensors are refused (the records carry them).
+
+        limits (an `EpisodeLimits`, with a `RowBuffers` only): SafeBalatroEnv's episode limits inside the launch (bg_step_many_rows_ex).  `terminated`
+        is then SB3's done, `rb.end_flags` says why, a killed step's reward is -50.0, an env the wrapper ended is reset inside the step, and
+        `limits.terminal()` has the records before those resets."""
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if actions.dim() != 2 or actions.shape[1] != self.num_envs:
@@ -370,14 +400,26 @@ class BalatroVecEnv:
             if obs_buffers.n != self.num_envs or obs_buffers.rows.device != self.device:
                 raise ValueError(f"obs_buffers must hold records of {self.num_envs} envs on {self.device}")
             self._stats.zero_()
-            rc = self._L.bg_step_many_rows(
-                self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
-                1 if obs_buffers.steps > 1 else 0, C.c_void_p(self._stats.data_ptr()), self._stream())
-            if rc != 0:
-                self._check(rc, "bg_step_many_rows")
+            if limits is not None:
+                if not isinstance(limits, EpisodeLimits) or limits.n != self.num_envs or limits.device != self.device:
+                    raise ValueError(f"limits must be an EpisodeLimits of {self.num_envs} envs on {self.device}")
+                rc = self._L.bg_step_many_rows_ex(
+                    self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
+                    1 if obs_buffers.steps > 1 else 0, C.byref(limits._struct()), C.c_void_p(self._stats.data_ptr()), self._stream())
+                if rc != 0:
+                    self._check(rc, "bg_step_many_rows_ex")
+                limits._terminal = None
+            else:
+                rc = self._L.bg_step_many_rows(
+                    self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
+                    1 if obs_buffers.steps > 1 else 0, C.c_void_p(self._stats.data_ptr()), self._stream())
+                if rc != 0:
+                    self._check(rc, "bg_step_many_rows")
             if self._rowbuf is not None:
                 self.observe()   # (obs_layout "rows": the live records follow)
             return obs_buffers.tensors, obs_buffers.reward, obs_buffers.terminated, None, None
+        if limits is not None:
+            raise ValueError("limits exist on the packed-record path: pass a RowBuffers as obs_buffers")
         keep = obs_buffers is not None and obs_buffers.steps > 1
         if keep and obs_buffers.steps < K:
             raise ValueError("obs_buffers has fewer rows than steps")
@@ -1093,6 +1135,70 @@ class EpisodeStats:
         if rc != 0:
             raise nat.NativeError(f"bg_episode_stats_rows failed ({rc}): {L.bg_last_error(None).decode()}")
         return (ep_return, ep_len, float(ms.value)) if timing else (ep_return, ep_len)
+
+
+class EpisodeLimits:
+    """SafeBalatroEnv's episode limits for `BalatroVecEnv.step_many(actions, obs_buffers=rows, limits=...)` (bg_step_many_rows_ex): owns, on the
+    device, the per-env counters the limits need across calls (int32 [n, 4]: episode_steps, consecutive_invalid, wrapper endings in the last call,
+    0) and the buffers for the records before the resets the wrapper causes -- SB3's info["terminal_observation"]: `terminal_rows` uint8
+    [S, n, row_stride] and `terminal_step` int32 [S, n] (the step of the last call whose ending filled the slot, else -1), S =
+    steps // min(limits) + 1 slots per env for calls of up to `steps` steps."""
+
+    def __init__(self, n: int, device, max_invalid_actions: int = 50, max_episode_steps: int = 1000, steps: int = 1, row_stride: int = 384):
+        self.n, self.steps = int(n), int(steps)
+        self.device = torch.device(device)
+        self.max_invalid_actions, self.max_episode_steps = int(max_invalid_actions), int(max_episode_steps)
+        self.row_stride = int(row_stride) or nat.ROW_BYTES
+        if self.n < 0 or self.steps < 1:
+            raise ValueError("n must be >= 0 and steps >= 1")
+        if min(self.max_invalid_actions, self.max_episode_steps) < nat.SAFE_MIN_LIMIT or max(self.max_invalid_actions, self.max_episode_steps) >= 2 ** 31:
+            raise ValueError(f"max_invalid_actions and max_episode_steps must be >= {nat.SAFE_MIN_LIMIT} (and fit an int32)")
+        if self.row_stride < nat.ROW_BYTES or self.row_stride % 16:
+            raise ValueError("row_stride must be a multiple of 16 and >= the 352-byte record")
+        self.slots = self.steps // min(self.max_invalid_actions, self.max_episode_steps) + 1   # bg_safe_terminal_slots
+        self.counters = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
+        self.terminal_rows = torch.zeros((self.slots, self.n, self.row_stride), dtype=torch.uint8, device=self.device)
+        self.terminal_step = torch.full((self.slots, self.n), -1, dtype=torch.int32, device=self.device)
+        self._terminal = None
+
+    def _struct(self) -> "nat.SafeLimits":
+        return nat.SafeLimits(self.max_invalid_actions, self.max_episode_steps, self.counters.data_ptr(), self.terminal_rows.data_ptr(),
+                              self.row_stride, self.terminal_step.data_ptr(), self.slots)
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Zero the counters (of the envs where `mask` is set): beside `env.reset(mask=...)`, as SafeBalatroEnv.reset does."""
+        if mask is None:
+            self.counters.zero_()
+            return
+        mask = torch.as_tensor(mask)
+        if tuple(mask.shape) != (self.n,):
+            raise ValueError(f"mask must have shape [{self.n}]")
+        self.counters.masked_fill_(mask.to(device=self.device, dtype=torch.bool).view(self.n, 1), 0)
+
+    def state_dict(self) -> dict:
+        return {"max_invalid_actions": self.max_invalid_actions, "max_episode_steps": self.max_episode_steps, "counters": self.counters.cpu().clone()}
+
+    def load_state_dict(self, state: dict) -> None:
+        if (int(state["max_invalid_actions"]), int(state["max_episode_steps"])) != (self.max_invalid_actions, self.max_episode_steps):
+            raise ValueError("the saved counters belong to other limits")
+        c = torch.as_tensor(state["counters"])
+        if tuple(c.shape) != (self.n, 4):
+            raise ValueError(f"counters must have shape [{self.n}, 4]")
+        self.counters.copy_(c.to(device=self.device, dtype=torch.int32))
+
+    def terminal(self):
+        """(index int32 [M], records uint8 [M, row_stride]) of the last call's wrapper endings: index = t * n + e, ascending (the index `minibatches` /
+        `ppo_loss(index=)` use for step t of env e); records[i] is the record of that step BEFORE the reset.  `encode_rows(records, layout)` -- with
+        `norm=` a RowNormalizer for VecNormalize's frozen statistics -- takes the [M, row_stride] tensor as it is, M = 0 included (`normalize_obs`
+        does not: it reads a 2-D tensor as ONE step of its N envs); the value network turns that matrix into `bootstrap_rewards`' terminal_values.  Made with torch on the
+        device (M is at most slots * n); the result is kept until the next call."""
+        if self._terminal is None:
+            ts = self.terminal_step.reshape(-1)
+            used = (ts >= 0).nonzero(as_tuple=False).flatten()          # slot j * n + e
+            index = ts[used].to(torch.int64) * self.n + used % self.n    # t * n + e: distinct, so the order is total
+            order = torch.argsort(index)
+            self._terminal = (index[order].to(torch.int32), self.terminal_rows.view(-1, self.row_stride)[used[order]].contiguous())
+        return self._terminal
 
 
 def _norm_rows(rows) -> torch.Tensor:

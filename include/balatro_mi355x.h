@@ -277,6 +277,49 @@ int bg_rollout_rows(bg_handle* h, int T, int policy, uint64_t policy_seed, uint6
 int bg_step_many_rows(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
                       int rows_stride_steps, bg_rollout_stats* stats_dev, void* stream);
 
+/* bg_step_many_rows under SafeBalatroEnv's episode limits, inside the launch (bg_engine3.h's SAFE instantiation; the rule is csrc/bg_safe.h).
+ * Replaces: `SafeBalatroEnv(env, max_invalid_actions=50, max_episode_steps=1000)` around every env of the reference's training scripts
+ * (train_balatro_fixed.py:228-277, :292; robust_training.py:35) and the reset SB3's VecEnv gives an env the wrapper ended.  Per step, in the
+ * reference's order:
+ *     episode_steps += 1
+ *     if reward == -1.0 (exactly, float64) and not the env's own terminated:  consecutive_invalid += 1; at max_invalid_actions: kill, reward = -50.0
+ *     else: consecutive_invalid = 0
+ *     max_steps = episode_steps >= max_episode_steps;  ended = env's terminated or kill or max_steps;  on `ended` both counters return to 0
+ * (a failed consumable, BG_ERR_CONSUMABLE*, has reward -1.0 and counts as an invalid action, as in the reference).
+ * limits == NULL: exactly bg_step_many_rows (byte BG_ROW_END_FLAGS stays 0).  With limits a record differs from bg_step_many_rows' in this:
+ *   byte BG_ROW_TERMINATED is SB3's `done` = ended, with its documented meaning -- the step ended the episode, the record already shows the new one --
+ *     so bg_gae_rows, bg_episode_stats_rows (Monitor sits outside SafeBalatroEnv) and bg_norm_reward_rows work on these records unchanged;
+ *   byte BG_ROW_END_FLAGS holds the BG_END_* bits, non-zero exactly when byte BG_ROW_TERMINATED is set;
+ *   a killed step's reward is -50.0 (every other reward is the step's own; the action word is the caller's value).
+ * A wrapper-made ending -- kill or max_steps while the env itself did not terminate -- resets the env inside the same step as a game over does (the
+ * same reset: templates re-applied, one ring deck consumed).  Before that reset the record as it stood -- SB3's info["terminal_observation"], with the
+ * step's reward, action and ending bytes, terminated = 1 -- goes to terminal_rows[j * N + e] and terminal_step[j * N + e] = t, the step of THIS call,
+ * where j counts the earlier wrapper endings of env e in this call: slots are per env, nothing is counted globally, two equal calls write equal
+ * bytes.  The call sets every unused terminal_step entry to -1 and leaves unused terminal records untouched.  SB3 bootstraps where the flags are
+ * exactly BG_END_MAX_STEPS (TimeLimit.truncated = truncated and not terminated).  stats_dev->episodes counts every ended episode.
+ * BG_E_ARG (text "bg_step_many_rows_ex: ..." in bg_last_error(h)) before anything is launched: a limit below 3 (the look-ahead rings are sized on
+ * episodes of at least 3 steps, which the game guarantees and such a limit would not), a handle without BG_FLAG_AUTORESET, a BG_ENGINE=1 handle,
+ * misaligned counters or terminal buffers, a terminal stride that is no record stride, terminal_slots below bg_safe_terminal_slots, only one of the
+ * two terminal pointers.  The counters are the caller's, like bg_episode_stats_rows' carries: zero them where bg_reset restarts an env. */
+#define BG_ROW_END_FLAGS 343      /* uint8: why the step ended the episode (bg_step_many_rows_ex with limits; 0 on every other path) */
+#define BG_END_GAME 1u            /* the env's own terminated (balatro_env_2.py:616-637, curriculum cap) */
+#define BG_END_INVALID 2u         /* info['invalid_action_termination'] */
+#define BG_END_MAX_STEPS 4u       /* info['max_steps_reached'] */
+typedef struct bg_safe_limits {
+  int32_t max_invalid_actions, max_episode_steps;  /* each >= 3 */
+  int32_t* counters_dev;          /* int32 [N, 4], 16-byte aligned, in/out, caller-owned: episode_steps, consecutive_invalid, wrapper endings in
+                                     this call (the library zeroes it at call start), 0 */
+  uint8_t* terminal_rows_dev;     /* [S, N] records, or NULL */
+  uint64_t terminal_stride_bytes; /* as row_stride_bytes */
+  int32_t* terminal_step_dev;     /* int32 [S, N]: the step t of this call whose ending filled slot (j, e), else -1; NULL iff terminal_rows_dev is */
+  int32_t terminal_slots;         /* S >= bg_safe_terminal_slots(K, limits) */
+} bg_safe_limits;
+/* K / min(limits) + 1: a call's first wrapper ending can come at its step 0 (the counters are carried in), each further one needs min(limits) more
+ * steps.  BG_E_ARG for K < 0 or a limit below 3. */
+int bg_safe_terminal_slots(int K, int max_invalid_actions, int max_episode_steps);
+int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                         int rows_stride_steps, const bg_safe_limits* limits, bg_rollout_stats* stats_dev, void* stream);
+
 /* Sharded jobs (one process per GPU): the exchange of the design -- every rank sees the CURRENT record of every env -- without a collective
  * behind the launch.  bufs[r] is rank r's gather buffer, uint8 [world][N][BG_ROW_BYTES], as mapped into THIS process (own buffer: an ordinary device
  * pointer; peers': hipIpcOpenMemHandle / torch's CUDA IPC over xGMI); N = this handle's env count, the same on every rank.  From then on the LAST launch
@@ -448,15 +491,16 @@ int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m
  *                        delta = (r + (g * nv) * nnt) - values[t][e];  last = delta + ((gl * nnt) * last)
  *                        advantages[t][e] = last;  returns[t][e] = last + values[t][e]
  * every operation rounded to float32, no fused multiply-add.  values_dev / advantages_dev / returns_dev are dense float32 [K, N], last_values_dev
- * [N]; returns_dev may be NULL (not written).  Outputs must not alias inputs or each other.  Truncation bootstraps are out of scope: the rows
- * path has no truncated flag.
+ * [N]; returns_dev may be NULL (not written).  Outputs must not alias inputs or each other.  A truncation bootstrap is the caller's addition to the
+ * rewards (bg_gae_rows_ex's rewards_dev): records of bg_step_many_rows_ex say in byte BG_ROW_END_FLAGS where the step limit alone ended an episode.
  *
  * bg_episode_stats_rows replaces: `Monitor` (hpc_train.py:26, train_balatro_fixed.py:290), the source of ep_rew_mean / ep_len_mean, as
  * info['episode']['r' / 'l'].  Per env, forwards: carry_return += reward[t] (a plain float64 sum in step order), carry_len += 1; on a set
  * terminated byte ep_return[t][e] / ep_len[t][e] = the carries and the carries return to 0.0 / 0, otherwise the outputs are written as 0.0 / 0.
  * The carries ([N], in / out) hold the running episode after the call, so 2 K steps give the same outputs in two calls of K as in one.  Monitor's own
  * presentation (round(..., 6), CPython's compensated sum) is not promised to the last bit.  ep_return_dev / ep_len_dev: dense [K, N], each may be NULL;
- * they must not alias the carries.  Wrapper-made endings (SafeBalatroEnv's invalid-action / step limits) do not exist on the rows path. */
+ * they must not alias the carries.  Wrapper-made endings (SafeBalatroEnv's invalid-action / step limits) are in the records of bg_step_many_rows_ex
+ * (terminated byte set, reward -50.0 on a kill: what Monitor, which sits outside SafeBalatroEnv, sees); no other rows call makes them. */
 int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
                 const float* values_dev, const float* last_values_dev, double gamma, double gae_lambda,
                 float* advantages_dev, float* returns_dev, float* kernel_ms_out, void* stream);
