@@ -64,7 +64,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_encode_cols", "bg_encode_rows", "bg_gae_rows", "bg_episode_stats_rows",
            "bg_gae_rows_ex", "bg_norm_workspace_bytes", "bg_norm_obs_rows", "bg_norm_reward_rows",
            "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex",
-           "bg_step_many_rows_ex", "bg_safe_terminal_slots"]
+           "bg_step_many_rows_ex", "bg_safe_terminal_slots",
+           "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -80,6 +81,9 @@ HEAD_F32, HEAD_BF16, HEAD_DETERMINISTIC = 0, 1, 1   # bg_sample_actions / bg_eva
 # bg_ppo_loss: the order of stats_dev (BG_PPO_STATS floats) and its flag
 PPO_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std", "excluded", "m")
 PPO_NORMALIZE_ADV = 1
+LIN_NONE, LIN_RELU = 0, 1   # bg_linear_rows / bg_linear_rows_grad (BG_LIN_*)
+LIN_ACTIVATIONS = {None: LIN_NONE, "relu": LIN_RELU}
+LIN_K = 153                 # the columns of a first-layer weight that are read: the "produced" ones
 NORM_COLS = 153   # BG_NORM_COLS: VecNormalize's statistics are one (mean, var) per column of the "produced" layout
 # the keys BalatroEnvFixed zero-fills (train_balatro_fixed.py:125-207), in the order of its observation space, with their element counts
 ENC_ZERO_KEYS = [("hand_one_hot", 416), ("hand_suits", 8), ("hand_ranks", 8), ("rank_counts", 13), ("suit_counts", 4), ("straight_potential", 1),
@@ -266,5 +270,10 @@ def load(build_if_missing: bool = True):
     L.bg_ppo_loss_workspace_bytes.argtypes = [i64]
     L.bg_ppo_loss.argtypes = [vp, i32, u64, vp, u64, vp, vp, vp, vp, vp, vp, i64, i64, C.c_float, C.c_float, C.c_float, u32, vp, u64, vp, vp, vp, vp, vp, u64,
                               C.POINTER(C.c_float), vp]
+    L.bg_linear_rows.argtypes = [vp, u64, i64, vp, i64, i32, vp, vp, C.c_double, C.c_double, vp, u64, vp, i32, i32, i32, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_linear_rows_workspace_bytes.restype = u64
+    L.bg_linear_rows_workspace_bytes.argtypes = [i64, i32]
+    L.bg_linear_rows_grad.argtypes = [vp, u64, i64, vp, i64, i32, vp, vp, C.c_double, C.c_double, vp, i32, u64, vp, i32, u64, i32, i32, vp, u64, vp, vp, u64,
+                                      C.POINTER(C.c_float), vp]
     _lib = L
     return L

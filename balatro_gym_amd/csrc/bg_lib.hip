@@ -361,6 +361,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
 #include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
 #include "bg_ppo.h"    // logits + stored rollout arrays -> PPO's clipped loss, its diagnostics and its gradient (operator-level)
+#include "bg_linear.h" // packed records -> the network's first layer and its weight gradient on the matrix cores (operator-level)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -2495,6 +2496,107 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
   if (bf16) hipLaunchKernelGGL((bg_ppo_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
   else hipLaunchKernelGGL((bg_ppo_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
   hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+// packed records -> the first layer of the network and its weight / bias gradient (bg_linear.h): the features of bg_encode_rows_ex are built in LDS
+// and consumed by the matrix cores in the same launch.
+static const char* bg_linear_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
+                                         const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, int H, int activation) {
+  const bool norm = mean_dev || var_dev;
+  if (layout == BG_ENC_EXTRACTOR) return "layout BG_ENC_EXTRACTOR is not supported (its 416 one-hot columns want an embedding gather): BG_ENC_PRODUCED or BG_ENC_FIXED";
+  if (layout != BG_ENC_PRODUCED && layout != BG_ENC_FIXED) return "layout must be BG_ENC_PRODUCED or BG_ENC_FIXED";
+  if (H < 32 || H > 4096 || H % 32) return "H must be a multiple of 32 in [32, 4096]";
+  if (activation != BG_LIN_NONE && activation != BG_LIN_RELU) return "activation must be BG_LIN_NONE or BG_LIN_RELU";
+  if (m < 0 || m > (int64_t)BG_LIN_ROWS * 0x7fffffffll) return "m out of range";
+  if (store_rows < 0) return "store_rows must be >= 0";
+  if (index_dev && store_rows > 0x7fffffffll) return "store_rows must be in [0, 2**31) when index_dev is given";
+  if (!index_dev && m > store_rows) return "m must be <= store_rows when index_dev is NULL";
+  if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) return r;
+  if ((uintptr_t)index_dev & 3) return "index_dev must be 4-byte aligned";
+  if (norm && (!mean_dev || !var_dev)) return "mean_dev and var_dev go together: both or neither";
+  if (norm && (((uintptr_t)mean_dev | (uintptr_t)var_dev) & 7)) return "mean_dev and var_dev must be 8-byte aligned";
+  if (norm && mean_dev == var_dev) return "mean_dev and var_dev must not be the same pointer";
+  if (norm && !(epsilon >= 0.0 && epsilon <= 1.7976931348623157e308 && clip_obs >= 0.0 && clip_obs <= 1.7976931348623157e308)) return "epsilon and clip_obs must be finite and >= 0 when statistics are given";
+  return nullptr;
+}
+
+int bg_linear_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
+                   const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, const void* weight_dev, uint64_t weight_stride_elems,
+                   const float* bias_dev, int H, int activation, int out_dtype, void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream) {
+  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const char* bad = bg_linear_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, layout, mean_dev, var_dev, epsilon, clip_obs, H, activation);
+  if (bad) {}
+  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (!weight_dev || ((uintptr_t)weight_dev & 1)) bad = "weight_dev must be a 2-byte aligned device pointer";
+  else if (weight_stride_elems < (uint64_t)BG_LIN_K || weight_stride_elems > 0x1000000ull) bad = "weight_stride_elems must be in [153, 2**24]";
+  else if ((uintptr_t)bias_dev & 3) bad = "bias_dev must be 4-byte aligned";
+  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
+  else if (out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= H";
+  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev ||
+           out_dev == weight_dev || out_dev == (const void*)bias_dev) bad = "out_dev must not be the same pointer as an input";
+  if (bad) { g_create_err = std::string("bg_linear_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (m == 0) return 0;
+  const unsigned gx = (unsigned)bg_lin_blocks(m);
+  const unsigned nchunks = (unsigned)((H + BG_LIN_WCHUNK - 1) / BG_LIN_WCHUNK);
+  unsigned ys = 1;
+  while ((uint64_t)gx * ys < 512u && ys * 2u <= nchunks) ys *= 2u;   // a short call: the chunks of H over more workgroups (a function of m and H alone)
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  const int relu = activation == BG_LIN_RELU;
+#define BG_LIN_GO(NORM, T) hipLaunchKernelGGL((bg_linear_rows_kernel<NORM, T>), dim3(gx, ys), dim3(BG_LIN_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, (const uint16_t*)weight_dev, weight_stride_elems, bias_dev, H, relu, out_dev, out_stride_elems)
+  if (mean_dev) { if (out_dtype == BG_ENC_F32) BG_LIN_GO(true, BG_ENC_F32); else BG_LIN_GO(true, BG_ENC_BF16); }
+  else { if (out_dtype == BG_ENC_F32) BG_LIN_GO(false, BG_ENC_F32); else BG_LIN_GO(false, BG_ENC_BF16); }
+#undef BG_LIN_GO
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+uint64_t bg_linear_rows_workspace_bytes(int64_t m, int H) {
+  if (m <= 0 || H < 32 || H > 4096 || H % 32) return 0;
+  return (uint64_t)bg_lin_groups(m, H) * BG_LIN_PART_ROWS * (uint64_t)H * sizeof(float);
+}
+
+int bg_linear_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
+                        const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, const void* dout_dev, int dout_dtype,
+                        uint64_t dout_stride_elems, const void* out_dev, int out_dtype, uint64_t out_stride_elems, int H, int activation,
+                        float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev, void* workspace_dev, uint64_t workspace_bytes,
+                        float* kernel_ms_out, void* stream) {
+  const uint64_t ds = dout_dtype == BG_ENC_F32 ? 4u : 2u, os = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const bool relu = activation == BG_LIN_RELU;
+  const char* bad = bg_linear_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, layout, mean_dev, var_dev, epsilon, clip_obs, H, activation);
+  if (bad) {}
+  else if (dout_dtype != BG_ENC_F32 && dout_dtype != BG_ENC_BF16) bad = "dout_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (!dout_dev || ((uintptr_t)dout_dev & (ds - 1))) bad = "dout_dev must be a device pointer aligned to its element type";
+  else if (dout_stride_elems < (uint64_t)H || dout_stride_elems > 0xffffffffull) bad = "dout_stride_elems must be >= H";
+  else if (relu != (out_dev != nullptr)) bad = "out_dev (the forward's output) is required with BG_LIN_RELU and must be NULL without it";
+  else if (relu && out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (relu && (((uintptr_t)out_dev & (os - 1)) || out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull)) bad = "out_dev must be aligned to its element type and out_stride_elems >= H";
+  else if (!dweight_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev must be a 4-byte aligned device pointer (dbias_dev 4-byte aligned)";
+  else if (dweight_stride_elems < (uint64_t)BG_LIN_K || dweight_stride_elems > 0xffffffffull) bad = "dweight_stride_elems must be >= 153";
+  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_linear_rows_workspace_bytes(m, H))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_linear_rows_workspace_bytes(m, H) bytes";
+  else if ((const void*)dweight_dev == dout_dev || (const void*)dweight_dev == out_dev || (const void*)dweight_dev == (const void*)rows_dev || dweight_dev == dbias_dev ||
+           (void*)dweight_dev == workspace_dev || (dbias_dev && ((void*)dbias_dev == workspace_dev || (const void*)dbias_dev == dout_dev || (const void*)dbias_dev == out_dev)) ||
+           workspace_dev == dout_dev || (workspace_dev && workspace_dev == out_dev)) bad = "outputs and the workspace must not be the same pointer as an input or as each other";
+  if (bad) { g_create_err = std::string("bg_linear_rows_grad: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  if (m == 0) return 0;
+  const long long per = bg_lin_blocks_per_group(m, H), groups = bg_lin_groups(m, H);
+  hipStream_t s = (hipStream_t)stream;
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+#define BG_LIN_GO(NORM) hipLaunchKernelGGL((bg_linear_rows_grad_kernel<NORM>), dim3((unsigned)groups, (unsigned)bg_lin_spans(H)), dim3(BG_LIN_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, dout_dev, (int)(dout_dtype == BG_ENC_BF16), dout_stride_elems, out_dev, (int)(out_dtype == BG_ENC_BF16), out_stride_elems, H, per, (float*)workspace_dev)
+  if (mean_dev) BG_LIN_GO(true); else BG_LIN_GO(false);
+#undef BG_LIN_GO
+  const long long items = (long long)BG_LIN_PART_ROWS * H;
+  hipLaunchKernelGGL(bg_linear_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)workspace_dev, groups, H, dweight_dev, dweight_stride_elems, dbias_dev);
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);

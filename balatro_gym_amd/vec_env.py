@@ -132,6 +132,11 @@ class RowBuffers:
         [m, D] matrix of those records under the statistics as they stand (frozen)."""
         return norm.normalize_obs(self.rows, layout, dtype, out, index=index)
 
+    def linear(self, layer: "RowLinear", index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None) -> torch.Tensor:
+        """The first layer of the network over these records, [steps * n, H] or with `index` [m, H] (`RowLinear.forward`: bg_linear_rows, and
+        bg_linear_rows_grad under autograd): the feature matrix is never written."""
+        return layer(self.rows, index, norm)
+
     def normalize_reward(self, norm: "RowNormalizer", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The records' rewards as VecNormalize would hand them to the learner, float64 [steps, n] (`RowNormalizer.normalize_reward`)."""
         return norm.normalize_reward(self.rows, out)
@@ -788,6 +793,227 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
         raise nat.NativeError(f"{name} failed ({rc}): {L.bg_last_error(None).decode()}")
     res = out[..., :D]
     return (res, float(ms.value)) if timing else res
+
+
+def _linear_common(rows, index, norm, layout, activation):
+    """The arguments linear_rows and its gradient share -> (stride, store_rows, m).  Every refusal is a ValueError before the library is loaded."""
+    if layout not in ("produced", "fixed"):
+        raise ValueError(f"layout must be 'produced' or 'fixed' (got {layout!r}): the extractor's one-hot columns want an embedding gather, not this layer")
+    if activation not in nat.LIN_ACTIVATIONS:
+        raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 1 or not rows.is_contiguous():
+        raise ValueError("rows must be a contiguous uint8 tensor [..., stride] of packed records")
+    stride = int(rows.shape[-1])
+    if stride < nat.ROW_BYTES or stride % 16:
+        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
+    store_rows = int(np.prod(tuple(rows.shape[:-1]), dtype=np.int64))
+    m = store_rows
+    if index is not None:
+        _check_index(index, None, rows.device)
+        if store_rows >= 2 ** 31:
+            raise ValueError("the stored records hold at most 2**31 - 1 rows")
+        m = int(index.shape[0])
+    if norm is not None:
+        if not isinstance(norm, RowNormalizer):
+            raise ValueError("norm must be a RowNormalizer")
+        if not norm.norm_obs:
+            raise ValueError("this RowNormalizer was made with norm_obs=False: call without norm")
+        if norm.device != rows.device:
+            raise ValueError(f"norm holds its statistics on {norm.device}, rows are on {rows.device}")
+        if not (np.isfinite(norm.epsilon) and norm.epsilon >= 0.0 and np.isfinite(norm.clip_obs) and norm.clip_obs >= 0.0):
+            raise ValueError("norm.epsilon and norm.clip_obs must be finite and >= 0")
+    return stride, store_rows, m
+
+
+def _linear_matrix(name: str, t, dtypes: tuple, m: int, H: int, device: torch.device) -> int:
+    """A [m, >= H] matrix with a contiguous last dimension -> its row pitch in elements."""
+    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != device or t.dim() != 2 or t.shape[0] != m or t.shape[1] < H \
+            or t.stride(1) != 1 or (m > 1 and t.stride(0) < t.shape[1]):
+        raise ValueError(f"{name} must be a {' / '.join(str(d) for d in dtypes)} tensor [{m}, >= {H}] on {device} with a contiguous last dimension")
+    return int(t.stride(0)) if m > 1 else int(t.shape[1])
+
+
+def _linear_weight(weight) -> int:
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.bfloat16 or weight.dim() != 2 or weight.shape[1] not in (nat.LIN_K, nat.ENC_COLS[nat.ENC_FIXED]) \
+            or not weight.is_contiguous():
+        raise ValueError("weight must be a contiguous torch.bfloat16 tensor [H, 153] or [H, 628] (nn.Linear.weight's orientation)")
+    H = int(weight.shape[0])
+    if H < 32 or H > 4096 or H % 32:
+        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
+    return H
+
+
+def _linear_rows_args(rows, index, norm):
+    return (C.c_void_p(norm.obs_mean.data_ptr()) if norm is not None else None, C.c_void_p(norm.obs_var.data_ptr()) if norm is not None else None,
+            C.c_double(norm.epsilon if norm is not None else 0.0), C.c_double(norm.clip_obs if norm is not None else 0.0))
+
+
+def linear_rows(rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, index: Optional[torch.Tensor] = None,
+                norm: Optional["RowNormalizer"] = None, layout: str = "fixed", activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16,
+                out: Optional[torch.Tensor] = None, timing: bool = False):
+    """The network's first layer straight from packed records, on the matrix cores, in one launch (bg_linear_rows):
+    act(x @ weight[:, :153].T + bias), x the bfloat16 rows `encode_rows(rows, layout, torch.bfloat16, index=index, norm=norm)` gives -- which are never
+    written.  weight: torch.bfloat16 [H, 153] or [H, 628] (nn.Linear.weight's orientation; of 628 columns only the first 153 are read: the others meet the
+    475 zeros of the "fixed" layout), H a multiple of 32 in [32, 4096]; bias: float32 [H] or None; activation: None or "relu".  layout "fixed" or
+    "produced": the same result.  index / norm: as `encode_rows`; a row whose index is out of range is act(bias).  dtype: torch.bfloat16 or
+    torch.float32 (float32 accumulation either way, one rounding).  out: optional [m, >= H] tensor of `dtype`; columns beyond H are left untouched.
+    Returns the [m, H] matrix (m = all records flattened, or len(index)); timing=True returns (matrix, kernel milliseconds).  There is no CPU path."""
+    stride, store_rows, m = _linear_common(rows, index, norm, layout, activation)
+    H = _linear_weight(weight)
+    if weight.device != rows.device:
+        raise ValueError(f"weight must be on {rows.device}")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (H,) or not bias.is_contiguous()
+                             or bias.device != rows.device):
+        raise ValueError(f"bias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+    pitch = _linear_matrix("out", out, (dtype,), m, H, rows.device) if out is not None else H
+    if not rows.is_cuda:
+        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+    if rows.data_ptr() % 16:
+        raise ValueError("rows must be 16-byte aligned")
+    if out is None:
+        out = torch.empty((m, H), dtype=dtype, device=rows.device)
+    if m == 0:
+        return (out[:, :H], 0.0) if timing else out[:, :H]
+    L = nat.load()
+    ms = C.c_float(0.0)
+    with torch.cuda.device(rows.device):
+        rc = L.bg_linear_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(store_rows), C.c_void_p(index.data_ptr()) if index is not None else None,
+                              C.c_int64(m), nat.ENC_LAYOUTS[layout], *_linear_rows_args(rows, index, norm), C.c_void_p(weight.data_ptr()),
+                              C.c_uint64(int(weight.shape[1])), C.c_void_p(bias.data_ptr()) if bias is not None else None, H, nat.LIN_ACTIVATIONS[activation],
+                              nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(out.data_ptr()), C.c_uint64(pitch),
+                              C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+    if rc != 0:
+        raise nat.NativeError(f"bg_linear_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+    return (out[:, :H], float(ms.value)) if timing else out[:, :H]
+
+
+def linear_rows_grad(rows: torch.Tensor, dout: torch.Tensor, *, out: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None,
+                     norm: Optional["RowNormalizer"] = None, layout: str = "fixed", activation: Optional[str] = None, dweight: Optional[torch.Tensor] = None,
+                     bias: bool = True, workspace: Optional[torch.Tensor] = None, timing: bool = False):
+    """The weight and bias gradient of `linear_rows`, straight from the records (bg_linear_rows_grad): dweight[n, k] = sum_i dp[i, n] * x[i, k],
+    dbias[n] = sum_i dp[i, n], dp = bfloat16(dout), under activation="relu" masked where the forward's `out` (required then) is not > 0.  dout: float32 or
+    bfloat16 [m, >= H].  dweight: optional float32 [H, 153] or [H, 628] (columns beyond 153 are not written); without one a zero-filled [H, 628] ("fixed")
+    or [H, 153] ("produced") is made, so the columns beyond 153 carry their exact gradient, zero.  Returns (dweight, dbias or None) -- with timing=True
+    (dweight, dbias, kernel milliseconds).  Sums over rows are deterministic (no atomics)."""
+    stride, store_rows, m = _linear_common(rows, index, norm, layout, activation)
+    if not isinstance(dout, torch.Tensor) or dout.dim() != 2:
+        raise ValueError("dout must be a float32 / bfloat16 tensor [m, H]")
+    H = int(dweight.shape[0]) if isinstance(dweight, torch.Tensor) and dweight.dim() == 2 else int(dout.shape[1])
+    if H < 32 or H > 4096 or H % 32:
+        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
+    dpitch = _linear_matrix("dout", dout, (torch.float32, torch.bfloat16), m, H, rows.device)
+    relu = activation == "relu"
+    if relu != (out is not None):
+        raise ValueError("out (the forward's output) is required with activation='relu' and must be None without it")
+    opitch = _linear_matrix("out", out, (torch.float32, torch.bfloat16), m, H, rows.device) if relu else 0
+    if dweight is not None and (not isinstance(dweight, torch.Tensor) or dweight.dtype != torch.float32 or dweight.dim() != 2 or dweight.shape[1] < nat.LIN_K
+                                or not dweight.is_contiguous() or dweight.device != rows.device):
+        raise ValueError(f"dweight must be a contiguous torch.float32 tensor [H, >= {nat.LIN_K}] on {rows.device}")
+    if not rows.is_cuda:
+        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+    if rows.data_ptr() % 16:
+        raise ValueError("rows must be 16-byte aligned")
+    if dweight is None:
+        dweight = torch.zeros((H, nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]), dtype=torch.float32, device=rows.device)
+    dbias = torch.zeros(H, dtype=torch.float32, device=rows.device) if bias else None
+    if m == 0:
+        dweight[:, :nat.LIN_K] = 0.0
+        return (dweight, dbias, 0.0) if timing else (dweight, dbias)
+    L = nat.load()
+    need = int(L.bg_linear_rows_workspace_bytes(C.c_int64(m), H))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != rows.device or not workspace.is_contiguous() \
+            or workspace.numel() < need:
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {rows.device}")
+    ms = C.c_float(0.0)
+    with torch.cuda.device(rows.device):
+        rc = L.bg_linear_rows_grad(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(store_rows), C.c_void_p(index.data_ptr()) if index is not None else None,
+                                   C.c_int64(m), nat.ENC_LAYOUTS[layout], *_linear_rows_args(rows, index, norm), C.c_void_p(dout.data_ptr()),
+                                   nat.ENC_F32 if dout.dtype == torch.float32 else nat.ENC_BF16, C.c_uint64(dpitch),
+                                   C.c_void_p(out.data_ptr()) if relu else None, (nat.ENC_F32 if out.dtype == torch.float32 else nat.ENC_BF16) if relu else 0,
+                                   C.c_uint64(opitch), H, nat.LIN_ACTIVATIONS[activation], C.c_void_p(dweight.data_ptr()), C.c_uint64(int(dweight.shape[1])),
+                                   C.c_void_p(dbias.data_ptr()) if bias else None, C.c_void_p(workspace.data_ptr()), C.c_uint64(workspace.numel()),
+                                   C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
+    if rc != 0:
+        raise nat.NativeError(f"bg_linear_rows_grad failed ({rc}): {L.bg_last_error(None).decode()}")
+    return (dweight, dbias, float(ms.value)) if timing else (dweight, dbias)
+
+
+class _RowLinearFn(torch.autograd.Function):
+    """out = linear_rows(records); backward = ONE bg_linear_rows_grad call.  The records carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, rows, index, norm, layout, activation, dtype):
+        out = linear_rows(rows, weight.detach().to(torch.bfloat16), bias.detach() if bias is not None else None, index=index, norm=norm, layout=layout,
+                          activation=activation, dtype=dtype)
+        ctx.save_for_backward(out)
+        ctx.call = (rows, index, norm, layout, activation, tuple(weight.shape), bias is not None)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        rows, index, norm, layout, activation, wshape, has_bias = ctx.call
+        out, = ctx.saved_tensors
+        dout = grad if grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.stride(1) == 1 and (grad.shape[0] <= 1 or grad.stride(0) >= grad.shape[1]) \
+            else grad.to(torch.float32).contiguous()
+        dweight = torch.zeros(wshape, dtype=torch.float32, device=rows.device)   # columns at or beyond 153: zero, their exact gradient
+        dweight, dbias = linear_rows_grad(rows, dout, out=out if activation == "relu" else None, index=index, norm=norm, layout=layout, activation=activation,
+                                          dweight=dweight, bias=has_bias)
+        return dweight, dbias, None, None, None, None, None, None
+
+
+class RowLinear(torch.nn.Module):
+    """The first `nn.Linear` of a policy over packed records: `forward(rows)` is `linear_rows` and its backward one `linear_rows_grad` call, so neither pass
+    materialises the feature matrix.  Parameters are float32 -- weight [out_features, 628] ("fixed": SB3's MultiInputPolicy over BalatroEnvFixed) or
+    [out_features, 153] ("produced"), bias [out_features] -- initialised as nn.Linear; `from_linear` / `to_linear` move them to and from an nn.Linear, so a
+    policy trained here loads into SB3's module and back.  The weight is cast to bfloat16 for every call (the master copy stays float32); columns at or
+    beyond 153 of a 628-wide weight get a zero gradient, which is their exact gradient: their inputs are zero."""
+
+    def __init__(self, out_features: int, in_layout: str = "fixed", activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16, device=None):
+        super().__init__()
+        if in_layout not in ("produced", "fixed"):
+            raise ValueError(f"in_layout must be 'produced' or 'fixed' (got {in_layout!r})")
+        if activation not in nat.LIN_ACTIVATIONS:
+            raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        out_features = int(out_features)
+        if out_features < 32 or out_features > 4096 or out_features % 32:
+            raise ValueError(f"out_features must be a multiple of 32 in [32, 4096] (got {out_features})")
+        self.out_features, self.in_layout, self.activation, self.dtype = out_features, in_layout, activation, dtype
+        self.in_features = nat.ENC_COLS[nat.ENC_LAYOUTS[in_layout]]
+        lin = torch.nn.Linear(self.in_features, out_features, device=device)   # nn.Linear's own initialisation
+        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
+        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+
+    @classmethod
+    def from_linear(cls, linear: torch.nn.Linear, activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16) -> "RowLinear":
+        if not isinstance(linear, torch.nn.Linear) or linear.in_features not in (nat.LIN_K, nat.ENC_COLS[nat.ENC_FIXED]) or linear.bias is None:
+            raise ValueError("from_linear takes an nn.Linear with bias and 153 ('produced') or 628 ('fixed') inputs")
+        layer = cls(linear.out_features, "produced" if linear.in_features == nat.LIN_K else "fixed", activation, dtype, device=linear.weight.device)
+        with torch.no_grad():
+            layer.weight.copy_(linear.weight)
+            layer.bias.copy_(linear.bias)
+        return layer
+
+    def to_linear(self) -> torch.nn.Linear:
+        lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
+        with torch.no_grad():
+            lin.weight.copy_(self.weight)
+            lin.bias.copy_(self.bias)
+        return lin
+
+    def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None) -> torch.Tensor:
+        _linear_common(rows, index, norm, self.in_layout, self.activation)
+        if not rows.is_cuda or self.weight.device != rows.device:
+            raise ValueError("rows and the layer must be on the same GPU (there is no CPU fallback)")
+        return _RowLinearFn.apply(self.weight, self.bias, rows, index, norm, self.in_layout, self.activation, self.dtype)
+
+    def extra_repr(self) -> str:
+        return f"in_layout={self.in_layout!r}, out_features={self.out_features}, activation={self.activation!r}, dtype={self.dtype}"
 
 
 def _head_logits(logits) -> tuple:

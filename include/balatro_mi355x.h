@@ -682,6 +682,60 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
                 float* stats_dev /* float32[BG_PPO_STATS = 10] */,
                 void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* The network's first layer straight from the stored records, on the matrix cores, forward and backward: the features of bg_encode_rows_ex are built in
+ * LDS and multiplied with the weight in the same launch, so the [m, 628] feature matrix exists neither for the forward pass nor for the weight gradient.
+ * The arithmetic and the tile shapes are csrc/bg_linear.h.
+ * Replaces: `CombinedExtractor`'s concatenation plus the first `nn.Linear` of `mlp_extractor` under `PPO("MultiInputPolicy", ...)` over
+ * `BalatroEnvFixed` -- 628 inputs into first layers of 512 units for policy and value (hpc_train.py:92-93, train_balatro_fixed.py:361-363) -- which
+ * runs once per collected step and n_epochs = 10 times per rollout, and the autograd backward of that layer.  475 of the 628 columns are the keys
+ * BalatroEnvFixed zero-fills (exactly 0.0 with frozen statistics too), so the reduction runs over the 153 produced columns; a first layer needs no
+ * gradient with respect to its input, so the backward pass is dweight and dbias alone.
+ *
+ * bg_linear_rows:       out[i, n] = act( sum over k < 153 of x[i, k] * w[n, k]  +  b[n] )
+ * x[i, :] = the first 153 columns of the row bg_encode_rows_ex writes with out_dtype BG_ENC_BF16 for the same rows_dev, row_stride_bytes, store_rows,
+ * index_dev, m, mean_dev / var_dev, epsilon, clip_obs -- bit for bit: the float32 value, then round to nearest even to bfloat16.  An index outside
+ * [0, store_rows) reads nothing and gives x = 0, so out = act(b).  layout BG_ENC_PRODUCED or BG_ENC_FIXED: identical results (columns 153..627 are
+ * zero and are never read from the weight); BG_ENC_EXTRACTOR is a BG_E_ARG (its 416 one-hot columns want an embedding gather).
+ * weight_dev: bfloat16 in torch's `nn.Linear.weight` orientation, [H, weight_stride_elems >= 153] (at most 2**24); a [H, 628] weight is passed in place and only its
+ * first 153 columns are read; 2-byte alignment is all that is required.  bias_dev: float32 [H] or NULL.  activation: BG_LIN_NONE, or BG_LIN_RELU =
+ * max(v, +0.0) (a NaN stays a NaN).  out_dtype BG_ENC_F32 or BG_ENC_BF16, out_stride_elems >= H; columns at or beyond H and rows at or beyond m are
+ * not touched.  H: a multiple of 32 in [32, 4096] (policy and value first layers run as one call on the concatenated weight).
+ * Products are bfloat16 x bfloat16 (exact in float32), accumulated in float32 by __builtin_amdgcn_mfma_f32_32x32x16_bf16 over the reduction padded to
+ * 160 with zeros; the bias is added in float32 behind the sum, then the activation, then ONE rounding to the output dtype.  The order inside the product
+ * is the instruction's own and a fixed function of (m, H): two calls give the same bits.
+ *
+ * bg_linear_rows_grad:  dweight[n, k] = sum over i of dp[i, n] * x[i, k]  (k < 153);    dbias[n] = sum over i of dp[i, n]
+ * x is the forward's, rebuilt from the records with the same arguments.  dp[i, n] = bfloat16(dout[i, n]) (round to nearest even; dout_dtype BG_ENC_F32
+ * or BG_ENC_BF16, dout_stride_elems >= H); with BG_LIN_RELU, dp[i, n] is that where out[i, n] > 0 and +0.0 elsewhere: out_dev / out_dtype /
+ * out_stride_elems are the forward's output, required exactly when the flag is set (NULL otherwise).  dweight_dev: float32 [H, dweight_stride_elems >=
+ * 153], columns at or beyond 153 untouched (their exact gradient is zero: the caller's business); dbias_dev: float32 [H] or NULL.  There is no gradient
+ * with respect to the records.  The sum over i has no floating-point atomics: the rows are cut into groups of consecutive 128-row blocks, a workgroup
+ * keeps float32 matrix-core accumulators over the rows of its group (its dbias sum: float32 in row order per lane), the groups' partials ([161, H]
+ * float32 each) go to workspace_dev and a second launch adds them in index order in float64, rounding once.  bg_linear_rows_workspace_bytes(m, H) =
+ * groups * 161 * H * 4 bytes, groups = ceil(B / ceil(B / max(1, 256 / ceil(H / 256)))) with B = ceil(m / 128): at most 256 partials, 42 MB at H >= 256;
+ * a group holds 128 * ceil(B / groups) rows at most.  workspace_dev: 16-byte aligned.  Two calls give the same bits.
+ *
+ * Both calls run on the current device, need no handle, return BG_E_ARG (text "bg_linear_rows: ..." / "bg_linear_rows_grad: ..." in
+ * bg_last_error(NULL)) before anything is launched, treat m == 0 as a no-op and never synchronise unless timing is asked for; kernel_ms_out as in
+ * bg_classify_batch_ex.  All record addressing is 64-bit.
+ * Out of scope: the extractor layout, tanh and other activations, a gradient with respect to the records, statistics updates, fp8 / MX formats,
+ * deeper layers and the optimiser. */
+#define BG_LIN_NONE 0
+#define BG_LIN_RELU 1
+int bg_linear_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                   const int32_t* index_dev /*nullable*/, int64_t m, int layout,
+                   const double* mean_dev /*nullable*/, const double* var_dev /*nullable*/, double epsilon, double clip_obs,
+                   const void* weight_dev, uint64_t weight_stride_elems, const float* bias_dev /*nullable*/, int H, int activation,
+                   int out_dtype, void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream);
+uint64_t bg_linear_rows_workspace_bytes(int64_t m, int H);
+int bg_linear_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                        const int32_t* index_dev /*nullable*/, int64_t m, int layout,
+                        const double* mean_dev /*nullable*/, const double* var_dev /*nullable*/, double epsilon, double clip_obs,
+                        const void* dout_dev, int dout_dtype, uint64_t dout_stride_elems,
+                        const void* out_dev /*nullable*/, int out_dtype, uint64_t out_stride_elems, int H, int activation,
+                        float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev /*nullable*/,
+                        void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
