@@ -199,14 +199,17 @@ BG_ENC_FN uint16_t bg_enc_bf16(uint32_t u) {
 BG_ENC_FN int64_t bg_enc_source_row(int32_t index, int64_t store_rows) { return index >= 0 && (int64_t)index < store_rows ? (int64_t)index : (int64_t)-1; }
 
 #ifndef BG_ENC_HOST
-// ---- the kernel ----
-// A workgroup of 256 lanes takes BG_ENC_RECS = 32 consecutive records, in three phases with a barrier between them:
-//   1  the records' 352 bytes are read from HBM once, 16 bytes per lane, into LDS (record pitch 356 bytes = 89 words: odd, so phase 2's lanes, one
-//      record each, read without bank conflicts);
-//   2  lane = (record, one of 8 column slices): the layout's DENSE columns -- the 153 produced ones; for EXTRACTOR the 31 behind the one-hot -- are
-//      converted with the column index a compile-time constant (the table folds away: one LDS read, a bit-field extract and a convert per column; the
-//      int64 and division sequences only where a column needs them) into a float32 tile in LDS (pitch 153 / 31 words: odd again);
-//   3  the lanes walk the output with consecutive lanes on consecutive 16-byte pieces, reading finished values from the tile:
+#include <type_traits>
+// ---- the records-to-tile pipeline ----
+// bg_encode_kernel, bg_norm_obs_kernel, their GATHER variants (bg_norm.h) and the first layer (bg_linear.h) are this code; they differ in the converter
+// of phase 2 alone.  A workgroup of 256 lanes takes BG_ENC_RECS = 32 records, in three phases with a barrier between them:
+//   1  bg_enc_stage: the records' 352 bytes are read from HBM once, 16 bytes per lane, into LDS (record pitch 356 bytes = 89 words: odd, so phase 2's
+//      lanes, one record each, read without bank conflicts);
+//   2  bg_enc_fill_tile: lane = (record, one of 8 column slices).  bg_enc_slices hands the slice to the converter as a compile-time constant, so the
+//      layout's DENSE columns -- the 153 produced ones; for EXTRACTOR the 31 behind the one-hot -- are converted with the column index a constant (the
+//      table folds away: one LDS read, a bit-field extract and a convert per column; the int64, division and float64 sequences only where a column
+//      needs them) into a float32 tile in LDS (pitch 153 / 31 words: odd again).  The converters: BgEncConvert<LAYOUT> here, BgNormConvert (bg_norm.h);
+//   3  bg_enc_store: the lanes walk the output with consecutive lanes on consecutive 16-byte pieces, reading finished values from the tile:
 //        BG_ENC_ST_ROWS  out_dev and the row pitch are 16-byte aligned: a piece is 4 (f32) / 8 (bf16) columns of one row, the row's tail by element
 //        BG_ENC_ST_FLAT  rows are not 16-byte aligned but the matrix is dense (pitch == columns) and out_dev aligned: a workgroup's rows are ONE
 //                        aligned run of RECS * D elements, so pieces run across row ends (RECS * D * 2 bytes is a multiple of 16)
@@ -214,11 +217,11 @@ BG_ENC_FN int64_t bg_enc_source_row(int32_t index, int64_t store_rows) { return 
 //      FIXED's 475 zero columns touch neither LDS nor the table; EXTRACTOR's 416 one-hot columns are computed here from the record's hand bytes
 //      (bg_enc_onehot: a byte read and a compare per element).
 // LDS: 11 392 bytes of records + 19 584 (153-column tile) or 3 968 (EXTRACTOR) bytes: five / eight workgroups per CU.
-// GATHER (bg_encode_rows_ex; a compile-time variant, the contiguous instantiations are the code above and nothing else): phase 1 first resolves the
-// workgroup's 32 indices once (bg_enc_source_row) into LDS, a barrier, then the 22 pieces of record r come from rows + src[r] * stride -- still
-// consecutive lanes on consecutive 16-byte pieces of a record, so a record of stride 384 is fetched as its three lines.  A record with no source is not
-// read: its LDS image is filled with 0xff (a hand of -1: phase 3's one-hot columns come out 0.0) and phase 2 writes zeros into its tile row, so phase 3
-// is the same code.  index == NULL is the identity (the norm variant without an index).
+// GATHER (bg_encode_rows_ex; a compile-time variant): phase 1 first resolves the workgroup's 32 indices once (bg_enc_source_row) into LDS, a barrier,
+// then the 22 pieces of record r come from rows + src[r] * stride -- still consecutive lanes on consecutive 16-byte pieces of a record, so a record of
+// stride 384 is fetched as its three lines.  A record with no source is not read: its LDS image is filled with 0xff (a hand of -1: phase 3's one-hot
+// columns come out 0.0) and phase 2 writes zeros into its tile row, so phase 3 is the same code.  index == NULL is the identity (statistics without an
+// index).
 #define BG_ENC_BLOCK 256
 #define BG_ENC_RECS 32
 #define BG_ENC_SLICES (BG_ENC_BLOCK / BG_ENC_RECS)
@@ -229,10 +232,31 @@ BG_ENC_FN int64_t bg_enc_source_row(int32_t index, int64_t store_rows) { return 
 #define BG_ENC_ST_ELEM 2
 static_assert(BG_ROW_BYTES % 16 == 0 && BG_ENC_RECS % 8 == 0, "records are staged in 16-byte pieces; a workgroup's dense output starts on a 16-byte boundary");
 static_assert((BG_ENC_REC_PITCH / 4) % 2 == 1 && BG_ENC_REC_PITCH % 4 == 0, "odd word pitch: lane = record reads are conflict-free");
+static_assert(BG_ENC_SLICES == 8, "bg_enc_slices names every slice");
 
 // the dense columns of a layout: [first, first + count) are staged in the tile
 constexpr int bg_enc_dense_first(int layout) { return layout == BG_ENC_EXTRACTOR ? BG_ENC_ONEHOT_COLS : 0; }
 constexpr int bg_enc_dense_cols(int layout) { return layout == BG_ENC_EXTRACTOR ? BG_ENC_EXTRACTOR_COLS - BG_ENC_ONEHOT_COLS : BG_ENC_PRODUCED_COLS; }
+
+// phase 1: the first nrec records of the workgroup into LDS, in 16-byte pieces, by BLOCK lanes.  from(r) is the record of `rows` that fills slot r; a
+// signed source may say -1 (no record: the image is 0xff and nothing is read), an unsigned one never does and the test folds away
+template <int BLOCK, class FROM>
+__device__ __forceinline__ void bg_enc_stage(const uint8_t* __restrict__ rows, uint64_t row_stride, int nrec, uint32_t* recs32, FROM from) {
+  for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BLOCK) {
+    const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
+    const auto at = from(r);
+    const uint4 v = at >= 0 ? *reinterpret_cast<const uint4*>(rows + (size_t)at * row_stride + p * 16) : make_uint4(~0u, ~0u, ~0u, ~0u);
+    uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
+    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+  }
+}
+// phase 1 of the GATHER variants: the workgroup's sources into LDS (one barrier), then the records
+__device__ __forceinline__ void bg_enc_stage_gather(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index, long long store_rows,
+                                                    long long rec0, int nrec, long long* src, uint32_t* recs32) {
+  if ((int)threadIdx.x < nrec) src[threadIdx.x] = index ? bg_enc_source_row(index[rec0 + threadIdx.x], store_rows) : rec0 + threadIdx.x;
+  __syncthreads();
+  bg_enc_stage<BG_ENC_BLOCK>(rows, row_stride, nrec, recs32, [src](int r) { return src[r]; });
+}
 
 template <int LAYOUT, int S>
 __device__ __forceinline__ void bg_enc_convert_slice(const uint8_t* rec, uint32_t* dst) {
@@ -241,6 +265,12 @@ __device__ __forceinline__ void bg_enc_convert_slice(const uint8_t* rec, uint32_
   for (int i = S * CH; i < (S + 1) * CH; i++)
     if (i < N) dst[i] = bg_enc_element<LAYOUT>(rec, BgEncTab<LAYOUT>::t.d[C0 + i]);
 }
+// a converter of phase 2: slice S of record `i` of the call, whose LDS image is `rec`, into its tile row `dst`
+template <int LAYOUT>
+struct BgEncConvert {
+  template <int S>
+  __device__ __forceinline__ void operator()(std::integral_constant<int, S>, const uint8_t* rec, long long, uint32_t* dst) const { bg_enc_convert_slice<LAYOUT, S>(rec, dst); }
+};
 
 // the tile row of a record without a source (GATHER): slice `s` of its N dense columns as +0.0
 template <int N>
@@ -249,68 +279,48 @@ __device__ __forceinline__ void bg_enc_zero_slice(int s, uint32_t* dst) {
   for (int i = s * CH; i < (s + 1) * CH && i < N; i++) dst[i] = 0u;
 }
 
-// phase 1 of the GATHER variants: the workgroup's sources into LDS (one barrier), then the records; -1 = no source, the image is 0xff and nothing is read
-__device__ __forceinline__ void bg_enc_stage_gather(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index, long long store_rows,
-                                                    long long rec0, int nrec, long long* src, uint32_t* recs32) {
-  if ((int)threadIdx.x < nrec) src[threadIdx.x] = index ? bg_enc_source_row(index[rec0 + threadIdx.x], store_rows) : rec0 + threadIdx.x;
-  __syncthreads();
-  for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
-    const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
-    const long long from = src[r];
-    const uint4 v = from >= 0 ? *reinterpret_cast<const uint4*>(rows + (size_t)from * row_stride + p * 16) : make_uint4(~0u, ~0u, ~0u, ~0u);
-    uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
-    w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
+// the lane's slice number -> f(std::integral_constant<int, slice>): what f indexes with it is a compile-time constant
+template <class F>
+__device__ __forceinline__ void bg_enc_slices(F f) {
+  switch (threadIdx.x / BG_ENC_RECS) {
+    case 0: f(std::integral_constant<int, 0>{}); break;
+    case 1: f(std::integral_constant<int, 1>{}); break;
+    case 2: f(std::integral_constant<int, 2>{}); break;
+    case 3: f(std::integral_constant<int, 3>{}); break;
+    case 4: f(std::integral_constant<int, 4>{}); break;
+    case 5: f(std::integral_constant<int, 5>{}); break;
+    case 6: f(std::integral_constant<int, 6>{}); break;
+    default: f(std::integral_constant<int, 7>{}); break;
   }
 }
+// phase 2: the staged records [rec0, rec0 + nrec) of the call -> tile rows of N columns.  src: the workgroup's resolved sources, read only with GATHER
+template <int N, bool GATHER, class CONVERT>
+__device__ __forceinline__ void bg_enc_fill_tile(const uint32_t* recs32, uint32_t* tile, long long rec0, int nrec, const long long* src, CONVERT convert) {
+  const int r = threadIdx.x % BG_ENC_RECS;
+  if (r >= nrec) return;
+  const uint8_t* const rec = reinterpret_cast<const uint8_t*>(recs32) + r * BG_ENC_REC_PITCH;
+  uint32_t* const dst = tile + r * N;
+  if (GATHER && src[r] < 0) bg_enc_zero_slice<N>(threadIdx.x / BG_ENC_RECS, dst);
+  else bg_enc_slices([&](auto s) { convert(s, rec, rec0 + r, dst); });
+}
 
+// whether column c of the layout holds anything: FIXED's never-filled columns are +0.0 and touch neither LDS nor the table
+template <int LAYOUT>
+__device__ __forceinline__ bool bg_enc_filled(int c) { return LAYOUT != BG_ENC_FIXED || c < BG_ENC_PRODUCED_COLS; }
 // one finished element in phase 3 (k-th column `c` of record `r` of the workgroup)
 template <int LAYOUT>
 __device__ __forceinline__ uint32_t bg_enc_fetch(const uint8_t* recs, const uint32_t* tile, int r, int c) {
-  if (LAYOUT == BG_ENC_FIXED && c >= BG_ENC_PRODUCED_COLS) return 0u;
+  if (!bg_enc_filled<LAYOUT>(c)) return 0u;
   if (LAYOUT == BG_ENC_EXTRACTOR && c < BG_ENC_ONEHOT_COLS)   // the table's rule for these columns, without the table: one byte of the record's hand
     return bg_enc_onehot((int8_t)recs[r * BG_ENC_REC_PITCH + BG_ROW_HAND + BG_ENC_ONEHOT_SLOT(c)], BG_ENC_ONEHOT_CARD(c));
   return tile[r * bg_enc_dense_cols(LAYOUT) + c - bg_enc_dense_first(LAYOUT)];
 }
 
-template <int LAYOUT, int DT, int ST, bool GATHER>
-__device__ __forceinline__ void bg_encode_body(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out, uint64_t pitch,
-                                               const int32_t* __restrict__ index, long long store_rows) {
-  __shared__ __attribute__((aligned(16))) uint32_t recs32[BG_ENC_RECS * BG_ENC_REC_PITCH / 4];
-  __shared__ __attribute__((aligned(16))) uint32_t tile[BG_ENC_RECS * bg_enc_dense_cols(LAYOUT)];
-  __shared__ long long src[GATHER ? BG_ENC_RECS : 1];
-  const uint8_t* const recs = reinterpret_cast<const uint8_t*>(recs32);
+// phase 3: rows [rec0, rec0 + nrec) of the caller's matrix from the tile (and, for EXTRACTOR, the records)
+template <int LAYOUT, int DT, int ST>
+__device__ __forceinline__ void bg_enc_store(const uint8_t* recs, const uint32_t* tile, long long rec0, int nrec, void* __restrict__ out, uint64_t pitch) {
   constexpr int D = bg_enc_cols(LAYOUT);
   constexpr int E = ST == BG_ENC_ST_ELEM ? 1 : DT == BG_ENC_F32 ? 4 : 8;   // elements of a 16-byte piece
-  const long long rec0 = (long long)blockIdx.x * BG_ENC_RECS;
-  const int nrec = (int)(m - rec0 < BG_ENC_RECS ? m - rec0 : BG_ENC_RECS);
-  if (GATHER) bg_enc_stage_gather(rows, row_stride, index, store_rows, rec0, nrec, src, recs32);
-  else
-    for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
-      const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
-      const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
-      uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    }
-  __syncthreads();
-  {
-    const int r = threadIdx.x % BG_ENC_RECS;
-    if (r < nrec) {
-      const uint8_t* const rec = recs + r * BG_ENC_REC_PITCH;
-      uint32_t* const dst = tile + r * bg_enc_dense_cols(LAYOUT);
-      if (GATHER && src[r] < 0) bg_enc_zero_slice<bg_enc_dense_cols(LAYOUT)>(threadIdx.x / BG_ENC_RECS, dst);
-      else switch (threadIdx.x / BG_ENC_RECS) {
-        case 0: bg_enc_convert_slice<LAYOUT, 0>(rec, dst); break;
-        case 1: bg_enc_convert_slice<LAYOUT, 1>(rec, dst); break;
-        case 2: bg_enc_convert_slice<LAYOUT, 2>(rec, dst); break;
-        case 3: bg_enc_convert_slice<LAYOUT, 3>(rec, dst); break;
-        case 4: bg_enc_convert_slice<LAYOUT, 4>(rec, dst); break;
-        case 5: bg_enc_convert_slice<LAYOUT, 5>(rec, dst); break;
-        case 6: bg_enc_convert_slice<LAYOUT, 6>(rec, dst); break;
-        default: bg_enc_convert_slice<LAYOUT, 7>(rec, dst); break;
-      }
-    }
-  }
-  __syncthreads();
   constexpr int U = (D + E - 1) / E;   // pieces of a row (BG_ENC_ST_ROWS)
   const int nunits = ST == BG_ENC_ST_ROWS ? nrec * U : (nrec * D + E - 1) / E;
   uint32_t* const o32 = reinterpret_cast<uint32_t*>(out);
@@ -322,7 +332,10 @@ __device__ __forceinline__ void bg_encode_body(const uint8_t* __restrict__ rows,
     else if (ST == BG_ENC_ST_FLAT) { const int e0 = u * E; r = e0 / D; c = e0 - r * D; nvalid = nrec * D - e0 < E ? nrec * D - e0 : E; at = (size_t)rec0 * D + e0; }
     else { r = u / D; c = u - r * D; nvalid = 1; at = (size_t)(rec0 + r) * pitch + c; }
     uint32_t w[E];
-    if (LAYOUT == BG_ENC_FIXED && c >= BG_ENC_PRODUCED_COLS && c + E <= D) {
+    // a piece inside FIXED's zero columns needs no fetch; tested only where a row's run of such pieces is as long as a wave, so that whole waves skip
+    // (float32 pieces and single elements: 118 / 475 per row; bfloat16 pieces are 59, the test would be pure cost)
+    constexpr bool ZERO_RUN = LAYOUT == BG_ENC_FIXED && (D - BG_ENC_PRODUCED_COLS) / E >= 64;
+    if (ZERO_RUN && c >= BG_ENC_PRODUCED_COLS && c + E <= D) {
 #pragma unroll
       for (int k = 0; k < E; k++) w[k] = 0u;
     } else {
@@ -330,7 +343,7 @@ __device__ __forceinline__ void bg_encode_body(const uint8_t* __restrict__ rows,
       for (int k = 0; k < E; k++) {
         int rk = r, ck = c + k;
         if (ST == BG_ENC_ST_FLAT && ck >= D) { ck -= D; rk++; }
-        w[k] = k < nvalid ? bg_enc_fetch<LAYOUT>(recs, tile, rk, ck) : 0u;
+        w[k] = k < nvalid && bg_enc_filled<LAYOUT>(ck) ? bg_enc_fetch<LAYOUT>(recs, tile, rk, ck) : 0u;   // one test in front of the LDS read, not two nested
       }
     }
     if (DT == BG_ENC_F32) {
@@ -349,31 +362,58 @@ __device__ __forceinline__ void bg_encode_body(const uint8_t* __restrict__ rows,
   }
 }
 
+// the three phases for the workgroup's 32 rows of the call; GATHER: row i is record index[i] (NULL: i) of the store_rows records at `rows`
+template <int LAYOUT, int DT, int ST, bool GATHER, class CONVERT>
+__device__ __forceinline__ void bg_enc_body(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out, uint64_t pitch,
+                                            const int32_t* __restrict__ index, long long store_rows, CONVERT convert) {
+  __shared__ __attribute__((aligned(16))) uint32_t recs32[BG_ENC_RECS * BG_ENC_REC_PITCH / 4];
+  __shared__ __attribute__((aligned(16))) uint32_t tile[BG_ENC_RECS * bg_enc_dense_cols(LAYOUT)];
+  __shared__ long long src[GATHER ? BG_ENC_RECS : 1];
+  const long long rec0 = (long long)blockIdx.x * BG_ENC_RECS;
+  const int nrec = (int)(m - rec0 < BG_ENC_RECS ? m - rec0 : BG_ENC_RECS);
+  if (GATHER) bg_enc_stage_gather(rows, row_stride, index, store_rows, rec0, nrec, src, recs32);
+  else bg_enc_stage<BG_ENC_BLOCK>(rows, row_stride, nrec, recs32, [rec0](int r) { return (size_t)(rec0 + r); });
+  __syncthreads();
+  bg_enc_fill_tile<bg_enc_dense_cols(LAYOUT), GATHER>(recs32, tile, rec0, nrec, src, convert);
+  __syncthreads();
+  bg_enc_store<LAYOUT, DT, ST>(reinterpret_cast<const uint8_t*>(recs32), tile, rec0, nrec, out, pitch);
+}
+
 template <int LAYOUT, int DT, int ST>
 __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, void* __restrict__ out,
                                                                  uint64_t pitch) {
-  bg_encode_body<LAYOUT, DT, ST, false>(rows, row_stride, m, out, pitch, nullptr, 0);
+  bg_enc_body<LAYOUT, DT, ST, false>(rows, row_stride, m, out, pitch, nullptr, 0, BgEncConvert<LAYOUT>{});
 }
 // output row i from record index[i] of the store_rows records at `rows` (bg_encode_rows_ex)
 template <int LAYOUT, int DT, int ST>
 __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_encode_gather_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index,
                                                                         long long store_rows, long long m, void* __restrict__ out, uint64_t pitch) {
-  bg_encode_body<LAYOUT, DT, ST, true>(rows, row_stride, m, out, pitch, index, store_rows);
+  bg_enc_body<LAYOUT, DT, ST, true>(rows, row_stride, m, out, pitch, index, store_rows, BgEncConvert<LAYOUT>{});
 }
 
-// host side: the store path `st` is chosen from the alignment of the caller's matrix (bg_encode_rows)
-template <int LAYOUT, int DT>
-static void bg_encode_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, long long m, void* out, uint64_t pitch) {
-  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
-  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
-  else hipLaunchKernelGGL((bg_encode_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, out, pitch);
+// ---- host side ----
+// the store path of a call, from the alignment of the caller's matrix of D columns of es bytes.  A dense [m, 628] float32 matrix has 2 512-byte rows, so
+// it is stored by rows: the <FIXED, f32, FLAT> instantiations exist for the dispatch's sake and are never launched
+static inline int bg_enc_store_path(const void* out_dev, uint64_t out_stride_elems, uint64_t es, int D) {
+  const bool base16 = ((uintptr_t)out_dev & 15) == 0;
+  return base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
 }
-template <int LAYOUT, int DT>
-static void bg_encode_gather_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, const int32_t* index, long long store_rows,
-                                    long long m, void* out, uint64_t pitch) {
-  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_encode_gather_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, out, pitch);
-  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_encode_gather_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, out, pitch);
-  else hipLaunchKernelGGL((bg_encode_gather_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, out, pitch);
+// v, one of A, B and C (C is taken for anything else), as a compile-time constant: f(std::integral_constant<int, v>)
+template <int A, int B, int C, class F>
+static inline void bg_enc_pick(int v, F f) {
+  if (v == A) f(std::integral_constant<int, A>{});
+  else if (v == B) f(std::integral_constant<int, B>{});
+  else f(std::integral_constant<int, C>{});
+}
+// (layout, out_dtype, st) of a checked call -> launch(LAYOUT, DT, ST) as constants, for the kernel family `launch` instantiates.  LAST is the family's
+// last layout: BG_ENC_EXTRACTOR, or BG_ENC_FIXED for the kernels with statistics, which have no EXTRACTOR instantiation
+template <int LAST, class F>
+static inline void bg_enc_dispatch(int layout, int out_dtype, int st, F launch) {
+  bg_enc_pick<BG_ENC_PRODUCED, BG_ENC_FIXED, LAST>(layout, [&](auto L) {
+    bg_enc_pick<BG_ENC_F32, BG_ENC_BF16, BG_ENC_BF16>(out_dtype, [&](auto T) {
+      bg_enc_pick<BG_ENC_ST_ROWS, BG_ENC_ST_FLAT, BG_ENC_ST_ELEM>(st, [&](auto S) { launch(L, T, S); });
+    });
+  });
 }
 #endif  // BG_ENC_HOST
 #endif

@@ -2110,6 +2110,14 @@ int bg_classify_batch(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t* h
 // packed records -> network input (bg_encode.h).  The store path follows the alignment of the caller's matrix.
 int bg_encode_cols(int layout) { const int d = bg_enc_cols(layout); return d > 0 ? d : BG_E_ARG; }
 
+// the output matrix of bg_encode_rows, bg_encode_rows_ex and bg_norm_obs_rows: D columns of es bytes.  optional: NULL asks for no matrix (bg_norm_obs_rows)
+static const char* bg_enc_out_args(const void* out_dev, uint64_t out_stride_elems, uint64_t es, int D, bool optional) {
+  if (optional && !out_dev) return nullptr;
+  if (!out_dev || ((uintptr_t)out_dev & (es - 1))) return optional ? "out_dev must be aligned to its element type" : "out_dev must be a device pointer aligned to its element type";
+  if (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull) return "out_stride_elems must be >= the layout's column count";
+  return nullptr;
+}
+
 int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m, int layout, int out_dtype, void* out_dev,
                    uint64_t out_stride_elems, float* kernel_ms_out, void* stream) {
   const int D = bg_enc_cols(layout);
@@ -2119,22 +2127,19 @@ int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m
   else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
   else if (m < 0 || m > (int64_t)BG_ENC_RECS * 0x7fffffffll) bad = "m out of range";
   else if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) bad = r;
-  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
-  else if (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= the layout's column count";
+  else if (const char* r = bg_enc_out_args(out_dev, out_stride_elems, es, D, false)) bad = r;
   if (bad) { g_create_err = std::string("bg_encode_rows: ") + bad; return BG_E_ARG; }
   if (kernel_ms_out) *kernel_ms_out = 0.f;
   if (m == 0) return 0;
-  const bool base16 = ((uintptr_t)out_dev & 15) == 0;
-  const int st = base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
+  const int st = bg_enc_store_path(out_dev, out_stride_elems, es, D);
   const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
   hipStream_t s = (hipStream_t)stream;
   BgOpTimer tm;
   int rc = tm.begin(kernel_ms_out, s);
   if (rc) return rc;
-#define BG_ENC_GO(L, T) bg_encode_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, (long long)m, out_dev, out_stride_elems)
-  if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_F32); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_F32); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_F32); }
-  else { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_BF16); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_BF16); }
-#undef BG_ENC_GO
+  bg_enc_dispatch<BG_ENC_EXTRACTOR>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
+    hipLaunchKernelGGL((bg_encode_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, (long long)m, out_dev, out_stride_elems);
+  });
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);
@@ -2223,8 +2228,7 @@ int bg_norm_obs_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, 
   else if ((uint64_t)K * (uint64_t)N > (uint64_t)BG_ENC_RECS * 0x7fffffffull) bad = "K * N out of range";
   else if (!mean_dev || !var_dev || !count_dev || (((uintptr_t)mean_dev | (uintptr_t)var_dev | (uintptr_t)count_dev | (uintptr_t)moments_dev) & 7)) bad = "mean_dev, var_dev and count_dev must be 8-byte aligned device pointers (moments_dev 8-byte aligned)";
   else if (mean_dev == var_dev || mean_dev == count_dev || var_dev == count_dev) bad = "mean_dev, var_dev and count_dev must not be the same pointer";
-  else if (out_dev && ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be aligned to its element type";
-  else if (out_dev && (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull)) bad = "out_stride_elems must be >= the layout's column count";
+  else if (const char* r = bg_enc_out_args(out_dev, out_stride_elems, es, D, true)) bad = r;
   else if (!update && moments_dev) bad = "moments_dev must be NULL when update == 0 (no batch moments are taken)";
   else if (!update && !out_dev) bad = "update == 0 with out_dev NULL asks for nothing";
   else if (!(epsilon == epsilon) || !(clip_obs == clip_obs)) bad = "epsilon and clip_obs must not be NaN";
@@ -2250,14 +2254,12 @@ int bg_norm_obs_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, 
     hipLaunchKernelGGL((bg_norm_obs_chain<false>), dim3(1), dim3(BG_NORM_PBLOCK), 0, s, mom, K, (double)N, epsilon, mean_dev, var_dev, count_dev, stat);
   if (out_dev) {
     const long long m = (long long)K * (long long)N;
-    const bool base16 = ((uintptr_t)out_dev & 15) == 0;
-    const int st = base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
+    const int st = bg_enc_store_path(out_dev, out_stride_elems, es, D);
     const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
     const size_t sstride = update ? 2 * BG_NORM_COLS : 0;
-#define BG_NORM_GO(L, T) bg_norm_obs_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, m, (long long)N, stat, sstride, clip_obs, out_dev, out_stride_elems)
-    if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_F32); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_F32); }
-    else { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_BF16); }
-#undef BG_NORM_GO
+    bg_enc_dispatch<BG_ENC_FIXED>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
+      hipLaunchKernelGGL((bg_norm_obs_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, m, (long long)N, stat, sstride, clip_obs, out_dev, out_stride_elems);
+    });
   }
   tm.mark(s);
   BG_HIP0(hipGetLastError());
@@ -2287,31 +2289,26 @@ int bg_encode_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_
   else if (norm && (((uintptr_t)mean_dev | (uintptr_t)var_dev) & 7)) bad = "mean_dev and var_dev must be 8-byte aligned";
   else if (norm && mean_dev == var_dev) bad = "mean_dev and var_dev must not be the same pointer";
   else if (norm && !(epsilon >= 0.0 && epsilon <= 1.7976931348623157e308 && clip_obs >= 0.0 && clip_obs <= 1.7976931348623157e308)) bad = "epsilon and clip_obs must be finite and >= 0 when statistics are given";
-  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
-  else if (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= the layout's column count";
+  else if (const char* r = bg_enc_out_args(out_dev, out_stride_elems, es, D, false)) bad = r;
   else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev) bad = "out_dev must not be the same pointer as an input";
   if (bad) { g_create_err = std::string("bg_encode_rows_ex: ") + bad; return BG_E_ARG; }
   if (!index_dev && !norm) return bg_encode_rows(rows_dev, row_stride_bytes, m, layout, out_dtype, out_dev, out_stride_elems, kernel_ms_out, stream);
   if (kernel_ms_out) *kernel_ms_out = 0.f;
   if (m == 0) return 0;
-  const bool base16 = ((uintptr_t)out_dev & 15) == 0;
-  const int st = base16 && (out_stride_elems * es) % 16 == 0 ? BG_ENC_ST_ROWS : base16 && out_stride_elems == (uint64_t)D ? BG_ENC_ST_FLAT : BG_ENC_ST_ELEM;
+  const int st = bg_enc_store_path(out_dev, out_stride_elems, es, D);
   const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
   hipStream_t s = (hipStream_t)stream;
   BgOpTimer tm;
   int rc = tm.begin(kernel_ms_out, s);
   if (rc) return rc;
-  if (norm) {
-#define BG_NORM_GO(L, T) bg_norm_obs_gather_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, out_dev, out_stride_elems)
-    if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_F32); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_F32); }
-    else { if (layout == BG_ENC_PRODUCED) BG_NORM_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else BG_NORM_GO(BG_ENC_FIXED, BG_ENC_BF16); }
-#undef BG_NORM_GO
-  } else {
-#define BG_ENC_GO(L, T) bg_encode_gather_launch<L, T>(st, grid, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, out_dev, out_stride_elems)
-    if (out_dtype == BG_ENC_F32) { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_F32); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_F32); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_F32); }
-    else { if (layout == BG_ENC_PRODUCED) BG_ENC_GO(BG_ENC_PRODUCED, BG_ENC_BF16); else if (layout == BG_ENC_FIXED) BG_ENC_GO(BG_ENC_FIXED, BG_ENC_BF16); else BG_ENC_GO(BG_ENC_EXTRACTOR, BG_ENC_BF16); }
-#undef BG_ENC_GO
-  }
+  if (norm)
+    bg_enc_dispatch<BG_ENC_FIXED>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
+      hipLaunchKernelGGL((bg_norm_obs_gather_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, out_dev, out_stride_elems);
+    });
+  else
+    bg_enc_dispatch<BG_ENC_EXTRACTOR>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
+      hipLaunchKernelGGL((bg_encode_gather_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, out_dev, out_stride_elems);
+    });
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);

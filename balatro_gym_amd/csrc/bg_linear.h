@@ -2,9 +2,9 @@
 //
 // The layer's input is the row bg_encode_rows_ex writes as bfloat16 ("produced" / "fixed", with or without frozen statistics).  Of its 628 columns
 // only the first 153 can be non-zero, so the product runs over 153 columns padded to 160 = ten k-steps of the matrix cores' 32x32x16 bfloat16
-// instruction; the feature matrix never exists in HBM.  Phases 1-2 of bg_encode_kernel / bg_norm_obs_gather_kernel (bg_encode.h, bg_norm.h) are
-// called as they are: records -> LDS -> a float32 tile of finished column values for 32 records; the tile is rounded to bfloat16 (bg_enc_bf16, the
-// rounding of bg_encode_rows_ex) into the operand image the matrix cores read.
+// instruction; the feature matrix never exists in HBM.  Phases 1-2 of the records-to-tile pipeline (bg_encode.h: bg_enc_stage_gather, bg_enc_fill_tile
+// with the converter of bg_encode_gather_kernel / bg_norm_obs_gather_kernel) give a float32 tile of finished column values for 32 records; the tile is
+// rounded to bfloat16 (bg_enc_bf16, the rounding of bg_encode_rows_ex) into the operand image the matrix cores read.
 //
 // The index arithmetic of the fragments is plain C++ behind BG_LIN_FN, so tests/test_linear_rows_host.py compiles it with g++ (define BG_LIN_HOST
 // before including) and drives it through a scalar model of the instruction.
@@ -97,32 +97,8 @@ __device__ __forceinline__ void bg_lin_tile32(const uint8_t* __restrict__ rows, 
   if (nrec <= 0) return;
   bg_enc_stage_gather(rows, row_stride, index, store_rows, rec0, nrec, src, recs32);
   __syncthreads();
-  const int r = threadIdx.x % BG_ENC_RECS;
-  if (r < nrec) {
-    const uint8_t* const rec = reinterpret_cast<const uint8_t*>(recs32) + r * BG_ENC_REC_PITCH;
-    uint32_t* const dst = tile + r * BG_LIN_K;
-    if (src[r] < 0) bg_enc_zero_slice<BG_LIN_K>(threadIdx.x / BG_ENC_RECS, dst);
-    else if (NORM) switch (threadIdx.x / BG_ENC_RECS) {
-      case 0: bg_norm_convert_slice<0, true>(rec, mean, denom, clip, dst); break;
-      case 1: bg_norm_convert_slice<1, true>(rec, mean, denom, clip, dst); break;
-      case 2: bg_norm_convert_slice<2, true>(rec, mean, denom, clip, dst); break;
-      case 3: bg_norm_convert_slice<3, true>(rec, mean, denom, clip, dst); break;
-      case 4: bg_norm_convert_slice<4, true>(rec, mean, denom, clip, dst); break;
-      case 5: bg_norm_convert_slice<5, true>(rec, mean, denom, clip, dst); break;
-      case 6: bg_norm_convert_slice<6, true>(rec, mean, denom, clip, dst); break;
-      default: bg_norm_convert_slice<7, true>(rec, mean, denom, clip, dst); break;
-    }
-    else switch (threadIdx.x / BG_ENC_RECS) {
-      case 0: bg_enc_convert_slice<BG_ENC_PRODUCED, 0>(rec, dst); break;
-      case 1: bg_enc_convert_slice<BG_ENC_PRODUCED, 1>(rec, dst); break;
-      case 2: bg_enc_convert_slice<BG_ENC_PRODUCED, 2>(rec, dst); break;
-      case 3: bg_enc_convert_slice<BG_ENC_PRODUCED, 3>(rec, dst); break;
-      case 4: bg_enc_convert_slice<BG_ENC_PRODUCED, 4>(rec, dst); break;
-      case 5: bg_enc_convert_slice<BG_ENC_PRODUCED, 5>(rec, dst); break;
-      case 6: bg_enc_convert_slice<BG_ENC_PRODUCED, 6>(rec, dst); break;
-      default: bg_enc_convert_slice<BG_ENC_PRODUCED, 7>(rec, dst); break;
-    }
-  }
+  if (NORM) bg_enc_fill_tile<BG_LIN_K, true>(recs32, tile, rec0, nrec, src, BgNormConvert<true>{mean, 0, 1, denom, clip});
+  else bg_enc_fill_tile<BG_LIN_K, true>(recs32, tile, rec0, nrec, src, BgEncConvert<BG_ENC_PRODUCED>{});
   __syncthreads();
 }
 

@@ -113,14 +113,14 @@ BG_NORM_FN double bg_norm_ret_done(double ret, bool done) { return done ? 0.0 : 
 // ---- the kernels ----
 // Observation call, update != 0, four launches on the caller's stream:
 //   1  bg_norm_obs_partials   grid K * ceil(N / 256): a workgroup of 192 lanes takes 256 consecutive envs of one step in 8 tiles of 32 records, each
-//      read from HBM once, 16 bytes per lane, into LDS (bg_encode_rows' phase 1: whole-line reads).  Lane = column (153 of 192): it decodes its
+//      read from HBM once, 16 bytes per lane, into LDS (bg_enc_stage: whole-line reads).  Lane = column (153 of 192): it decodes its
 //      column of the tile's records into registers, takes the tile's moments (bg_norm_tile) and merges them, tile after tile, into its triple;
 //      one division per column and tile, not per element.  The triple (mean, M2; n follows from the chunk index) goes to the workspace.
 //   2  bg_norm_obs_combine    grid K, lane = column: the chunks of a step merged left to right -> batch mean / batch variance of the step.
 //   3  bg_norm_obs_chain      one workgroup, lane = column: the K RunningMeanStd updates in order; per step the mean and sqrt(var + epsilon) the rows of
 //      that step are normalised with go to the workspace (a sqrt per column and step instead of per element), the final statistics to the caller.
-//   4  bg_norm_obs_kernel     bg_encode_kernel's three phases with float64 arithmetic in phase 2: (x - mean) / denom, clip, convert, into the float32
-//      tile; the stores are bg_encode_rows' (16-byte pieces where the caller's matrix allows).
+//   4  bg_norm_obs_kernel     the records-to-tile pipeline of bg_encode.h with BgNormConvert in phase 2: (x - mean) / denom, clip, convert, in float64,
+//      into the float32 tile.
 // update == 0: a one-step launch of 3 that only takes the square roots of the frozen statistics, then 4.
 // Every order of merging is fixed by indices alone: no atomics, nothing depends on scheduling.
 #define BG_NORM_PBLOCK 192
@@ -141,12 +141,7 @@ __global__ __launch_bounds__(BG_NORM_PBLOCK) void bg_norm_obs_partials(const uin
     const int nrec = nenv - r0 < BG_NORM_TILE ? nenv - r0 : BG_NORM_TILE;
     const size_t rec0 = (size_t)t * (size_t)N + (size_t)(e0 + r0);
     if (r0) __syncthreads();
-    for (int q = threadIdx.x; q < nrec * BG_ENC_CHUNKS; q += BG_NORM_PBLOCK) {
-      const int r = q / BG_ENC_CHUNKS, p = q - r * BG_ENC_CHUNKS;
-      const uint4 v = *reinterpret_cast<const uint4*>(rows + (rec0 + r) * row_stride + p * 16);
-      uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    }
+    bg_enc_stage<BG_NORM_PBLOCK>(rows, row_stride, nrec, recs32, [rec0](int r) { return rec0 + r; });
     __syncthreads();
     if (c < BG_NORM_COLS) {
       double v[BG_NORM_TILE];
@@ -214,118 +209,41 @@ __device__ __forceinline__ void bg_norm_convert_slice(const uint8_t* rec, const 
     if (i < BG_NORM_COLS) dst[i] = bg_norm_obs_bits(bg_norm_value64(rec, BgEncTab<BG_ENC_PRODUCED>::t.d[i]), st[i], SPLIT ? dn[i] : st[BG_NORM_COLS + i], clip);
 }
 
-// LAYOUT BG_ENC_PRODUCED | BG_ENC_FIXED; DT / ST as bg_encode_kernel.  Record i of the call belongs to step i / N; stat_step_stride is 0 for frozen statistics.
-// GATHER (bg_encode_rows_ex with statistics; bg_encode_kernel's compile-time variant, the contiguous instantiations are untouched by it): the call has
-// no workspace, so `stat` is the caller's 153 means and `var` its 153 variances: lane c < 153 takes sqrt(var[c] + epsilon) -- the expression and the
-// bits of bg_norm_obs_chain<false> -- into LDS once per workgroup (1 224 bytes: still five workgroups per CU); phase 1 is bg_enc_stage_gather and a
-// record without a source becomes a row of +0.0, not of normalised zeros.
-template <int LAYOUT, int DT, int ST, bool GATHER>
-__device__ __forceinline__ void bg_norm_obs_body(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, long long N, const double* __restrict__ stat,
-                                                 size_t stat_step_stride, double clip, void* __restrict__ out, uint64_t pitch, const int32_t* __restrict__ index,
-                                                 long long store_rows, const double* __restrict__ var, double epsilon) {
-  __shared__ __attribute__((aligned(16))) uint32_t recs32[BG_ENC_RECS * BG_ENC_REC_PITCH / 4];
-  __shared__ __attribute__((aligned(16))) uint32_t tile[BG_ENC_RECS * BG_NORM_COLS];
-  __shared__ long long src[GATHER ? BG_ENC_RECS : 1];
-  __shared__ double denom[GATHER ? BG_NORM_COLS : 1];
-  const uint8_t* const recs = reinterpret_cast<const uint8_t*>(recs32);
-  constexpr int D = bg_enc_cols(LAYOUT);
-  constexpr int E = ST == BG_ENC_ST_ELEM ? 1 : DT == BG_ENC_F32 ? 4 : 8;
-  const long long rec0 = (long long)blockIdx.x * BG_ENC_RECS;
-  const int nrec = (int)(m - rec0 < BG_ENC_RECS ? m - rec0 : BG_ENC_RECS);
-  if (GATHER) {
-    if (threadIdx.x < BG_NORM_COLS) denom[threadIdx.x] = bg_norm_denom(var[threadIdx.x], epsilon);
-    bg_enc_stage_gather(rows, row_stride, index, store_rows, rec0, nrec, src, recs32);
-  } else
-    for (int c = threadIdx.x; c < nrec * BG_ENC_CHUNKS; c += BG_ENC_BLOCK) {
-      const int r = c / BG_ENC_CHUNKS, p = c - r * BG_ENC_CHUNKS;
-      const uint4 v = *reinterpret_cast<const uint4*>(rows + (size_t)(rec0 + r) * row_stride + p * 16);
-      uint32_t* const w = recs32 + r * (BG_ENC_REC_PITCH / 4) + p * 4;
-      w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w;
-    }
-  __syncthreads();
-  {
-    const int r = threadIdx.x % BG_ENC_RECS;
-    if (r < nrec) {
-      const uint8_t* const rec = recs + r * BG_ENC_REC_PITCH;
-      uint32_t* const dst = tile + r * BG_NORM_COLS;
-      const double* const st = stat + (size_t)((rec0 + r) / N) * stat_step_stride;
-      const double* const dn = GATHER ? denom : nullptr;
-      if (GATHER && src[r] < 0) bg_enc_zero_slice<BG_NORM_COLS>(threadIdx.x / BG_ENC_RECS, dst);
-      else switch (threadIdx.x / BG_ENC_RECS) {
-        case 0: bg_norm_convert_slice<0, GATHER>(rec, st, dn, clip, dst); break;
-        case 1: bg_norm_convert_slice<1, GATHER>(rec, st, dn, clip, dst); break;
-        case 2: bg_norm_convert_slice<2, GATHER>(rec, st, dn, clip, dst); break;
-        case 3: bg_norm_convert_slice<3, GATHER>(rec, st, dn, clip, dst); break;
-        case 4: bg_norm_convert_slice<4, GATHER>(rec, st, dn, clip, dst); break;
-        case 5: bg_norm_convert_slice<5, GATHER>(rec, st, dn, clip, dst); break;
-        case 6: bg_norm_convert_slice<6, GATHER>(rec, st, dn, clip, dst); break;
-        default: bg_norm_convert_slice<7, GATHER>(rec, st, dn, clip, dst); break;
-      }
-    }
+// the converter of phase 2 (bg_encode.h) with statistics.  Record i of the call belongs to step i / N: it is normalised with stat + (i / N) * step_stride
+// (step_stride 0: frozen statistics, one set for every record)
+template <bool SPLIT>
+struct BgNormConvert {
+  const double* stat;
+  size_t step_stride;
+  long long N;
+  const double* dn;
+  double clip;
+  template <int S>
+  __device__ __forceinline__ void operator()(std::integral_constant<int, S>, const uint8_t* rec, long long i, uint32_t* dst) const {
+    bg_norm_convert_slice<S, SPLIT>(rec, stat + (size_t)(i / N) * step_stride, dn, clip, dst);
   }
-  __syncthreads();
-  constexpr int U = (D + E - 1) / E;
-  const int nunits = ST == BG_ENC_ST_ROWS ? nrec * U : (nrec * D + E - 1) / E;
-  uint32_t* const o32 = reinterpret_cast<uint32_t*>(out);
-  uint16_t* const o16 = reinterpret_cast<uint16_t*>(out);
-  for (int u = threadIdx.x; u < nunits; u += BG_ENC_BLOCK) {
-    int r, c, nvalid;
-    size_t at;
-    if (ST == BG_ENC_ST_ROWS) { r = u / U; c = (u - r * U) * E; nvalid = D - c < E ? D - c : E; at = (size_t)(rec0 + r) * pitch + c; }
-    else if (ST == BG_ENC_ST_FLAT) { const int e0 = u * E; r = e0 / D; c = e0 - r * D; nvalid = nrec * D - e0 < E ? nrec * D - e0 : E; at = (size_t)rec0 * D + e0; }
-    else { r = u / D; c = u - r * D; nvalid = 1; at = (size_t)(rec0 + r) * pitch + c; }
-    uint32_t w[E];
-#pragma unroll
-    for (int k = 0; k < E; k++) {
-      int rk = r, ck = c + k;
-      if (ST == BG_ENC_ST_FLAT && ck >= D) { ck -= D; rk++; }
-      w[k] = k < nvalid && ck < BG_NORM_COLS ? tile[rk * BG_NORM_COLS + ck] : 0u;   // FIXED's never-filled columns: (0 - 0) / sqrt(var + epsilon) = 0.0
-    }
-    if (DT == BG_ENC_F32) {
-      if (E == 4 && nvalid == E) *reinterpret_cast<uint4*>(o32 + at) = make_uint4(w[0], w[E > 1 ? 1 : 0], w[E > 2 ? 2 : 0], w[E > 3 ? 3 : 0]);
-      else
-        for (int k = 0; k < nvalid; k++) o32[at + k] = w[k];
-    } else {
-      if (E == 8 && nvalid == E) {
-        uint32_t p[4];
-#pragma unroll
-        for (int k = 0; k < 4; k++) p[k] = (uint32_t)bg_enc_bf16(w[E > 1 ? 2 * k : 0]) | (uint32_t)bg_enc_bf16(w[E > 1 ? 2 * k + 1 : 0]) << 16;
-        *reinterpret_cast<uint4*>(o16 + at) = make_uint4(p[0], p[1], p[2], p[3]);
-      } else
-        for (int k = 0; k < nvalid; k++) o16[at + k] = bg_enc_bf16(w[k]);
-    }
-  }
-}
+};
 
+// LAYOUT BG_ENC_PRODUCED | BG_ENC_FIXED; DT / ST as bg_encode_kernel; FIXED's never-filled columns are (0 - 0) / sqrt(var + epsilon) = +0.0, which is
+// what bg_enc_store writes for them.
 template <int LAYOUT, int DT, int ST>
 __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, long long m, long long N,
                                                                    const double* __restrict__ stat, size_t stat_step_stride, double clip, void* __restrict__ out,
                                                                    uint64_t pitch) {
-  bg_norm_obs_body<LAYOUT, DT, ST, false>(rows, row_stride, m, N, stat, stat_step_stride, clip, out, pitch, nullptr, 0, nullptr, 0.0);
+  bg_enc_body<LAYOUT, DT, ST, false>(rows, row_stride, m, out, pitch, nullptr, 0, BgNormConvert<false>{stat, stat_step_stride, N, nullptr, clip});
 }
-// output row i from record index[i] (NULL: record i), normalised with the frozen statistics mean / var (bg_encode_rows_ex)
+// output row i from record index[i] (NULL: record i), normalised with the frozen statistics mean / var (bg_encode_rows_ex).  The call has no workspace,
+// so lane c < 153 takes sqrt(var[c] + epsilon) -- the expression and the bits of bg_norm_obs_chain<false> -- into LDS once per workgroup (1 224 bytes:
+// still five workgroups per CU; bg_enc_stage_gather's barrier is in front of its use).  A record without a source becomes a row of +0.0, not of
+// normalised zeros.
 template <int LAYOUT, int DT, int ST>
 __global__ __launch_bounds__(BG_ENC_BLOCK) void bg_norm_obs_gather_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index,
                                                                           long long store_rows, long long m, const double* __restrict__ mean,
                                                                           const double* __restrict__ var, double epsilon, double clip, void* __restrict__ out,
                                                                           uint64_t pitch) {
-  bg_norm_obs_body<LAYOUT, DT, ST, true>(rows, row_stride, m, 1, mean, 0, clip, out, pitch, index, store_rows, var, epsilon);
-}
-
-template <int LAYOUT, int DT>
-static void bg_norm_obs_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, long long m, long long N, const double* stat,
-                               size_t stat_step_stride, double clip, void* out, uint64_t pitch) {
-  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_norm_obs_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, N, stat, stat_step_stride, clip, out, pitch);
-  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_norm_obs_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, N, stat, stat_step_stride, clip, out, pitch);
-  else hipLaunchKernelGGL((bg_norm_obs_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, m, N, stat, stat_step_stride, clip, out, pitch);
-}
-
-template <int LAYOUT, int DT>
-static void bg_norm_obs_gather_launch(int st, unsigned grid, hipStream_t s, const uint8_t* rows, uint64_t stride, const int32_t* index, long long store_rows,
-                                      long long m, const double* mean, const double* var, double epsilon, double clip, void* out, uint64_t pitch) {
-  if (st == BG_ENC_ST_ROWS) hipLaunchKernelGGL((bg_norm_obs_gather_kernel<LAYOUT, DT, BG_ENC_ST_ROWS>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, mean, var, epsilon, clip, out, pitch);
-  else if (st == BG_ENC_ST_FLAT) hipLaunchKernelGGL((bg_norm_obs_gather_kernel<LAYOUT, DT, BG_ENC_ST_FLAT>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, mean, var, epsilon, clip, out, pitch);
-  else hipLaunchKernelGGL((bg_norm_obs_gather_kernel<LAYOUT, DT, BG_ENC_ST_ELEM>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows, stride, index, store_rows, m, mean, var, epsilon, clip, out, pitch);
+  __shared__ double denom[BG_NORM_COLS];
+  if (threadIdx.x < BG_NORM_COLS) denom[threadIdx.x] = bg_norm_denom(var[threadIdx.x], epsilon);
+  bg_enc_body<LAYOUT, DT, ST, true>(rows, row_stride, m, out, pitch, index, store_rows, BgNormConvert<true>{mean, 0, 1, denom, clip});
 }
 
 // Reward call, update != 0, four launches:

@@ -309,7 +309,7 @@ def test_update_0_and_frozen_state():
 
 
 def test_strides_null_outputs_and_bad_arguments():
-    """6: out_stride_elems > cols keeps the poison in the extra columns (16-byte rows, odd rows, one element per lane); out_dev / rewards_dev NULL update the
+    """6: out_stride_elems > cols keeps the poison in the extra columns (16-byte rows, odd rows, one element per lane), == cols is the dense matrix; out_dev / rewards_dev NULL update the
     statistics only; every bad argument returns BG_E_ARG with a message and writes nothing."""
     torch = _torch()
     from balatro_gym_amd import _native as nat
@@ -323,7 +323,9 @@ def test_strides_null_outputs_and_bad_arguments():
     want = ref.from_moments(rows_host, {"obs": mo, "ret": mr}, s0, **KW)
     full = d.state_bits()
     for layout, dtype, pitch in (("produced", "float32", 156), ("produced", "float32", 155), ("produced", "bfloat16", 160), ("produced", "bfloat16", 157),
-                                 ("fixed", "float32", 633), ("fixed", "bfloat16", 632)):
+                                 ("fixed", "float32", 633), ("fixed", "bfloat16", 632),
+                                 # dense: rows that are not 16-byte aligned run across row ends; [m, 628] float32 has 2 512-byte rows, so it is stored by rows
+                                 ("produced", "bfloat16", 153), ("fixed", "float32", 628), ("fixed", "bfloat16", 628)):
         d.load(s0)
         wide, _, ok = d.obs(rows, layout, dtype, pitch=pitch)
         D = ref.COLS if layout == "produced" else ref.FIXED_COLS
