@@ -65,7 +65,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_gae_rows_ex", "bg_norm_workspace_bytes", "bg_norm_obs_rows", "bg_norm_reward_rows",
            "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex",
            "bg_step_many_rows_ex", "bg_safe_terminal_slots",
-           "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad"]
+           "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad",
+           "bg_get_states", "bg_set_states", "bg_copy_states"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -240,6 +241,9 @@ def load(build_if_missing: bool = True):
     L.bg_state_blob_bytes.argtypes = [vp]
     L.bg_get_state.argtypes = [vp, i32, vp, u64]
     L.bg_set_state.argtypes = [vp, i32, vp, u64]
+    L.bg_get_states.argtypes = [vp, vp, i32, vp, u64, vp]
+    L.bg_set_states.argtypes = [vp, vp, i32, vp, u64, i32, vp, vp]
+    L.bg_copy_states.argtypes = [vp, vp, vp, vp, i32, vp]
     L.bg_refill.argtypes = [vp, vp]
     L.bg_check.argtypes = [vp, vp]
     L.bg_set_profiling.argtypes = [vp, i32]

@@ -362,6 +362,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
 #include "bg_ppo.h"    // logits + stored rollout arrays -> PPO's clipped loss, its diagnostics and its gradient (operator-level)
 #include "bg_linear.h" // packed records -> the network's first layer and its weight gradient on the matrix cores (operator-level)
+#include "bg_snapshot.h" // many envs' state between a handle's arrays and dense blobs, or two handles (bg_get_states / bg_set_states / bg_copy_states)
 
 // DeterministicRNG(seed) (balatro_env_2.py:84-106) for streams 0 ('deck_shuffle') and 2 ('shop_generation'), plus the
 // per-env global stream seeded G(seed).  Streams are seeded `(master + 1000 * i) % 2**32` (:105).
@@ -748,6 +749,10 @@ struct bg_handle {
   int e3_cfg, e3_epw;
   // sharded jobs (bg_set_gather_peers): every rank's gather buffer as mapped into THIS process, the size of the job and this handle's rank
   uint8_t* gpeer[8]; uint8_t** d_gpeer; int gworld, grank;   // d_gpeer: the same eight pointers in device memory (what the kernel reads)
+  // bg_get_states / bg_set_states / bg_copy_states: the index lists of a call (src then dst, pinned on the host and their copy on the device, grown on
+  // demand; ev_snap = the upload of the previous call's, which must be over before the pinned copy is written again) and bg_set_states' read-back
+  int32_t* snap_idx_host = nullptr; int32_t* snap_idx_dev = nullptr; size_t snap_idx_cap = 0; hipEvent_t ev_snap = nullptr;
+  uint4* snap_meta_dev = nullptr; size_t snap_meta_cap = 0; std::vector<uint4> snap_meta_host;
 };
 
 static std::string g_create_err;
@@ -1028,6 +1033,9 @@ int bg_destroy(bg_handle* h) {
   for (hipEvent_t e : h->ev_pool) (void)hipEventDestroy(e);
   for (auto* v : {&h->ev_rollout_t, &h->ev_refill_t, &h->ev_step_t}) for (hipEvent_t e : *v) (void)hipEventDestroy(e);
   hipFree(h->d_prod[0]); hipFree(h->d_prod[1]);
+  if (h->ev_snap) (void)hipEventDestroy(h->ev_snap);
+  if (h->snap_idx_host) (void)hipHostFree(h->snap_idx_host);
+  hipFree(h->snap_idx_dev); hipFree(h->snap_meta_dev);
   hipFree(d.hot); hipFree(d.deck); hipFree(d.cold); hipFree(d.tmpl); hipFree(d.ndeck); hipFree(d.gblk); hipFree(d.sblk); hipFree(d.sovf);
   hipFree(d.deckmt); hipFree(d.shopgenmt); hipFree(d.err); hipFree(h->d_seeds); hipFree(h->d_mask); hipFree(d.wl_count); hipFree(d.wl); hipFree(d.wl_shop); hipFree(d.sseed); hipFree(d.smeta); hipFree(d.dbg); hipFree(h->d_jtab); hipFree(h->d_gpeer); hipFree(d.cstate); hipFree(d.ctmpl); hipFree(d.cardmt); hipFree(d.sealmt);
   }
@@ -1942,6 +1950,225 @@ int bg_set_state(bg_handle* h, int env_index, const void* blob_host, uint64_t bl
   }
   h->seeded = true;
   h->steps_since_refill = 1 << 30; // the restored env's look-ahead is as deep as it was when the blob was taken: top up before the next step
+  return 0;
+}
+
+// ---- many envs at once, the blobs on the device (bg_snapshot.h): one launch per call ----
+static int bg_snap_dev_table(bg_handle* h, const char* fn, BgSnapTable& t, int* prod_slice) {
+  std::vector<BgSlice> v;
+  bg_slices(h, v);
+  if (v.size() > BG_SNAP_MAX_SLICES) { h->err = std::string(fn) + ": more slices than BG_SNAP_MAX_SLICES"; return BG_E_INTERNAL; }
+  t.n = (int)v.size();
+  *prod_slice = -1;
+  for (int j = 0; j < t.n; j++) {
+    t.s[j].base = (uint8_t*)v[j].base; t.s[j].env_stride = v[j].env_stride; t.s[j].row_stride = v[j].row_stride; t.s[j].elem = (uint32_t)v[j].elem; t.s[j].rows = (uint32_t)v[j].rows;
+    if (v[j].base == (void*)bg_prod_latest(h)) *prod_slice = j;
+  }
+  return 0;
+}
+static int bg_snap_blob_args(bg_handle* h, const char* fn, const void* blobs, uint64_t stride) {
+  char buf[200];
+  if (!blobs) { h->err = std::string(fn) + ": null blobs_dev"; return BG_E_ARG; }
+  if ((uintptr_t)blobs & 15) { h->err = std::string(fn) + ": blobs_dev must be 16-byte aligned"; return BG_E_ARG; }
+  const uint64_t want = bg_state_blob_bytes(h);
+  if ((stride & 15) || stride < want) {
+    snprintf(buf, sizeof(buf), "%s: blob_stride_bytes %llu must be a multiple of 16 and at least this handle's blob size, %llu bytes", fn, (unsigned long long)stride, (unsigned long long)want);
+    h->err = buf; return BG_E_ARG;
+  }
+  return 0;
+}
+// bg_snap_check_indices' verdict as text (err = the handle that reports)
+static int bg_snap_index_args(bg_handle* err, const char* fn, const int32_t* src, int64_t n_src, const char* src_name, const int32_t* dst, int64_t n_dst, const char* dst_name,
+                              int m, bool need_src, bool need_dst, bool distinct_dst, bool same) {
+  std::vector<uint8_t> seen(distinct_dst && m > 0 ? (size_t)n_dst : 0);
+  int pair = -1;
+  const int code = bg_snap_check_indices(src, n_src, dst, n_dst, m, need_src, need_dst, distinct_dst, same, seen.data(), &pair);
+  if (code == BG_SNAP_OK) return 0;
+  char buf[240];
+  const long long sv = pair >= 0 ? (src ? src[pair] : pair) : 0, dv = pair >= 0 ? (dst ? dst[pair] : pair) : 0;
+  switch (code) {
+    case BG_SNAP_E_M: snprintf(buf, sizeof(buf), "%s: m = %d is negative", fn, m); break;
+    case BG_SNAP_E_NULL: snprintf(buf, sizeof(buf), "%s: null index list", fn); break;
+    case BG_SNAP_E_SRC_RANGE: snprintf(buf, sizeof(buf), "%s: %s[%d] = %lld out of range [0, %lld)", fn, src_name, pair, sv, (long long)n_src); break;
+    case BG_SNAP_E_DST_RANGE: snprintf(buf, sizeof(buf), "%s: %s[%d] = %lld out of range [0, %lld)", fn, dst_name, pair, dv, (long long)n_dst); break;
+    case BG_SNAP_E_DST_TWICE: snprintf(buf, sizeof(buf), "%s: %s[%d] = %lld is listed twice (every env may be written once)", fn, dst_name, pair, dv); break;
+    default: snprintf(buf, sizeof(buf), "%s: env %lld (%s[%d]) is written by another pair of the same call (dst / src overlap)", fn, sv, src_name, pair); break;
+  }
+  err->err = buf;
+  return BG_E_ARG;
+}
+// The index lists of a call onto the device, queued on s: a -> *a_dev, b -> *b_dev (a null list stays null).  The pinned copy is written again only
+// when the previous call's upload is over (an event: that upload sits in front of its kernel, so it is long done in a loop of calls).
+static int bg_snap_upload(bg_handle* h, const int32_t* a, const int32_t* b, int m, hipStream_t s, const int32_t** a_dev, const int32_t** b_dev) {
+  *a_dev = *b_dev = nullptr;
+  if (!a && !b) return 0;
+  if (!h->ev_snap) BG_HIP(hipEventCreateWithFlags(&h->ev_snap, hipEventDisableTiming));
+  else BG_HIP(hipEventSynchronize(h->ev_snap));
+  if ((size_t)2 * (size_t)m > h->snap_idx_cap) {
+    size_t cap = 2048;
+    while (cap < (size_t)2 * (size_t)m) cap *= 2;
+    if (h->snap_idx_host) { BG_HIP(hipHostFree(h->snap_idx_host)); h->snap_idx_host = nullptr; }
+    if (h->snap_idx_dev) { BG_HIP(hipFree(h->snap_idx_dev)); h->snap_idx_dev = nullptr; }   // (hipFree waits for the kernels that read it)
+    h->snap_idx_cap = 0;
+    BG_HIP(hipHostMalloc((void**)&h->snap_idx_host, cap * sizeof(int32_t), hipHostMallocDefault));
+    BG_HIP(hipMalloc((void**)&h->snap_idx_dev, cap * sizeof(int32_t)));
+    h->snap_idx_cap = cap;
+  }
+  if (a) { memcpy(h->snap_idx_host, a, (size_t)m * sizeof(int32_t)); *a_dev = h->snap_idx_dev; }
+  if (b) { memcpy(h->snap_idx_host + m, b, (size_t)m * sizeof(int32_t)); *b_dev = h->snap_idx_dev + m; }
+  int32_t* const from = a ? h->snap_idx_host : h->snap_idx_host + m;
+  int32_t* const to = a ? h->snap_idx_dev : h->snap_idx_dev + m;
+  BG_HIP(hipMemcpyAsync(to, from, (size_t)(a && b ? 2 : 1) * (size_t)m * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  BG_HIP(hipEventRecord(h->ev_snap, s));
+  return 0;
+}
+static uint4 bg_blob_header(const bg_handle* h) {
+  return make_uint4(BG_BLOB_MAGIC, BG_BLOB_VERSION, (uint32_t)h->dev.KG | (h->dev.cstate ? 0x10000u : 0u), (uint32_t)h->dev.KS | ((uint32_t)h->dev.KD << 16));
+}
+// err: the handle that reports (the kernel runs on its device)
+static int bg_snap_launch(bg_handle* err, const char* fn, BgSnapArgs& a, int m, hipStream_t s) {
+  bg_handle* h = err;
+  const int pc = bg_snap_plan(a.src, a.dst, a.plan);
+  if (pc) { h->err = std::string(fn) + ": the two sides' slices do not match (internal)"; return BG_E_INTERNAL; }
+  a.tiles = (a.plan.units + 1u + BG_SNAP_TILE - 1u) / BG_SNAP_TILE;   // (+ 1: the header's unit)
+  if ((uint64_t)a.tiles * (uint64_t)m > 0x7fffffffull) { h->err = std::string(fn) + ": too many envs for one launch"; return BG_E_ARG; }
+  hipLaunchKernelGGL(bg_snapshot_kernel, dim3(a.tiles * (uint32_t)m), dim3(BG_SNAP_BLOCK), 0, s, a);
+  BG_HIP(hipGetLastError());
+  return 0;
+}
+
+int bg_get_states(bg_handle* h, const int32_t* env_index_host, int m, void* blobs_dev, uint64_t blob_stride_bytes, void* stream) {
+  if (!h) return BG_E_ARG;
+  static const char* fn = "bg_get_states";
+  int rc = bg_snap_index_args(h, fn, env_index_host, h->dev.N, "env_index", nullptr, m, "blob", m, false, false, false, false);
+  if (rc) return rc;
+  rc = bg_snap_blob_args(h, fn, blobs_dev, blob_stride_bytes);
+  if (rc || m == 0) return rc;
+  BG_GUARD(h);
+  hipStream_t s = (hipStream_t)stream;
+  BgSnapArgs a;
+  memset(&a, 0, sizeof(a));
+  rc = bg_snap_dev_table(h, fn, a.src, &a.prod_slice);
+  if (rc) return rc;
+  a.dst = bg_snap_blob_table(a.src, blobs_dev, blob_stride_bytes);
+  a.prod_slice = -1; a.prod_other = nullptr;
+  a.hdr_base = (uint8_t*)blobs_dev; a.hdr_stride = blob_stride_bytes; a.hdr = bg_blob_header(h);
+  // the pending pieces of a sliced refill fill ring slots the producer word already counts (bg_get_state): issued now, and the copy waits for them
+  rc = bg_wait_refill(h, s, 0);
+  if (rc) return rc;
+  rc = bg_snap_upload(h, env_index_host, nullptr, m, s, &a.src_idx, &a.dst_idx);
+  if (rc) return rc;
+  return bg_snap_launch(h, fn, a, m, s);
+}
+
+int bg_set_states(bg_handle* h, const int32_t* env_index_host, int m, const void* blobs_dev, uint64_t blob_stride_bytes, int n_blobs,
+                  const int32_t* blob_index_host, void* stream) {
+  if (!h) return BG_E_ARG;
+  static const char* fn = "bg_set_states";
+  if (m > 0 && n_blobs < (blob_index_host ? 1 : m)) { h->err = std::string(fn) + (blob_index_host ? ": n_blobs must be positive" : ": fewer blobs than envs (n_blobs < m) and no blob_index"); return BG_E_ARG; }
+  int rc = bg_snap_index_args(h, fn, blob_index_host, n_blobs, "blob_index", env_index_host, h->dev.N, "env_index", m, false, true, true, false);
+  if (rc) return rc;
+  rc = bg_snap_blob_args(h, fn, blobs_dev, blob_stride_bytes);
+  if (rc || m == 0) return rc;
+  BG_GUARD(h);
+  hipStream_t s = (hipStream_t)stream;
+  BgSnapArgs a;
+  memset(&a, 0, sizeof(a));
+  rc = bg_snap_dev_table(h, fn, a.dst, &a.prod_slice);
+  if (rc) return rc;
+  a.src = bg_snap_blob_table(a.dst, const_cast<void*>(blobs_dev), blob_stride_bytes);
+  rc = bg_snap_upload(h, blob_index_host, env_index_host, m, s, &a.src_idx, &a.dst_idx);
+  if (rc) return rc;
+  // every pair's header + the words the host mirrors need, in one read-back (this is where the call waits for the stream)
+  if ((size_t)m > h->snap_meta_cap) {
+    if (h->snap_meta_dev) { BG_HIP(hipFree(h->snap_meta_dev)); h->snap_meta_dev = nullptr; h->snap_meta_cap = 0; }
+    size_t cap = 1024;
+    while (cap < (size_t)m) cap *= 2;
+    BG_HIP(hipMalloc((void**)&h->snap_meta_dev, cap * 4 * sizeof(uint4)));
+    h->snap_meta_cap = cap;
+  }
+  const size_t N = (size_t)h->dev.N;
+  const uint32_t hot_off = (uint32_t)(a.src.s[0].base - (const uint8_t*)blobs_dev), tmpl_off = (uint32_t)(a.src.s[3].base - (const uint8_t*)blobs_dev);   // slices 0 and 3 (bg_slices)
+  hipLaunchKernelGGL(bg_snapshot_meta_kernel, dim3((m + 15) / 16), dim3(64), 0, s, (const uint8_t*)blobs_dev, blob_stride_bytes, a.src_idx, m, hot_off + 7u * 16u, tmpl_off,
+                     h->snap_meta_dev);
+  BG_HIP(hipGetLastError());
+  h->snap_meta_host.resize((size_t)m * 4);
+  BG_HIP(hipMemcpyAsync(h->snap_meta_host.data(), h->snap_meta_dev, (size_t)m * 4 * sizeof(uint4), hipMemcpyDeviceToHost, s));
+  BG_HIP(hipStreamSynchronize(s));
+  const uint4 want = bg_blob_header(h);
+  char buf[240];
+  for (int i = 0; i < m; i++) {
+    const uint4 hd = h->snap_meta_host[(size_t)i * 4];
+    const int bi = blob_index_host ? blob_index_host[i] : i;
+    if (hd.x != BG_BLOB_MAGIC) { snprintf(buf, sizeof(buf), "%s: blob %d is not a state blob (bad magic)", fn, bi); h->err = buf; return BG_E_ARG; }
+    if (hd.y != BG_BLOB_VERSION) { snprintf(buf, sizeof(buf), "%s: blob %d has version %u, this library reads version %u", fn, bi, hd.y, BG_BLOB_VERSION); h->err = buf; return BG_E_ARG; }
+    if (hd.z != want.z || hd.w != want.w) {
+      snprintf(buf, sizeof(buf), "%s: blob %d was saved with ring depths %u/%u/%u%s, this handle has %d/%d/%d%s", fn, bi, hd.z & 0xffffu, hd.w & 0xffffu, hd.w >> 16,
+               (hd.z & 0x10000u) ? " + card states" : "", h->dev.KG, h->dev.KS, h->dev.KD, h->dev.cstate ? " + card states" : "");
+      h->err = buf; return BG_E_ARG;
+    }
+  }
+  // pending refill pieces hold work items of the state that is about to be replaced: they write their ring slots BEFORE the blobs land (bg_set_state)
+  rc = bg_wait_refill(h, s, 0);
+  if (rc) return rc;
+  a.prod_other = h->d_prod[0] == bg_prod_latest(h) ? h->d_prod[1] : h->d_prod[0];
+  rc = bg_snap_launch(h, fn, a, m, s);
+  if (rc) return rc;
+  for (int i = 0; i < m; i++) {   // the host mirrors follow (bg_set_state)
+    const size_t e = (size_t)env_index_host[i];
+    const uint4* mt = &h->snap_meta_host[(size_t)i * 4];
+    h->h_cap[e] = (uint8_t)((mt[1].w >> 16) & 0xffu);
+    for (int r = 0; r < BG_NTMPL; r++) h->h_tmpl[bg_tmpl_at(N, e, r)] = mt[2 + r];
+  }
+  h->seeded = true;
+  h->steps_since_refill = 1 << 30;   // the restored envs' look-ahead is as deep as it was when the blobs were taken: top up before the next step
+  return 0;
+}
+
+int bg_copy_states(bg_handle* dst, const int32_t* dst_index_host, bg_handle* src, const int32_t* src_index_host, int m, void* stream) {
+  if (!dst) return BG_E_ARG;
+  bg_handle* h = dst;   // the handle that reports
+  static const char* fn = "bg_copy_states";
+  if (!src) { h->err = std::string(fn) + ": null source handle"; return BG_E_ARG; }
+  if (src->device_id != dst->device_id) { h->err = std::string(fn) + ": the two handles are on different devices (peer copies are out of scope)"; return BG_E_ARG; }
+  if (src->dev.KG != dst->dev.KG || src->dev.KS != dst->dev.KS || src->dev.KD != dst->dev.KD || (src->dev.cstate != nullptr) != (dst->dev.cstate != nullptr)) {
+    char buf[240];
+    snprintf(buf, sizeof(buf), "%s: the source handle has ring depths %d/%d/%d%s, the destination %d/%d/%d%s", fn, src->dev.KG, src->dev.KS, src->dev.KD,
+             src->dev.cstate ? " + card states" : "", dst->dev.KG, dst->dev.KS, dst->dev.KD, dst->dev.cstate ? " + card states" : "");
+    h->err = buf; return BG_E_ARG;
+  }
+  int rc = bg_snap_index_args(h, fn, src_index_host, src->dev.N, "src_index", dst_index_host, dst->dev.N, "dst_index", m, true, true, true, src == dst);
+  if (rc || m == 0) return rc;
+  BG_GUARD(h);
+  hipStream_t s = (hipStream_t)stream;
+  BgSnapArgs a;
+  memset(&a, 0, sizeof(a));
+  int src_prod = -1;
+  rc = bg_snap_dev_table(src, fn, a.src, &src_prod);
+  if (rc) { h->err = src->err; return rc; }
+  rc = bg_snap_dev_table(dst, fn, a.dst, &a.prod_slice);
+  if (rc) return rc;
+  // both handles' latest refills must have run: the source's fills slots its producer words already count, the destination's must not write on
+  // top of what lands (its work items belong to the state that is replaced)
+  rc = bg_wait_refill(src, s, 0);
+  if (rc) { h->err = src->err; return rc; }
+  if (src != dst) { rc = bg_wait_refill(dst, s, 0); if (rc) return rc; }
+  rc = bg_snap_upload(h, src_index_host, dst_index_host, m, s, &a.src_idx, &a.dst_idx);
+  if (rc) return rc;
+  a.prod_other = dst->d_prod[0] == bg_prod_latest(dst) ? dst->d_prod[1] : dst->d_prod[0];
+  rc = bg_snap_launch(h, fn, a, m, s);
+  if (rc) return rc;
+  const size_t Ns = (size_t)src->dev.N, Nd = (size_t)dst->dev.N;
+  for (int i = 0; i < m; i++) {   // mirror to mirror (on one handle no dst is another pair's src: the order does not matter)
+    const size_t se = (size_t)src_index_host[i], de = (size_t)dst_index_host[i];
+    dst->h_cap[de] = src->h_cap[se];
+    for (int r = 0; r < BG_NTMPL; r++) dst->h_tmpl[bg_tmpl_at(Nd, de, r)] = src->h_tmpl[bg_tmpl_at(Ns, se, r)];
+  }
+  if (src != dst) {
+    if (src->seeded) dst->seeded = true;
+    dst->steps_since_refill = 1 << 30;   // the copies' rings are as deep as the SOURCE handle's schedule left them: top up before the next step
+  }
+  // (one handle: a copy's consumer and producer counters are its source's, so every bound the refill schedule holds for the source holds for the copy)
   return 0;
 }
 

@@ -621,11 +621,90 @@ class BalatroVecEnv:
         buf = (C.c_uint8 * len(blob)).from_buffer_copy(blob)
         self._check(self._L.bg_set_state(self._h, int(env_index), buf, len(blob)), "bg_set_state")
 
+    # ------------------------------------------------------------------ many envs at once: checkpoint, restore, fork (bg_snapshot.h)
+    @property
+    def state_blob_stride(self) -> int:
+        """Bytes per row of `get_states()`: the blob size (bg_state_blob_bytes) rounded up to 16."""
+        return (int(self._L.bg_state_blob_bytes(self._h)) + 15) & ~15
+
+    @staticmethod
+    def _host_indices(idx, what: str) -> np.ndarray:
+        """An index list (sequence, range, numpy array or tensor -- a device tensor is brought to the host) as contiguous int32."""
+        if isinstance(idx, torch.Tensor):
+            idx = idx.detach().to("cpu").numpy()
+        a = np.asarray(idx if isinstance(idx, np.ndarray) else list(idx))
+        if a.ndim != 1 or (a.size and a.dtype.kind not in "iu"):
+            raise ValueError(f"{what} must be a one-dimensional list of integers")
+        if a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31):
+            raise ValueError(f"{what} must fit int32")
+        return np.ascontiguousarray(a.astype(np.int32))
+
+    def _blob_matrix(self, t: torch.Tensor, what: str) -> torch.Tensor:
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != 2 or t.device != self.device or not t.is_contiguous():
+            raise ValueError(f"{what} must be a contiguous uint8 [blobs, stride] tensor on {self.device}")
+        return t
+
+    def get_states(self, env_indices=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The state blobs of many envs (all when env_indices is None; repeats are allowed) as uint8 [m, stride] on this env's device, in one
+        kernel launch (bg_get_states): row i is byte for byte `get_state(env_indices[i])`, then padding up to the stride, which is never written.
+        `out`: a contiguous uint8 [>= m, stride] tensor on this device, stride a multiple of 16 and at least the blob size.  `torch.save` the
+        result beside `RowNormalizer.state_dict()` to checkpoint a job; the caller's EpisodeLimits / EpisodeStats / RowNormalizer carries are
+        not part of a blob.  `parse_state_blob` reads a row."""
+        idx = None if env_indices is None else self._host_indices(env_indices, "env_indices")
+        m = self.num_envs if idx is None else int(idx.size)
+        if out is None:
+            out = torch.empty((m, self.state_blob_stride), dtype=torch.uint8, device=self.device)
+            out[:, int(self._L.bg_state_blob_bytes(self._h)):].zero_()   # (the kernel never writes the padding: a saved checkpoint is the same bytes every time)
+        else:
+            self._blob_matrix(out, "out")
+            if out.shape[0] < m:
+                raise ValueError(f"out holds {out.shape[0]} blobs, {m} are asked for")
+        if m:
+            self._check(self._L.bg_get_states(self._h, None if idx is None else idx.ctypes.data_as(C.c_void_p), m, C.c_void_p(out.data_ptr()),
+                                              C.c_uint64(out.shape[1]), self._stream()), "bg_get_states")
+        return out[:m]
+
+    def set_states(self, env_indices, blobs: torch.Tensor, blob_index=None, observe: bool = True):
+        """Restore many envs in one launch (bg_set_states): env env_indices[i] becomes blob blob_index[i] (row i when blob_index is None) of
+        `blobs`, a uint8 [n, stride] tensor on this device as `get_states` returns it.  One blob may go to many envs; env_indices must be distinct.
+        observe=True refreshes the live observation (`obs` / `obs_rows`) afterwards, as `inject(apply_now=True)` does."""
+        idx = self._host_indices(env_indices, "env_indices")
+        bidx = None if blob_index is None else self._host_indices(blob_index, "blob_index")
+        if bidx is not None and bidx.size != idx.size:
+            raise ValueError("blob_index must name one blob per env index")
+        self._blob_matrix(blobs, "blobs")
+        self._check(self._L.bg_set_states(self._h, idx.ctypes.data_as(C.c_void_p), int(idx.size), C.c_void_p(blobs.data_ptr()), C.c_uint64(blobs.shape[1]),
+                                          int(blobs.shape[0]), None if bidx is None else bidx.ctypes.data_as(C.c_void_p), self._stream()), "bg_set_states")
+        if observe and idx.size:
+            self.observe()
+
+    def copy_states(self, dst_indices, src_indices, source: Optional["BalatroVecEnv"] = None, observe: bool = True):
+        """Env src_indices[i] of `source` (this env when None) -> env dst_indices[i] of this env, on the device and with no blob in between
+        (bg_copy_states): the call a search loop makes every step.  `source` must be on the same device with the same ring depths and card-state
+        flag; dst_indices must be distinct and, on one env, no dst may be the src of another pair."""
+        src = self if source is None else source
+        d, s = self._host_indices(dst_indices, "dst_indices"), self._host_indices(src_indices, "src_indices")
+        if d.size != s.size:
+            raise ValueError("dst_indices and src_indices must have the same length")
+        self._check(self._L.bg_copy_states(self._h, d.ctypes.data_as(C.c_void_p), src._h, s.ctypes.data_as(C.c_void_p), int(d.size), self._stream()),
+                    "bg_copy_states")
+        if observe and d.size:
+            self.observe()
+
+    def fork(self, src_env: int, dst_indices, observe: bool = True):
+        """Env `src_env` into every env of dst_indices (`copy_states` with one repeated source): 60 copies stepped with the 60 actions are an
+        exact one-step look-ahead."""
+        d = self._host_indices(dst_indices, "dst_indices")
+        self.copy_states(d, np.full(d.size, int(src_env), np.int32), observe=observe)
+
     @staticmethod
     def parse_state_blob(blob: bytes) -> Dict[str, object]:
         """Named views of a state blob (bg_get_state): what save_state() (balatro_env_2.py:1575-1593) leaves out -- the RNG streams --
         is in here, so tests can look at a full shuffled deck, the pre-shuffled decks, the raw global-stream blocks and the shop seeds."""
-        b = np.frombuffer(blob, np.uint8)
+        padded = not isinstance(blob, (bytes, bytearray))   # a row of `get_states` (a uint8 tensor or array) carries padding behind the blob
+        if isinstance(blob, torch.Tensor):
+            blob = blob.detach().to("cpu").numpy()
+        b = np.ascontiguousarray(blob, np.uint8).reshape(-1) if padded else np.frombuffer(blob, np.uint8)
         hdr = b[:16].view(np.uint32)
         kg, cards, ks, kd = int(hdr[2] & 0xffff), bool(hdr[2] & 0x10000), int(hdr[3] & 0xffff), int(hdr[3] >> 16)
         out: Dict[str, object] = {"magic": int(hdr[0]), "version": int(hdr[1]), "KG": kg, "KS": ks, "KD": kd, "card_states": cards}
@@ -654,7 +733,7 @@ class BalatroVecEnv:
             take("card_template", nat.BLOB_NCST * 16, np.uint16)
             take("card_stream", nat.BLOB_MTS * 4, np.uint32)
             take("seal_stream", nat.BLOB_MTS * 4, np.uint32)
-        if off != len(b):
+        if off != len(b) and not (padded and off < len(b)):   # (a row of get_states: the blob, then padding up to the stride)
             raise ValueError(f"state blob of {len(b)} bytes does not parse ({off} bytes understood)")
         out["deck"] = out["deck"][:52]
         out["ring_decks"] = out["ring_decks"][:, :52]

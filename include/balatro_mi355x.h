@@ -368,6 +368,37 @@ uint64_t bg_state_blob_bytes(const bg_handle* h);
 int bg_get_state(bg_handle* h, int env_index, void* blob_host, uint64_t blob_bytes);
 int bg_set_state(bg_handle* h, int env_index, const void* blob_host, uint64_t blob_bytes);
 
+/* The same for MANY envs at once, the blobs staying on the device: one kernel launch (csrc/bg_snapshot.h) moves every slice of all m envs, 16 bytes
+ * per lane wherever the piece allows.  Replaces: a loop of save_state() / load_state() over the envs of a SubprocVecEnv -- a checkpoint of the whole job
+ * beside the normaliser's, or the N envs as branches of a search (fork one env into 60 and step each with another action: an exact one-step look-ahead).
+ * The caller's EpisodeLimits / EpisodeStats / RowNormalizer carries are not part of a blob.
+ *
+ * Blobs: blob i starts at blobs_dev + i * blob_stride_bytes; blobs_dev is 16-byte aligned, the stride a multiple of 16 and at least
+ * bg_state_blob_bytes(h); the bytes of a slot beyond the blob size are never written.  Index lists are int32 on the HOST and are copied before the
+ * call returns.  All three are queued on `stream` like a step: they issue the pending pieces of a sliced refill and make `stream` wait for the handle's
+ * latest refill with an EVENT (no device synchronisation); work of the handles that the caller put on OTHER streams is the caller's to order.
+ *
+ * bg_get_states: blob i = byte for byte what bg_get_state(h, env_index[i], ...) returns at that point of the stream, header included
+ *   (env_index_host NULL = envs 0..m-1; repeated indices are allowed).  Does not wait for the host.
+ * bg_set_states: env env_index[i] ends up exactly as bg_set_state(h, env_index[i], blob blob_index[i]) leaves it (blob_index_host NULL = blob i): the
+ *   device state, both producer-counter buffers, the host mirrors of the reset template and the curriculum cap, and the handle counts as seeded.  One
+ *   blob may go to many envs; env_index must be distinct.  The headers of all referenced blobs (magic, version, ring depths, card-state flag) are
+ *   checked before anything is written: they are read back, with the template and cap words the mirrors need (64 bytes per pair, one copy), which
+ *   SYNCHRONISES `stream` with the host.  The rings are topped up before the next step (as after bg_set_state).
+ * bg_copy_states: env src_index[i] of `src` -> env dst_index[i] of `dst`, no blob in between.  dst == src (one handle) is allowed, and so is another
+ *   handle on the same device with the same ring depths (KG / KS / KD) and card-state flag.  dst_index must be distinct; on one handle no dst may be the
+ *   src of another pair, and a pair with dst == src moves nothing.  The host mirrors are copied mirror to mirror: no read-back, the call does not wait for
+ *   the device -- the one a search loop calls every step.  Across handles the rings of `dst` are topped up before its next step; inside one handle
+ *   the handle's own refill schedule already covers the copies (a dst's rings are exactly as deep as its src's: DESIGN.md section 3, "Many envs at once").
+ *
+ * BG_E_ARG, text "bg_get_states: ..." / "bg_set_states: ..." / "bg_copy_states: ..." in bg_last_error(h) (of `dst` for a copy), nothing written: an index
+ * out of range, a repeated dst, dst / src overlap, m < 0, a null pointer, a misaligned base, a stride too small or no multiple of 16, a blob_index outside
+ * [0, n_blobs), a bad header, handles on different devices or of different depths.  m == 0 is a no-op. */
+int bg_get_states(bg_handle* h, const int32_t* env_index_host /*[m] or NULL = 0..m-1*/, int m, void* blobs_dev, uint64_t blob_stride_bytes, void* stream);
+int bg_set_states(bg_handle* h, const int32_t* env_index_host /*[m]*/, int m, const void* blobs_dev, uint64_t blob_stride_bytes, int n_blobs,
+                  const int32_t* blob_index_host /*[m] or NULL = i*/, void* stream);
+int bg_copy_states(bg_handle* dst, const int32_t* dst_index_host, bg_handle* src, const int32_t* src_index_host, int m, void* stream);
+
 /* Top up the RNG look-ahead rings (pre-shuffled decks, pre-seeded shop streams, global-stream blocks).  bg_step /
  * bg_reset / bg_rollout call it themselves; exposed for tests and for overlapping it on a side stream. */
 int bg_refill(bg_handle* h, void* stream);
