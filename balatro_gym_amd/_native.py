@@ -43,9 +43,19 @@ ROW_OFFSETS = {
     "phase": 339, "boss_blind_active": 340, "boss_blind_type": 341,
 }
 # (end_flags: byte BG_ROW_END_FLAGS, written by bg_step_many_rows_ex with limits -- its BG_END_* bits are below -- and 0 on every other path)
-ROW_EXTRA = {"reward": (136, "float64"), "action": (172, "int32"), "terminated": (342, "uint8"), "end_flags": (343, "uint8")}
+# (end_ante / end_round / end_chips: the ended episode's final state.ante, state.round and min(chips_scored, 2**32 - 1), in the records of ended steps
+#  of bg_step_many_rows_ex with limits on a handle whose episode summary is on -- bg_set_episode_summary -- and 0 everywhere else)
+ROW_EXTRA = {"reward": (136, "float64"), "action": (172, "int32"), "terminated": (342, "uint8"), "end_flags": (343, "uint8"),
+             "end_ante": (344, "int16"), "end_round": (346, "int8"), "end_chips": (348, "uint32")}
 ROW_END_FLAGS = ROW_EXTRA["end_flags"][0]
+ROW_END_ANTE, ROW_END_ROUND, ROW_END_CHIPS = ROW_EXTRA["end_ante"][0], ROW_EXTRA["end_round"][0], ROW_EXTRA["end_chips"][0]
 END_GAME, END_INVALID, END_MAX_STEPS = 1, 2, 4
+# bg_episode_ends_rows: the words of its report (csrc/bg_ends.h BG_ENDS_W_*; the histogram of end antes is words 16 + min(ante, 15))
+ENDS_WORDS = 32
+ENDS_REPORT = {"ended": 0, "game": 1, "invalid": 2, "max_steps": 3, "ante_sum": 4, "ante_max": 5, "chips_sum": 6, "chips_max": 7, "raised": 8,
+               "no_summary": 9}
+ENDS_HIST = 16
+CURRICULUM_CAP_MAX = 255
 SAFE_MIN_LIMIT = 3
 INFO_KEYS = ["final_score", "error", "flags", "aux", "hand_type", "cards_played", "reward_terms", "score_breakdown"]
 INFO_SPEC = {"final_score": ("int64", ()), "error": ("int32", ()), "flags": ("int32", ()), "aux": ("int32", ()),
@@ -66,7 +76,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex",
            "bg_step_many_rows_ex", "bg_safe_terminal_slots",
            "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad",
-           "bg_get_states", "bg_set_states", "bg_copy_states"]
+           "bg_get_states", "bg_set_states", "bg_copy_states",
+           "bg_set_episode_summary", "bg_episode_ends_rows"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -132,6 +143,12 @@ class SafeLimits(C.Structure):
     _fields_ = [("max_invalid_actions", C.c_int32), ("max_episode_steps", C.c_int32), ("counters_dev", C.c_void_p),
                 ("terminal_rows_dev", C.c_void_p), ("terminal_stride_bytes", C.c_uint64), ("terminal_step_dev", C.c_void_p),
                 ("terminal_slots", C.c_int32)]
+
+
+class Curriculum(C.Structure):
+    """bg_curriculum (include/balatro_mi355x.h)."""
+    _fields_ = [("cap_dev", C.c_void_p), ("hist_dev", C.c_void_p), ("count_dev", C.c_void_p), ("at_level_dev", C.c_void_p),
+                ("raised_dev", C.c_void_p), ("window", C.c_int32), ("increment", C.c_int32), ("threshold", C.c_double)]
 
 
 class NativeError(RuntimeError):
@@ -233,6 +250,8 @@ def load(build_if_missing: bool = True):
     L.bg_step_many_rows.argtypes = [vp, i32, vp, vp, u64, i32, vp, vp]
     L.bg_step_many_rows_ex.argtypes = [vp, i32, vp, vp, u64, i32, C.POINTER(SafeLimits), vp, vp]
     L.bg_safe_terminal_slots.argtypes = [i32, i32, i32]
+    L.bg_set_episode_summary.argtypes = [vp, i32]
+    L.bg_episode_ends_rows.argtypes = [vp, u64, i32, i64, vp, C.POINTER(Curriculum), C.POINTER(C.c_float), vp]
     L.bg_set_gather_peers.argtypes = [vp, vp, i32, i32]
     L.bg_inject.argtypes = [vp, vp, vp, vp, vp, vp, vp, i32, vp]
     L.bg_inject_cards.argtypes = [vp, vp, vp, vp, vp, i32, vp]

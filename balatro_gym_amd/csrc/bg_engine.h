@@ -53,6 +53,7 @@ struct SafeArgs {
   int32_t* term_step;          // int32 [slots, N]
   uint32_t term_stride, slots;
   int32_t max_invalid, max_steps;
+  uint32_t summary;            // != 0: the records of ended steps carry the ended episode's summary (bg_set_episode_summary)
 };
 static_assert(sizeof(SafeArgs) <= sizeof(InfoPtrs), "SafeArgs rides in the bytes of EngineArgs::info");
 struct EngineArgs {

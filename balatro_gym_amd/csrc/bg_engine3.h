@@ -85,7 +85,12 @@ struct E3Lds {
 //     wave skips guards and dispatch, resets the env exactly as a game over does (ring deck, templates, the LDS deck hand-over through s_ndst), and
 //     writes the new episode's mask and observation into the image around the step's reward, action and ending bytes, which it read there first.
 //     The owner waits for the answer like for any other (`waiting`, s_ans, the same BG_SPIN_LIMIT bounds), then counts the step and lists the record;
-//   * such a step counts TWO requests in s_ans (mod 2**16; a launch fuses far fewer than 2**15 steps).
+//   * such a step counts TWO requests in s_ans (mod 2**16; a launch fuses far fewer than 2**15 steps);
+//   * the episode summary (a.safe.summary, bg_set_episode_summary; a wave-uniform branch, no instantiation of its own): every ending passes through a
+//     service wave's reset block -- the reset-only requests included -- where `e` still holds the final state; its ante, round and chips_scored go
+//     into words 86 / 87 of the image (BG_ROW_END_ANTE / _ROUND / _CHIPS) behind the observation writer, which leaves zeros there.  The owner's cheap
+//     steps patch the image, so each clears the two words: only the record of the ended step carries them, and a terminal record (written before the
+//     reset) has zeros.
 template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT = false, bool SAFE = false>
 // (Round 5 measured reading the arguments THROUGH the kernarg segment pointer instead of as by-value parameters -- whose 16-register blocks the compiler
 //  spills to VGPR lanes and reloads whole, 12 % of the kernel's instructions being v_readlane / v_writelane / s_nop: SGPR spills 237 -> 61, 14 454 -> 13 114
@@ -332,6 +337,8 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
             *(__attribute__((address_space(3))) double*)&img32[34] = reward;  // BG_ROW_REWARD
             img32[43] = (uint32_t)action;                                      // BG_ROW_ACTION
             img8[BG_ROW_TERMINATED] = 0;
+            // (a cheap step PATCHES the image: directly behind an ending it would carry that episode's summary along)
+            if constexpr (SAFE) if (a.safe.summary) *(lds_u64*)&img32[BG_ROW_END_ANTE / 4] = 0ull;
           }
         }
         // ---- SAFE: the wrapper's rule on the finished record (bg_safe.h); the answer of a reset-only request is a record the rule has already seen
@@ -584,7 +591,14 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           if (e.max_ante > 0 && e.ante > e.max_ante) { o.terminated = true; o.flags |= 256; }
           }
           if (o.terminated) n_eps++;
+          // SAFE with the episode summary: every ending -- game over, curriculum cap, the reset-only request of a wrapper ending -- comes through
+          // here with the FINAL state still in `e`: ante | round << 16 and min(chips_scored, 2**32 - 1), for words 86 / 87 of the image (BG_ROW_END_*)
+          uint32_t sum_ar = 0u, sum_chips = 0u;
           if (o.terminated && a.autoreset) {
+            if constexpr (SAFE) if (a.safe.summary) {
+              sum_ar = ((uint32_t)e.ante & 0xffffu) | (((uint32_t)e.round & 0xffu) << 16);
+              sum_chips = e.chips_scored < 0 ? 0u : (e.chips_scored > 0xffffffffll ? 0xffffffffu : (uint32_t)e.chips_scored);
+            }
             const bool have = bg_lds_ld(&s_ndst[l]) == 1u;
             bg_env_reset(d, env, e, dk, nullptr, have ? (lds_cu4*)&s_nd[0][l] : (lds_cu4*)nullptr, NE);
             // the slot after it, if the ring (as this launch may see it) holds one: the env's owner fetches it
@@ -599,6 +613,8 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           const ObsPtrs none{};
           bg_write_obs_impl<false, 3>(d, env, 0, e, dk, none, mask, sr, RowExtra{o.reward, action, o.terminated ? 1u : 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
           if constexpr (SAFE) if (ronly) ((lds_u8*)&s_img[l][0])[BG_ROW_END_FLAGS] = (uint8_t)endb;
+          // (the writer has left zeros in words 86 / 87; a step that ended nothing keeps them)
+          if constexpr (SAFE) if (sum_ar) *(lds_u64*)&((lds_u32*)&s_img[l][0])[BG_ROW_END_ANTE / 4] = (uint64_t)sum_ar | ((uint64_t)sum_chips << 32);
           BG_PROBE(26);
           bg_pack(e, c);
 #pragma unroll

@@ -358,6 +358,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_sim.h" // balatro_sim.py evaluator / scorer (operator-level)
 #include "bg_encode.h" // packed records -> policy-network input (operator-level)
 #include "bg_gae.h"    // packed records -> advantages / returns and episode statistics (operator-level)
+#include "bg_ends.h"   // packed records -> the report of a rollout's ended episodes and the curriculum's cap updates (operator-level)
 #include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
 #include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
 #include "bg_ppo.h"    // logits + stored rollout arrays -> PPO's clipped loss, its diagnostics and its gradient (operator-level)
@@ -725,6 +726,7 @@ struct bg_handle {
   std::string err;
   // optional per-kernel timing with HIP events on the launch stream (bench.py roofline leg)
   bool profiling;
+  bool episode_summary;  // bg_set_episode_summary: bg_step_many_rows_ex with limits leaves the ended episode's ante / round / chips in the records of ended steps
   // refill pipeline: double-buffered producer counters, a side stream and per-parity completion events
   uint32_t* d_prod[2];
   long refill_seq;       // refills launched so far; refill #i writes d_prod[i & 1]
@@ -909,7 +911,7 @@ int bg_create_ex(int n_envs, int device_id, uint32_t flags, int max_ante, int fu
   }
   if (device_id < 0 || device_id >= ndev) { g_create_err = "bg_create: device_id out of range"; return BG_E_ARG; }
   bg_handle* h = new bg_handle();
-  h->device_id = device_id; h->seeded = false; h->bytes = 0; h->profiling = false;
+  h->device_id = device_id; h->seeded = false; h->bytes = 0; h->profiling = false; h->episode_summary = false;
   { const char* av = getenv("BG_ASYNC_REFILL"); h->async_refill = av ? atoi(av) != 0 : true; }
   { // every tunable is read here, once per handle (a process may A/B two handles with different settings)
     auto geti = [](const char* k, int dflt) { const char* v = getenv(k); return v ? atoi(v) : dflt; };
@@ -1681,6 +1683,7 @@ int bg_safe_terminal_slots(int K, int max_invalid_actions, int max_episode_steps
 
 int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
                          int rows_stride_steps, const bg_safe_limits* limits, bg_rollout_stats* stats_dev, void* stream) {
+  if (!limits && h && h->episode_summary) { h->err = "bg_step_many_rows_ex: the episode summary needs limits (bg_set_episode_summary is on)"; return BG_E_ARG; }
   if (!limits) return bg_step_many_rows(h, K, actions_dev, rows_dev, row_stride_bytes, rows_stride_steps, stats_dev, stream);
   if (!h) return BG_E_ARG;
   const char* bad = nullptr;
@@ -1712,6 +1715,7 @@ int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_
   memset(&sa, 0, sizeof(sa));
   sa.counters = limits->counters_dev;
   sa.max_invalid = limits->max_invalid_actions; sa.max_steps = limits->max_episode_steps;
+  sa.summary = h->episode_summary ? 1u : 0u;
   if (limits->terminal_rows_dev) {
     BG_HIP(hipMemsetAsync(limits->terminal_step_dev, 0xff, (size_t)limits->terminal_slots * (size_t)h->dev.N * sizeof(int32_t), st));
     sa.term_rows = limits->terminal_rows_dev; sa.term_step = limits->terminal_step_dev;
@@ -1720,6 +1724,13 @@ int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_
   }
   return bg_rollout_impl(h, K, 0, 0, 0, 0, nullptr, rows_dev, (size_t)row_stride_bytes, rows_stride_steps, nullptr, nullptr, nullptr, stats_dev,
                          stream, actions_dev, true, &sa);
+}
+
+int bg_set_episode_summary(bg_handle* h, int enable) {
+  if (!h) return BG_E_ARG;
+  if (enable != 0 && enable != 1) { h->err = "bg_set_episode_summary: enable must be 0 or 1"; return BG_E_ARG; }
+  h->episode_summary = enable != 0;
+  return 0;
 }
 
 __global__ __launch_bounds__(BG_BLOCK) void bg_inject_cards_kernel(BgDev d, const uint16_t* __restrict__ cs, const uint8_t* __restrict__ mask_in, int apply_now) {
@@ -2427,6 +2438,38 @@ int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, in
   if (ep_return_dev) { if (ep_len_dev) BG_EPS_GO(true, true); else BG_EPS_GO(true, false); }
   else { if (ep_len_dev) BG_EPS_GO(false, true); else BG_EPS_GO(false, false); }
 #undef BG_EPS_GO
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+// packed records -> the ended episodes of a rollout (bg_ends.h): the report, and the curriculum's state advanced per env in step order
+int bg_episode_ends_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, int64_t* report_dev, const bg_curriculum* cur,
+                         float* kernel_ms_out, void* stream) {
+  static_assert(BG_ENDS_ENVS == BG_GAE_ENVS, "bg_scan_args bounds N by the grid of a 64-env workgroup");
+  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
+  if (!bad && (!report_dev || ((uintptr_t)report_dev & 7))) bad = "report_dev must be an 8-byte aligned device pointer to int64 [BG_ENDS_WORDS]";
+  else if (!bad && cur) {
+    if (!cur->cap_dev || !cur->hist_dev || !cur->count_dev || !cur->at_level_dev || !cur->raised_dev) bad = "cur: cap_dev, hist_dev, count_dev, at_level_dev and raised_dev must all be device pointers";
+    else if ((((uintptr_t)cur->cap_dev | (uintptr_t)cur->at_level_dev) & 3) || ((uintptr_t)cur->hist_dev & 1) || ((uintptr_t)cur->count_dev & 7)) bad = "cur: int32 arrays must be 4-byte aligned, hist_dev 2-byte, count_dev 8-byte";
+    else if (cur->window < 1) bad = "cur: window must be >= 1";
+    else if (cur->increment < 1 || cur->increment > BG_ENDS_CAP_MAX) bad = "cur: increment must be in 1..255";
+    else if (!std::isfinite(cur->threshold)) bad = "cur: threshold must be finite";
+  }
+  if (bad) { g_create_err = std::string("bg_episode_ends_rows: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  hipStream_t s = (hipStream_t)stream;
+  BG_HIP0(hipMemsetAsync(report_dev, 0, BG_ENDS_WORDS * sizeof(int64_t), s));
+  if (K == 0 || N == 0) {
+    if (cur && N > 0) BG_HIP0(hipMemsetAsync(cur->raised_dev, 0, (size_t)N, s));   // (no step: no cap rose)
+    return 0;
+  }
+  const unsigned grid = (unsigned)((N + BG_ENDS_ENVS - 1) / BG_ENDS_ENVS);
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (cur) hipLaunchKernelGGL((bg_episode_ends_kernel<true>), dim3(grid), dim3(BG_ENDS_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, (unsigned long long*)report_dev, *cur);
+  else hipLaunchKernelGGL((bg_episode_ends_kernel<false>), dim3(grid), dim3(BG_ENDS_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, (unsigned long long*)report_dev, bg_curriculum{});
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);

@@ -17,7 +17,7 @@ import torch
 from . import _native as nat
 
 _TORCH_DT = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
-             "float32": torch.float32, "float64": torch.float64, "uint8": torch.uint8}
+             "float32": torch.float32, "float64": torch.float64, "uint8": torch.uint8, "uint32": torch.uint32}
 
 
 def _align(n: int, a: int = 256) -> int:
@@ -92,6 +92,11 @@ class RowBuffers:
         self.terminated = self._view(nat.ROW_EXTRA["terminated"][0], "uint8", ())
         # byte BG_ROW_END_FLAGS: why a step ended its episode (END_GAME | END_INVALID | END_MAX_STEPS), written by `step_many(..., limits=)`; 0 otherwise
         self.end_flags = self._view(nat.ROW_EXTRA["end_flags"][0], "uint8", ())
+        # the ended episode's final ante (int16), round (int8) and min(chips_scored, 2**32 - 1) (uint32; `.to(torch.int64)` for arithmetic) where
+        # `terminated` is set, written by `step_many(..., limits=EpisodeLimits(..., summary=True))`; 0 otherwise
+        self.end_ante = self._view(*nat.ROW_EXTRA["end_ante"], ())
+        self.end_round = self._view(*nat.ROW_EXTRA["end_round"], ())
+        self.end_chips = self._view(*nat.ROW_EXTRA["end_chips"], ())
 
     def encode(self, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None, *,
                index: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -173,6 +178,11 @@ class RowBuffers:
     def episode_stats(self, stats: "EpisodeStats"):
         """(ep_return float64, ep_len int32) [steps, n] of these records, continuing the episodes `stats` carries (`EpisodeStats.update`)."""
         return stats.update(self.rows)
+
+    def episode_ends(self, curriculum: Optional["RowCurriculum"] = None, apply: bool = True) -> torch.Tensor:
+        """The report of these records' ended episodes, int64 [32] on the device (`episode_ends`); with a `RowCurriculum` its state is advanced and
+        its raised caps are set (`RowCurriculum.update`)."""
+        return episode_ends(self.rows) if curriculum is None else curriculum.update(self.rows, apply=apply)
 
     def _view(self, off: int, dt: str, shape) -> torch.Tensor:
         item = np.dtype(dt).itemsize
@@ -389,7 +399,8 @@ class BalatroVecEnv:
 
         limits (an `EpisodeLimits`, with a `RowBuffers` only): SafeBalatroEnv's episode limits inside the launch (bg_step_many_rows_ex).  `terminated`
         is then SB3's done, `rb.end_flags` says why, a killed step's reward is -50.0, an env the wrapper ended is reset inside the step, and
-        `limits.terminal()` has the records before those resets."""
+        `limits.terminal()` has the records before those resets.  With `EpisodeLimits(..., summary=True)` the record of every ended step also
+        carries the ended episode's final ante, round and score (`rb.end_ante` / `rb.end_round` / `rb.end_chips`; bg_set_episode_summary)."""
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if actions.dim() != 2 or actions.shape[1] != self.num_envs:
@@ -408,6 +419,7 @@ class BalatroVecEnv:
             if limits is not None:
                 if not isinstance(limits, EpisodeLimits) or limits.n != self.num_envs or limits.device != self.device:
                     raise ValueError(f"limits must be an EpisodeLimits of {self.num_envs} envs on {self.device}")
+                self._check(self._L.bg_set_episode_summary(self._h, 1 if limits.summary else 0), "bg_set_episode_summary")
                 rc = self._L.bg_step_many_rows_ex(
                     self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
                     1 if obs_buffers.steps > 1 else 0, C.byref(limits._struct()), C.c_void_p(self._stats.data_ptr()), self._stream())
@@ -1447,9 +1459,14 @@ class EpisodeLimits:
     device, the per-env counters the limits need across calls (int32 [n, 4]: episode_steps, consecutive_invalid, wrapper endings in the last call,
     0) and the buffers for the records before the resets the wrapper causes -- SB3's info["terminal_observation"]: `terminal_rows` uint8
     [S, n, row_stride] and `terminal_step` int32 [S, n] (the step of the last call whose ending filled the slot, else -1), S =
-    steps // min(limits) + 1 slots per env for calls of up to `steps` steps."""
+    steps // min(limits) + 1 slots per env for calls of up to `steps` steps.  summary=True: `step_many` turns the handle's episode summary on
+    (bg_set_episode_summary), and the record of every ended step carries the ended episode's final ante, round and score."""
 
-    def __init__(self, n: int, device, max_invalid_actions: int = 50, max_episode_steps: int = 1000, steps: int = 1, row_stride: int = 384):
+    def __init__(self, n: int, device, max_invalid_actions: int = 50, max_episode_steps: int = 1000, steps: int = 1, row_stride: int = 384,
+                 summary: bool = False):
+        if not isinstance(summary, (bool, np.bool_)):
+            raise ValueError("summary must be a bool")
+        self.summary = bool(summary)
         self.n, self.steps = int(n), int(steps)
         self.device = torch.device(device)
         self.max_invalid_actions, self.max_episode_steps = int(max_invalid_actions), int(max_episode_steps)
@@ -1504,6 +1521,106 @@ class EpisodeLimits:
             order = torch.argsort(index)
             self._terminal = (index[order].to(torch.int32), self.terminal_rows.view(-1, self.row_stride)[used[order]].contiguous())
         return self._terminal
+
+
+def _episode_ends_call(rows, cur: Optional["nat.Curriculum"], n_expected: Optional[int], timing: bool):
+    K, N, stride = _check_scan_rows(rows)
+    if n_expected is not None and N != n_expected:
+        raise ValueError(f"rows must hold records of {n_expected} envs (got {N})")
+    if not rows.is_cuda:
+        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
+    if rows.data_ptr() % 16:
+        raise ValueError("rows must be 16-byte aligned")
+    dev = rows.device
+    if K * N == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
+        return torch.zeros(nat.ENDS_WORDS, dtype=torch.int64, device=dev), 0.0
+    report = torch.empty(nat.ENDS_WORDS, dtype=torch.int64, device=dev)
+    L = nat.load()
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        rc = L.bg_episode_ends_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(report.data_ptr()),
+                                    None if cur is None else C.byref(cur), C.byref(ms) if timing else None,
+                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise nat.NativeError(f"bg_episode_ends_rows failed ({rc}): {L.bg_last_error(None).decode()}")
+    return report, float(ms.value)
+
+
+def episode_ends(rows: torch.Tensor, timing: bool = False):
+    """The ended episodes of a finished [K, N] rollout of packed records in one launch (bg_episode_ends_rows): int64 [32] on the device, words by
+    `_native.ENDS_REPORT` -- ended records, of which game overs / kills / step-limit-only endings, sum and maximum of the end ante and of the end
+    chips, records without a summary -- and from `_native.ENDS_HIST` on the histogram of min(end ante, 15).  rows: contiguous uint8 device tensor
+    [K, N, stride] (`RowBuffers.rows`) of `step_many(..., limits=EpisodeLimits(..., summary=True))`.  timing=True returns (report, kernel ms)."""
+    report, ms = _episode_ends_call(rows, None, None, timing)
+    return (report, ms) if timing else report
+
+
+class RowCurriculum:
+    """`CurriculumBalatroEnv` (train_balatro_agent.py:126-170) for the packed-record path, on the device: `sb3_adapter.CurriculumTracker`'s state --
+    `cap` int32 [n], `hist` int16 [window, n] (the final antes of the last `window` episodes), `count` int64 [n], `at_level` int32 [n] -- advanced
+    by bg_episode_ends_rows from the records of `step_many(..., limits=EpisodeLimits(..., summary=True))`.  A raised cap takes effect at the call
+    boundary: episodes an env finishes later in the same rollout were played under the old cap and enter the history as played."""
+
+    def __init__(self, env: "BalatroVecEnv", initial_max_ante: int = 3, ante_increment: int = 1, success_threshold: float = 0.8, window: int = 100):
+        self.env = env
+        self.n = int(env.num_envs)
+        self.device = torch.device(env.device)
+        self.increment, self.threshold, self.window = int(ante_increment), float(success_threshold), int(window)
+        if not 1 <= int(initial_max_ante) <= nat.CURRICULUM_CAP_MAX:
+            raise ValueError(f"initial_max_ante must be in 1..{nat.CURRICULUM_CAP_MAX}")
+        if not 1 <= self.increment <= nat.CURRICULUM_CAP_MAX:
+            raise ValueError(f"ante_increment must be in 1..{nat.CURRICULUM_CAP_MAX}")
+        if self.window < 1 or self.window >= 2 ** 31:
+            raise ValueError("window must be >= 1 (and fit an int32)")
+        if not np.isfinite(self.threshold):
+            raise ValueError("success_threshold must be finite")
+        self.cap = torch.full((self.n,), int(initial_max_ante), dtype=torch.int32, device=self.device)
+        self.hist = torch.zeros((self.window, self.n), dtype=torch.int16, device=self.device)
+        self.count = torch.zeros(self.n, dtype=torch.int64, device=self.device)
+        self.at_level = torch.zeros(self.n, dtype=torch.int32, device=self.device)
+        self.raised = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
+        env.set_max_ante(int(initial_max_ante))
+
+    def _struct(self) -> "nat.Curriculum":
+        return nat.Curriculum(self.cap.data_ptr(), self.hist.data_ptr(), self.count.data_ptr(), self.at_level.data_ptr(), self.raised.data_ptr(),
+                              self.window, self.increment, self.threshold)
+
+    def update(self, rows: torch.Tensor, apply: bool = True, timing: bool = False):
+        """The ended episodes of rows (contiguous uint8 [K, n, stride] on the env's device) through the rule, per env in step order.  Returns the
+        report (`episode_ends`; word `_native.ENDS_REPORT["raised"]` counts the envs whose cap rose, `self.raised` marks them); timing=True appends
+        the kernel milliseconds.  apply=True reads that word -- the call's one 8-byte synchronisation -- and, only when it is non-zero, hands the
+        raised caps to `env.set_max_ante`, which keeps the library's host mirror of the caps in step.  apply=False leaves that to the caller."""
+        if isinstance(rows, torch.Tensor) and rows.device != self.device:
+            raise ValueError(f"rows must hold records of {self.n} envs on {self.device} (got {rows.device})")
+        report, ms = _episode_ends_call(rows, self._struct(), self.n, timing)
+        if rows.shape[0] * rows.shape[1] == 0:
+            self.raised.zero_()
+        elif apply and int(report[nat.ENDS_REPORT["raised"]].item()):
+            self.env.set_max_ante(self.cap.cpu().numpy(), mask=self.raised.cpu().numpy())
+        return (report, ms) if timing else report
+
+    def state_dict(self) -> dict:
+        return {"window": self.window, "ante_increment": self.increment, "success_threshold": self.threshold, "cap": self.cap.cpu().clone(),
+                "hist": self.hist.cpu().clone(), "count": self.count.cpu().clone(), "at_level": self.at_level.cpu().clone()}
+
+    def load_state_dict(self, state: dict, apply: bool = True) -> None:
+        """Restores the rule's state; apply=True also sets the env's caps from it (`env.set_max_ante`)."""
+        if int(state["window"]) != self.window:
+            raise ValueError("the saved history belongs to another window")
+        new = {}
+        for name, dt, shape in (("cap", torch.int32, (self.n,)), ("hist", torch.int16, (self.window, self.n)), ("count", torch.int64, (self.n,)),
+                                ("at_level", torch.int32, (self.n,))):
+            t = torch.as_tensor(state[name])
+            if tuple(t.shape) != shape:
+                raise ValueError(f"{name} must have shape {list(shape)}")
+            new[name] = t.to(dtype=dt)
+        if new["cap"].numel() and (int(new["cap"].min()) < 0 or int(new["cap"].max()) > nat.CURRICULUM_CAP_MAX):
+            raise ValueError(f"cap must be in 0..{nat.CURRICULUM_CAP_MAX}")
+        self.increment, self.threshold = int(state["ante_increment"]), float(state["success_threshold"])
+        for name, t in new.items():
+            getattr(self, name).copy_(t.to(self.device))
+        if apply:
+            self.env.set_max_ante(new["cap"].numpy())
 
 
 def _norm_rows(rows) -> torch.Tensor:

@@ -320,6 +320,22 @@ int bg_safe_terminal_slots(int K, int max_invalid_actions, int max_episode_steps
 int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
                          int rows_stride_steps, const bg_safe_limits* limits, bg_rollout_stats* stats_dev, void* stream);
 
+/* The ended episode's final ante, round and score in the record of the step that ended it: a switch of the handle, off by default.
+ * Replaces: what the reference's callbacks log of every finished episode -- info's ante and chips_scored at `done` (train_balatro_agent.py:189-209)
+ * -- and the `ante_at_end` CurriculumBalatroEnv's rule needs (train_balatro_agent.py:126-170), which SAME_STEP auto-reset overwrites before a
+ * record is written.  With the switch on, every record of bg_step_many_rows_ex WITH limits whose byte BG_ROW_TERMINATED is set carries, in bytes
+ * 344..351 (spare bytes inside BG_ROW_BYTES), the state the episode ended in -- the same whoever ended it: a game over, a curriculum cap (the end
+ * ante is then cap + 1), an invalid-action kill or the step limit; every record whose terminated byte is 0 has zeros there.  Terminal records
+ * (bg_safe_limits.terminal_rows_dev) are written before the reset: their observation IS the final state, and their bytes 344..351 stay 0.
+ * With the switch on and limits == NULL, bg_step_many_rows_ex returns BG_E_ARG ("the episode summary needs limits").  bg_step_many_rows,
+ * bg_rollout_rows, bg_step_rows and BG_ENGINE=1 never write the summary: their bytes 344..351 are 0 whatever the switch says.  The switch is handle
+ * state, not part of a state blob (bg_get_state / bg_get_states).  Off: every byte the library writes is what it wrote before the switch existed.
+ * enable: 0 or 1, BG_E_ARG otherwise. */
+int bg_set_episode_summary(bg_handle* h, int enable);
+#define BG_ROW_END_ANTE 344       /* int16: state.ante when the episode ended (>= 1) */
+#define BG_ROW_END_ROUND 346      /* int8: state.round then; byte 347 stays 0 */
+#define BG_ROW_END_CHIPS 348      /* uint32: min(chips_scored then, 2**32 - 1) */
+
 /* Sharded jobs (one process per GPU): the exchange of the design -- every rank sees the CURRENT record of every env -- without a collective
  * behind the launch.  bufs[r] is rank r's gather buffer, uint8 [world][N][BG_ROW_BYTES], as mapped into THIS process (own buffer: an ordinary device
  * pointer; peers': hipIpcOpenMemHandle / torch's CUDA IPC over xGMI); N = this handle's env count, the same on every rank.  From then on the LAST launch
@@ -545,6 +561,43 @@ int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, in
 int bg_gae_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
                    const float* values_dev, const float* last_values_dev, double gamma, double gae_lambda,
                    float* advantages_dev, float* returns_dev, const double* rewards_dev, float* kernel_ms_out, void* stream);
+
+/* The ended episodes of a finished [K, N] rollout of packed records, in ONE launch (csrc/bg_ends.h): a report for logging and, optionally, the
+ * curriculum's cap updates, on the device.  Reads the last 16 bytes of every record (336..351: the terminated byte, BG_ROW_END_FLAGS and the episode
+ * summary of bg_set_episode_summary), i.e. one 128-byte line per record.  Record layout, alignment, BG_E_ARG (text in bg_last_error(NULL)) before
+ * anything is launched, the current device and kernel_ms_out are as in bg_gae_rows; lane = env, forwards along K.
+ * Replaces: the per-episode logging of the reference's callbacks (train_balatro_agent.py:189-209) and `CurriculumBalatroEnv` (:126-170), which
+ * sb3_adapter.CurriculumTracker.update vectorises on the host.
+ * report_dev: int64 [BG_ENDS_WORDS], 8-byte aligned, overwritten by every call (K * N == 0: zeros); integer sums, so two calls give equal values:
+ *     0       records with byte BG_ROW_TERMINATED set ("ended records")
+ *     1 2 3   of those: BG_ROW_END_FLAGS & BG_END_GAME, & BG_END_INVALID, == BG_END_MAX_STEPS
+ *     4 5     sum and maximum of the end ante              6 7   sum and maximum of the end chips
+ *     8       envs whose cap this call raised (0 without cur)
+ *     9       ended records whose end ante is <= 0, i.e. made without the summary: they count in words 0..3 only and are not fed to the curriculum
+ *     10..15  0
+ *     16 + min(end ante, 15)   histogram of the end ante
+ * cur (NULL: the report alone): per env, for every ended record with a summary in step order, CurriculumTracker.update's rule for that env:
+ *     hist[count % window][e] = end ante;  count += 1;  at_level += 1
+ *     if at_level >= window and (number of kept entries >= cap) / float64(window) >= threshold:  cap = min(cap + increment, 255);  at_level = 0
+ * where the kept entries are the first `count` while count < window (the division is by `window` all the same, as in the reference); the float64
+ * division and compare are done as written, so the decision is exact.  An env with cap 0 (no cap) keeps its history and is never raised.
+ * A raised cap takes effect at the CALL BOUNDARY: the caller hands cap_dev to bg_set_max_ante behind the call (where word 8 is non-zero).  Episodes
+ * the env finishes later in the same rollout were played under the old cap and enter the history as played, judged against the new cap.
+ * cap_dev int32 [N] in / out; hist_dev int16 [window, N] in / out; count_dev int64 [N] in / out; at_level_dev int32 [N] in / out (saturates at
+ * 2**31 - 1); raised_dev uint8 [N] out: 1 where this call raised the env's cap at least once, else 0.
+ * BG_E_ARG: K < 0 or N < 0, rows_dev / row_stride_bytes that are no records, report_dev NULL or misaligned; with cur: a NULL or misaligned array,
+ * window < 1, increment outside 1..255, a threshold that is not finite. */
+#define BG_ENDS_WORDS 32
+typedef struct bg_curriculum {
+  int32_t* cap_dev;      /* [N] in/out, current_max_ante per env, 1..255; an env with cap 0 is never raised */
+  int16_t* hist_dev;     /* [window, N] in/out: final antes of the last `window` episodes, slot count % window */
+  int64_t* count_dev;    /* [N] in/out: episodes ever finished */
+  int32_t* at_level_dev; /* [N] in/out: episodes since the env's last raise */
+  uint8_t* raised_dev;   /* [N] out: 1 where this call raised the cap at least once */
+  int32_t window, increment; double threshold;
+} bg_curriculum;
+int bg_episode_ends_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
+                         int64_t* report_dev, const bg_curriculum* cur, float* kernel_ms_out, void* stream);
 
 /* SB3's VecNormalize over [K, N] packed records, on the device: the last wrapper between the env and the network in the reference's training scripts.
  * Replaces: `VecNormalize(env, norm_obs=True, norm_reward=True, clip_obs=10.0)` (hpc_train.py:68,72; train_balatro_agent.py:319,323), whose pickle is
