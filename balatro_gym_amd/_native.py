@@ -50,6 +50,8 @@ ROW_EXTRA = {"reward": (136, "float64"), "action": (172, "int32"), "terminated":
 ROW_END_FLAGS = ROW_EXTRA["end_flags"][0]
 ROW_END_ANTE, ROW_END_ROUND, ROW_END_CHIPS = ROW_EXTRA["end_ante"][0], ROW_EXTRA["end_round"][0], ROW_EXTRA["end_chips"][0]
 END_GAME, END_INVALID, END_MAX_STEPS = 1, 2, 4
+END_STUCK = 8               # bg_step_many_rows_progress: ProgressionRewardWrapper's own ending (info['stuck_on_ante_1'])
+PROGRESS_STUCK_STEPS = 300  # csrc/bg_progress.h: more steps than this on ante 1 end the episode
 # bg_episode_ends_rows: the words of its report (csrc/bg_ends.h BG_ENDS_W_*; the histogram of end antes is words 16 + min(ante, 15))
 ENDS_WORDS = 32
 ENDS_REPORT = {"ended": 0, "game": 1, "invalid": 2, "max_steps": 3, "ante_sum": 4, "ante_max": 5, "chips_sum": 6, "chips_max": 7, "raised": 8,
@@ -77,7 +79,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_step_many_rows_ex", "bg_safe_terminal_slots",
            "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad",
            "bg_get_states", "bg_set_states", "bg_copy_states",
-           "bg_set_episode_summary", "bg_episode_ends_rows"]
+           "bg_set_episode_summary", "bg_episode_ends_rows",
+           "bg_step_many_rows_progress", "bg_progress_terminal_slots"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -136,6 +139,11 @@ class InfoPtrs(C.Structure):
 class RolloutStats(C.Structure):
     _fields_ = [("steps", C.c_uint64), ("episodes", C.c_uint64), ("plays", C.c_uint64), ("score_sum", C.c_int64),
                 ("reward_bits", C.c_uint64), ("obs_hash", C.c_uint64)]
+
+
+class ProgressRewards(C.Structure):
+    """bg_progress_rewards (include/balatro_mi355x.h)."""
+    _fields_ = [("counters_dev", C.c_void_p)]
 
 
 class SafeLimits(C.Structure):
@@ -250,6 +258,8 @@ def load(build_if_missing: bool = True):
     L.bg_step_many_rows.argtypes = [vp, i32, vp, vp, u64, i32, vp, vp]
     L.bg_step_many_rows_ex.argtypes = [vp, i32, vp, vp, u64, i32, C.POINTER(SafeLimits), vp, vp]
     L.bg_safe_terminal_slots.argtypes = [i32, i32, i32]
+    L.bg_step_many_rows_progress.argtypes = [vp, i32, vp, vp, u64, i32, C.POINTER(SafeLimits), C.POINTER(ProgressRewards), vp, vp]
+    L.bg_progress_terminal_slots.argtypes = [i32, i32, i32]
     L.bg_set_episode_summary.argtypes = [vp, i32]
     L.bg_episode_ends_rows.argtypes = [vp, u64, i32, i64, vp, C.POINTER(Curriculum), C.POINTER(C.c_float), vp]
     L.bg_set_gather_peers.argtypes = [vp, vp, i32, i32]

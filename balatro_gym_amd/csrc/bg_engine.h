@@ -54,6 +54,7 @@ struct SafeArgs {
   uint32_t term_stride, slots;
   int32_t max_invalid, max_steps;
   uint32_t summary;            // != 0: the records of ended steps carry the ended episode's summary (bg_set_episode_summary)
+  int32_t* progress;           // bg_step_many_rows_progress: int32 [N, 4], ProgressionRewardWrapper's state as bg_progress.h packs it (the PROG instantiations); else null
 };
 static_assert(sizeof(SafeArgs) <= sizeof(InfoPtrs), "SafeArgs rides in the bytes of EngineArgs::info");
 struct EngineArgs {

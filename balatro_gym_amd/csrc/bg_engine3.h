@@ -91,13 +91,25 @@ struct E3Lds {
 //     into words 86 / 87 of the image (BG_ROW_END_ANTE / _ROUND / _CHIPS) behind the observation writer, which leaves zeros there.  The owner's cheap
 //     steps patch the image, so each clears the two words: only the record of the ended step carries them, and a terminal record (written before the
 //     reset) has zeros.
-template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT = false, bool SAFE = false>
+// PROG (bg_step_many_rows_progress; implies SAFE): ProgressionRewardWrapper (bg_progress.h) in front of SafeBalatroEnv's rule, all of it behind
+// `if constexpr (PROG)` (the other instantiations compile to what they were):
+//   * the owner lane keeps the wrapper's state of its env -- four packed words, a.safe.progress -- in registers beside the limits' counters: one 16-byte
+//     load in the prologue, one store behind the loop, handed over between launches and calls like them;
+//   * where bg_safe_step runs, bg_progress_step runs first, on the reward in the image and on state.ante / state.round: chunk 3 of the env, which the
+//     owner holds in registers, unless the ENV ended the episode -- then the image and chunk 3 already show the new episode, and the final state's two
+//     values come from the service wave's reset block, which leaves them in s_fin[env] in front of its answer (whatever the summary switch says: words
+//     86 / 87 of the image obey the switch as before).  The shaped reward goes back into the image, and bg_safe_step sees it and `terminated or stuck`;
+//   * a stuck ending the env did not make itself is a wrapper-made ending like a kill: terminal record, reset-only request, BG_END_STUCK in byte 343;
+//   * every ending returns the wrapper's state to reset()'s: four zero words.
+// (the body of the kernels below: bg_engine3_kernel's own template list stops at SAFE, and the PROG launches have a kernel name of their own)
+template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT, bool SAFE, bool PROG>
 // (Round 5 measured reading the arguments THROUGH the kernarg segment pointer instead of as by-value parameters -- whose 16-register blocks the compiler
 //  spills to VGPR lanes and reloads whole, 12 % of the kernel's instructions being v_readlane / v_writelane / s_nop: SGPR spills 237 -> 61, 14 454 -> 13 114
 //  instructions, and 3.4 % SLOWER at both launch lengths: a scalar load per use waits longer than sixteen lane reads.  profiles/r05/play_path_ab.txt.)
-__global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(BgDev d, EngineArgs a) {
+__device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs a) {
   constexpr int NE = NOW * KS * BG_BLOCK, LNE = NE == 256 ? 8 : (NE == 128 ? 7 : 6);
   static_assert(ACT || !SAFE, "the limits exist on the caller's-actions path");
+  static_assert(SAFE || !PROG, "the progression rewards sit inside the limits");
   static_assert(NE == 64 || NE == 128 || NE == 256, "envs per workgroup (a request carries the env's lane in 8 bits)");
   // (static LDS: the compiler then pads the register allocation to the 256 VGPRs that two waves per SIMD leave each -- which this kernel needs
   //  anyway: with dynamic LDS and the same cap it compiles to 256 VGPRs plus a spilled one)
@@ -106,6 +118,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
   auto& s_ctl = L.s_ctl; auto& s_win = L.s_win; auto& s_list = L.s_list; auto& s_zero = L.s_zero; auto& s_owners_left = L.s_owners_left; auto& jt = L.jt;
   auto& s_nd = L.s_nd; auto& s_ndst = L.s_ndst;
   __shared__ int s_actb[ACT ? BG_E3_ACTB : 1][ACT ? NE : 1];   // ACT: the next actions of every env (row j: step abase + j); not referenced, so not allocated, otherwise
+  __shared__ uint32_t s_fin[PROG ? NE : 1];                    // PROG: ante | round << 16 of the state an env's last ending left (written by the reset block); not allocated otherwise
   __builtin_amdgcn_s_setprio(2);
   const unsigned long long e3_k0 = kE3Tl ? wall_clock64() : 0ull;
   BG_PROBE_INIT();
@@ -191,6 +204,8 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
     // SAFE: the env's counters (bg_safe.h), its wrapper endings so far in this call (= its next terminal slot), and "the request I wait for is a reset-only one"
     int32_t csteps[KS], cinv[KS], cwrap[KS];
     bool rwait[KS];
+    // PROG: ProgressionRewardWrapper's state of the env, packed (bg_progress.h)
+    BgProgressPacked pcar[PROG ? KS : 1];
 #pragma unroll
     for (int s = 0; s < KS; s++) {
       t[s] = 0; nreq[s] = 0; waiting[s] = false;
@@ -214,6 +229,13 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
         if (l < n_live) {
           const int4 cv = *(const int4*)(a.safe.counters + 4 * (size_t)(env0 + l));
           csteps[s] = cv.x; cinv[s] = cv.y; cwrap[s] = cv.z;
+        }
+      }
+      if constexpr (PROG) {
+        pcar[s] = BgProgressPacked{{0, 0, 0, 0}};
+        if (l < n_live) {
+          const int4 pv = *(const int4*)(a.safe.progress + 4 * (size_t)(env0 + l));
+          pcar[s] = BgProgressPacked{{pv.x, pv.y, pv.z, pv.w}};
         }
       }
       rc3[s] = s_c34[0][l]; rc4[s] = s_c34[1][l]; rmask[s] = s_mask[l];
@@ -346,7 +368,24 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           if (fin && rwait[s]) rwait[s] = false;
           else if (fin) {
             const bool env_term = img8[BG_ROW_TERMINATED] != 0;
-            const BgSafeStep so = bg_safe_step(*(__attribute__((address_space(3))) const double*)&img32[34], env_term, csteps[s], cinv[s], a.safe.max_invalid, a.safe.max_steps);
+            bool stuck = false;
+            if constexpr (PROG) {
+              // state.ante / state.round behind the step: chunk 3 (a cheap step changes neither; an answer has brought the new chunk), or, when the env
+              // ended the episode and has been reset, what the reset block kept of the final state
+              uint32_t ar = bg_b(rc3[s].x, 0) | (bg_b(rc3[s].x, 1) << 16);
+              if (env_term) ar = bg_lds_ld(&s_fin[l]);
+              const BgProgressStep po = bg_progress_step(*(__attribute__((address_space(3))) const double*)&img32[34], (int32_t)(ar & 0xffffu), (int32_t)(ar >> 16),
+                                                         bg_progress_unpack(pcar[s]));
+              *(__attribute__((address_space(3))) double*)&img32[34] = po.reward;
+              pcar[s] = bg_progress_pack(po.carry);
+              stuck = po.stuck;
+            }
+            BgSafeStep so = bg_safe_step(*(__attribute__((address_space(3))) const double*)&img32[34], env_term || stuck, csteps[s], cinv[s], a.safe.max_invalid, a.safe.max_steps);
+            // (PROG: BG_END_GAME is the ENV's ending only; the wrapper's own has its bit)
+            if constexpr (PROG) {
+              so.flags = (so.flags & ~BG_SAFE_END_GAME) | (env_term ? BG_SAFE_END_GAME : 0u) | (stuck ? BG_PROGRESS_END_STUCK : 0u);
+              if (so.flags) pcar[s] = BgProgressPacked{{0, 0, 0, 0}};   // reset(), :33-41
+            }
             csteps[s] = so.episode_steps; cinv[s] = so.consecutive_invalid;
             if (so.flags & BG_SAFE_END_INVALID) *(__attribute__((address_space(3))) double*)&img32[34] = so.reward;
             // bytes 342 (SB3's done) and 343 (why), every step: the image keeps the bytes of the env's last ending
@@ -501,6 +540,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
       for (int s = 0; s < KS; s++) {
         const int l = (wave * KS + s) * BG_BLOCK + lane;
         if (l < n_live) *(int4*)(a.safe.counters + 4 * (size_t)(env0 + l)) = make_int4(csteps[s], cinv[s], cwrap[s], 0);
+        if constexpr (PROG) if (l < n_live) *(int4*)(a.safe.progress + 4 * (size_t)(env0 + l)) = make_int4(pcar[s].w[0], pcar[s].w[1], pcar[s].w[2], pcar[s].w[3]);
       }
     }
     if (lane == 0) __hip_atomic_fetch_sub(&s_owners_left, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -595,6 +635,7 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
           // here with the FINAL state still in `e`: ante | round << 16 and min(chips_scored, 2**32 - 1), for words 86 / 87 of the image (BG_ROW_END_*)
           uint32_t sum_ar = 0u, sum_chips = 0u;
           if (o.terminated && a.autoreset) {
+            if constexpr (PROG) bg_lds_st(&s_fin[l], ((uint32_t)e.ante & 0xffffu) | (((uint32_t)e.round & 0xffu) << 16));   // for the owner's bg_progress_step
             if constexpr (SAFE) if (a.safe.summary) {
               sum_ar = ((uint32_t)e.ante & 0xffffu) | (((uint32_t)e.round & 0xffu) << 16);
               sum_chips = e.chips_scored < 0 ? 0u : (e.chips_scored > 0xffffffffll ? 0xffffffffu : (uint32_t)e.chips_scored);
@@ -642,4 +683,13 @@ __global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(B
   }
   if (a.stats) bg_stats_flush(a.stats, L.s_stats, tid);
   if constexpr (kE3Tl) if (tid == 0 && d.dbg) atomicAdd(&d.dbg[31], wall_clock64() - e3_k0);   // workgroup end
+}
+template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT = false, bool SAFE = false>
+__global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_kernel(BgDev d, EngineArgs a) {
+  bg_engine3_body<HASH, CARDS, NOW, KS, NSV, ACT, SAFE, false>(d, a);
+}
+// bg_step_many_rows_progress: the caller's actions under both wrappers (ACT, SAFE and PROG)
+template <bool CARDS, int NOW, int KS, int NSV>
+__global__ __launch_bounds__((NOW + NSV) * BG_BLOCK, 2) void bg_engine3_progress_kernel(BgDev d, EngineArgs a) {
+  bg_engine3_body<false, CARDS, NOW, KS, NSV, true, true, true>(d, a);
 }

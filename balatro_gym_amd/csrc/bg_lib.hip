@@ -52,6 +52,7 @@ __device__ __forceinline__ void bg_emit_info(size_t row, const StepOut& o, uint8
 }
 
 #include "bg_safe.h"   // SafeBalatroEnv's episode limits: the rule of one step (bg_engine3.h's SAFE launches, bg_step_many_rows_ex)
+#include "bg_progress.h"   // ProgressionRewardWrapper's reward shaping: the rule of one step (bg_engine3.h's PROG launches, bg_step_many_rows_progress)
 #include "bg_engine.h" // the step engine: one kernel behind bg_step / bg_step_many / bg_rollout / bg_rollout_rows
 #include "bg_engine3.h" // owner waves + service waves in ONE workgroup (packed-record rollouts)
 
@@ -1329,10 +1330,16 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
       const dim3 g_((NOWV * KSV == 1) ? (h->dev.N + epw - 1) / epw : (h->dev.N + NOWV * KSV * 64 - 1) / (NOWV * KSV * 64)), b_((NOWV + NSVV) * BG_BLOCK); \
       if (ev_a) hipExtLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV, ##__VA_ARGS__>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
       else hipLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV, ##__VA_ARGS__>), g_, b_, 0, st, dv, a); } while (0)
+#define BG_E3P(CV, NOWV, KSV, NSVV) do { \
+      const dim3 g_((NOWV * KSV == 1) ? (h->dev.N + epw - 1) / epw : (h->dev.N + NOWV * KSV * 64 - 1) / (NOWV * KSV * 64)), b_((NOWV + NSVV) * BG_BLOCK); \
+      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_progress_kernel<CV, NOWV, KSV, NSVV>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
+      else hipLaunchKernelGGL((bg_engine3_progress_kernel<CV, NOWV, KSV, NSVV>), g_, b_, 0, st, dv, a); } while (0)
     // (the caller's actions: bg_step_many_rows asks for no observation hash, so the action mode has no HASH variant; with bg_step_many_rows_ex's
-    //  limits -- a.safe, which shares the bytes of the info pointers no launch of this branch has -- the SAFE instantiation of the same shape)
+    //  limits -- a.safe, which shares the bytes of the info pointers no launch of this branch has -- the SAFE instantiation of the same shape, and with
+    //  bg_step_many_rows_progress' carry the PROG one)
 #define BG_E3(NOWV, KSV, NSVV) do { \
-      if (a.actions_in && a.safe.counters) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true, true); } \
+      if (a.actions_in && a.safe.counters && a.safe.progress) { if (cards) BG_E3P(true, NOWV, KSV, NSVV); else BG_E3P(false, NOWV, KSV, NSVV); } \
+      else if (a.actions_in && a.safe.counters) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true, true); } \
       else if (a.actions_in) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true); } \
       else if (hash && cards) BG_E3K(true, true, NOWV, KSV, NSVV, false); else if (hash) BG_E3K(true, false, NOWV, KSV, NSVV, false); \
       else if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, false); else BG_E3K(false, false, NOWV, KSV, NSVV, false); } while (0)
@@ -1343,6 +1350,7 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
     }
 #undef BG_E3
 #undef BG_E3K
+#undef BG_E3P
     return;
   }
   a.n_waves = (uint32_t)bg_engine_waves((int)a.T);
@@ -1681,10 +1689,35 @@ int bg_safe_terminal_slots(int K, int max_invalid_actions, int max_episode_steps
   return bg_safe_slots(K, max_invalid_actions, max_episode_steps);
 }
 
+static_assert(BG_PROGRESS_END_STUCK == BG_END_STUCK, "bg_progress.h's ending bit is include/balatro_mi355x.h's");
+static_assert((BG_PROGRESS_END_STUCK & (BG_SAFE_END_GAME | BG_SAFE_END_INVALID | BG_SAFE_END_MAX_STEPS)) == 0u, "the ending bits are distinct");
+int bg_progress_terminal_slots(int K, int max_invalid_actions, int max_episode_steps) {
+  if (K < 0 || max_invalid_actions < BG_SAFE_MIN_LIMIT || max_episode_steps < BG_SAFE_MIN_LIMIT) return BG_E_ARG;
+  return bg_progress_slots(K, max_invalid_actions, max_episode_steps);
+}
+
+// bg_step_many_rows_ex with limits (progress == nullptr, who = its name) and bg_step_many_rows_progress with both
+static int bg_step_many_limits(const char* who, bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                               int rows_stride_steps, const bg_safe_limits* limits, const bg_progress_rewards* progress, bg_rollout_stats* stats_dev, void* stream);
+
 int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
                          int rows_stride_steps, const bg_safe_limits* limits, bg_rollout_stats* stats_dev, void* stream) {
   if (!limits && h && h->episode_summary) { h->err = "bg_step_many_rows_ex: the episode summary needs limits (bg_set_episode_summary is on)"; return BG_E_ARG; }
   if (!limits) return bg_step_many_rows(h, K, actions_dev, rows_dev, row_stride_bytes, rows_stride_steps, stats_dev, stream);
+  return bg_step_many_limits("bg_step_many_rows_ex", h, K, actions_dev, rows_dev, row_stride_bytes, rows_stride_steps, limits, nullptr, stats_dev, stream);
+}
+
+int bg_step_many_rows_progress(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes, int rows_stride_steps,
+                               const bg_safe_limits* limits, const bg_progress_rewards* progress, bg_rollout_stats* stats_dev, void* stream) {
+  if (!progress) return bg_step_many_rows_ex(h, K, actions_dev, rows_dev, row_stride_bytes, rows_stride_steps, limits, stats_dev, stream);
+  if (!h) return BG_E_ARG;
+  // (the wrapper sits INSIDE SafeBalatroEnv in the reference's stack, and the engine applies it where it applies the limits)
+  if (!limits) { h->err = "bg_step_many_rows_progress: progress needs limits (ProgressionRewardWrapper runs inside SafeBalatroEnv's rule)"; return BG_E_ARG; }
+  return bg_step_many_limits("bg_step_many_rows_progress", h, K, actions_dev, rows_dev, row_stride_bytes, rows_stride_steps, limits, progress, stats_dev, stream);
+}
+
+static int bg_step_many_limits(const char* who, bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                               int rows_stride_steps, const bg_safe_limits* limits, const bg_progress_rewards* progress, bg_rollout_stats* stats_dev, void* stream) {
   if (!h) return BG_E_ARG;
   const char* bad = nullptr;
   if (!actions_dev || K <= 0) bad = "actions_dev must be a device pointer to [K, N] int32 actions, K > 0";
@@ -1698,13 +1731,16 @@ int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_
   else if (!(h->dev.flags & BG_FLAG_AUTORESET)) bad = "limits need a handle with BG_FLAG_AUTORESET (an ended episode is reset inside the step)";
   else if (h->engine != 3) bad = "limits exist on bg_engine3.h only (BG_ENGINE=3)";
   else if (!limits->counters_dev || ((uintptr_t)limits->counters_dev & 15)) bad = "counters_dev must be a 16-byte aligned device pointer to int32 [N, 4]";
+  else if (progress && (!progress->counters_dev || ((uintptr_t)progress->counters_dev & 15))) bad = "progress->counters_dev must be a 16-byte aligned device pointer to int32 [N, 4]";
+  else if (progress && progress->counters_dev == limits->counters_dev) bad = "progress->counters_dev must not be the limits' counters";
   else if ((limits->terminal_rows_dev == nullptr) != (limits->terminal_step_dev == nullptr)) bad = "terminal_rows_dev and terminal_step_dev must both be set or both be NULL";
   else if (limits->terminal_rows_dev) {
     if (bg_rows_args(limits->terminal_rows_dev, limits->terminal_stride_bytes)) bad = "terminal_rows_dev must be 16-byte aligned and terminal_stride_bytes a multiple of 16, >= BG_ROW_BYTES";
     else if ((uintptr_t)limits->terminal_step_dev & 3) bad = "terminal_step_dev must be a 4-byte aligned device pointer to int32 [terminal_slots, N]";
-    else if (limits->terminal_slots < bg_safe_slots(K, limits->max_invalid_actions, limits->max_episode_steps)) bad = "terminal_slots must be >= bg_safe_terminal_slots(K, limits)";
+    else if (!progress && limits->terminal_slots < bg_safe_slots(K, limits->max_invalid_actions, limits->max_episode_steps)) bad = "terminal_slots must be >= bg_safe_terminal_slots(K, limits)";
+    else if (progress && limits->terminal_slots < bg_progress_slots(K, limits->max_invalid_actions, limits->max_episode_steps)) bad = "terminal_slots must be >= bg_progress_terminal_slots(K, limits)";
   }
-  if (bad) { h->err = std::string("bg_step_many_rows_ex: ") + bad; return BG_E_ARG; }
+  if (bad) { h->err = std::string(who) + ": " + bad; return BG_E_ARG; }
   // (bg_rollout_impl's own refusals, in front of the memsets below: nothing of the caller's is written by a call that returns an error code for its arguments)
   { const int rcs = bg_require_seeded(h); if (rcs) return rcs; }
   BG_GUARD(h);
@@ -1716,6 +1752,7 @@ int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_
   sa.counters = limits->counters_dev;
   sa.max_invalid = limits->max_invalid_actions; sa.max_steps = limits->max_episode_steps;
   sa.summary = h->episode_summary ? 1u : 0u;
+  sa.progress = progress ? progress->counters_dev : nullptr;
   if (limits->terminal_rows_dev) {
     BG_HIP(hipMemsetAsync(limits->terminal_step_dev, 0xff, (size_t)limits->terminal_slots * (size_t)h->dev.N * sizeof(int32_t), st));
     sa.term_rows = limits->terminal_rows_dev; sa.term_step = limits->terminal_step_dev;

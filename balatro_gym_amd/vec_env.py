@@ -90,7 +90,8 @@ class RowBuffers:
         self.reward = self._view(nat.ROW_EXTRA["reward"][0], "float64", ())
         self.action = self._view(nat.ROW_EXTRA["action"][0], "int32", ())
         self.terminated = self._view(nat.ROW_EXTRA["terminated"][0], "uint8", ())
-        # byte BG_ROW_END_FLAGS: why a step ended its episode (END_GAME | END_INVALID | END_MAX_STEPS), written by `step_many(..., limits=)`; 0 otherwise
+        # byte BG_ROW_END_FLAGS: why a step ended its episode (END_GAME | END_INVALID | END_MAX_STEPS, and with `progression=` END_STUCK, bit 8: the
+        # ProgressionRewardWrapper's own ending), written by `step_many(..., limits=)`; 0 otherwise
         self.end_flags = self._view(nat.ROW_EXTRA["end_flags"][0], "uint8", ())
         # the ended episode's final ante (int16), round (int8) and min(chips_scored, 2**32 - 1) (uint32; `.to(torch.int64)` for arithmetic) where
         # `terminated` is set, written by `step_many(..., limits=EpisodeLimits(..., summary=True))`; 0 otherwise
@@ -384,7 +385,8 @@ class BalatroVecEnv:
         return self._obs.tensors, self.reward, self.terminated, self.truncated, self.info
 
     def step_many(self, actions: torch.Tensor, obs_buffers: Optional["ObsBuffers"] = None, reward: Optional[torch.Tensor] = None,
-                  terminated: Optional[torch.Tensor] = None, limits: Optional["EpisodeLimits"] = None):
+                  terminated: Optional[torch.Tensor] = None, limits: Optional["EpisodeLimits"] = None,
+                  progression: Optional["ProgressionRewards"] = None):
         """K consecutive `step()` calls in one launch (bg_step_many): actions int32 [K, N].  With `obs_buffers` of at least K rows
         every call's observation is kept, and so are its reward / terminated when float64 / uint8 [>= K, N] tensors on this device are
         given; the returned truncated and info are None, and so is reward / terminated when no tensor was given for it: this call
@@ -400,7 +402,12 @@ class BalatroVecEnv:
         limits (an `EpisodeLimits`, with a `RowBuffers` only): SafeBalatroEnv's episode limits inside the launch (bg_step_many_rows_ex).  `terminated`
         is then SB3's done, `rb.end_flags` says why, a killed step's reward is -50.0, an env the wrapper ended is reset inside the step, and
         `limits.terminal()` has the records before those resets.  With `EpisodeLimits(..., summary=True)` the record of every ended step also
-        carries the ended episode's final ante, round and score (`rb.end_ante` / `rb.end_round` / `rb.end_chips`; bg_set_episode_summary)."""
+        carries the ended episode's final ante, round and score (`rb.end_ante` / `rb.end_round` / `rb.end_chips`; bg_set_episode_summary).
+
+        progression (a `ProgressionRewards`, with `limits` only): ProgressionRewardWrapper's reward shaping in front of the limits, as
+        train_progressive.py stacks them (bg_step_many_rows_progress).  The records' rewards are then the shaped ones, an episode the wrapper ends
+        for being stuck on ante 1 has END_STUCK in `rb.end_flags` and a terminal record like a kill; `limits` must have been made with
+        `progression=True` (a stuck ending needs terminal slots of its own)."""
         if actions.dtype != torch.int32 or actions.device != self.device or not actions.is_contiguous():
             actions = actions.to(device=self.device, dtype=torch.int32).contiguous()
         if actions.dim() != 2 or actions.shape[1] != self.num_envs:
@@ -419,13 +426,25 @@ class BalatroVecEnv:
             if limits is not None:
                 if not isinstance(limits, EpisodeLimits) or limits.n != self.num_envs or limits.device != self.device:
                     raise ValueError(f"limits must be an EpisodeLimits of {self.num_envs} envs on {self.device}")
+                if progression is not None and (not isinstance(progression, ProgressionRewards) or progression.n != self.num_envs or progression.device != self.device):
+                    raise ValueError(f"progression must be a ProgressionRewards of {self.num_envs} envs on {self.device}")
                 self._check(self._L.bg_set_episode_summary(self._h, 1 if limits.summary else 0), "bg_set_episode_summary")
-                rc = self._L.bg_step_many_rows_ex(
-                    self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
-                    1 if obs_buffers.steps > 1 else 0, C.byref(limits._struct()), C.c_void_p(self._stats.data_ptr()), self._stream())
-                if rc != 0:
-                    self._check(rc, "bg_step_many_rows_ex")
+                if progression is not None:
+                    rc = self._L.bg_step_many_rows_progress(
+                        self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
+                        1 if obs_buffers.steps > 1 else 0, C.byref(limits._struct()), C.byref(progression._struct()),
+                        C.c_void_p(self._stats.data_ptr()), self._stream())
+                    if rc != 0:
+                        self._check(rc, "bg_step_many_rows_progress")
+                else:
+                    rc = self._L.bg_step_many_rows_ex(
+                        self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
+                        1 if obs_buffers.steps > 1 else 0, C.byref(limits._struct()), C.c_void_p(self._stats.data_ptr()), self._stream())
+                    if rc != 0:
+                        self._check(rc, "bg_step_many_rows_ex")
                 limits._terminal = None
+            elif progression is not None:
+                raise ValueError("progression needs limits: ProgressionRewardWrapper runs inside SafeBalatroEnv's rule (pass an EpisodeLimits)")
             else:
                 rc = self._L.bg_step_many_rows(
                     self._h, K, C.c_void_p(actions.data_ptr()), C.c_void_p(obs_buffers.rows.data_ptr()), C.c_uint64(obs_buffers.row_stride),
@@ -435,7 +454,7 @@ class BalatroVecEnv:
             if self._rowbuf is not None:
                 self.observe()   # (obs_layout "rows": the live records follow)
             return obs_buffers.tensors, obs_buffers.reward, obs_buffers.terminated, None, None
-        if limits is not None:
+        if limits is not None or progression is not None:
             raise ValueError("limits exist on the packed-record path: pass a RowBuffers as obs_buffers")
         keep = obs_buffers is not None and obs_buffers.steps > 1
         if keep and obs_buffers.steps < K:
@@ -1460,13 +1479,17 @@ class EpisodeLimits:
     0) and the buffers for the records before the resets the wrapper causes -- SB3's info["terminal_observation"]: `terminal_rows` uint8
     [S, n, row_stride] and `terminal_step` int32 [S, n] (the step of the last call whose ending filled the slot, else -1), S =
     steps // min(limits) + 1 slots per env for calls of up to `steps` steps.  summary=True: `step_many` turns the handle's episode summary on
-    (bg_set_episode_summary), and the record of every ended step carries the ended episode's final ante, round and score."""
+    (bg_set_episode_summary), and the record of every ended step carries the ended episode's final ante, round and score.  progression=True: sized
+    for `step_many(..., progression=)`, whose stuck endings need steps // min(limits, 301) + 1 slots (bg_progress_terminal_slots)."""
 
     def __init__(self, n: int, device, max_invalid_actions: int = 50, max_episode_steps: int = 1000, steps: int = 1, row_stride: int = 384,
-                 summary: bool = False):
+                 summary: bool = False, progression: bool = False):
         if not isinstance(summary, (bool, np.bool_)):
             raise ValueError("summary must be a bool")
+        if not isinstance(progression, (bool, np.bool_)):
+            raise ValueError("progression must be a bool")
         self.summary = bool(summary)
+        self.progression = bool(progression)
         self.n, self.steps = int(n), int(steps)
         self.device = torch.device(device)
         self.max_invalid_actions, self.max_episode_steps = int(max_invalid_actions), int(max_episode_steps)
@@ -1478,6 +1501,8 @@ class EpisodeLimits:
         if self.row_stride < nat.ROW_BYTES or self.row_stride % 16:
             raise ValueError("row_stride must be a multiple of 16 and >= the 352-byte record")
         self.slots = self.steps // min(self.max_invalid_actions, self.max_episode_steps) + 1   # bg_safe_terminal_slots
+        if self.progression:
+            self.slots = self.steps // min(self.max_invalid_actions, self.max_episode_steps, nat.PROGRESS_STUCK_STEPS + 1) + 1   # bg_progress_terminal_slots
         self.counters = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
         self.terminal_rows = torch.zeros((self.slots, self.n, self.row_stride), dtype=torch.uint8, device=self.device)
         self.terminal_step = torch.full((self.slots, self.n), -1, dtype=torch.int32, device=self.device)
@@ -1521,6 +1546,42 @@ class EpisodeLimits:
             order = torch.argsort(index)
             self._terminal = (index[order].to(torch.int32), self.terminal_rows.view(-1, self.row_stride)[used[order]].contiguous())
         return self._terminal
+
+
+class ProgressionRewards:
+    """ProgressionRewardWrapper's state for `BalatroVecEnv.step_many(actions, obs_buffers=rows, limits=..., progression=...)`
+    (bg_step_many_rows_progress): owns, on the device, the per-env carry of the wrapper across calls -- int32 [n, 4]: total_steps,
+    steps_on_current_ante, (last_ante - 1) | (max_ante_reached - 1) << 16, last_round - 1, so that zeros are the state after the wrapper's reset().
+    The constants of the rule are the reference's (train_progressive.py:21-120), not parameters."""
+
+    def __init__(self, n: int, device):
+        self.n = int(n)
+        if self.n < 0:
+            raise ValueError("n must be >= 0")
+        self.device = torch.device(device)
+        self.counters = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
+
+    def _struct(self) -> "nat.ProgressRewards":
+        return nat.ProgressRewards(self.counters.data_ptr())
+
+    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
+        """Zero the carry (of the envs where `mask` is set): beside `env.reset(mask=...)`, as ProgressionRewardWrapper.reset does."""
+        if mask is None:
+            self.counters.zero_()
+            return
+        mask = torch.as_tensor(mask)
+        if tuple(mask.shape) != (self.n,):
+            raise ValueError(f"mask must have shape [{self.n}]")
+        self.counters.masked_fill_(mask.to(device=self.device, dtype=torch.bool).view(self.n, 1), 0)
+
+    def state_dict(self) -> dict:
+        return {"counters": self.counters.cpu().clone()}
+
+    def load_state_dict(self, state: dict) -> None:
+        c = torch.as_tensor(state["counters"])
+        if tuple(c.shape) != (self.n, 4):
+            raise ValueError(f"counters must have shape [{self.n}, 4]")
+        self.counters.copy_(c.to(device=self.device, dtype=torch.int32))
 
 
 def _episode_ends_call(rows, cur: Optional["nat.Curriculum"], n_expected: Optional[int], timing: bool):

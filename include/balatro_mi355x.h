@@ -320,6 +320,46 @@ int bg_safe_terminal_slots(int K, int max_invalid_actions, int max_episode_steps
 int bg_step_many_rows_ex(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
                          int rows_stride_steps, const bg_safe_limits* limits, bg_rollout_stats* stats_dev, void* stream);
 
+/* bg_step_many_rows_ex with ProgressionRewardWrapper's reward shaping in front of the limits, inside the launch (bg_engine3.h's PROG instantiation; the
+ * rule is csrc/bg_progress.h).
+ * Replaces: `SafeBalatroEnv(ProgressionRewardWrapper(BalatroEnvFixed(seed + rank)), 50, 1000)` of train_progressive.py:123-131 (the wrapper:
+ * train_progressive.py:21-120).  Per step, on the env's reward and on state.ante / state.round behind the step (the FINAL state's when the step ended
+ * the game), in the reference's order, every addition one float64 rounding:
+ *     total_steps += 1                                                                                   (:45)
+ *     steps_on_current_ante = steps_on_current_ante + 1 if ante == last_ante else 0                      (:60-63)
+ *     if ante > last_ante:  reward += 200 * (ante - last_ante); last_ante = ante                         (:66-72)
+ *     if round > last_round and ante == last_ante:  reward += 20; last_round = round                     (:75-78)
+ *     if ante > max_ante_reached:  max_ante_reached = ante; reward += 100                                (:81-86)
+ *     if ante == 1 and steps_on_current_ante > 150:  reward += -0.5 * (steps_on_current_ante - 150)      (:91-93)
+ *         if steps_on_current_ante > 300:  terminated = True ("stuck"); reward -= 50                     (:96-99)
+ *     if total_steps > 200 and ante < 2: reward -= 0.2   elif total_steps > 400 and ante < 3: reward -= 0.3
+ *                                                         elif total_steps > 600 and ante < 4: reward -= 0.4   (:103-108)
+ *     if ante >= 3 and total_steps < 300:  reward += 50   (on every such step)                           (:111-114)
+ *     if ante != last_ante:  last_round = round                                                          (:117-118)
+ * and then SafeBalatroEnv's rule (above) on the SHAPED reward and on `the env's terminated or stuck`: an invalid action whose shaped reward is not
+ * exactly -1.0 (-1.2 past step 200 on ante 1) is not counted, as in the reference; a stuck step zeroes consecutive_invalid like any terminated one.
+ * The record's reward is the shaped one (-50.0 on a kill).  Byte BG_ROW_END_FLAGS: BG_END_STUCK when the wrapper ended the episode, BG_END_GAME only
+ * for the env's own ending, BG_END_INVALID / BG_END_MAX_STEPS as above; a stuck step can carry BG_END_GAME or BG_END_MAX_STEPS too, and is never
+ * bootstrapped (SB3 bootstraps only where the flags are exactly BG_END_MAX_STEPS).  A stuck ending the env did not make itself is a wrapper-made
+ * ending like a kill: terminal record with the shaped reward to the env's next terminal slot, reset inside the step, the same accounting.  Every
+ * ending returns the limits' counters and the progression carry to the reset state.  The episode summary (bg_set_episode_summary) works as with
+ * bg_step_many_rows_ex: bytes 344..351 obey the switch; the rule reads the final ante and round whatever the switch says.
+ * progress->counters_dev: int32 [N, 4], 16-byte aligned, in/out, caller-owned: total_steps, steps_on_current_ante,
+ * (last_ante - 1) | (max_ante_reached - 1) << 16, last_round - 1 -- an all-zero row is the state after reset() (:33-41); zero it where bg_reset
+ * restarts an env.  progress == NULL: exactly bg_step_many_rows_ex.
+ * BG_E_ARG (text "bg_step_many_rows_progress: ..." in bg_last_error(h)) before anything is launched: progress without limits, a misaligned or missing
+ * carry (or the limits' own counters passed as the carry), terminal_slots below bg_progress_terminal_slots, and everything bg_step_many_rows_ex
+ * refuses (no auto-reset, BG_ENGINE=1, a limit below 3, ...). */
+#define BG_END_STUCK 8u           /* info['stuck_on_ante_1'] (train_progressive.py:96-99) */
+typedef struct bg_progress_rewards {
+  int32_t* counters_dev;
+} bg_progress_rewards;
+/* K / min(max_invalid_actions, max_episode_steps, 301) + 1: a stuck ending needs 301 steps on ante 1.  BG_E_ARG for K < 0 or a limit below 3. */
+int bg_progress_terminal_slots(int K, int max_invalid_actions, int max_episode_steps);
+int bg_step_many_rows_progress(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* rows_dev, uint64_t row_stride_bytes,
+                               int rows_stride_steps, const bg_safe_limits* limits, const bg_progress_rewards* progress,
+                               bg_rollout_stats* stats_dev, void* stream);
+
 /* The ended episode's final ante, round and score in the record of the step that ended it: a switch of the handle, off by default.
  * Replaces: what the reference's callbacks log of every finished episode -- info's ante and chips_scored at `done` (train_balatro_agent.py:189-209)
  * -- and the `ante_at_end` CurriculumBalatroEnv's rule needs (train_balatro_agent.py:126-170), which SAME_STEP auto-reset overwrites before a
