@@ -80,7 +80,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad",
            "bg_get_states", "bg_set_states", "bg_copy_states",
            "bg_set_episode_summary", "bg_episode_ends_rows",
-           "bg_step_many_rows_progress", "bg_progress_terminal_slots"]
+           "bg_step_many_rows_progress", "bg_progress_terminal_slots",
+           "bg_dqn_loss", "bg_dqn_loss_workspace_bytes", "bg_sample_actions_eps"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -96,6 +97,9 @@ HEAD_F32, HEAD_BF16, HEAD_DETERMINISTIC = 0, 1, 1   # bg_sample_actions / bg_eva
 # bg_ppo_loss: the order of stats_dev (BG_PPO_STATS floats) and its flag
 PPO_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std", "excluded", "m")
 PPO_NORMALIZE_ADV = 1
+# bg_dqn_loss: the order of stats_dev (BG_DQN_STATS floats) and its flags
+DQN_STATS = ("loss", "q_mean", "target_mean", "abs_td_mean", "abs_td_max", "done_share", "excluded", "m")
+DQN_MASK_NEXT, DQN_MSE, DQN_TIMEOUT_EXCLUDE = 1, 2, 4
 LIN_NONE, LIN_RELU = 0, 1   # bg_linear_rows / bg_linear_rows_grad (BG_LIN_*)
 LIN_ACTIVATIONS = {None: LIN_NONE, "relu": LIN_RELU}
 LIN_K = 153                 # the columns of a first-layer weight that are read: the "produced" ones
@@ -303,6 +307,10 @@ def load(build_if_missing: bool = True):
     L.bg_ppo_loss_workspace_bytes.argtypes = [i64]
     L.bg_ppo_loss.argtypes = [vp, i32, u64, vp, u64, vp, vp, vp, vp, vp, vp, i64, i64, C.c_float, C.c_float, C.c_float, u32, vp, u64, vp, vp, vp, vp, vp, u64,
                               C.POINTER(C.c_float), vp]
+    L.bg_dqn_loss_workspace_bytes.restype = u64
+    L.bg_dqn_loss_workspace_bytes.argtypes = [i64]
+    L.bg_dqn_loss.argtypes = [vp, u64, vp, u64, vp, u64, i32, vp, u64, i64, vp, vp, i64, C.c_float, u32, vp, u64, vp, vp, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_sample_actions_eps.argtypes = [vp, i32, u64, vp, u64, i64, u32, u64, u64, u64, C.c_float, vp, vp, vp, C.POINTER(C.c_float), vp]
     L.bg_linear_rows.argtypes = [vp, u64, i64, vp, i64, i32, vp, vp, C.c_double, C.c_double, vp, u64, vp, i32, i32, i32, vp, u64, C.POINTER(C.c_float), vp]
     L.bg_linear_rows_workspace_bytes.restype = u64
     L.bg_linear_rows_workspace_bytes.argtypes = [i64, i32]

@@ -363,6 +363,7 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
 #include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
 #include "bg_ppo.h"    // logits + stored rollout arrays -> PPO's clipped loss, its diagnostics and its gradient (operator-level)
+#include "bg_dqn.h"    // Q values + a ring of records -> DQN's TD loss and its gradient; epsilon-greedy in the masked head (operator-level)
 #include "bg_linear.h" // packed records -> the network's first layer and its weight gradient on the matrix cores (operator-level)
 #include "bg_snapshot.h" // many envs' state between a handle's arrays and dense blobs, or two handles (bg_get_states / bg_set_states / bg_copy_states)
 
@@ -2664,7 +2665,7 @@ int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int 
 // logits + action masks -> the policy head (bg_head.h).  The load paths follow the alignment of the caller's matrices.
 static int bg_head_call(const char* who, int mode, const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev,
                         uint64_t mask_stride_bytes, int64_t m, uint64_t seed, uint64_t index0, uint64_t t, const int32_t* actions_in, int32_t* actions_out,
-                        float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream) {
+                        float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream, float epsilon = 0.0f) {
   const bool bf16 = logits_dtype == BG_HEAD_BF16;
   const uint64_t es = bf16 ? 2u : 4u;
   const void* const act = mode == BG_HEAD_EVALUATE ? (const void*)actions_in : (const void*)actions_out;
@@ -2699,7 +2700,8 @@ static int bg_head_call(const char* who, int mode, const void* logits_dev, int l
   int rc = tm.begin(kernel_ms_out, s);
   if (rc) return rc;
 #define BG_HEAD_GO(M) hipLaunchKernelGGL((bg_head_kernel<M>), dim3(grid), dim3(BG_HEAD_BLOCK), 0, s, logits_dev, bf16 ? 1 : 0, lld, logits_stride_elems, mask_dev, mld, mask_stride_bytes, (long long)m, seed, index0, t, actions_in, actions_out, log_prob_dev, entropy_dev)
-  if (mode == BG_HEAD_SAMPLE) BG_HEAD_GO(BG_HEAD_SAMPLE); else if (mode == BG_HEAD_ARGMAX) BG_HEAD_GO(BG_HEAD_ARGMAX); else BG_HEAD_GO(BG_HEAD_EVALUATE);
+  if (mode == BG_HEAD_EPS) hipLaunchKernelGGL(bg_head_eps_kernel, dim3(grid), dim3(BG_HEAD_BLOCK), 0, s, logits_dev, bf16 ? 1 : 0, lld, logits_stride_elems, mask_dev, mld, mask_stride_bytes, (long long)m, seed, index0, t, epsilon, actions_out);
+  else if (mode == BG_HEAD_SAMPLE) BG_HEAD_GO(BG_HEAD_SAMPLE); else if (mode == BG_HEAD_ARGMAX) BG_HEAD_GO(BG_HEAD_ARGMAX); else BG_HEAD_GO(BG_HEAD_EVALUATE);
 #undef BG_HEAD_GO
   tm.mark(s);
   BG_HIP0(hipGetLastError());
@@ -2800,6 +2802,94 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
   if (bf16) hipLaunchKernelGGL((bg_ppo_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
   else hipLaunchKernelGGL((bg_ppo_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
   hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
+  tm.mark(s);
+  BG_HIP0(hipGetLastError());
+  return tm.end(kernel_ms_out);
+}
+
+// epsilon-greedy over the masked head (bg_dqn.h): bg_sample_actions' arguments and checks, plus epsilon; no log_prob / entropy
+int bg_sample_actions_eps(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
+                          uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, float epsilon, int32_t* actions_dev, float* log_prob_dev,
+                          float* entropy_dev, float* kernel_ms_out, void* stream) {
+  if (flags) { g_create_err = "bg_sample_actions_eps: flags must be 0"; return BG_E_ARG; }
+  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) { g_create_err = "bg_sample_actions_eps: epsilon must be in [0, 1]"; return BG_E_ARG; }
+  if (log_prob_dev || entropy_dev) { g_create_err = "bg_sample_actions_eps: log_prob_dev and entropy_dev must be NULL (an epsilon-greedy action has no categorical log-probability)"; return BG_E_ARG; }
+  return bg_head_call("bg_sample_actions_eps: ", BG_HEAD_EPS, logits_dev, logits_dtype, logits_stride_elems, mask_dev, mask_stride_bytes, m, seed, index0, t, nullptr,
+                      actions_dev, nullptr, nullptr, kernel_ms_out, stream, epsilon);
+}
+
+// Q values + the ring of records -> DQN's TD loss, diagnostics and gradient (bg_dqn.h).  Workspace: seven float64 values per 64 rows.
+uint64_t bg_dqn_loss_workspace_bytes(int64_t m) {
+  if (m <= 0) return 0;
+  return bg_dqn_row_parts(m) * (BG_DQN_SUMS * sizeof(double));
+}
+
+static int bg_dqn_path(const void* p, uint64_t stride, bool bf16) {
+  const uint64_t es = bf16 ? 2u : 4u;
+  const bool a16 = ((uintptr_t)p & 15) == 0;
+  if (a16 && (stride * es) % 16 == 0) return BG_HEAD_LD_ROWS16;
+  if (bf16 && a16 && stride == BG_HEAD_ACTIONS) return BG_HEAD_LD_FLAT16;
+  if (!bf16 || (((uintptr_t)p & 3) == 0 && stride % 2 == 0)) return BG_HEAD_LD_WORD;
+  return BG_HEAD_LD_HALF;
+}
+
+int bg_dqn_loss(const void* q_dev, uint64_t q_stride_elems, const void* q_next_dev, uint64_t q_next_stride_elems, const void* q_next_online_dev,
+                uint64_t q_next_online_stride_elems, int q_dtype, const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                const int32_t* next_index_dev, const float* rewards_dev, int64_t m, float gamma, uint32_t flags, void* dq_dev, uint64_t dq_stride_elems,
+                float* td_dev, float* stats_dev, void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
+  const bool bf16 = q_dtype == BG_HEAD_BF16;
+  const uint64_t es = bf16 ? 2u : 4u;
+  const void* const ins[] = {q_dev, q_next_dev, q_next_online_dev, rows_dev, next_index_dev, rewards_dev};
+  const void* const outs[] = {dq_dev, td_dev, stats_dev, workspace_dev};
+  bool alias = false;
+  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
+    if (!outs[o]) continue;
+    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
+    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
+  }
+  auto bad_matrix = [&](const void* p, uint64_t stride) { return !p || ((uintptr_t)p & (es - 1)) || stride < BG_HEAD_ACTIONS || stride > 0xffffffffull; };
+  const char* bad = nullptr;
+  if (q_dtype != BG_HEAD_F32 && q_dtype != BG_HEAD_BF16) bad = "q_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
+  else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
+  else if (flags & ~(BG_DQN_MASK_NEXT | BG_DQN_MSE | BG_DQN_TIMEOUT_EXCLUDE)) bad = "flags must be a combination of BG_DQN_MASK_NEXT, BG_DQN_MSE and BG_DQN_TIMEOUT_EXCLUDE";
+  else if (!(gamma >= 0.0f && gamma <= 1.0f)) bad = "gamma must be in [0, 1]";
+  else if (bad_matrix(q_dev, q_stride_elems)) bad = "q_dev must be a device pointer aligned to its element type, q_stride_elems >= 60";
+  else if (bad_matrix(q_next_dev, q_next_stride_elems)) bad = "q_next_dev must be a device pointer aligned to its element type, q_next_stride_elems >= 60";
+  else if (q_next_online_dev && bad_matrix(q_next_online_dev, q_next_online_stride_elems)) bad = "q_next_online_dev must be aligned to its element type, q_next_online_stride_elems >= 60";
+  else if (bad_matrix(dq_dev, dq_stride_elems)) bad = "dq_dev must be a device pointer aligned to its element type, dq_stride_elems >= 60";
+  else if (!rows_dev || ((uintptr_t)rows_dev & 15)) bad = "rows_dev must be a 16-byte aligned device pointer";
+  else if (row_stride_bytes < BG_ROW_BYTES || (row_stride_bytes & 15) || row_stride_bytes > 0xffffffffull) bad = "row_stride_bytes must be a multiple of 16, >= BG_ROW_BYTES";
+  else if (store_rows < 0 || store_rows > 0x7fffffffll) bad = "store_rows must be in [0, 2**31)";
+  else if (!next_index_dev || ((uintptr_t)next_index_dev & 3)) bad = "next_index_dev must be a 4-byte aligned device pointer";
+  else if (((uintptr_t)rewards_dev | (uintptr_t)td_dev) & 3) bad = "rewards_dev and td_dev must be 4-byte aligned";
+  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_DQN_STATS floats";
+  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_dqn_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_dqn_loss_workspace_bytes(m) bytes";
+  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  if (bad) { g_create_err = std::string("bg_dqn_loss: ") + bad; return BG_E_ARG; }
+  if (kernel_ms_out) *kernel_ms_out = 0.f;
+  hipStream_t s = (hipStream_t)stream;
+  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_DQN_STATS * sizeof(float), s)); return 0; }
+  BgDqnArgs A;
+  A.q = q_dev; A.qstride = q_stride_elems;
+  A.qn = q_next_dev; A.nstride = q_next_stride_elems; A.nld = bg_dqn_path(q_next_dev, q_next_stride_elems, bf16);
+  A.qo = q_next_online_dev; A.ostride = q_next_online_stride_elems; A.old = q_next_online_dev ? bg_dqn_path(q_next_online_dev, q_next_online_stride_elems, bf16) : BG_HEAD_LD_NONE;
+  A.rows = rows_dev; A.rstride = row_stride_bytes; A.store_rows = (long long)store_rows;
+  A.next_index = next_index_dev; A.rewards = rewards_dev; A.m = (long long)m;
+  A.gamma = gamma; A.fm = (float)m; A.flags = flags;
+  A.dq = dq_dev; A.dstride = dq_stride_elems; A.dst = bg_dqn_path(dq_dev, dq_stride_elems, bf16);
+  A.td = td_dev; A.partials = (double*)workspace_dev;
+  const uint64_t RP = bg_dqn_row_parts(m);
+  BgOpTimer tm;
+  int rc = tm.begin(kernel_ms_out, s);
+  if (rc) return rc;
+  if (q_next_online_dev) {
+    if (bf16) hipLaunchKernelGGL((bg_dqn_kernel<true, true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+    else hipLaunchKernelGGL((bg_dqn_kernel<false, true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+  } else {
+    if (bf16) hipLaunchKernelGGL((bg_dqn_kernel<true, false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+    else hipLaunchKernelGGL((bg_dqn_kernel<false, false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+  }
+  hipLaunchKernelGGL(bg_dqn_finish, dim3(1), dim3(BG_DQN_LANES), 0, s, A.partials, (long long)RP, (long long)m, stats_dev);
   tm.mark(s);
   BG_HIP0(hipGetLastError());
   return tm.end(kernel_ms_out);

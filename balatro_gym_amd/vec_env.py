@@ -149,7 +149,8 @@ class RowBuffers:
 
     def sample(self, logits: torch.Tensor, step: int = -1, **kwargs):
         """(actions, log_prob, entropy) drawn from `logits` [n, 60] under the action mask of record row `step` (`sample_actions`; seed= and t= are
-        required): the mask a record carries is the one after its step, i.e. the mask of the action to take next."""
+        required): the mask a record carries is the one after its step, i.e. the mask of the action to take next.  epsilon= gives the
+        epsilon-greedy actions of `sample_actions(epsilon=)` instead: (actions, None, None)."""
         return sample_actions(logits, self.rows[step], **kwargs)
 
     def bootstrap_rewards(self, limits: "EpisodeLimits", terminal_values: torch.Tensor, gamma: float = 0.99,
@@ -277,12 +278,12 @@ class BalatroVecEnv:
         return encode_rows(self._rowbuf.rows[0], layout, dtype, out)
 
     def act(self, logits: torch.Tensor, *, seed: int, t: int, deterministic: bool = False, log_prob: Optional[torch.Tensor] = None,
-            entropy: Optional[torch.Tensor] = None) -> torch.Tensor:
+            entropy: Optional[torch.Tensor] = None, epsilon: Optional[float] = None) -> torch.Tensor:
         """int32 [N] actions for `step()`, drawn from `logits` [N, 60] under the CURRENT action mask (`sample_actions` with index0 = 0: the live records
         of an obs_layout="rows" env, `obs["action_mask"]` otherwise), so no env takes an invalid action.  log_prob / entropy: float32 [N] tensors that
-        receive what PPO stores."""
+        receive what PPO stores.  epsilon: epsilon-greedy over `logits` as Q values instead (`sample_actions(epsilon=)`: DQN's exploration, per env)."""
         mask = self._rowbuf.rows[0] if self._rowbuf is not None else self._obs.tensors["action_mask"]
-        return sample_actions(logits, mask, seed=seed, t=t, deterministic=deterministic, log_prob=log_prob, entropy=entropy)[0]
+        return sample_actions(logits, mask, seed=seed, t=t, deterministic=deterministic, log_prob=log_prob, entropy=entropy, epsilon=epsilon)[0]
 
     @property
     def obs_flat(self) -> torch.Tensor:
@@ -1170,10 +1171,13 @@ def _head_mask(mask, lead: tuple, device: torch.device) -> tuple:
     return mask, off, stride
 
 
-def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: int, t: int, actions, log_prob, entropy, timing: bool):
+def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: int, t: int, actions, log_prob, entropy, timing: bool,
+               epsilon: Optional[float] = None):
     lead, m, pitch = _head_logits(logits)
     dev = logits.device
     mask, moff, mstride = _head_mask(mask, lead, dev)
+    if epsilon is not None:
+        return _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, index0, t, actions, log_prob, entropy, timing, epsilon)
     for what, v in (("seed", seed), ("index0", index0), ("t", t)):
         if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
             raise ValueError(f"{what} must be an integer in [0, 2**64)")
@@ -1216,18 +1220,60 @@ def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: in
     return res + (float(ms.value),) if timing else res
 
 
+def _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, index0, t, actions, log_prob, entropy, timing, epsilon):
+    """bg_sample_actions_eps: the checks of `_head_call` for the sampling form, then the epsilon-greedy launch -> (actions, None, None)."""
+    dev = logits.device
+    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
+        raise ValueError("epsilon must be a number in [0, 1] (or None: the categorical head)")
+    if flags:
+        raise ValueError("epsilon and deterministic=True exclude each other (epsilon=0.0 is the greedy rule)")
+    if log_prob is not None or entropy is not None:
+        raise ValueError("an epsilon-greedy action has no categorical log_prob / entropy: pass neither with epsilon")
+    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"{what} must be an integer in [0, 2**64)")
+    if actions is not None:
+        _check_scan_tensor("actions", actions, torch.int32, lead, dev)
+    if not logits.is_cuda:
+        raise ValueError("logits must be a device tensor (there is no CPU fallback)")
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+    if actions is None:
+        actions = torch.empty(lead, dtype=torch.int32, device=dev)
+    res = (actions, None, None)
+    if m == 0:
+        return res + (0.0,) if timing else res
+    if actions.data_ptr() in {logits.data_ptr()} | ({mask.data_ptr()} if mask is not None else set()):
+        raise ValueError("outputs must not share memory with the inputs or with each other")
+    L = nat.load()
+    ms = C.c_float(0.0)
+    with torch.cuda.device(dev):
+        rc = L.bg_sample_actions_eps(C.c_void_p(logits.data_ptr()), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
+                                     C.c_void_p(mask.data_ptr() + moff) if mask is not None else None, C.c_uint64(mstride), C.c_int64(m), C.c_uint32(0),
+                                     C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), C.c_float(float(epsilon)),
+                                     C.c_void_p(actions.data_ptr()), None, None, C.byref(ms) if timing else None,
+                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    if rc != 0:
+        raise nat.NativeError(f"bg_sample_actions_eps failed ({rc}): {L.bg_last_error(None).decode()}")
+    return res + (float(ms.value),) if timing else res
+
+
 def sample_actions(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, *, seed: int, t: int, index0: int = 0, deterministic: bool = False,
                    actions: Optional[torch.Tensor] = None, log_prob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
-                   timing: bool = False):
+                   timing: bool = False, epsilon: Optional[float] = None):
     """The masked categorical policy head in one launch (bg_sample_actions): logits float32 / bfloat16 [..., 60] -> (actions int32, log_prob float32,
     entropy float32), each [...].  mask: packed records (a contiguous uint8 tensor [..., stride]: `RowBuffers.rows[t]`, `env.obs_rows` -- their
     action_mask field is read in place), an int8 [..., 60] matrix (`obs["action_mask"]`) or None (every action valid).  A masked action is never
     drawn; a row with no valid action (or a NaN / +inf valid logit) gives action -1 and NaN.  Row i draws with the counter hash of (seed, index0 + i,
     t), the rollout's: the same arguments give the same bits, whatever the batch shape or sharding (a shard passes its first global env as index0).
     deterministic=True takes the first valid maximum instead (SB3's `mode()`).  A record's mask is the mask AFTER its step: it goes with the logits
-    computed from that record.  actions / log_prob / entropy: optional contiguous tensors to write into.  timing=True appends kernel milliseconds."""
+    computed from that record.  actions / log_prob / entropy: optional contiguous tensors to write into.  timing=True appends kernel milliseconds.
+    epsilon (None: the categorical head above, untouched): epsilon-greedy over the logits as Q values (bg_sample_actions_eps) -> (actions, None,
+    None).  Row i explores when its uniform draw u -- the one the categorical head would use -- is below epsilon, and then takes a uniformly drawn
+    valid action from a second hash; otherwise the first valid maximum.  The decision is PER ENV (SB3's DQN draws once for the whole batch, which
+    at 65 536 envs would make every env explore together).  epsilon excludes deterministic=True, log_prob and entropy."""
     return _head_call("bg_sample_actions", logits, mask, None, nat.HEAD_DETERMINISTIC if deterministic else 0, seed, index0, t, actions, log_prob,
-                      entropy, timing)
+                      entropy, timing, epsilon)
 
 
 def evaluate_actions(logits: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None, *, log_prob: Optional[torch.Tensor] = None,
@@ -1351,6 +1397,220 @@ def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Te
     if torch.is_grad_enabled() and (logits.requires_grad or (values is not None and values.requires_grad)):
         loss = _PpoLossGrad.apply(loss, dlogits, dvalues, logits, values)
     return loss, stats
+
+
+class DqnStats:
+    """What `dqn_loss` returns beside the loss: the scalars of `_native.DQN_STATS` as 0-dim float32 device tensors (views of `raw`, no host
+    synchronisation), `td` float32 [...] (q[a] - y per row, NaN on an excluded row: for prioritised replay), and the gradient the call produced --
+    `dq` [..., 60] in the dtype of q.  `kernel_ms` with timing=True."""
+
+    def __init__(self, raw, td, dq, kernel_ms=None):
+        self.raw, self.td, self.dq, self.kernel_ms = raw, td, dq, kernel_ms
+        for k, name in enumerate(nat.DQN_STATS):
+            setattr(self, name, raw[k])
+
+    def __repr__(self):
+        return "DqnStats(" + ", ".join(nat.DQN_STATS) + ", td, dq)"
+
+
+class _DqnLossGrad(torch.autograd.Function):
+    """The node `dqn_loss` hangs on its loss (`_PpoLossGrad`'s pattern): the forward pass already produced the gradient."""
+
+    @staticmethod
+    def forward(ctx, loss, dq, q):
+        ctx.save_for_backward(dq)
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        dq, = ctx.saved_tensors
+        return None, None, (dq * grad).to(dq.dtype) if ctx.needs_input_grad[2] else None
+
+
+_dqn_workspaces: dict = {}
+
+
+def _dqn_workspace(L, dev: torch.device, m: int) -> torch.Tensor:
+    need = int(L.bg_dqn_loss_workspace_bytes(C.c_int64(m)))
+    key = (dev, need)
+    if key not in _dqn_workspaces:
+        _dqn_workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+    return _dqn_workspaces[key]
+
+
+def dqn_loss(q: torch.Tensor, q_next: torch.Tensor, rows: torch.Tensor, next_index: torch.Tensor, *, q_next_online: Optional[torch.Tensor] = None,
+             rewards: Optional[torch.Tensor] = None, gamma: float = 0.99, mask_next: bool = True, loss: str = "huber", timeouts: str = "exclude",
+             timing: bool = False):
+    """SB3's `DQN.train` loss over a store of packed records, its diagnostics and its gradient with respect to q, in one pass (bg_dqn_loss):
+    -> (loss, stats).  loss: 0-dim float32; when `q` requires grad it carries an autograd node whose backward is grad_output * stats.dq -- nothing
+    is recomputed.  stats: `DqnStats`.
+    q float32 / bfloat16 [..., 60]: the online network at the OBSERVATION records (`encode_rows(store, index=index)`); q_next, same dtype and leading
+    shape: the target network at the NEXT records (`index=next_index`); q_next_online: the online network there -- given, it selects double DQN.
+    rows: the store, a contiguous uint8 [..., stride] tensor of records (`RowReplay.store`).  next_index int32 [...]: the flat row of each transition's
+    next record -- the record that holds the step's action, reward, terminated byte and end flags and the mask of the next decision, all read in
+    place.  rewards: float32 with the store's leading shape, read at next_index instead of the records' rewards (normalised rewards).
+    mask_next: the maximum over the next record's valid actions only.  loss: "huber" (SB3's smooth_l1) or "mse".  timeouts: "exclude" leaves out rows
+    that only the step limit ended (SB3 bootstraps them from a terminal observation the store does not hold); "terminal" treats them as ordinary done
+    rows.  mask_next=False, loss="huber", timeouts="terminal" is SB3's rule literally.  A row that cannot take part (next_index or action out of
+    range, non-finite reward, q[a] or target, no valid next action) is excluded: zero gradient, NaN td, counted in stats.excluded, the divisor stays m."""
+    lead, m, pitch = _head_logits(q)
+    dev = q.device
+    if not isinstance(q_next, torch.Tensor) or q_next.dtype != q.dtype:
+        raise ValueError("q_next must be a tensor [..., 60] of the dtype of q")
+    nlead, _, npitch = _head_logits(q_next)
+    if nlead != lead or q_next.device != dev:
+        raise ValueError(f"q_next must have the leading shape of q {list(lead)} on {dev}")
+    opitch = 0
+    if q_next_online is not None:
+        if not isinstance(q_next_online, torch.Tensor) or q_next_online.dtype != q.dtype:
+            raise ValueError("q_next_online must be a tensor [..., 60] of the dtype of q")
+        olead, _, opitch = _head_logits(q_next_online)
+        if olead != lead or q_next_online.device != dev:
+            raise ValueError(f"q_next_online must have the leading shape of q {list(lead)} on {dev}")
+    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 2 or not rows.is_contiguous() or rows.device != dev:
+        raise ValueError(f"rows must be a contiguous uint8 tensor [..., stride] of packed records on {dev}")
+    stride = int(rows.shape[-1])
+    if stride < nat.ROW_BYTES or stride % 16:
+        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
+    store = tuple(rows.shape[:-1])
+    store_rows = int(np.prod(store, dtype=np.int64))
+    if store_rows >= 2 ** 31:
+        raise ValueError("the store holds at most 2**31 - 1 records")
+    if not isinstance(next_index, torch.Tensor) or next_index.dtype != torch.int32 or tuple(next_index.shape) != lead or not next_index.is_contiguous() \
+            or next_index.device != dev:
+        raise ValueError(f"next_index must be a contiguous torch.int32 tensor of shape {list(lead)} on {dev}")
+    if rewards is not None:
+        _check_scan_tensor("rewards", rewards, torch.float32, store, dev)
+    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not 0.0 <= float(gamma) <= 1.0:
+        raise ValueError("gamma must be a number in [0, 1]")
+    if loss not in ("huber", "mse"):
+        raise ValueError("loss must be 'huber' or 'mse'")
+    if timeouts not in ("exclude", "terminal"):
+        raise ValueError("timeouts must be 'exclude' or 'terminal'")
+    if not q.is_cuda:
+        raise ValueError("q must be a device tensor (there is no CPU fallback)")
+    if rows.data_ptr() % 16:
+        raise ValueError("rows must be 16-byte aligned")
+    flags = (nat.DQN_MASK_NEXT if mask_next else 0) | (nat.DQN_MSE if loss == "mse" else 0) | (nat.DQN_TIMEOUT_EXCLUDE if timeouts == "exclude" else 0)
+    qd, qn = q.detach(), q_next.detach()
+    qo = q_next_online.detach() if q_next_online is not None else None
+    raw = torch.zeros(len(nat.DQN_STATS), dtype=torch.float32, device=dev)
+    dq = torch.empty(lead + (60,), dtype=q.dtype, device=dev)
+    td = torch.empty(lead, dtype=torch.float32, device=dev)
+    ms = C.c_float(0.0)
+    if m > 0:
+        L = nat.load()
+
+        def ptr(t):
+            return C.c_void_p(t.data_ptr()) if t is not None else None
+        with torch.cuda.device(dev):
+            ws = _dqn_workspace(L, dev, m)
+            rc = L.bg_dqn_loss(ptr(qd), C.c_uint64(pitch), ptr(qn), C.c_uint64(npitch), ptr(qo), C.c_uint64(opitch),
+                               nat.HEAD_F32 if q.dtype == torch.float32 else nat.HEAD_BF16, ptr(rows), C.c_uint64(stride), C.c_int64(store_rows),
+                               ptr(next_index), ptr(rewards), C.c_int64(m), C.c_float(float(gamma)), C.c_uint32(flags), ptr(dq), C.c_uint64(60), ptr(td),
+                               ptr(raw), ptr(ws), C.c_uint64(ws.numel()), C.byref(ms) if timing else None,
+                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+        if rc != 0:
+            raise nat.NativeError(f"bg_dqn_loss failed ({rc}): {L.bg_last_error(None).decode()}")
+    stats = DqnStats(raw, td, dq, float(ms.value) if timing else None)
+    out = raw[0]
+    if torch.is_grad_enabled() and q.requires_grad:
+        out = _DqnLossGrad.apply(out, dq, q)
+    return out, stats
+
+
+class RowReplay:
+    """DQN's replay buffer as a ring of packed records: `capacity_steps` slots of `n` records, [C, N, stride] uint8, 128-byte aligned.  A record
+    already carries the observation and action mask of one decision and the action, reward, terminated byte and end flags of the step that led to
+    it, so consecutive slots (s, s + 1) of one env ARE a transition and nothing is stored twice (SB3's DictReplayBuffer keeps obs and next_obs).
+    `store` goes to `encode_rows(index=)` / `RowLinear(index=)` / `dqn_loss` as it is.
+    The ring holds ONE unbroken chain of steps: `start(env.obs_rows)` writes the record before the first step, every `add(buf.rows)` the K records
+    of a `step_many` call that continues from the last record added.  Auto-reset envs never break the chain (a record whose terminated byte is set
+    already shows the new episode, and `dqn_loss` does not bootstrap across it); a caller who resets envs by hand calls `clear()` and `start()`
+    again.  Writing `step_many`'s records into the ring in place is out of scope: `add` is one device copy (two where the ring wraps)."""
+
+    def __init__(self, capacity_steps: int, n: int, device, row_stride: int = 384):
+        C_, N, stride = int(capacity_steps), int(n), int(row_stride)
+        if C_ < 2 or N < 1:
+            raise ValueError("capacity_steps must be >= 2 (a transition is two records) and n >= 1")
+        if stride < nat.ROW_BYTES or stride % 16:
+            raise ValueError(f"row_stride must be a multiple of 16 and >= the {nat.ROW_BYTES}-byte record")
+        if C_ * N >= 2 ** 31:
+            raise ValueError("capacity_steps * n must be below 2**31 (int32 row indices)")
+        self.capacity_steps, self.n, self.row_stride = C_, N, stride
+        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        nbytes = C_ * N * stride
+        self._flat = torch.zeros(nbytes + 128, dtype=torch.uint8, device=self.device)
+        off = (-self._flat.data_ptr()) % 128
+        self.store = self._flat[off:off + nbytes].view(C_, N, stride)
+        self._head = 0      # the slot the next record goes to (the write head)
+        self._filled = 0    # slots that hold a record
+
+    def __len__(self) -> int:
+        """Valid transitions: (filled slots - 1) * n."""
+        return max(self._filled - 1, 0) * self.n
+
+    def clear(self) -> None:
+        self._head, self._filled = 0, 0
+
+    def _check_records(self, what: str, t, dims: int):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != dims or tuple(t.shape[-2:]) != (self.n, self.row_stride) \
+                or t.device != self.device:
+            lead = "[K, " if dims == 3 else "["
+            raise ValueError(f"{what} must be a uint8 tensor {lead}{self.n}, {self.row_stride}] of packed records on {self.device}")
+
+    def start(self, obs_rows: torch.Tensor) -> None:
+        """Begin a chain: the record BEFORE the first step (`env.obs_rows`, [N, stride]).  Whatever the ring held is dropped."""
+        self._check_records("obs_rows", obs_rows, 2)
+        self.store[0].copy_(obs_rows)
+        self._head, self._filled = 1 % self.capacity_steps, 1
+
+    def add(self, rows_kn: torch.Tensor) -> None:
+        """Append the K step records of one `step_many` call ([K, N, stride], `RowBuffers.rows`), wrapping."""
+        self._check_records("rows_kn", rows_kn, 3)
+        K, C_ = int(rows_kn.shape[0]), self.capacity_steps
+        if K >= C_:
+            raise ValueError(f"K = {K} step records do not fit a ring of {C_} slots beside the record they continue from (K < capacity_steps)")
+        if self._filled == 0:
+            raise ValueError("start(obs_rows) writes the record before the first step; add() continues from it")
+        first = min(K, C_ - self._head)
+        self.store[self._head:self._head + first].copy_(rows_kn[:first])
+        if first < K:
+            self.store[:K - first].copy_(rows_kn[first:])
+        self._head = (self._head + K) % C_
+        self._filled = min(self._filled + K, C_)
+
+    def sample(self, m: int, generator: Optional[torch.Generator] = None):
+        """(index, next_index): int32 [m] device tensors, drawn on the device with no host synchronisation.  The slot s is uniform over the slots
+        whose successor (s + 1) % C is also filled and is not the write head, the env uniform over n; index = s * n + env names the observation
+        record, next_index = ((s + 1) % C) * n + env the record of the step taken there."""
+        m = int(m)
+        if m < 0:
+            raise ValueError("m must be >= 0")
+        count = self._filled - 1
+        if count < 1:
+            raise ValueError("the ring holds no transition yet (start() and at least one add())")
+        C_, N = self.capacity_steps, self.n
+        oldest = self._head if self._filled == C_ else 0
+        gdev = generator.device if generator is not None else self.device
+        r = torch.randint(0, count * N, (m,), generator=generator, device=gdev, dtype=torch.int64).to(self.device)
+        j, env = r // N, r % N
+        s = (j + oldest) % C_
+        return (s * N + env).to(torch.int32), (((s + 1) % C_) * N + env).to(torch.int32)
+
+    def state_dict(self) -> dict:
+        return {"store": self.store.clone(), "head": self._head, "filled": self._filled, "capacity_steps": self.capacity_steps, "n": self.n,
+                "row_stride": self.row_stride}
+
+    def load_state_dict(self, state: dict) -> None:
+        shape = (int(state["capacity_steps"]), int(state["n"]), int(state["row_stride"]))
+        if shape != (self.capacity_steps, self.n, self.row_stride):
+            raise ValueError(f"the state is of a ring {list(shape)}, this one is {[self.capacity_steps, self.n, self.row_stride]}")
+        head, filled = int(state["head"]), int(state["filled"])
+        if not 0 <= filled <= self.capacity_steps or not 0 <= head < self.capacity_steps or (filled < self.capacity_steps and head != filled % self.capacity_steps):
+            raise ValueError("the state's head / filled do not describe a ring of this capacity")
+        self.store.copy_(state["store"])
+        self._head, self._filled = head, filled
 
 
 def _check_scan_rows(rows) -> tuple:

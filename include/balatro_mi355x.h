@@ -806,6 +806,67 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
                 float* stats_dev /* float32[BG_PPO_STATS = 10] */,
                 void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* DQN over packed records: the temporal-difference loss of SB3's `DQN.train`, its gradient with respect to the online Q values and its diagnostics, in
+ * one pass over the minibatch; and epsilon-greedy exploration in the masked head above.  The arithmetic and the order of every operation are
+ * csrc/bg_dqn.h.  Replaces: the DQN branch of the reference's main training script (`--algorithm {PPO, DQN, A2C}`, train_balatro_agent.py:344-362:
+ * buffer_size 100 000, batch_size 32, exploration 1.0 -> 0.05, target_update_interval 1000, tau 1.0) between "two [m, 60] Q matrices" and "a gradient":
+ * gather -> masked max -> where(done) -> multiply-add -> smooth_l1_loss -> mean, and their backward.
+ *
+ * A ring of records is the replay buffer: record nx = next_index[i] is the transition's NEXT record and holds the action (BG_ROW_ACTION), the reward
+ * (BG_ROW_REWARD), BG_ROW_TERMINATED and BG_ROW_END_FLAGS of the step that produced it, and the action mask (BG_ROW_ACTION_MASK) of the next decision;
+ * the observation record is not an argument (the caller computed q from it).  q_dev [m, 60]: the online network at the observation records;
+ * q_next_dev [m, 60]: the target network at the next records; q_next_online_dev [m, 60], nullable: the online network at the next records (non-NULL
+ * selects double DQN).  All three BG_HEAD_F32 or BG_HEAD_BF16 (q_dtype; widened exactly), each with its own row stride >= 60 under the alignment rules
+ * of bg_ppo_loss.  rewards_dev float32 [store_rows], nullable: read at next_index[i] instead of the record's float64 reward (normalised rewards, as
+ * bg_gae_rows_ex).  All arithmetic is float32, every operation rounded on its own (no fused multiply-add); the sums across rows are float64:
+ *     a = record action;  r = float(record reward) or rewards[next_index[i]];  done = terminated != 0
+ *     V' = the j whose next-record mask byte is non-zero (BG_DQN_MASK_NEXT), else all 60
+ *     plain:   n = max over V' of q_next[j]
+ *     double:  a' = the smallest j in V' with q_next_online[j] == max over V' of q_next_online;  n = q_next[a']
+ *     y = done ? r : r + gamma * n          (a done row reads neither q_next matrix: a NaN there does not matter)
+ *     d = q[a] - y
+ *     Huber (SB3's smooth_l1, beta 1):  term = |d| < 1 ? (0.5 * d) * d : |d| - 0.5;  g = |d| < 1 ? d : copysign(1, d)
+ *     BG_DQN_MSE:                        term = d * d;  g = 2 * d
+ *     dq[i, a] = g / float(m);  every other column of the row +0.0;  padding columns of a strided dq are not written;  td[i] = d
+ * An EXCLUDED row -- next_index outside [0, store_rows) (nothing is read for it); the action outside [0, 60) (the record carries the caller's value as
+ * given); r or q[a] not finite; not done and V' empty, a Q value that enters a max NaN, or n not finite; BG_DQN_TIMEOUT_EXCLUDE set, done and
+ * end_flags == BG_END_MAX_STEPS exactly -- has a dq row of +0.0 and td = quiet NaN, adds nothing to any sum, is counted, and the divisor stays m.
+ * The last rule is the step-limit ending: SB3 bootstraps such a row from `terminal_observation`, a record that is not in the ring; without the flag it
+ * is an ordinary done row.  Bootstrapping it from the terminal record is out of scope.
+ * dq_dev: the dtype of q (bfloat16: the float32 value rounded to nearest even), its own stride.  td_dev float32 [m], nullable (for prioritised replay).
+ * stats_dev float32 [BG_DQN_STATS], each from float64 sums over the included rows rounded to float32 once: loss = (sum term) / m, mean q[a], mean y,
+ * mean |d| (each sum / m), max |d|, the share of done rows, the number of excluded rows, m.  The sums take a fixed order (64 rows per workgroup by a
+ * tree, the workgroups' partials from workspace_dev in index order by slices and a tree in a one-workgroup kernel; no floating-point atomics): two calls
+ * give the same bits.  workspace_dev: 16-byte aligned, bg_dqn_loss_workspace_bytes(m) bytes.
+ * BG_E_ARG (text "bg_dqn_loss: ..." in bg_last_error(NULL)) before anything is launched for: wrong alignment, a stride < 60, a row stride below
+ * BG_ROW_BYTES or no multiple of 16, an output that is the same pointer as an input or another output, gamma not finite or outside [0, 1],
+ * store_rows >= 2**31, a workspace too small, unknown flags.  m == 0 writes zeros to stats_dev and launches nothing else.  Never synchronises unless
+ * timing is asked for.  Out of scope: Polyak / hard target updates, the optimiser, gradient clipping, prioritised sampling, n-step returns.
+ *
+ * bg_sample_actions_eps: bg_sample_actions' arguments plus epsilon in [0, 1]; flags must be 0 and log_prob_dev / entropy_dev NULL.
+ *     h = bg_policy_hash(seed, index0 + i, t) and u = float(h >> 8) * 2^-24 as bg_sample_actions;  explore = u < epsilon (exact float32 comparison)
+ *     greedy rows take the BG_HEAD_DETERMINISTIC rule;  exploring rows take h2 = bg_policy_hash(seed + 0x632BE59BD9B4E019 mod 2^64, index0 + i, t) and,
+ *     with k the number of valid actions, the ((uint64)h2 * k) >> 32 -th valid action in index order;  a degenerate row gives -1 in both branches.
+ * DEVIATION from SB3: the decision is per env.  SB3 draws once for the whole batch, which at 65 536 envs would make every env explore together. */
+#define BG_DQN_STATS 8
+#define BG_DQN_MASK_NEXT 1u       /* flags: the max / argmax at the next record runs over its action mask */
+#define BG_DQN_MSE 2u             /* flags: squared error instead of Huber */
+#define BG_DQN_TIMEOUT_EXCLUDE 4u /* flags: leave out rows that only the step limit ended */
+uint64_t bg_dqn_loss_workspace_bytes(int64_t m);
+int bg_dqn_loss(const void* q_dev, uint64_t q_stride_elems, const void* q_next_dev, uint64_t q_next_stride_elems,
+                const void* q_next_online_dev /*nullable*/, uint64_t q_next_online_stride_elems, int q_dtype,
+                const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                const int32_t* next_index_dev, const float* rewards_dev /*nullable*/, int64_t m,
+                float gamma, uint32_t flags,
+                void* dq_dev, uint64_t dq_stride_elems, float* td_dev /*nullable*/,
+                float* stats_dev /* float32[BG_DQN_STATS = 8] */,
+                void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+int bg_sample_actions_eps(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems,
+                          const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m, uint32_t flags,
+                          uint64_t seed, uint64_t index0, uint64_t t, float epsilon,
+                          int32_t* actions_dev, float* log_prob_dev /*must be NULL*/, float* entropy_dev /*must be NULL*/,
+                          float* kernel_ms_out, void* stream);
+
 /* The network's first layer straight from the stored records, on the matrix cores, forward and backward: the features of bg_encode_rows_ex are built in
  * LDS and multiplied with the weight in the same launch, so the [m, 628] feature matrix exists neither for the forward pass nor for the weight gradient.
  * The arithmetic and the tile shapes are csrc/bg_linear.h.
