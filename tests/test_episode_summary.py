@@ -148,10 +148,11 @@ def _run_scenario(monkeypatch, cfg=None, cards=False, one_call=False, summary=Tr
     return env, rb, lim, outs
 
 
-@pytest.mark.parametrize("cfg,cards", [(None, False), (213, False), (413, False), (None, True)], ids=["113", "213", "413", "113-cards"])
+@pytest.mark.parametrize("cfg,cards", [(None, False), (213, False), (413, False), (None, True), (213, True), (413, True)],
+                         ids=["113", "213", "413", "113-cards", "213-cards", "413-cards"])
 def test_every_byte_vs_wrapped_oracle(monkeypatch, cfg, cards):
     """Every record byte 0..351 of three 48-step calls -- the summary's bytes 344..351 from the oracle's observation before the reset -- and every
-    terminal record, under all three workgroup shapes and once with card states."""
+    terminal record, under all three workgroup shapes, each also on a handle with card states."""
     _scenario_conditions()
     env, _, _, _ = _run_scenario(monkeypatch, cfg, cards)
     env.close()

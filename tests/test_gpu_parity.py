@@ -3,6 +3,7 @@
 libbalatro_mi355x.so), against (1) the committed golden traces generated from the Python reference and (2) the CPU
 oracle on fresh seeds.  Integer / byte / index results and float64 rewards must be BIT-exact (tolerance 0).
 """
+import functools
 import os
 import random
 
@@ -332,7 +333,8 @@ def _oracle_rollout(n, seeds, T, policy, pseed, scorer, max_ante, jokers, env_in
             o.set_consumables(cs)
     obs = {k: [] for k in OBS_KEYS}
     rewards = np.zeros((T, n)); terms = np.zeros((T, n), np.uint8); acts = np.zeros((T, n), np.int32)
-    stats = {"steps": 0, "episodes": 0, "plays": 0, "score_sum": 0, "reward_bits": 0}
+    # (plays_by_step / score_by_step: the same two counters per step, for callers that check a part of the run: _stats_of_steps)
+    stats = {"steps": 0, "episodes": 0, "plays": 0, "score_sum": 0, "reward_bits": 0, "plays_by_step": [0] * T, "score_by_step": [0] * T}
     for t in range(T):
         row = []
         if caps and t in caps:
@@ -359,10 +361,23 @@ def _oracle_rollout(n, seeds, T, policy, pseed, scorer, max_ante, jokers, env_in
             if info.hand_type >= 0:
                 stats["plays"] += 1
                 stats["score_sum"] += info.final_score
+                stats["plays_by_step"][t] += 1
+                stats["score_by_step"][t] += info.final_score
             row.append(ob)
         for k in OBS_KEYS:
             obs[k].append(np.stack([r[k] for r in row]))
     return {k: np.stack(v) for k, v in obs.items()}, rewards, terms, acts, stats
+
+
+def _stats_of_steps(wr, wt, wstats, lo, hi, t0=0):
+    """The five oracle-checked stats of steps lo .. hi - 1 of an _oracle_rollout run by themselves (rewards wr, terminated wt, its stats), the
+    reward checksum with step lo counted as step t0."""
+    bits = 0
+    for t in range(lo, hi):
+        for b in wr[t].view(np.uint64):
+            bits ^= (int(b) * (2 * (t0 + t - lo) + 1)) & (2 ** 64 - 1)
+    return {"steps": (hi - lo) * wr.shape[1], "episodes": int((wt[lo:hi] != 0).sum()), "plays": sum(wstats["plays_by_step"][lo:hi]),
+            "score_sum": sum(wstats["score_by_step"][lo:hi]), "reward_bits": bits}
 
 
 @pytest.mark.parametrize("layout", ["keys", "rows"])
@@ -731,6 +746,44 @@ def test_engine_env_vars_are_per_handle_and_validated(monkeypatch):
         _vec(64, [1 + i for i in range(64)])
 
 
+CARD_N, CARD_T, CARD_CHUNKS, CARD_CAP, CARD_PSEED, CARD_INDEX0 = 333, 48, 2, 6, 13, 2
+
+
+def _card_state_inputs(n):
+    """(seeds, jokers, consumables, cards) of the card-state tests: jokers from all 150 ids, two consumables per env and episode, card states on
+    half of every deck (26 of 52)."""
+    seeds = [93_000 + SEED_OFFSET + 5 * i for i in range(n)]
+    jokers = [random.Random(5200 + i).sample(range(1, 151), 5) for i in range(n)]
+    cons_ids = list(range(1, 23)) + list(range(30, 42)) + list(range(50, 68))
+    cons = [[cons_ids[(3 * i) % 52], cons_ids[(11 * i + 5) % 52]] for i in range(n)]
+    cards = []
+    for i in range(n):
+        rr = random.Random(6000 + i)
+        cards.append([(d, rr.choice([0, 1, 4, 5, 6, 7, 8]), rr.choice([0, 0, 1]), rr.choice([0, 0, 1, 2, 3, 4])) for d in rr.sample(range(52), 26)])
+    return seeds, jokers, cons, cards
+
+
+@functools.lru_cache(maxsize=None)
+def _card_state_rollout():
+    """The 333-env card-state job (cap 6, uniform policy, seed 13, env_index0 2) on the oracle, 2 x 48 steps: the inputs and _oracle_rollout's result.
+    Computed once per session and shared (the arrays are read-only); the twin handles of tests/test_engine3_instantiations.py replay its actions."""
+    seeds, jokers, cons, cards = _card_state_inputs(CARD_N)
+    out = _oracle_rollout(CARD_N, seeds, CARD_T * CARD_CHUNKS, 0, CARD_PSEED, True, CARD_CAP, jokers, env_index0=CARD_INDEX0, cards=cards, consumables=cons)
+    for a in list(out[0].values()) + list(out[1:4]):
+        a.setflags(write=False)
+    return (seeds, jokers, cons, cards), out
+
+
+def _card_state_env(n, inputs):
+    """A handle with card states and the inputs injected into the live state and the reset template."""
+    seeds, jokers, cons, cards = inputs
+    env = _vec(n, seeds, scorer_jokers=True, autoreset=True, max_ante=CARD_CAP, card_states=True)
+    env.inject(jokers=jokers, apply_now=True)
+    env.inject_cards(cards, apply_now=True)
+    env.inject_consumables(cons, apply_now=True)
+    return env
+
+
 @pytest.mark.parametrize("cfg,n", [("213", 333), ("413", 333), (None, 16385 + 63)])
 def test_card_states_every_workgroup_shape_vs_oracle(cfg, n, monkeypatch):
     """The CARDS instantiation of bg_engine3_kernel in the shapes the small tests never reached (they all ran 64 envs per workgroup): 128 and
@@ -740,25 +793,20 @@ def test_card_states_every_workgroup_shape_vs_oracle(cfg, n, monkeypatch):
     if cfg:
         monkeypatch.setenv("BG_E3_CFG", cfg)
     big = n > 4096
-    T, chunks = (6, 2) if big else (48, 2)
-    seeds = [93_000 + SEED_OFFSET + 5 * i for i in range(n)]
-    jokers = [random.Random(5200 + i).sample(range(1, 151), 5) for i in range(n)]
-    cons_ids = list(range(1, 23)) + list(range(30, 42)) + list(range(50, 68))
-    cons = [[cons_ids[(3 * i) % 52], cons_ids[(11 * i + 5) % 52]] for i in range(n)]
-    cards = []
-    for i in range(n):
-        rr = random.Random(6000 + i)
-        cards.append([(d, rr.choice([0, 1, 4, 5, 6, 7, 8]), rr.choice([0, 0, 1]), rr.choice([0, 0, 1, 2, 3, 4])) for d in rr.sample(range(52), 26)])
-    env = _vec(n, seeds, scorer_jokers=True, autoreset=True, max_ante=6, card_states=True)
-    env.inject(jokers=jokers, apply_now=True)
-    env.inject_cards(cards, apply_now=True)
-    env.inject_consumables(cons, apply_now=True)
+    T, chunks = (6, 2) if big else (CARD_T, CARD_CHUNKS)
+    if big:
+        inputs = _card_state_inputs(n)
+        seeds, jokers, cons, cards = inputs
+        wobs, wr, wt, wa, wstats = _oracle_rollout(n, seeds, T * chunks, 0, CARD_PSEED, True, CARD_CAP, jokers, env_index0=CARD_INDEX0, cards=cards, consumables=cons)
+    else:
+        assert n == CARD_N
+        inputs, (wobs, wr, wt, wa, wstats) = _card_state_rollout()
+    env = _card_state_env(n, inputs)
     rbc = [RowBuffers(n, env.device, steps=T, row_stride=384) for _ in range(chunks)]
     for c in range(chunks):
-        env.rollout(T, policy=0, policy_seed=13, env_index0=2, t0=c * T, obs_buffers=rbc[c], zero_stats=(c == 0))
+        env.rollout(T, policy=0, policy_seed=CARD_PSEED, env_index0=CARD_INDEX0, t0=c * T, obs_buffers=rbc[c], zero_stats=(c == 0))
     env.check()
     got_stats = env.stats()
-    wobs, wr, wt, wa, wstats = _oracle_rollout(n, seeds, T * chunks, 0, 13, True, 6, jokers, env_index0=2, cards=cards, consumables=cons)
     for c in range(chunks):
         sl = slice(c * T, (c + 1) * T)
         assert np.array_equal(rbc[c].action.cpu().numpy(), wa[sl])

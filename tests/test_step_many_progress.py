@@ -1,6 +1,7 @@
 """GPU tests of bg_step_many_rows_progress (BalatroVecEnv.step_many(..., limits=EpisodeLimits(progression=True), progression=ProgressionRewards)):
 ProgressionRewardWrapper's reward shaping in front of SafeBalatroEnv's limits inside the packed-record launch (bg_engine3.h's PROG instantiation).
-300 envs: one full 256-env workgroup plus a partial one of 44.  Every byte 0..351 of every record and terminal record, terminal_step, both carries
+300 envs, which the library runs in its 64-env workgroup shape (113) with 16 live envs per workgroup; tests/test_engine3_instantiations.py runs the
+scenarios here in every shape (`cfg` / `epw` / `cards` of _make and _run).  Every byte 0..351 of every record and terminal record, terminal_step, both carries
 and the stats are compared against the CPU oracle stepped on the host under tests/progress_ref.py (which tests/test_step_many_progress_host.py holds
 to the reference's own wrapper stack)."""
 import functools
@@ -29,7 +30,16 @@ SPECS = {
     "long": ((620,), (50, 610), 0, lambda i: ("idle_ante2", "idle_ante3", "idle")[i % 3]),
     # a never-valid action from step 0: killed at 50 with -50; the same begun after step 200 on ante 1: shaped to -1.2 and below, never counted
     "invalid": ((320,), (50, 1000), 0, lambda i: ("invalid", "invalid_late")[i % 2]),
+    # the progress scenario with role AND cap by the env's 64-env block as well as by i (tests/test_engine3_instantiations.py: envs 64, 128 and 192
+    # apart -- the same lane of another owner wave or slice -- never end their episodes alike; _shapes_conditions states it from the oracle side)
+    "shapes": ((32, 32, 32), (50, 1000), lambda i: 2 + i // 64, lambda i: ("play", "play_ante2", "play", "lose")[(i + i // 64) % 4]),
 }
+
+
+def _cap_of(name):
+    """The curriculum cap of env i: a spec's cap entry is one int for every env or a function of i."""
+    cap = SPECS[name][2]
+    return cap if callable(cap) else (lambda i: cap)
 
 
 def _ante0(role):
@@ -62,9 +72,9 @@ def _scenario(name, summary):
     """The scenario on the oracle under progress_ref.ProgressSafe.  Per call: actions [K, N], the expected records [K, N, 352], the expected terminal
     records [(t, e, record)], the limits' counters [N, 2] and the packed progression carry [N, 4] behind the call.  Computed once, never modified."""
     from oracle import pyoracle as po
-    calls_k, limits, cap, role_of = SPECS[name]
+    calls_k, limits, _, role_of = SPECS[name]
     roles = [role_of(i) for i in range(N)]
-    orc = [po.OracleEnv(s, max_ante=cap) for s in _seeds(name)]
+    orc = [po.OracleEnv(s, max_ante=_cap_of(name)(i)) for i, s in enumerate(_seeds(name))]
 
     def prep(o, role):
         if _ante0(role):
@@ -113,12 +123,20 @@ def _rewards(want):
     return want[:, :, R_REWARD:R_REWARD + 8].copy().view(np.float64)[:, :, 0]
 
 
-def _make(name, monkeypatch=None, shallow=False):
+def _make(name, monkeypatch=None, shallow=False, cfg=None, epw=None, cards=False):
+    """The scenario's handle.  `cfg` / `epw`: BG_E3_CFG / BG_E3_EPW, which bg_create_ex reads per handle (the workgroup shape of bg_engine3.h);
+    `cards`: a handle with card states (the CARDS instantiation; nothing is injected, so the oracle side is the same)."""
     _, limits, cap, role_of = SPECS[name]
     if shallow:
         _shallow_rings(monkeypatch)
+    if cfg is not None:
+        monkeypatch.setenv("BG_E3_CFG", str(cfg))
+    if epw is not None:
+        monkeypatch.setenv("BG_E3_EPW", str(epw))
     roles = [role_of(i) for i in range(N)]
-    env = _vec(N, _seeds(name), autoreset=True, max_ante=cap)
+    env = _vec(N, _seeds(name), autoreset=True, max_ante=0 if callable(cap) else cap, card_states=cards)
+    if callable(cap):
+        env.set_max_ante([cap(i) for i in range(N)])
     antes = [_ante0(r) for r in roles]
     levels = np.array([[15] * 12 if _leveled(r) else [0] * 12 for r in roles], np.uint8)
     if any(antes) or levels.any():
@@ -126,14 +144,14 @@ def _make(name, monkeypatch=None, shallow=False):
     return env
 
 
-def _run(name, monkeypatch=None, summary=False, one_call=False, shallow=False):
+def _run(name, monkeypatch=None, summary=False, one_call=False, shallow=False, cfg=None, epw=None, cards=False):
     """The scenario on the device, call by call (or as one call), every output against the oracle's."""
     import torch
     from balatro_gym_amd import EpisodeLimits, ProgressionRewards
     from balatro_gym_amd.vec_env import RowBuffers
     calls_k, limits, _, _ = SPECS[name]
     _, calls = _scenario(name, summary)
-    env = _make(name, monkeypatch, shallow)
+    env = _make(name, monkeypatch, shallow, cfg, epw, cards)
     groups = [calls] if one_call else [[c] for c in calls]
     KK = max(sum(len(c[0]) for c in g) for g in groups)
     rb = RowBuffers(N, env.device, steps=KK + 1, row_stride=384)
@@ -150,7 +168,7 @@ def _run(name, monkeypatch=None, summary=False, one_call=False, shallow=False):
             off += len(c[0])
         poison_(rb.rows); poison_(lim.terminal_rows); poison_(lim.terminal_step)
         env.step_many(torch.from_numpy(acts).to(env.device), obs_buffers=rb, limits=lim, progression=prog)
-        ctx = f"{name} summary {summary} call {gi}"
+        ctx = f"{name} summary {summary} call {gi}" + (f" cfg {cfg} epw {epw} cards {cards}" if cfg or epw or cards else "")
         if shallow:
             assert env.get_profile()["rollout_launches"] >= 3, ctx
         got = rb.rows.cpu().numpy()

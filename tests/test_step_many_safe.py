@@ -190,11 +190,13 @@ def _run_scenario(monkeypatch, cfg=None, cards=False, one_call=False):
     return env, rb, lim
 
 
-@pytest.mark.parametrize("cfg,cards", [(None, False), (213, False), (413, False), (None, True)], ids=["113", "213", "413", "113-cards"])
+@pytest.mark.parametrize("cfg,cards", [(None, False), (213, False), (413, False), (None, True), (213, True), (413, True)],
+                         ids=["113", "213", "413", "113-cards", "213-cards", "413-cards"])
 def test_every_byte_vs_wrapped_oracle(monkeypatch, cfg, cards):
     """Every record byte 0..351 of three 48-step calls and every terminal record against pyoracle.OracleEnv + safe_ref (on a wrapper ending the
-    oracle env is reset() and its jokers re-applied), under all three workgroup shapes and once with card states; terminal slots that were not
-    used keep their byte pattern, the counters and stats agree, env.check() is clean."""
+    oracle env is reset() and its jokers re-applied), under all three workgroup shapes, each also on a handle with card states (none injected:
+    tests/test_engine3_instantiations.py has the case with injected ones); terminal slots that were not used keep their byte pattern, the counters
+    and stats agree, env.check() is clean."""
     kills, limit_only, game = _scenario_conditions()
     env, _, _ = _run_scenario(monkeypatch, cfg, cards)
     env.close()
