@@ -33,6 +33,11 @@
 #define BG_ENG_LNE 8     // log2 of the envs per workgroup.  Only 8 is supported: 7 (128 envs: twice the workgroups for a small job) passes the parity tests and
                          // gives +9 % at 4 096 envs, 6 gives +15 % but trips a bounded wait (profiles/r03_small_workgroups_ab.txt)
 static_assert(BG_ENG_LNE == 8, "only 256 envs per workgroup are supported: items carry the env lane in 8 bits, copy-queue generations in 7, and the epilogue assumes NE = 256");
+// Bit 63 of an env's cached action mask in LDS (the mask has 60 bits): the env stands ABOVE its curriculum cap (Env::max_ante, hot chunk 7), so every
+// step it takes ends its episode, whatever the action (CurriculumBalatroEnv.step, train_balatro_agent.py:147-152) -- also a toggle, a shop leave or a
+// rejected action, which a cheap step would otherwise settle on the image with terminated = 0.  A cheap step has only chunks 3 / 4 in LDS; the bit rides
+// in a word it reads anyway (no further LDS read, no further bank conflict).  The ante changes in service steps only: the prologue and every service step set it.
+#define BG_MASK_ABOVE_CAP (1ull << 63)
 #define BG_ENG_NE (1 << BG_ENG_LNE)   // envs per workgroup: 256 (an item holds the env's lane in 8 bits; rings have NE entries, an item's generation = position >> LNE)
 // Waves per workgroup.  SEVEN, not eight: a wave of this kernel needs 256 VGPRs, so eight fill the register file of all four SIMDs and
 // nothing can be placed beside the workgroup -- the RNG refill of the previous launch (~1 ms of one-wave workgroups) then waits for
@@ -212,10 +217,11 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
       bg_unpack(c, pe);
       bg_derive_ready(pe, prod);
       const uint64_t pmask = bg_action_mask(d, envp, pe, psr);
-      s_mask[l0] = pmask;
+      const bool above = pe.max_ante > 0 && pe.ante > pe.max_ante;   // (a cap lowered below a live env's ante: bg_set_max_ante checks the reset template only)
+      s_mask[l0] = pmask | (above ? BG_MASK_ABOVE_CAP : 0ull);
       if (a.actions_in) {
         const bool valid = act0 >= 0 && act0 < 60 && ((pmask >> (act0 & 63)) & 1ull);
-        const bool terminal = pe.ante > 100 || pe.chips_scored > 1000000000ll;
+        const bool terminal = pe.ante > 100 || pe.chips_scored > 1000000000ll || above;
         const bool cheap = !terminal && (!valid || (pe.phase == 0 && act0 >= 2 && act0 < 10) || (pe.phase == 1 && act0 == 31 && pe.hand_size <= pe.nhand));
         svc = !cheap;
         if (svc) {
@@ -242,7 +248,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
       ShopRegs psr; psr.valid = false;
       bg_unpack(c, pe);
       bg_derive_ready(pe, s_prod[l0]);
-      const uint64_t pmask = s_mask[l0];
+      const uint64_t pmask = s_mask[l0] & ~BG_MASK_ABOVE_CAP;
       DeckT dk; dk.col = (lds_u32*)&s_deck[0][l0];
       const ObsPtrs none{};
       bg_write_obs_impl<false, 3>(d, envp, 0, pe, dk, none, pmask, psr, RowExtra{0.0, 0, 0u}, RowStage{(lds_u4*)&s_img[l0][0], nullptr});
@@ -472,6 +478,8 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
     auto cheap_step = [&](int& action, double& reward, StepOut& o) __attribute__((always_inline)) -> bool {
       bool fin = false;
       uint64_t mask = s_mask[l];
+      const bool above = (mask & BG_MASK_ABOVE_CAP) != 0ull;
+      mask &= ~BG_MASK_ABOVE_CAP;
       lds_u32* img32 = (lds_u32*)&s_img[l][0];
       lds_u8* img8 = (lds_u8*)&s_img[l][0];
       const uint4 c3 = s_c34[0][l];
@@ -487,7 +495,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
       }
       const int64_t chips_scored = (int64_t)(((uint64_t)img32[33] << 32) | img32[32]);
       const bool valid = action >= 0 && action < 60 && ((mask >> (action & 63)) & 1ull);
-      const bool terminal = ante > 100u || chips_scored > 1000000000ll;   // :619-623, settled by a service batch (it resets the env)
+      const bool terminal = ante > 100u || chips_scored > 1000000000ll || above;   // :619-623 and the curriculum cap, settled by a service batch (it resets the env)
       if (!terminal && valid && phase == 0u && action >= 2 && action < 10) {
         // :1052-1058 toggle position `pos` in state.selected_cards (bg_toggle_select on chunk 4)
         const int pos = action - 2;
@@ -584,7 +592,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         StepOut o;
         if (cls == BG_Q_RUN) fin = cheap_step(action, reward, o);
         else {
-          uint64_t mask = s_mask[l];
+          uint64_t mask = s_mask[l] & ~BG_MASK_ABOVE_CAP;
         action = a.actions_in ? a.actions_in[(size_t)t * N + env] : (int)((item >> 16) & 0x7fffu);
         BG_PROBE_BEGIN();
         uint4 c[BG_NHOT];
@@ -619,7 +627,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
 #pragma unroll
         for (int k = 0; k < BG_NHOT; k++) if (k != 3 && k != 4) *bg_hot(d, env, k) = c[k];
         s_c34[0][l] = c[3]; s_c34[1][l] = c[4];
-        s_mask[l] = mask;
+        s_mask[l] = mask | ((e.max_ante > 0 && e.ante > e.max_ante) ? BG_MASK_ABOVE_CAP : 0ull);   // (auto-reset off: the env stays above its cap)
         BG_PROBE(27);
         reward = o.reward; terminated = o.terminated;
         if (o.hand_type >= 0) { n_plays++; ssum += o.final_score; }

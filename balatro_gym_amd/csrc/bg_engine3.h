@@ -210,13 +210,16 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
     for (int s = 0; s < KS; s++) {
       t[s] = 0; nreq[s] = 0; waiting[s] = false;
       const int l = (wave * KS + s) * BG_BLOCK + lane;
+      // the ante above which the env is terminal when the launch starts: 100 (:619) or its curriculum cap -- a cap may have been LOWERED below a live
+      // env's ante between two launches (bg_set_max_ante checks the reset template only), and such an env ends its episode on its next step
+      uint32_t thr0 = 100u;
+      if (l < n_live) {   // (the envs past N of the last workgroup have no state)
+        const uint32_t cap = (bg_hot(d, env0 + l, 7)->w >> 16) & 0xffu;   // Env::max_ante (bg_unpack), a constant of the launch
+        if (cap > 0u && cap < 100u) thr0 = cap;
+      }
       if constexpr (ACT) {
-        abase[s] = 0; athr[s] = 100u;
+        abase[s] = 0; athr[s] = thr0;
         prow[s] = (size_t)(env0 + l);
-        if (l < n_live) {   // (the envs past N of the last workgroup have no state)
-          const uint32_t cap = (bg_hot(d, env0 + l, 7)->w >> 16) & 0xffu;   // Env::max_ante (bg_unpack), a constant of the launch
-          if (cap > 0u && cap < 100u) athr[s] = cap;
-        }
       } else {
         const int env = env0 + l;
         const uint64_t gi0 = a.env_index0 + (uint64_t)env;
@@ -240,7 +243,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
       }
       rc3[s] = s_c34[0][l]; rc4[s] = s_c34[1][l]; rmask[s] = s_mask[l];
       const lds_u32* im = (const lds_u32*)&s_img[l][0];
-      terminal[s] = bg_b(rc3[s].x, 0) > (ACT ? athr[s] : 100u) || (int64_t)(((uint64_t)im[33] << 32) | im[32]) > 1000000000ll;   // :619-623
+      terminal[s] = bg_b(rc3[s].x, 0) > thr0 || (int64_t)(((uint64_t)im[33] << 32) | im[32]) > 1000000000ll;   // :619-623
     }
     uint64_t n_steps = 0, rbits = 0, ohash = 0;
     uint32_t idle = 0, aiter = 0;
@@ -298,6 +301,8 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
             ndp[s] = true;
           }
           rc3[s] = s_c34[0][l]; rc4[s] = s_c34[1][l]; rmask[s] = s_mask[l];
+          // (a policy launch always auto-resets: behind a service wave's answer the env is at or below its cap -- the service step applied the cap and
+          //  reset the env to the template ante, which never exceeds it -- so 100 is all that is left to test, and the cap needs no live register)
           terminal[s] = bg_b(rc3[s].x, 0) > (ACT ? athr[s] : 100u) || (int64_t)(((uint64_t)img32[33] << 32) | img32[32]) > 1000000000ll;
         }
         // ---- the cheap step of every ready env (bg_engine.h: cheap_step)

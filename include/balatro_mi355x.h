@@ -157,7 +157,13 @@ int bg_create_ex(int n_envs, int device_id, uint32_t flags, int max_ante, int fu
  * cap rises by ante_increment when 80 % of the last 100 episodes reached it).  The cap is part of an env's state: it survives
  * reset() and travels in state blobs.  per_env_host == NULL sets `max_ante` for the masked envs (mask_host NULL = all),
  * otherwise per_env_host[i]; 0 = no cap; caps are in [0, 255].  The host decides WHEN to raise a cap (the statistics it needs
- * are the terminated flags and the ante of the finished episodes); see balatro_gym_amd/sb3_adapter.py CurriculumTracker. */
+ * are the terminated flags and the ante of the finished episodes); see balatro_gym_amd/sb3_adapter.py CurriculumTracker.
+ * A new cap is checked against the env's reset template only, so it may be LOWERED below the ante of a running env.  As in the reference
+ * (train_balatro_agent.py:147-152: `state.ante > current_max_ante` is tested on every step), such an env ends its episode on its NEXT
+ * step, whatever the action -- a card toggle, a shop leave or a rejected action included: terminated = 1, BG_INFO_CURRICULUM (256) in the
+ * info flags, the reward the action earns, and the reset under auto-reset.  With auto-reset off the env stays above its cap and every
+ * further step reports the same until the caller resets it.  This holds on every step path: bg_step, bg_step_rows, bg_step_many,
+ * bg_step_many_rows (with limits and progression rewards too), bg_rollout and bg_rollout_rows. */
 int bg_set_max_ante(bg_handle* h, int max_ante, const int32_t* per_env_host /*[N] or NULL*/, const uint8_t* mask_host, void* stream);
 int bg_destroy(bg_handle* h);
 const char* bg_last_error(const bg_handle* h); /* also valid with h == NULL after a failed bg_create */

@@ -327,3 +327,113 @@ def test_reference_wrapper_over_the_drop_in_space():
     with np.load(os.path.join(GOLD, "sb3_fixed.npz")) as z:
         assert [str(x) for x in z["keys"]] == list(fixed["keys"])
         assert [str(x) for x in z["dtypes"]] == list(fixed["dtype"])
+
+
+# ---------------------------------------------------------------------------------------------------------
+# Envs ABOVE their curriculum cap (train_balatro_agent.py:147-152): the live reference, not a log -- skipped where the reference tree is absent
+# ---------------------------------------------------------------------------------------------------------
+@pytest.fixture
+def live_reference():
+    """The reference imported into this process (oracle/refharness.py).  Its root goes on sys.path for the length of the test and comes off again: the
+    tree holds a `tests` package of its own, which a process spawned later in the run (tests/test_sharded_gloo.py) would import in place of this one."""
+    import sys
+    if not rh.reference_available():
+        pytest.skip("the reference tree is not on this machine")
+    if rh.REFERENCE_ROOT not in sys.path:
+        sys.path.insert(0, rh.REFERENCE_ROOT)
+    rh.load_reference()
+    yield
+    while rh.REFERENCE_ROOT in sys.path:
+        sys.path.remove(rh.REFERENCE_ROOT)
+
+
+def _above_cap_lockstep(seed, lowered):
+    """Reference and oracle with level-15 hands under the uniform policy until the ante is at least 3; then, `lowered`: max_ante 3 -> 1 on both, else
+    the cap is 2 from the start and play itself exceeds it.  From the first step above the cap on NEITHER side is reset, and the actions cycle
+    through the kinds of tests/above_cap_ref.py by the env's phase: a toggle, an out-of-range action, an in-range action the mask forbids, PLAY_HAND,
+    a blind selection, a shop leave, DISCARD, a shop reroll.  Observation, reward, terminated and the curriculum flag at every step; returns how many
+    steps were taken above the cap per kind of step (above_cap_ref.DONE)."""
+    from tests import above_cap_ref as ac
+    cap = 3 if lowered else 2
+    r = rh.RefEnv(seed, max_ante=cap)
+    o = po.OracleEnv(seed, max_ante=cap)
+    for e in (r, o):
+        for ht in range(12):
+            e.set_hand_level(ht, 15)
+    obs = r.obs()
+    assert_obs_equal(o.obs(), obs, f"seed {seed} initial")
+    done = np.zeros(len(ac.DONE), np.int64)
+    t = above_steps = 0
+    while above_steps < 18:
+        assert t < 2000, "the ante never rose above the cap"
+        if lowered and cap == 3 and int(obs["ante"]) >= 3:
+            cap = 1
+            r.max_ante = 1
+            o.set_max_ante(1)
+        above = int(obs["ante"]) > cap
+        if above:
+            a = ac.kind_action(ac.kind_of(seed, t, int(obs["phase"])), seed, t, obs["action_mask"])
+            done[ac.classify(int(obs["phase"]), a, obs["action_mask"])] += 1
+            above_steps += 1
+        else:
+            a = rh.policy_action(obs["action_mask"], int(obs["phase"]), rh.POLICY_UNIFORM, 11, seed, t)
+            assert o.policy_action(rh.POLICY_UNIFORM, 11, seed, t) == a
+        ctx = f"seed {seed} lowered {lowered} t {t} action {a} above {above}"
+        if not 0 <= a < 60:
+            # the reference indexes its mask with the action (balatro_env_2.py:1424): an action of 60 or more raises IndexError before anything changes
+            # (and a negative one would index from the end).  A batch cannot raise: the restatement rejects it -- reward -1.0, nothing changes -- and the
+            # cap rule of the wrapper then applies as to any other step
+            a = max(a, 60)
+            with pytest.raises(IndexError):
+                r.step(a)
+            obs_o, ro, to, _, io = o.step(a)
+            assert_obs_equal(obs_o, r.obs(), ctx)
+            assert ro == -1.0 and to and io.flags & 256 and io.error, ctx
+            t += 1
+            continue
+        obs, rr, tr, _, ir = r.step(a)
+        obs_o, ro, to, _, io = o.step(a)
+        assert_obs_equal(obs_o, obs, ctx)
+        assert ro == rr and to == tr, f"{ctx}: reward {ro!r} vs {rr!r}, terminated {to} vs {tr}"
+        assert bool(io.flags & 256) == bool(ir.get("curriculum_limit_reached", False)), ctx
+        if above:
+            assert tr and io.flags & 256, f"{ctx}: a step above the cap that does not end the episode"
+        elif tr and int(obs["ante"]) <= cap:   # (an ending below the cap, a lost blind: both sides start again; the step that EXCEEDS the cap is stepped on)
+            r.reset(); o.reset()
+            for e in (r, o):
+                for ht in range(12):
+                    e.set_hand_level(ht, 15)
+            obs = r.obs()
+            assert_obs_equal(o.obs(), obs, ctx + " reset")
+        t += 1
+    return done
+
+
+@pytest.mark.parametrize("lowered", [True, False], ids=["cap_lowered", "cap_exceeded_by_play"])
+def test_env_lockstep_above_the_cap(lowered, live_reference):
+    """The ground truth tests/test_above_cap.py rests on: an env above its cap -- because the cap was lowered below its ante, or because play exceeded
+    it -- that is stepped on WITHOUT a reset ends its episode on every step, whatever the action, and the state moves on as the action says."""
+    from tests import above_cap_ref as ac
+    done = np.zeros(len(ac.DONE), np.int64)
+    for seed in range(7100, 7124):
+        done += _above_cap_lockstep(seed, lowered)
+    got = dict(zip(ac.DONE, done.tolist()))
+    assert all(got[k] >= 8 for k in ("toggle", "leave", "invalid", "play")), got
+    assert got["blind"] == 0, got   # never on offer above ante 1 (above_cap_ref.DONE): the forced case below
+
+
+def test_blind_selection_above_the_cap_vs_reference(live_reference):
+    """A blind selection above the cap cannot arise by play (the game offers one only behind a reset); forced by set_ante on both sides it ends the
+    episode like any other step, and the blind is selected."""
+    for seed, blind in ((7200, 45), (7201, 45), (7202, 48)):
+        r = rh.RefEnv(seed, max_ante=1)
+        o = po.OracleEnv(seed, max_ante=1)
+        for e in (r, o):
+            e.set_ante(3)
+        obs = r.obs()
+        assert int(obs["phase"]) == 2 and obs["action_mask"][blind]
+        for a in (blind, 2, 59, 3):
+            obs, rr, tr, _, ir = r.step(a)
+            obs_o, ro, to, _, io = o.step(a)
+            assert_obs_equal(obs_o, obs, f"seed {seed} action {a}")
+            assert ro == rr and to == tr and tr and io.flags & 256 and ir.get("curriculum_limit_reached"), (seed, a, ro, rr, to, tr)
