@@ -60,14 +60,13 @@ BG_HD size_t bg_ndeck_chunks(size_t N, size_t KD) { return N * KD * BG_NDECK; }
 #define BG_DEVERR_SHOPRING 8u // pre-seeded shop ring empty at shop generation
 
 // Agent-scope (sc1) accesses: they bypass the CU's vector L1, which another CU's stores never refresh (MI355X_MICROARCH.md, "inter-workgroup
-// visibility").  The two-kernel engine (bg_engine2.h) serves an env's steps on whichever CU of its XCD has a free service wave, so every
-// load of MUTABLE per-env state on the service path goes through these; stores are plain (they reach the XCD's L2, the one point all
-// accesses to that env share during a launch).
+// visibility").  They came with a retired engine that served an env's steps on whichever CU of its XCD had a free service wave; both
+// engines of today touch an env's state from one CU only.  What still goes through them -- the shop chunks of the cold state (bg_shop_load)
+// and a deck index beyond the first 16 cards (bg_card) -- is live code that emits these loads; stores are plain.
 typedef __attribute__((address_space(1))) unsigned long long g_u64;
 typedef __attribute__((address_space(1))) uint32_t g_u32;
 __device__ __forceinline__ unsigned long long bg_ld8a(const void* p) { return __hip_atomic_load((g_u64*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint32_t bg_ld4a(const void* p) { return __hip_atomic_load((g_u32*)p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-__device__ __forceinline__ void bg_st8a(void* p, unsigned long long v) { __hip_atomic_store((g_u64*)p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
 __device__ __forceinline__ uint4 bg_ld16a(const void* p) { // two 8-byte agent-scope loads (global_load_dwordx2 sc1)
   const unsigned long long a = bg_ld8a(p), b = bg_ld8a((const char*)p + 8);
   return make_uint4((uint32_t)a, (uint32_t)(a >> 32), (uint32_t)b, (uint32_t)(b >> 32));
@@ -303,18 +302,15 @@ __shared__ unsigned long long bg_probe_lds[32];
 #define BG_PROBE_FLUSH(d) do {} while (0)
 #endif
 
-// The 52 card codes of an env's deck, as seen by the step code.  lane-per-env kernels keep the first 16 in registers
-// and read the rest from HBM; the block-compacted rollout kernel keeps every deck of its workgroup in LDS
-// ([dword 0..15][lane of the workgroup], bank = lane) so that no card lookup of a step -- phase B's gather, the boss
+// The 52 card codes of an env's deck, as seen by the step code.  lane-per-env kernels and bg_engine3.h keep the first 16 in
+// registers and read the rest from HBM (Deck0); bg_engine.h keeps every deck of its workgroup in LDS
+// ([dword 0..15][lane of the workgroup], bank = lane: DeckLdsS below) so that no card lookup of a step -- the play's gather, the boss
 // checks, the observation's hand -- is an HBM round trip.
-#define BG_RB 128 // envs per workgroup of bg_rollout2_kernel: two workgroups per CU, whose phases overlap each other
 typedef __attribute__((address_space(3))) uint8_t lds_u8;
 typedef __attribute__((address_space(3))) uint32_t lds_u32;
 struct Deck0 { uint64_t lo, hi; static constexpr bool kCards = false; };   // first 16 cards in registers, the rest read from HBM
-struct DeckLds { lds_u32* col; static constexpr bool kCards = false; };     // &s_deck[0][lane of the workgroup]
-// the same decks in kernels built for card states (cards.py CardState: enhancement / edition / seal per deck index)
+// the same deck in kernels built for card states (cards.py CardState: enhancement / edition / seal per deck index)
 struct Deck0C : Deck0 { static constexpr bool kCards = true; };
-struct DeckLdsC : DeckLds { static constexpr bool kCards = true; };
 #define BG_NCST 7 // 16-byte chunks of card state per env
 __device__ __forceinline__ uint32_t bg_cstate(const BgDev& d, int env, int ci) { // enh | edition << 4 | seal << 8
   return (uint32_t)((const uint16_t*)&d.cstate[(size_t)(ci >> 3) * d.N + env])[ci & 7];
@@ -330,9 +326,6 @@ __device__ __forceinline__ Deck0 bg_load_deck0(const BgDev& d, int env) {
 __device__ __forceinline__ void bg_deck_set(Deck0& dk, int k, uint4 c) {
   if (k == 0) { dk.lo = ((uint64_t)c.y << 32) | c.x; dk.hi = ((uint64_t)c.w << 32) | c.z; }
 }
-__device__ __forceinline__ void bg_deck_set(DeckLds& dk, int k, uint4 c) {
-  dk.col[(4 * k) * BG_RB] = c.x; dk.col[(4 * k + 1) * BG_RB] = c.y; dk.col[(4 * k + 2) * BG_RB] = c.z; dk.col[(4 * k + 3) * BG_RB] = c.w;
-}
 __device__ __forceinline__ int bg_card(const BgDev& d, int env, const Deck0& k, int idx) {
   if (idx < 16) return (int)(((idx < 8 ? k.lo : k.hi) >> (8 * (idx & 7))) & 0xffull);
   const uint32_t* p = (const uint32_t*)bg_deck(d, env, idx >> 4);   // (rare: past the L1, see bg_ld4a)
@@ -347,9 +340,6 @@ __device__ __forceinline__ void bg_deck_set(DeckLdsS<S, C>& dk, int k, uint4 c) 
 template <int S, bool C>
 __device__ __forceinline__ int bg_card(const BgDev& d, int env, const DeckLdsS<S, C>& k, int idx) {
   return (int)((const lds_u8*)k.col)[(idx >> 2) * (S * 4) + (idx & 3)];
-}
-__device__ __forceinline__ int bg_card(const BgDev& d, int env, const DeckLds& k, int idx) {
-  return (int)((const lds_u8*)k.col)[(idx >> 2) * (BG_RB * 4) + (idx & 3)];
 }
 
 // The first 16 cards of the deck in two registers: every deck index a hand normally holds (the hand is a
@@ -481,13 +471,6 @@ __device__ __forceinline__ const uint32_t* bg_gpeek_addr(const BgDev& d, int env
   ok = e.g_valid >= need;
   return bg_gblock(d, env, ok ? blk : e.g_cur) + (ok ? idx : 0);
 }
-// one raw word `off` positions ahead, for its LINE (nobody looks at the value; 0 without a load when the ring does not hold it yet)
-__device__ __forceinline__ uint32_t bg_gtouch(const BgDev& d, int env, const Env& e, int off) {
-  int idx = e.g_idx + off, blk = e.g_cur, need = 1;
-  if (idx >= BG_MT_N) { idx -= BG_MT_N; blk = (blk + 1 == d.KG) ? 0 : blk + 1; need = 2; }
-  if (idx >= BG_MT_N) { idx -= BG_MT_N; blk = (blk + 1 == d.KG) ? 0 : blk + 1; need = 3; }
-  return e.g_valid >= need ? bg_gblock(d, env, blk)[idx] : 0u;
-}
 // the 12 tempered words `skip` positions ahead of the cursor, in three (unaligned) 16-byte loads: the spare words behind a
 // ring block mirror the head of the next one (bg_refill_gblk_kernel).  avail = which of them the ring already holds.
 struct __attribute__((packed, aligned(4))) BgU4 { uint32_t x, y, z, w; };
@@ -564,7 +547,7 @@ __device__ __forceinline__ void bg_shop_overflow(const BgDev& d, int env, Env& e
 }
 __device__ __forceinline__ const uint32_t* bg_sbase(const BgDev& d, int env, const Env& e, bool& full) {
   full = (e.bflags & BG_BF_SHOP_OVF) != 0;
-  // the overflow block may have been (re)written by another CU since this CU last cached its lines (two-kernel engine): rare path, one L1 invalidate
+  // (rare path, one L1 invalidate; the fence came with a retired engine that served an env from several CUs -- today one CU writes and reads the block)
   if (full) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
   return full ? bg_sovf(d, env) : bg_sblock(d, env, e.s_cur);
 }

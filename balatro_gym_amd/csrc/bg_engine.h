@@ -112,6 +112,32 @@ __device__ __forceinline__ void bg_lds_st(uint16_t* p, uint32_t v) {
   __hip_atomic_store(p, (uint16_t)v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
 }
 __device__ __forceinline__ void bg_vm_drain() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); }
+
+// ---- the queue protocol's arithmetic, stated once for this file and bg_engine3.h (LNE = log2 of a ring's positions = of the workgroup's envs).
+// Only what compiles to the instructions it replaced is here: DESIGN.md, "Source-only changes to the engines".
+// A ring's item: env lane | generation of its ring position << 8 | 15 bits for the action << 16 | VALID.
+template <int LNE>
+__device__ __forceinline__ uint32_t bg_q_item(uint32_t l, uint32_t slot, uint32_t act15 = 0u) {
+  return l | (((slot >> LNE) & 0xffu) << 8) | (act15 << 16) | BG_ITEM_VALID;
+}
+// items between a queue's head and its tail, as read by a wave that polls both (never more than the envs there are: anything else is a torn pair)
+template <int LNE>
+__device__ __forceinline__ uint32_t bg_q_queued(uint32_t tail, uint32_t head) { const uint32_t k = tail - head; return k <= (1u << LNE) ? k : 0u; }
+// Does `item` carry the generation of ring position `pos`?  A producer bumps the tail first and writes the item next, so a claimer polls its slot
+// until this holds (bounded by BG_SPIN_LIMIT; the loop itself stays with each claimer: as one shared function it compiled differently).
+template <int LNE>
+__device__ __forceinline__ bool bg_q_is(uint32_t item, uint32_t pos) { return (item & (BG_ITEM_VALID | 0xff00u)) == (BG_ITEM_VALID | (((pos >> LNE) & 0xffu) << 8)); }
+// Per-lane constants of the WHOLE-LINE copy-out (records 384 bytes apart = 24 pieces: the image's 22 and two of zeros).  Eight records are exactly
+// three rounds of the wave, so which record of its group of eight (rsel) and which piece a lane handles in round j is a per-lane constant: no
+// division, no selects in the loop.  Image byte address = env lane * mul + ib (images `pitch` bytes apart; a padding piece: 0 * lane + the zero
+// piece, `zero_off` bytes behind image 0); gl = the piece's byte offset in the record.  (One round per call, the arrays and the loop over j stay
+// with the caller: filling the four arrays in one call compiled differently.)
+__device__ __forceinline__ void bg_line_const(int lane, int j, uint32_t pitch, uint32_t zero_off, uint32_t& rsel, uint32_t& mul, uint32_t& ib, uint32_t& gl) {
+  const uint32_t pidx = (uint32_t)j * BG_BLOCK + (uint32_t)lane, rs = (pidx * 2731u) >> 16, c = pidx - 24u * rs;
+  rsel = rs; gl = 16u * c;
+  mul = c < 22u ? pitch : 0u;
+  ib = c < 22u ? 16u * c : zero_off;
+}
 #ifdef BG_ENG_TL   // development: the timeline of a workgroup in 10 ns ticks, summed over workgroups into d.dbg (tools/eng_timeline.py)
 constexpr bool kEngTl = true;
 #else
@@ -227,7 +253,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         if (svc) {
           const int q = (!terminal && pe.phase == 0 && act0 == 0) ? BG_Q_PLAY : BG_Q_OTHER;
           const uint32_t slot = __hip_atomic_fetch_add(&s_tail[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);   // (< NE: generation 0)
-          bg_lds_st(&s_q[q][slot & (NE - 1)], (uint32_t)l0 | (((slot >> BG_ENG_LNE) & 0xffu) << 8) | (((uint32_t)act0 & 0x7fffu) << 16) | BG_ITEM_VALID);
+          bg_lds_st(&s_q[q][slot & (NE - 1)], bg_q_item<BG_ENG_LNE>((uint32_t)l0, slot, (uint32_t)act0 & 0x7fffu));
         }
       }
     }
@@ -251,9 +277,9 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
       const uint64_t pmask = s_mask[l0] & ~BG_MASK_ABOVE_CAP;
       DeckT dk; dk.col = (lds_u32*)&s_deck[0][l0];
       const ObsPtrs none{};
-      bg_write_obs_impl<false, 3>(d, envp, 0, pe, dk, none, pmask, psr, RowExtra{0.0, 0, 0u}, RowStage{(lds_u4*)&s_img[l0][0], nullptr});
+      bg_write_obs_impl<3>(d, envp, 0, pe, dk, none, pmask, psr, RowExtra{0.0, 0, 0u}, RowStage{(lds_u4*)&s_img[l0][0], nullptr});
       const uint32_t slot = __hip_atomic_fetch_add(&s_tail[BG_Q_RUN], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      bg_lds_st(&s_q[BG_Q_RUN][slot & (NE - 1)], (uint32_t)l0 | (((slot >> BG_ENG_LNE) & 0xffu) << 8) | BG_ITEM_VALID);
+      bg_lds_st(&s_q[BG_Q_RUN][slot & (NE - 1)], bg_q_item<BG_ENG_LNE>((uint32_t)l0, slot));
     }
   }
   if (tid == 0) BG_TL(4);
@@ -314,12 +340,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         lds_cc* const imgb = (lds_cc*)&s_img[0][0];
         lds_cc* const cqb = (lds_cc*)&s_cq[0];
 #pragma unroll
-        for (int j = 0; j < 3; j++) {
-          const uint32_t pidx = (uint32_t)j * BG_BLOCK + (uint32_t)lane, rs = (pidx * 2731u) >> 16, c = pidx - 24u * rs;
-          rsel[j] = rs; gl[j] = 16u * c;
-          mul[j] = c < 22u ? 16u * BG_ENG_IMG_PIECES : 0u;                     // image byte address = l * mul + ib
-          ib[j] = c < 22u ? 16u * c : (uint32_t)((lds_cc*)&s_zero - imgb);
-        }
+        for (int j = 0; j < 3; j++) bg_line_const(lane, j, 16u * BG_ENG_IMG_PIECES, (uint32_t)((lds_cc*)&s_zero - imgb), rsel[j], mul[j], ib[j], gl[j]);
         for (uint32_t g0 = 0; g0 < nb; g0 += 32u) {
           bg_u32x2 ce[4][3];
           bg_u32x4 v[4][3];
@@ -375,7 +396,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         base = __builtin_amdgcn_readlane(base, __ffsll((long long)rm) - 1);
         if (valid && !through) {
           const uint32_t slot = base + __builtin_amdgcn_mbcnt_hi((uint32_t)(rm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)rm, 0u));
-          bg_lds_st(&s_q[BG_Q_RUN][slot & (NE - 1)], (ent.y & 0xffu) | (((slot >> BG_ENG_LNE) & 0xffu) << 8) | BG_ITEM_VALID);
+          bg_lds_st(&s_q[BG_Q_RUN][slot & (NE - 1)], bg_q_item<BG_ENG_LNE>(ent.y & 0xffu, slot));
         }
       }
       if (dm && lane == 0) __hip_atomic_fetch_add(&s_done, (uint32_t)__popcll(dm), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -406,9 +427,8 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
     const bg_u32x4 ct = *(volatile __attribute__((address_space(3))) bg_u32x4*)&s_ctl[0];
     asm volatile("" ::: "memory");
     const uint32_t hr = __builtin_amdgcn_readfirstlane(ch.x), hp = __builtin_amdgcn_readfirstlane(ch.y), ho = __builtin_amdgcn_readfirstlane(ch.z);
-    auto queued = [&](uint32_t tail, uint32_t head) -> uint32_t { const uint32_t k = tail - head; return k <= (uint32_t)NE ? k : 0u; }; // (never more than the envs there are)
-    const uint32_t nr = queued(__builtin_amdgcn_readfirstlane(ct.x), hr);
-    const uint32_t np = can_serve ? queued(__builtin_amdgcn_readfirstlane(ct.y), hp) : 0u, no = can_serve ? queued(__builtin_amdgcn_readfirstlane(ct.z), ho) : 0u;
+    const uint32_t nr = bg_q_queued<BG_ENG_LNE>(__builtin_amdgcn_readfirstlane(ct.x), hr);
+    const uint32_t np = can_serve ? bg_q_queued<BG_ENG_LNE>(__builtin_amdgcn_readfirstlane(ct.y), hp) : 0u, no = can_serve ? bg_q_queued<BG_ENG_LNE>(__builtin_amdgcn_readfirstlane(ct.z), ho) : 0u;
     int cls = -1;
     if (np >= a.th_play) cls = BG_Q_PLAY;          // a service-capable wave serves first: the long chains are the critical path
     else if (no >= a.th_other) cls = BG_Q_OTHER;
@@ -468,9 +488,9 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
     uint32_t t = 0;
     if ((uint32_t)lane < nb) {
       uint32_t spin = 0;
-      const uint32_t want = BG_ITEM_VALID | ((((head + (uint32_t)lane) >> BG_ENG_LNE) & 0xffu) << 8);
-      while ((item & (BG_ITEM_VALID | 0xff00u)) != want && ++spin < BG_SPIN_LIMIT) { __builtin_amdgcn_s_sleep(1); item = bg_lds_ld(slotp); }
-      if ((item & (BG_ITEM_VALID | 0xff00u)) != want) atomicOr(d.err, BG_DEVERR_SPIN);
+      const uint32_t pos = head + (uint32_t)lane;
+      while (!bg_q_is<BG_ENG_LNE>(item, pos) && ++spin < BG_SPIN_LIMIT) { __builtin_amdgcn_s_sleep(1); item = bg_lds_ld(slotp); }
+      if (!bg_q_is<BG_ENG_LNE>(item, pos)) atomicOr(d.err, BG_DEVERR_SPIN);
       else { active = true; l = (int)(item & 0xffu); env = env0 + l; t = s_t[l]; }
     }
     // one CHEAP step of this lane's env on its image: a card-select toggle, shop end, or an action the guards reject; anything
@@ -532,7 +552,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
       else {
         const int q = (!terminal && phase == 0u && action == 0) ? BG_Q_PLAY : BG_Q_OTHER;
         const uint32_t slot = __hip_atomic_fetch_add(&s_tail[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-        bg_lds_st(&s_q[q][slot & (NE - 1)], (uint32_t)l | (((slot >> BG_ENG_LNE) & 0xffu) << 8) | (((uint32_t)action & 0x7fffu) << 16) | BG_ITEM_VALID);
+        bg_lds_st(&s_q[q][slot & (NE - 1)], bg_q_item<BG_ENG_LNE>((uint32_t)l, slot, (uint32_t)action & 0x7fffu));
         active = false;                                                   // the env is the service queue's now
       }
       if (fin) {
@@ -609,6 +629,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         bg_win_init(w, &s_win[serve_idx][0][lane], &jt);
         bg_step_init(o);
         if constexpr (INFO) if (a.info.score_breakdown) o.bd_dst = a.info.score_breakdown + row * 8;
+        // (guards, dispatch and the cap rule are spelt out here and in bg_engine3.h's service step, not shared: DESIGN.md, "Source-only changes to the engines")
         if (bg_step_guards(e, mask, action, o)) bg_env_dispatch(d, env, e, w, sr, dk, action, o);
         BG_PROBE(cls == BG_Q_PLAY ? 20 : 21);
         if (e.max_ante > 0 && e.ante > e.max_ante) { o.terminated = true; o.flags |= 256; }
@@ -620,7 +641,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
         BG_PROBE(25);
         {
           const ObsPtrs none{};   // (the image only -- per-key arrays are written from it, by finish() or behind the loop; bg_engine3.h's service step has the note on what passing a.obs costs in scalar registers)
-          bg_write_obs_impl<false, 3>(d, env, row, e, dk, none, mask, sr, RowExtra{o.reward, action, o.terminated ? 1u : 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
+          bg_write_obs_impl<3>(d, env, row, e, dk, none, mask, sr, RowExtra{o.reward, action, o.terminated ? 1u : 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
         }
         BG_PROBE(26);
         bg_pack(e, c);
@@ -655,7 +676,7 @@ __global__ __launch_bounds__(BG_ENG_NW * BG_BLOCK, BG_ENG_OCC) void bg_engine_ke
     // ---- hand the remaining envs back to the run queue
     if (active) {
       const uint32_t slot = __hip_atomic_fetch_add(&s_tail[BG_Q_RUN], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      bg_lds_st(&s_q[BG_Q_RUN][slot & (NE - 1)], (uint32_t)l | (((slot >> BG_ENG_LNE) & 0xffu) << 8) | BG_ITEM_VALID);
+      bg_lds_st(&s_q[BG_Q_RUN][slot & (NE - 1)], bg_q_item<BG_ENG_LNE>((uint32_t)l, slot));
     }
     if (lane == 0) __hip_atomic_fetch_sub(&s_busy, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); // after the pushes of this batch
     if constexpr (kEngTl) if (lane == 0) {

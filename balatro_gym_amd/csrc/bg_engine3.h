@@ -102,6 +102,7 @@ struct E3Lds {
 //   * a stuck ending the env did not make itself is a wrapper-made ending like a kill: terminal record, reset-only request, BG_END_STUCK in byte 343;
 //   * every ending returns the wrapper's state to reset()'s: four zero words.
 // (the body of the kernels below: bg_engine3_kernel's own template list stops at SAFE, and the PROG launches have a kernel name of their own)
+// (KS is 1 in every instantiation; why it is still a parameter: DESIGN.md, "Source-only changes to the engines")
 template <bool HASH, bool CARDS, int NOW, int KS, int NSV, bool ACT, bool SAFE, bool PROG>
 // (Round 5 measured reading the arguments THROUGH the kernarg segment pointer instead of as by-value parameters -- whose 16-register blocks the compiler
 //  spills to VGPR lanes and reloads whole, 12 % of the kernel's instructions being v_readlane / v_writelane / s_nop: SGPR spills 237 -> 61, 14 454 -> 13 114
@@ -161,7 +162,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
       const uint64_t mask = bg_action_mask(d, env, e, sr);
       s_mask[l] = mask;
       const ObsPtrs none{};
-      bg_write_obs_impl<false, 3>(d, env, 0, e, dk, none, mask, sr, RowExtra{0.0, 0, 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
+      bg_write_obs_impl<3>(d, env, 0, e, dk, none, mask, sr, RowExtra{0.0, 0, 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
     }
   }
   __syncthreads();
@@ -180,12 +181,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
     // per-lane constants of the whole-line copy-out (bg_engine.h, copier): eight records = three rounds of the wave
     uint32_t rsel[3], cmul[3], cib[3], cgl[3];
 #pragma unroll
-    for (int j = 0; j < 3; j++) {
-      const uint32_t pidx = (uint32_t)j * BG_BLOCK + (uint32_t)lane, rs = (pidx * 2731u) >> 16, c = pidx - 24u * rs;
-      rsel[j] = rs; cgl[j] = 16u * c;
-      cmul[j] = c < 22u ? 16u * 22u : 0u;
-      cib[j] = c < 22u ? 16u * c : (uint32_t)((lds_cc*)&s_zero - imgb);
-    }
+    for (int j = 0; j < 3; j++) bg_line_const(lane, j, 16u * 22u, (uint32_t)((lds_cc*)&s_zero - imgb), rsel[j], cmul[j], cib[j], cgl[j]);
     uint32_t t[KS], nreq[KS];   // per slice: steps done; requests posted (the service wave counts them in s_ans)
     bool waiting[KS], terminal[KS];
     // chunks 3 / 4 and the action mask of the lane's env live in REGISTERS between two service steps (a toggle is then LDS writes only -- the image --,
@@ -356,7 +352,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
             if constexpr (ACT) img32[43] = (uint32_t)action;   // the whole int32, for the service wave (BG_ROW_ACTION: it writes the same value back)
             const int q = (!term && phase == 0u && action == 0) ? 0 : 1;
             const uint32_t slot = __hip_atomic_fetch_add(&s_ctl[q], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            bg_lds_st(&s_q[q][slot & (NE - 1)], (uint32_t)l | (((slot >> LNE) & 0xffu) << 8) | ((SAFE ? 0u : ((uint32_t)action & 0x7fffu)) << 16) | BG_ITEM_VALID);
+            bg_lds_st(&s_q[q][slot & (NE - 1)], bg_q_item<LNE>((uint32_t)l, slot, SAFE ? 0u : ((uint32_t)action & 0x7fffu)));
             nreq[s]++;
             waiting[s] = true;
           }
@@ -413,7 +409,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
               // the reset-only request: chunks 3 / 4 and the mask to LDS as for any request; the step is finished when its answer is seen
               s_c34[0][l] = rc3[s]; s_c34[1][l] = rc4[s]; s_mask[l] = rmask[s];
               const uint32_t slot = __hip_atomic_fetch_add(&s_ctl[1], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-              bg_lds_st(&s_q[1][slot & (NE - 1)], (uint32_t)l | (((slot >> LNE) & 0xffu) << 8) | (0x7fffu << 16) | BG_ITEM_VALID);
+              bg_lds_st(&s_q[1][slot & (NE - 1)], bg_q_item<LNE>((uint32_t)l, slot, 0x7fffu));
               nreq[s]++;
               waiting[s] = true; rwait[s] = true;
               fin = false;
@@ -568,8 +564,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
       const bg_u32x4 ct = *(volatile __attribute__((address_space(3))) bg_u32x4*)&s_ctl[0];
       asm volatile("" ::: "memory");
       const uint32_t hp = __builtin_amdgcn_readfirstlane(ch.x), ho = __builtin_amdgcn_readfirstlane(ch.y);
-      auto queued = [&](uint32_t tail, uint32_t head) -> uint32_t { const uint32_t k = tail - head; return k <= (uint32_t)NE ? k : 0u; };
-      const uint32_t np = queued(__builtin_amdgcn_readfirstlane(ct.x), hp), no = queued(__builtin_amdgcn_readfirstlane(ct.y), ho);
+      const uint32_t np = bg_q_queued<LNE>(__builtin_amdgcn_readfirstlane(ct.x), hp), no = bg_q_queued<LNE>(__builtin_amdgcn_readfirstlane(ct.y), ho);
       if ((np | no) == 0u) {
         if (__builtin_amdgcn_readfirstlane(bg_lds_ld(&s_owners_left)) == 0u) break;   // every owner wave is through: nothing can arrive any more
         __builtin_amdgcn_s_sleep(2);
@@ -602,9 +597,9 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
       E3T(0);
       if ((uint32_t)lane < nb) {
         uint32_t spin = 0;
-        const uint32_t want = BG_ITEM_VALID | ((((head + (uint32_t)lane) >> LNE) & 0xffu) << 8);
-        while ((item & (BG_ITEM_VALID | 0xff00u)) != want && ++spin < BG_SPIN_LIMIT) { __builtin_amdgcn_s_sleep(1); item = bg_lds_ld(slotp); }
-        if ((item & (BG_ITEM_VALID | 0xff00u)) != want) atomicOr(d.err, BG_DEVERR_SPIN);
+        const uint32_t pos = head + (uint32_t)lane;
+        while (!bg_q_is<LNE>(item, pos) && ++spin < BG_SPIN_LIMIT) { __builtin_amdgcn_s_sleep(1); item = bg_lds_ld(slotp); }
+        if (!bg_q_is<LNE>(item, pos)) atomicOr(d.err, BG_DEVERR_SPIN);
         else {
           const int l = (int)(item & 0xffu), env = env0 + l;
           // (ACT: the caller's int32 as the owner left it in the image, in front of the queue word)
@@ -631,6 +626,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
           o.bd_dst = nullptr;
           if (SAFE && ronly) { o.terminated = true; o.reward = *(__attribute__((address_space(3))) const double*)&((const lds_u32*)&s_img[l][0])[34]; }
           else {
+          // (guards, dispatch and the cap rule are spelt out here and in bg_engine.h's service step, not shared: DESIGN.md, "Source-only changes to the engines")
           if (bg_step_guards(e, mask, action, o)) bg_env_dispatch(d, env, e, w, sr, dk, action, o);
           BG_PROBE(cls == 0 ? 20 : 21);
           if (e.max_ante > 0 && e.ante > e.max_ante) { o.terminated = true; o.flags |= 256; }
@@ -657,7 +653,7 @@ __device__ __forceinline__ void bg_engine3_body(const BgDev d, const EngineArgs 
           // (the record goes to the env's IMAGE and nowhere else: an all-null ObsPtrs, as in the prologue.  Handed the launch's own -- whose `rows` the
           //  compiler cannot know to be set -- the per-key writer's 31 pointers stayed live in scalar registers through the whole service step.)
           const ObsPtrs none{};
-          bg_write_obs_impl<false, 3>(d, env, 0, e, dk, none, mask, sr, RowExtra{o.reward, action, o.terminated ? 1u : 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
+          bg_write_obs_impl<3>(d, env, 0, e, dk, none, mask, sr, RowExtra{o.reward, action, o.terminated ? 1u : 0u}, RowStage{(lds_u4*)&s_img[l][0], nullptr});
           if constexpr (SAFE) if (ronly) ((lds_u8*)&s_img[l][0])[BG_ROW_END_FLAGS] = (uint8_t)endb;
           // (the writer has left zeros in words 86 / 87; a step that ended nothing keeps them)
           if constexpr (SAFE) if (sum_ar) *(lds_u64*)&((lds_u32*)&s_img[l][0])[BG_ROW_END_ANTE / 4] = (uint64_t)sum_ar | ((uint64_t)sum_chips << 32);

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_reset_kernel(BgDev d, const uint8
   if (!mask_in || mask_in[env]) { bg_env_reset(d, env, e, dk); bg_store_env(d, env, e); }
   ShopRegs sr; sr.valid = false;
   uint64_t mask = bg_action_mask(d, env, e, sr);
-  bg_write_obs<false>(d, env, (size_t)env, e, dk, obs, mask, sr, RowExtra{0.0, 0, 0u});
+  bg_write_obs(d, env, (size_t)env, e, dk, obs, mask, sr, RowExtra{0.0, 0, 0u});
 }
 
 __global__ __launch_bounds__(BG_BLOCK) void bg_observe_kernel(BgDev d, ObsPtrs obs) {
@@ -78,7 +78,7 @@ __global__ __launch_bounds__(BG_BLOCK) void bg_observe_kernel(BgDev d, ObsPtrs o
   Deck0 dk = bg_load_deck0(d, env);
   ShopRegs sr; sr.valid = false;
   uint64_t mask = bg_action_mask(d, env, e, sr);
-  bg_write_obs<false>(d, env, (size_t)env, e, dk, obs, mask, sr, RowExtra{0.0, 0, 0u});
+  bg_write_obs(d, env, (size_t)env, e, dk, obs, mask, sr, RowExtra{0.0, 0, 0u});
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -830,6 +830,29 @@ static double bg_ev_sum(bg_handle* h, std::vector<hipEvent_t>& v) {
   return ms;
 }
 
+// ---- launching the step engines (bg_engine_launch below picks the shape and the thresholds).  ev_a / ev_b: the launch's own start / stop events, or null.
+typedef void (*bg_engine_fn)(BgDev, EngineArgs);
+static void bg_engine_go(bg_engine_fn k, dim3 g, dim3 b, const BgDev& dv, const EngineArgs& a, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b) {
+  if (ev_a) hipExtLaunchKernelGGL(k, g, b, 0, st, ev_a, ev_b, 0, dv, a);
+  else hipLaunchKernelGGL(k, g, b, 0, st, dv, a);
+}
+// One launch of bg_engine3.h in the shape NOW owner waves x 1 slice of 64 envs x 3 service waves (epw: live envs per workgroup of the 64-env shape).
+// Which instantiation: the caller's actions (bg_step_many_rows asks for no observation hash, so the action mode has no HASH variant) -- with
+// bg_step_many_rows_ex's limits (a.safe, which shares the bytes of the info pointers no engine-3 launch has) the SAFE instantiation of the same shape,
+// and with bg_step_many_rows_progress' carry the PROG one -- or the policy's, with or without the observation hash.
+template <int NOW>
+static void bg_engine3_launch(const BgDev& dv, const EngineArgs& a, bool cards, bool hash, int epw, hipStream_t st, hipEvent_t ev_a, hipEvent_t ev_b) {
+  constexpr int KS = 1, NSV = 3;
+  const dim3 g(NOW * KS == 1 ? (dv.N + epw - 1) / epw : (dv.N + NOW * KS * 64 - 1) / (NOW * KS * 64)), b((NOW + NSV) * BG_BLOCK);
+  bg_engine_fn k;
+  if (a.actions_in && a.safe.counters && a.safe.progress) k = cards ? bg_engine3_progress_kernel<true, NOW, KS, NSV> : bg_engine3_progress_kernel<false, NOW, KS, NSV>;
+  else if (a.actions_in && a.safe.counters) k = cards ? bg_engine3_kernel<false, true, NOW, KS, NSV, true, true> : bg_engine3_kernel<false, false, NOW, KS, NSV, true, true>;
+  else if (a.actions_in) k = cards ? bg_engine3_kernel<false, true, NOW, KS, NSV, true> : bg_engine3_kernel<false, false, NOW, KS, NSV, true>;
+  else if (hash) k = cards ? bg_engine3_kernel<true, true, NOW, KS, NSV, false> : bg_engine3_kernel<true, false, NOW, KS, NSV, false>;
+  else k = cards ? bg_engine3_kernel<false, true, NOW, KS, NSV, false> : bg_engine3_kernel<false, false, NOW, KS, NSV, false>;
+  bg_engine_go(k, g, b, dv, a, st, ev_a, ev_b);
+}
+
 #ifndef BG_BUILD_SIGNATURE
 #define BG_BUILD_SIGNATURE "unsigned"
 #endif
@@ -1327,31 +1350,11 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
       if (!h->e3_epw) { while (epw > 16 && (h->dev.N + epw - 1) / epw < 256) epw >>= 1; }
       a.epw = (uint32_t)epw;
     }
-#define BG_E3K(HV, CV, NOWV, KSV, NSVV, AV, ...) do { \
-      const dim3 g_((NOWV * KSV == 1) ? (h->dev.N + epw - 1) / epw : (h->dev.N + NOWV * KSV * 64 - 1) / (NOWV * KSV * 64)), b_((NOWV + NSVV) * BG_BLOCK); \
-      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV, ##__VA_ARGS__>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
-      else hipLaunchKernelGGL((bg_engine3_kernel<HV, CV, NOWV, KSV, NSVV, AV, ##__VA_ARGS__>), g_, b_, 0, st, dv, a); } while (0)
-#define BG_E3P(CV, NOWV, KSV, NSVV) do { \
-      const dim3 g_((NOWV * KSV == 1) ? (h->dev.N + epw - 1) / epw : (h->dev.N + NOWV * KSV * 64 - 1) / (NOWV * KSV * 64)), b_((NOWV + NSVV) * BG_BLOCK); \
-      if (ev_a) hipExtLaunchKernelGGL((bg_engine3_progress_kernel<CV, NOWV, KSV, NSVV>), g_, b_, 0, st, ev_a, ev_b, 0, dv, a); \
-      else hipLaunchKernelGGL((bg_engine3_progress_kernel<CV, NOWV, KSV, NSVV>), g_, b_, 0, st, dv, a); } while (0)
-    // (the caller's actions: bg_step_many_rows asks for no observation hash, so the action mode has no HASH variant; with bg_step_many_rows_ex's
-    //  limits -- a.safe, which shares the bytes of the info pointers no launch of this branch has -- the SAFE instantiation of the same shape, and with
-    //  bg_step_many_rows_progress' carry the PROG one)
-#define BG_E3(NOWV, KSV, NSVV) do { \
-      if (a.actions_in && a.safe.counters && a.safe.progress) { if (cards) BG_E3P(true, NOWV, KSV, NSVV); else BG_E3P(false, NOWV, KSV, NSVV); } \
-      else if (a.actions_in && a.safe.counters) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true, true); } \
-      else if (a.actions_in) { if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, true); else BG_E3K(false, false, NOWV, KSV, NSVV, true); } \
-      else if (hash && cards) BG_E3K(true, true, NOWV, KSV, NSVV, false); else if (hash) BG_E3K(true, false, NOWV, KSV, NSVV, false); \
-      else if (cards) BG_E3K(false, true, NOWV, KSV, NSVV, false); else BG_E3K(false, false, NOWV, KSV, NSVV, false); } while (0)
     switch (cfg) {   // (other shapes were measured and dropped: profiles/r04_engine3/wave_split_ab.txt, small_jobs.txt, profiles/r05/scheduling_ab.txt)
-      case 113: BG_E3(1, 1, 3); break;
-      case 213: BG_E3(2, 1, 3); break;
-      default: BG_E3(4, 1, 3); break;
+      case 113: bg_engine3_launch<1>(dv, a, cards, hash, epw, st, ev_a, ev_b); break;
+      case 213: bg_engine3_launch<2>(dv, a, cards, hash, epw, st, ev_a, ev_b); break;
+      default: bg_engine3_launch<4>(dv, a, cards, hash, epw, st, ev_a, ev_b); break;
     }
-#undef BG_E3
-#undef BG_E3K
-#undef BG_E3P
     return;
   }
   a.n_waves = (uint32_t)bg_engine_waves((int)a.T);
@@ -1375,15 +1378,11 @@ static void bg_engine_launch(bg_handle* h, const BgDev& dv, const EngineArgs& a0
   if ((a.serve_mask & ((1u << a.n_waves) - 1u)) == 0u)
     a.serve_mask = a.n_waves <= BG_ENG_NSV ? (1u << a.n_waves) - 1u : ((1u << BG_ENG_NSV) - 1u) << (a.n_waves - BG_ENG_NSV);
   const dim3 g((h->dev.N + BG_ENG_NE - 1) / BG_ENG_NE), b(BG_ENG_NW * BG_BLOCK);
-#define BG_ENG(HASHV, CARDSV, INFOV) do { \
-    if (ev_a) hipExtLaunchKernelGGL((bg_engine_kernel<HASHV, CARDSV, INFOV>), g, b, 0, st, ev_a, ev_b, 0, dv, a); \
-    else hipLaunchKernelGGL((bg_engine_kernel<HASHV, CARDSV, INFOV>), g, b, 0, st, dv, a); } while (0)
-  if (info) { if (cards) BG_ENG(false, true, true); else BG_ENG(false, false, true); }
-  else if (hash && cards) BG_ENG(true, true, false);
-  else if (hash) BG_ENG(true, false, false);
-  else if (cards) BG_ENG(false, true, false);
-  else BG_ENG(false, false, false);
-#undef BG_ENG
+  bg_engine_fn k;
+  if (info) k = cards ? bg_engine_kernel<false, true, true> : bg_engine_kernel<false, false, true>;
+  else if (hash) k = cards ? bg_engine_kernel<true, true, false> : bg_engine_kernel<true, false, false>;
+  else k = cards ? bg_engine_kernel<false, true, false> : bg_engine_kernel<false, false, false>;
+  bg_engine_go(k, g, b, dv, a, st, ev_a, ev_b);
 }
 
 // bg_engine.h's queue thresholds -- a queue is served once it holds 64 requests, or 1 while other waves are busy, with no further cheap steps inside a
@@ -1457,6 +1456,11 @@ int bg_step_many(bg_handle* h, int K, const int32_t* actions_dev, const bg_obs_p
 static const char* bg_rows_args(const void* rows_dev, uint64_t row_stride_bytes) {
   if (!rows_dev || row_stride_bytes < BG_ROW_BYTES || (row_stride_bytes & 15) || ((uintptr_t)rows_dev & 15) || row_stride_bytes > 0xffffffffull)
     return "rows_dev must be 16-byte aligned and row_stride_bytes a multiple of 16, >= BG_ROW_BYTES";
+  return nullptr;
+}
+// a record's row of a launch (env + t * N) travels in 32 bits: the engines' copy-out lists and copy queues
+static const char* bg_records_args(const bg_handle* h) {
+  if ((uint64_t)h->dev.N * (uint64_t)bg_max_fused_steps(h) > 0xffffffffull) return "more than 2**32 records per launch (envs x fused steps)";
   return nullptr;
 }
 
@@ -1662,11 +1666,8 @@ int bg_rollout_rows(bg_handle* h, int T, int policy, uint64_t policy_seed, uint6
                     uint8_t* rows_dev, uint64_t row_stride_bytes, int rows_stride_steps, bg_rollout_stats* stats_dev,
                     void* stream) {
   if (!h) return BG_E_ARG;
-  if ((uint64_t)h->dev.N * (uint64_t)bg_max_fused_steps(h) > 0xffffffffull) { h->err = "bg_rollout_rows: more than 2**32 records per launch (envs x fused steps)"; return BG_E_ARG; }
-  if (!rows_dev || row_stride_bytes < BG_ROW_BYTES || (row_stride_bytes & 15) || ((uintptr_t)rows_dev & 15) || row_stride_bytes > 0xffffffffull) {
-    h->err = "bg_rollout_rows: rows_dev must be 16-byte aligned and row_stride_bytes a multiple of 16, >= BG_ROW_BYTES";
-    return BG_E_ARG;
-  }
+  if (const char* m = bg_records_args(h)) { h->err = std::string("bg_rollout_rows: ") + m; return BG_E_ARG; }
+  if (const char* m = bg_rows_args(rows_dev, row_stride_bytes)) { h->err = std::string("bg_rollout_rows: ") + m; return BG_E_ARG; }
   return bg_rollout_impl(h, T, policy, policy_seed, env_index0, t0, nullptr, rows_dev, (size_t)row_stride_bytes,
                          rows_stride_steps, nullptr, nullptr, nullptr, stats_dev, stream);
 }
@@ -1675,7 +1676,7 @@ int bg_step_many_rows(bg_handle* h, int K, const int32_t* actions_dev, uint8_t* 
                       int rows_stride_steps, bg_rollout_stats* stats_dev, void* stream) {
   if (!h) return BG_E_ARG;
   if (!actions_dev || K <= 0) { h->err = "bg_step_many_rows: actions_dev must be a device pointer to [K, N] int32 actions, K > 0"; return BG_E_ARG; }
-  if ((uint64_t)h->dev.N * (uint64_t)bg_max_fused_steps(h) > 0xffffffffull) { h->err = "bg_step_many_rows: more than 2**32 records per launch (envs x fused steps)"; return BG_E_ARG; }
+  if (const char* m = bg_records_args(h)) { h->err = std::string("bg_step_many_rows: ") + m; return BG_E_ARG; }
   if (const char* m = bg_rows_args(rows_dev, row_stride_bytes)) { h->err = std::string("bg_step_many_rows: ") + m; return BG_E_ARG; }
   // bg_rollout_rows' host path (lazy overlapped refill in pieces, chunks of bg_max_fused_steps, profiling events, gather of the last step) with the
   // caller's actions and the handle's auto-reset flag.  BG_ENGINE=1: bg_engine.h reads actions_in and writes records through its copier wave.
@@ -1722,7 +1723,7 @@ static int bg_step_many_limits(const char* who, bg_handle* h, int K, const int32
   if (!h) return BG_E_ARG;
   const char* bad = nullptr;
   if (!actions_dev || K <= 0) bad = "actions_dev must be a device pointer to [K, N] int32 actions, K > 0";
-  else if ((uint64_t)h->dev.N * (uint64_t)bg_max_fused_steps(h) > 0xffffffffull) bad = "more than 2**32 records per launch (envs x fused steps)";
+  else if (const char* m = bg_records_args(h)) bad = m;
   else if (const char* m = bg_rows_args(rows_dev, row_stride_bytes)) bad = m;
   // Both limits >= 3: bg_chunk_limit sizes a launch on "an env consumes at most one pre-shuffled deck per 3 steps" (the shortest episode the game
   // itself allows: reset -> blind -> select -> failing play).  A wrapper ending consumes a ring deck like a game over does; with both limits >= 3

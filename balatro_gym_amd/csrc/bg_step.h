@@ -313,8 +313,6 @@ __device__ __forceinline__ void bg_advance_round(const BgDev& d, int env, Env& e
 // Joker chain (unified_scoring.py:111-299 + complete_joker_effects.py:35-184), jokers by jokers.py id.
 // Played cards are (rank, suit, chips) packed per card: rank | suit << 4 | chips << 8.
 // ---------------------------------------------------------------------------------------------------------
-struct JEff { int chips, mult; double x; };
-
 // complete_joker_effects.py:35-129 (main 'scoring' phase) as a descriptor per joker id:
 //   bits 0..4 condition index into a per-play condition bit set, 5..7 value kind, 8..23 constant.
 // conditions: 0 always | 1 <= 3 scoring cards | 2 hands_left == 1 | 3 discards_left == 0 | 4..7 a scoring card of suit
@@ -1405,21 +1403,14 @@ __device__ __forceinline__ void bg_env_dispatch(const BgDev& d, int env, Env& e,
   if (w.need_inv) { BG_PROBE_BEGIN(); bg_shop_inventory(d, env, e, w, sr); w.need_inv = false; BG_PROBE(22); }
 }
 
-// the guards in front of the dispatch (balatro_env_2.py:619-627); returns true when the action must be dispatched
+// the guards in front of the dispatch (balatro_env_2.py:619-627); returns true when the action must be dispatched.
+// balatro_env_2.py:616-637 step() = bg_step_init, these guards, bg_env_dispatch, then the curriculum cap: the service step of each
+// engine spells that sequence out itself ("Source-only changes to the engines", has why it is not one shared function).
 __device__ __forceinline__ bool bg_step_guards(const Env& e, uint64_t mask, int action, StepOut& o) {
   if (e.ante > 100) { o.terminated = true; o.error = 9; return false; }
   if (e.chips_scored > 1000000000ll) { o.terminated = true; o.error = 10; return false; }
   if (action < 0 || action >= 60 || !((mask >> action) & 1ull)) { o.reward = -1.0; o.error = 1; return false; }
   return true;
-}
-
-// balatro_env_2.py:616-637 step()
-template <class DK>
-__device__ __forceinline__ void bg_env_step(const BgDev& d, int env, Env& e, RngWin& w, ShopRegs& sr, const DK& dk, uint64_t mask,
-                                            int action, StepOut& o) {
-  bg_step_init(o);
-  if (bg_step_guards(e, mask, action, o)) bg_env_dispatch(d, env, e, w, sr, dk, action, o);
-  if (e.max_ante > 0 && e.ante > e.max_ante) { o.terminated = true; o.flags |= 256; }
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -1437,9 +1428,10 @@ struct ObsPtrs {
   uint8_t* rows;        // non-null: one BG_ROW_BYTES record per (step, env) instead of the per-key arrays
   uint32_t row_stride;  // bytes between consecutive records (multiple of 16)
 };
+// (nothing sets `cached`: the writer always computes the three values behind it.  Without these four members the kernels that hold the writer
+//  compile to other code -- DESIGN.md, "Source-only changes to the engines" -- so deleting them is a change to measure, not a cleanup.)
 struct RowExtra { double reward; int32_t action; uint32_t terminated; bool cached = false; float prf = 0.0f; uint64_t handb = 0; uint32_t selm = 0; };
-// The two observation values that only change in the heavy actions (so the service-wave kernel lets the service lane compute
-// them and the env lane carry them): the hand as card codes (8 LDS byte reads) and progress_ratio (a float64 division).
+// The observation values that take more than a shift: the hand as card codes, the selection as a bit mask, progress_ratio (a float64 division).
 template <class DK>
 __device__ __forceinline__ uint64_t bg_obs_handb(const BgDev& d, int env, const Env& e, const DK& dk) {
   // (round 5: eight selects and ONE branch for the rare deck index beyond the 16 cards held in registers -- it was a branch per hand position, in
@@ -1477,11 +1469,11 @@ __device__ __forceinline__ float bg_obs_prf(const Env& e) { // :1497 min(2, roun
   double pr = (double)e.round_chips / (double)need1;
   return (float)(pr < 2.0 ? pr : 2.0);
 }
-// LDS staging of packed records (block-compacted rollout kernel): 64 slots x 6 pieces of 16 bytes + one address per slot
+// a record image in LDS: 22 pieces of 16 bytes (RowStage::stage = the image the writer fills, STAGE 3 below; nothing reads `addr`, always null,
+// and it stays for the reason RowExtra's unused members do)
 typedef uint32_t bg_u32x4 __attribute__((ext_vector_type(4)));
 typedef __attribute__((address_space(3))) bg_u32x4 lds_u4;
 typedef __attribute__((address_space(3))) unsigned long long lds_u64;
-#define BG_STAGE_NP 11 // 16-byte pieces of a record staged at a time: runs of 176 bytes per row and store instruction
 struct RowStage { lds_u4* stage; lds_u64* addr; };
 // lanes of one wave exchanging data through LDS: the hardware queue is in order per wave, the compiler must not move
 // LDS accesses across the hand-over point
@@ -1518,35 +1510,23 @@ __device__ __forceinline__ void bg_stats_flush(bg_rollout_stats* out, const unsi
 }
 static_assert(sizeof(bg_rollout_stats) == 48, "six 64-bit fields, in the order bg_stats_flush assumes");
 
-// `row` = env + t * N for [T, N, ...] rollout buffers.  Returns a 64-bit hash of the row (rollout checksum; the same
-// value for both output layouts).
+// `row` = env + t * N for [T, N, ...] rollout buffers.
 //
 // Packed records (p.rows): the lanes of a workgroup sit on different steps, so with one array per key every 32-byte
 // sector of the narrow keys is completed by several partial writes issued iterations apart -- measured 2.2x the
 // algorithmic write traffic.  A record is 22 whole 16-byte stores owned by ONE lane: nothing is shared between lanes.
-// STAGE: 0 = every lane stores its own record directly, 1 = two slices of BG_STAGE_NP pieces through LDS, 2 = three slices of
-// 8 / 7 / 7 pieces (8 KB of staging per wave), 3 = the record goes to the env's IMAGE in LDS (rs.stage = its 22 pieces; the
-// step engine copies images out cooperatively and patches them in place on cheap steps) -- and, when p.rows is null, the
-// per-key arrays are written as well
-template <bool HASH, int STAGE, class DK>
-__device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, size_t row, const Env& e, const DK& dk,
+// STAGE: 0 = every lane stores its own record directly (p.rows), or writes the per-key arrays when p.rows is null;
+// 3 = the record goes to the env's IMAGE in LDS (rs.stage = its 22 pieces; the step engines copy images out cooperatively
+// and patch them in place on cheap steps) -- and, when p.rows is null, the per-key arrays are written as well
+template <int STAGE, class DK>
+__device__ __forceinline__ void bg_write_obs_impl(const BgDev& d, int env, size_t row, const Env& e, const DK& dk,
                                                 const ObsPtrs& p, uint64_t mask, ShopRegs& sr, const RowExtra& rx,
                                                 const RowStage& rs) {
-  uint64_t hsh = 0x9E3779B97F4A7C15ull;
-#define BG_MIX(v) do { if (HASH) { hsh ^= (uint64_t)(v); hsh *= 0xBF58476D1CE4E5B9ull; hsh ^= hsh >> 29; } } while (0)
+  static_assert(STAGE == 0 || STAGE == 3, "a direct store per lane, or the env's image in LDS");
   // ---- values
   const uint64_t handb = rx.cached ? rx.handb : bg_obs_handb(d, env, e, dk);
-  BG_MIX(handb);
   const uint32_t selm = rx.cached ? rx.selm : bg_obs_selm(e);
-  BG_MIX(selm | ((uint64_t)e.face_down << 8) | ((uint64_t)e.nhand << 16));
-  BG_MIX(e.chips_scored); BG_MIX(e.round_chips);
-  int64_t need1 = e.chips_needed > 1 ? e.chips_needed : 1;
   const float prf = rx.cached ? rx.prf : bg_obs_prf(e);
-  BG_MIX(__float_as_uint(prf));
-  BG_MIX(((uint64_t)(uint32_t)e.chips_needed << 32) | (uint32_t)e.money);
-  BG_MIX((uint64_t)e.ante | ((uint64_t)e.round << 8) | ((uint64_t)e.hands_left << 16) | ((uint64_t)e.discards_left << 24) |
-         ((uint64_t)e.njokers << 32) | ((uint64_t)e.ncons << 40) | ((uint64_t)e.phase << 48));
-  BG_MIX(e.jokers);
   uint32_t jq[5]; // joker_ids int16[10]: byte i of e.jokers -> halfword i (ids beyond njokers read as 0)
   {
     const uint64_t jm = e.jokers & (e.njokers >= 8 ? ~0ull : ((1ull << (8 * e.njokers)) - 1ull));
@@ -1557,7 +1537,6 @@ __device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, s
     jq[3] = ((jh >> 16) & 0xffu) | ((jh >> 24) << 16);
     jq[4] = 0u;
   }
-  BG_MIX(e.cons0 | (e.cons1 << 8) | ((uint32_t)e.ndrop << 16) | ((uint32_t)e.nfo << 24));
   const uint32_t cq = (uint32_t)((e.ncons > 0 && !(e.cons0 & 0x80u)) ? e.cons0 : 0) | ((uint32_t)((e.ncons > 1 && !(e.cons1 & 0x80u)) ? e.cons1 : 0) << 16); // enum-form names map to 0 (:1570)
   // shop rows only in SHOP phase (:1534-1539)
   uint32_t it[5] = {0, 0, 0, 0, 0}, co[5] = {0, 0, 0, 0, 0};
@@ -1572,9 +1551,6 @@ __device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, s
         co[i >> 1] |= ((uint32_t)costs[i] & 0xffffu) << (16 * (i & 1));
       }
   }
-#pragma unroll
-  for (int i = 0; i < 5; i++) { BG_MIX(((uint64_t)it[i] << 32) | co[i]); }
-  BG_MIX(e.shop_reroll_state);
   uint32_t lv[3]; // hand_levels int8[12]: nibble ht of (levels, excess) -> byte ht of their sum (<= 30: no carry between bytes)
 #pragma unroll
   for (int w = 0; w < 3; w++) {
@@ -1582,9 +1558,7 @@ __device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, s
     a = (a | (a << 8)) & 0x00ff00ffu; a = (a | (a << 4)) & 0x0f0f0f0fu;
     b = (b | (b << 8)) & 0x00ff00ffu; b = (b | (b << 4)) & 0x0f0f0f0fu;
     lv[w] = a + b;
-    BG_MIX(lv[w]);
   }
-  BG_MIX(mask);
   uint32_t mq[15];
 #pragma unroll
   for (int w = 0; w < 15; w++) {
@@ -1592,9 +1566,6 @@ __device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, s
     const uint32_t bits = (uint32_t)(mask >> (4 * w)) & 0xfu;
     mq[w] = __umul24(bits, 0x204081u) & 0x01010101u;
   }
-  BG_MIX(((uint64_t)(uint32_t)e.hp_total << 32) | (uint32_t)e.best_hand);
-  BG_MIX(e.boss_type);
-#undef BG_MIX
   // ---- packed record (offsets: BG_ROW_* in include/balatro_mi355x.h)
   if (p.rows || STAGE == 3) {
     uint32_t w[88];
@@ -1623,65 +1594,15 @@ __device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, s
     w[84] = 5u | (((uint32_t)e.ncons & 0xffu) << 8) | (2u << 16) | (((uint32_t)e.phase & 0xffu) << 24); // 336 joker_slots, consumable_count, consumable_slots, phase
     w[85] = (e.boss_type ? 1u : 0u) | (((uint32_t)e.boss_type & 0xffu) << 8) | ((rx.terminated & 1u) << 16); // 340 boss_blind_active, boss_blind_type, terminated
     w[86] = 0u; w[87] = 0u;
-    uint8_t* rowp = p.rows + row * (size_t)p.row_stride;
     if constexpr (STAGE == 3) {
 #pragma unroll
       for (int k = 0; k < 22; k++) rs.stage[k] = bg_u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]};
-    } else if constexpr (STAGE == 2) {
-      // as below, in three slices of 8 / 7 / 7 pieces (runs of 128 / 112 bytes per row and store instruction)
-      const unsigned long long act = __ballot(1);
-      const uint32_t A = (uint32_t)__popcll(act);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
-      rs.addr[rank] = (unsigned long long)rowp;
-#pragma unroll
-      for (int sl = 0; sl < 3; sl++) {
-        const int np = sl == 0 ? 8 : 7, base = sl == 0 ? 0 : (sl == 1 ? 8 : 15);
-#pragma unroll
-        for (int c = 0; c < np; c++) { const int k = base + c; rs.stage[rank * np + c] = bg_u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]}; }
-        BG_WAVE_SYNC();
-#pragma unroll
-        for (int k = 0; k < np; k++) {
-          const uint32_t q = (uint32_t)k * A + rank;                                  // < np * A
-          const uint32_t r = np == 8 ? q >> 3 : (q * 9363u) >> 16;                    // q / np (exact for q < 64 * np)
-          const uint32_t c = q - r * (uint32_t)np;
-          const unsigned long long a = rs.addr[r];
-          *(__attribute__((address_space(1))) bg_u32x4*)(a + 16ull * (uint32_t)base + 16ull * c) = rs.stage[q];
-        }
-        BG_WAVE_SYNC();
-      }
-    } else if constexpr (STAGE == 1) {
-      // The lanes that finished a step this iteration write their records out TOGETHER: 16 bytes per lane straight to
-      // 64 different rows keeps the store path busy ~4x longer than the same bytes in row-contiguous runs (measured:
-      // 22 such stores were a quarter of the kernel).  BG_STAGE_NP 16-byte pieces of every record go to LDS, then lane `rank`
-      // stores pieces rank, rank + A, ... of the A x BG_STAGE_NP staged ones: consecutive lanes = consecutive pieces of a row.
-      const unsigned long long act = __ballot(1);
-      const uint32_t A = (uint32_t)__popcll(act);
-      const uint32_t rank = __builtin_amdgcn_mbcnt_hi((uint32_t)(act >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)act, 0u));
-      rs.addr[rank] = (unsigned long long)rowp;
-#pragma unroll
-      for (int sl = 0; sl < 22 / BG_STAGE_NP; sl++) {
-        constexpr int np = BG_STAGE_NP; // pieces per slice (divides 22)
-#pragma unroll
-        for (int c = 0; c < np; c++) { const int k = np * sl + c; rs.stage[rank * np + c] = bg_u32x4{w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]}; }
-        // other lanes of this wave read what this lane just wrote: make the writes of the whole wave land first (the
-        // LDS queue is in order per wave; the fence keeps the compiler from moving the reads across)
-        BG_WAVE_SYNC();
-#pragma unroll
-        for (int k = 0; k < np; k++) {
-          const uint32_t q = (uint32_t)k * A + rank;                        // < np * A
-          const uint32_t r = (q * (uint32_t)((65536 + np - 1) / np)) >> 16; // q / np (exact for q < 64 * np, np in {2, 11, 22})
-          const uint32_t c = q - r * (uint32_t)np;
-          const unsigned long long a = rs.addr[r];
-          *(__attribute__((address_space(1))) bg_u32x4*)(a + 16ull * (uint32_t)(np * sl) + 16ull * c) = rs.stage[q]; // global_store, not flat
-        }
-        BG_WAVE_SYNC(); // ... and the reads before the next slice overwrites the staging
-      }
     } else {
-      uint4* q = (uint4*)rowp;
+      uint4* q = (uint4*)(p.rows + row * (size_t)p.row_stride);
 #pragma unroll
       for (int k = 0; k < 22; k++) q[k] = make_uint4(w[4 * k], w[4 * k + 1], w[4 * k + 2], w[4 * k + 3]);
     }
-    if (STAGE != 3 || p.rows) return hsh;
+    if (STAGE != 3 || p.rows) return;
   }
   // ---- one array per key
   if (p.hand) ((uint64_t*)p.hand)[row] = handb;
@@ -1738,13 +1659,12 @@ __device__ __forceinline__ uint64_t bg_write_obs_impl(const BgDev& d, int env, s
 #pragma unroll
     for (int i = 0; i < 4; i++) q[i] = make_ulonglong2((e.face_down >> (2 * i)) & 1u, (e.face_down >> (2 * i + 1)) & 1u);
   }
-  return hsh;
 }
 
-template <bool HASH, class DK>
-__device__ __forceinline__ uint64_t bg_write_obs(const BgDev& d, int env, size_t row, const Env& e, const DK& dk, const ObsPtrs& p,
-                                                uint64_t mask, ShopRegs& sr, const RowExtra& rx) {
-  return bg_write_obs_impl<HASH, 0>(d, env, row, e, dk, p, mask, sr, rx, RowStage{nullptr, nullptr});
+template <class DK>
+__device__ __forceinline__ void bg_write_obs(const BgDev& d, int env, size_t row, const Env& e, const DK& dk, const ObsPtrs& p,
+                                             uint64_t mask, ShopRegs& sr, const RowExtra& rx) {
+  bg_write_obs_impl<0>(d, env, row, e, dk, p, mask, sr, rx, RowStage{nullptr, nullptr});
 }
 
 // ---- record images (LDS): one 352-byte record per env, 22 pieces of 16 bytes, kept current by the step engine
@@ -1815,45 +1735,13 @@ __device__ __forceinline__ uint64_t bg_hash_image(const lds_u4* img) {
   return h;
 }
 
-// The same policy with everything that depends only on the env hoisted out of the step loop (the 64-bit `% 3` and one of
-// the three 64-bit multiplies), and the k-th valid action found by a branch-free popcount descent instead of a loop whose
-// trip count differs per lane.
+// The counter-hash policy on a 60-bit action mask: the k-th valid action, k = bg_policy_hash(policy_seed, env_index, t) % (number of
+// valid actions); the scripted policies (policy != 0) override it by phase -- leave the shop, and a blind choice that is a constant of the env.
+// What depends only on the env is hoisted out of the step loop (PolicyLane: the 64-bit `% 3` and one of the hash's three 64-bit multiplies), and
+// the k-th valid action is found by a branch-free popcount descent instead of a loop whose trip count differs per lane.
 struct PolicyLane { uint64_t seed_env; int blind; };
-__device__ __forceinline__ PolicyLane bg_policy_lane(int policy, uint64_t policy_seed, uint64_t env_index) {
-  PolicyLane p;
-  p.seed_env = policy_seed + 0x9E3779B97F4A7C15ull * (env_index + 1);
-  p.blind = policy == 2 ? 45 + (int)(env_index % 3) : 45;
-  return p;
-}
-__device__ __forceinline__ int bg_policy_action(const Env& e, uint64_t mask, int policy, const PolicyLane& pl, uint64_t t) {
-  if (policy != 0) {
-    if (e.phase == 2) return pl.blind;
-    if (e.phase == 1) return 31;
-  }
-  const int nv = __popcll(mask);
-  if (!nv) return 0;
-  uint64_t x = pl.seed_env + 0xD1B54A32D192ED03ull * (t + 1);
-  x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
-  x ^= x >> 27; x *= 0x94D049BB133111EBull;
-  x ^= x >> 31;
-  uint32_t k = (uint32_t)(x >> 32) % (uint32_t)nv;
-  const uint32_t lo = (uint32_t)mask, hi = (uint32_t)(mask >> 32);
-  uint32_t c = (uint32_t)__popc(lo);
-  uint32_t w = k < c ? lo : hi;
-  int base = k < c ? 0 : 32;
-  k = k < c ? k : k - c;
-#pragma unroll
-  for (int sh = 16; sh >= 1; sh >>= 1) { // k-th set bit of w
-    c = (uint32_t)__popc(w & ((1u << sh) - 1u));
-    const bool up = k >= c;
-    w = up ? w >> sh : w;
-    base += up ? sh : 0;
-    k = up ? k - c : k;
-  }
-  return base;
-}
 
-// The same policy for a lane that keeps x0 = seed_env + psi * (t + 1) itself (+= psi per step: no 64-bit multiply for it) and
+// The lane keeps x0 = seed_env + psi * (t + 1) itself (+= psi per step: no 64-bit multiply for it) and
 // takes h % nv from a reciprocal table: q = umulhi(h, floor(2**32 / nv)) is the quotient or one less, so one conditional
 // subtraction makes the remainder exact.
 #define BG_POLICY_PSI 0xD1B54A32D192ED03ull
@@ -1885,20 +1773,4 @@ __device__ __forceinline__ int bg_policy_action_fast(const Env& e, uint64_t mask
     k = up ? k - c : k;
   }
   return base;
-}
-
-// counter-hash policy on a 60-bit action mask; phase overrides for the scripted policies
-__device__ __forceinline__ int bg_policy_action(const Env& e, uint64_t mask, int policy, uint64_t policy_seed,
-                                                uint64_t env_index, uint64_t t) {
-  if (policy != 0) {
-    if (e.phase == 2) return policy == 2 ? 45 + (int)(env_index % 3) : 45;
-    if (e.phase == 1) return 31;
-  }
-  int nv = __popcll(mask);
-  if (!nv) return 0;
-  uint32_t k = bg_policy_hash(policy_seed, env_index, t) % (uint32_t)nv;
-  uint64_t m = mask;
-#pragma unroll 1
-  for (uint32_t i = 0; i < k; i++) m &= m - 1; // clear the k lowest set bits
-  return __ffsll((long long)m) - 1;
 }
