@@ -2284,795 +2284,6 @@ int bg_set_max_ante(bg_handle* h, int max_ante, const int32_t* per_env_host, con
   return 0;
 }
 
-// ---- operator-level entry points (no handle: they run on the CURRENT device, on caller-owned device buffers) ----
-#define BG_HIP0(call)                                                                                  \
-  do {                                                                                                 \
-    hipError_t _e = (call);                                                                            \
-    if (_e != hipSuccess) {                                                                            \
-      g_create_err = std::string(#call) + ": " + hipGetErrorString(_e);                                \
-      return BG_E_HIP;                                                                                 \
-    }                                                                                                  \
-  } while (0)
-
-// ---- measurement hook: streaming copy (bench.py's `peak_measured`: what this GPU's HBM sustains for a plain 16-byte-per-lane
-// copy, the yardstick SURVEY 8(d) asks the roofline fraction to be quoted against beside the 8 TB/s nominal) ----
-// Shape from a sweep on the MI355X (tools/micro/copybw.hip, profiles/r03_copybw.txt): ONE pass per workgroup (no grid-stride loop), four
-// 16-byte pieces per lane, non-temporal loads and stores: 6.5 TB/s read + written at 1 GiB (the guide's float4 copy: 6.29; the
-// grid-stride kernel of rounds 1-2: 5.1-5.6).  A plain one-pass fill writes 6.8 TB/s.
-__global__ __launch_bounds__(256) void bg_stream_copy_kernel(const bg_cp_u32x4* __restrict__ src, bg_cp_u32x4* __restrict__ dst, size_t n16) {
-  const size_t i = (size_t)blockIdx.x * 256 * 4 + threadIdx.x;
-  bg_cp_u32x4 v[4];
-#pragma unroll
-  for (int k = 0; k < 4; k++) if (i + (size_t)k * 256 < n16) v[k] = __builtin_nontemporal_load(&src[i + (size_t)k * 256]);
-#pragma unroll
-  for (int k = 0; k < 4; k++) if (i + (size_t)k * 256 < n16) __builtin_nontemporal_store(v[k], &dst[i + (size_t)k * 256]);
-}
-int bg_bench_copy(const void* src_dev, void* dst_dev, uint64_t bytes, int iters, double* gbps_out, void* stream) {
-  if (!src_dev || !dst_dev || !gbps_out || bytes < 16 || iters < 1 || ((uintptr_t)src_dev & 15) || ((uintptr_t)dst_dev & 15)) { g_create_err = "bg_bench_copy: bad arguments"; return BG_E_ARG; }
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n16 = bytes / 16;
-  const unsigned grid = (unsigned)((n16 + 1023) / 1024);
-  hipEvent_t a, b;
-  BG_HIP0(hipEventCreate(&a)); BG_HIP0(hipEventCreate(&b));
-  for (int i = 0; i < 2; i++) hipLaunchKernelGGL(bg_stream_copy_kernel, dim3(grid), dim3(256), 0, s, (const bg_cp_u32x4*)src_dev, (bg_cp_u32x4*)dst_dev, n16); // warm-up
-  BG_HIP0(hipEventRecord(a, s));
-  for (int i = 0; i < iters; i++) hipLaunchKernelGGL(bg_stream_copy_kernel, dim3(grid), dim3(256), 0, s, (const bg_cp_u32x4*)src_dev, (bg_cp_u32x4*)dst_dev, n16);
-  BG_HIP0(hipEventRecord(b, s));
-  BG_HIP0(hipGetLastError());
-  BG_HIP0(hipEventSynchronize(b));
-  float ms = 0;
-  BG_HIP0(hipEventElapsedTime(&ms, a, b));
-  (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-  *gbps_out = ms > 0 ? 2.0 * (double)(n16 * 16) * iters / (ms * 1e-3) / 1e9 : 0.0; // bytes read + bytes written
-  return 0;
-}
-
-// write-only twin: the step engine's traffic is ~80 % stores (the record of every step), so the store bandwidth is its real ceiling
-__global__ __launch_bounds__(256) void bg_stream_fill_kernel(uint4* __restrict__ dst, size_t n16, uint32_t seed) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i < n16) dst[i] = make_uint4(seed, (uint32_t)i, 0u, seed ^ (uint32_t)i);
-}
-int bg_bench_fill(void* dst_dev, uint64_t bytes, int iters, double* gbps_out, void* stream) {
-  if (!dst_dev || !gbps_out || bytes < 16 || iters < 1 || ((uintptr_t)dst_dev & 15)) { g_create_err = "bg_bench_fill: bad arguments"; return BG_E_ARG; }
-  hipStream_t s = (hipStream_t)stream;
-  const size_t n16 = bytes / 16;
-  const unsigned grid = (unsigned)((n16 + 255) / 256);
-  hipEvent_t a, b;
-  BG_HIP0(hipEventCreate(&a)); BG_HIP0(hipEventCreate(&b));
-  for (int i = 0; i < 2; i++) hipLaunchKernelGGL(bg_stream_fill_kernel, dim3(grid), dim3(256), 0, s, (uint4*)dst_dev, n16, 0u); // warm-up
-  BG_HIP0(hipEventRecord(a, s));
-  for (int i = 0; i < iters; i++) hipLaunchKernelGGL(bg_stream_fill_kernel, dim3(grid), dim3(256), 0, s, (uint4*)dst_dev, n16, (uint32_t)i + 1u);
-  BG_HIP0(hipEventRecord(b, s));
-  BG_HIP0(hipGetLastError());
-  BG_HIP0(hipEventSynchronize(b));
-  float ms = 0;
-  BG_HIP0(hipEventElapsedTime(&ms, a, b));
-  (void)hipEventDestroy(a); (void)hipEventDestroy(b);
-  *gbps_out = ms > 0 ? (double)(n16 * 16) * iters / (ms * 1e-3) / 1e9 : 0.0; // bytes written
-  return 0;
-}
-
-// kernel-only time of a batch op (the A/B of the two lane mappings): events on the caller's stream around the launch
-struct BgOpTimer {
-  hipEvent_t a = nullptr, b = nullptr;
-  bool on = false;
-  int begin(float* out, hipStream_t s) { on = out != nullptr; if (!on) return 0; BG_HIP0(hipEventCreate(&a)); BG_HIP0(hipEventCreate(&b)); BG_HIP0(hipEventRecord(a, s)); return 0; }
-  void mark(hipStream_t s) { if (on) (void)hipEventRecord(b, s); }
-  int end(float* out) { if (!on) return 0; BG_HIP0(hipEventSynchronize(b)); BG_HIP0(hipEventElapsedTime(out, a, b)); (void)hipEventDestroy(a); (void)hipEventDestroy(b); return 0; }
-};
-
-int bg_classify_batch_ex(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t* hand_type_dev, int64_t m, int lanes_per_case,
-                         float* kernel_ms_out, void* stream) {
-  if (!cards_dev || !n_dev || !hand_type_dev || m < 0 || ((uintptr_t)cards_dev & 7) || (lanes_per_case != 1 && lanes_per_case != 8)) {
-    g_create_err = "bg_classify_batch: bad arguments (cards_dev must be 8-byte aligned, lanes_per_case 1 or 8)"; return BG_E_ARG;
-  }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (lanes_per_case == 1)
-    hipLaunchKernelGGL(bg_classify_batch_kernel, dim3((unsigned)((m + BG_BLOCK - 1) / BG_BLOCK)), dim3(BG_BLOCK), 0, s, cards_dev, n_dev, hand_type_dev, (long long)m);
-  else
-    hipLaunchKernelGGL(bg_classify_batch_l8_kernel, dim3((unsigned)((m * 8 + BG_BLOCK - 1) / BG_BLOCK)), dim3(BG_BLOCK), 0, s, cards_dev, n_dev, hand_type_dev, (long long)m);
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-int bg_classify_batch(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t* hand_type_dev, int64_t m, void* stream) {
-  return bg_classify_batch_ex(cards_dev, n_dev, hand_type_dev, m, 1, nullptr, stream);
-}
-
-// packed records -> network input (bg_encode.h).  The store path follows the alignment of the caller's matrix.
-int bg_encode_cols(int layout) { const int d = bg_enc_cols(layout); return d > 0 ? d : BG_E_ARG; }
-
-// the output matrix of bg_encode_rows, bg_encode_rows_ex and bg_norm_obs_rows: D columns of es bytes.  optional: NULL asks for no matrix (bg_norm_obs_rows)
-static const char* bg_enc_out_args(const void* out_dev, uint64_t out_stride_elems, uint64_t es, int D, bool optional) {
-  if (optional && !out_dev) return nullptr;
-  if (!out_dev || ((uintptr_t)out_dev & (es - 1))) return optional ? "out_dev must be aligned to its element type" : "out_dev must be a device pointer aligned to its element type";
-  if (out_stride_elems < (uint64_t)D || out_stride_elems > 0xffffffffull) return "out_stride_elems must be >= the layout's column count";
-  return nullptr;
-}
-
-int bg_encode_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t m, int layout, int out_dtype, void* out_dev,
-                   uint64_t out_stride_elems, float* kernel_ms_out, void* stream) {
-  const int D = bg_enc_cols(layout);
-  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const char* bad = nullptr;
-  if (D < 0) bad = "layout must be BG_ENC_PRODUCED, BG_ENC_FIXED or BG_ENC_EXTRACTOR";
-  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (m < 0 || m > (int64_t)BG_ENC_RECS * 0x7fffffffll) bad = "m out of range";
-  else if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) bad = r;
-  else if (const char* r = bg_enc_out_args(out_dev, out_stride_elems, es, D, false)) bad = r;
-  if (bad) { g_create_err = std::string("bg_encode_rows: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  const int st = bg_enc_store_path(out_dev, out_stride_elems, es, D);
-  const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  bg_enc_dispatch<BG_ENC_EXTRACTOR>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
-    hipLaunchKernelGGL((bg_encode_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, (long long)m, out_dev, out_stride_elems);
-  });
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// packed records -> PPO's scans along K (bg_gae.h): advantages / returns, and per-episode reward sums / lengths with a per-env carry
-static const char* bg_scan_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N) {
-  if (K < 0 || N < 0 || N > (int64_t)BG_GAE_ENVS * 0x7fffffffll) return "K / N out of range";
-  return bg_rows_args(rows_dev, row_stride_bytes);
-}
-
-int bg_gae_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* values_dev, const float* last_values_dev,
-                   double gamma, double gae_lambda, float* advantages_dev, float* returns_dev, const double* rewards_dev, float* kernel_ms_out, void* stream) {
-  const char* const who = rewards_dev ? "bg_gae_rows_ex: " : "bg_gae_rows: ";
-  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
-  if (!bad && (!values_dev || !last_values_dev || !advantages_dev)) bad = "values_dev, last_values_dev and advantages_dev must be device pointers";
-  else if (!bad && (((uintptr_t)values_dev | (uintptr_t)last_values_dev | (uintptr_t)advantages_dev | (uintptr_t)returns_dev) & 3)) bad = "float arrays must be 4-byte aligned";
-  else if (!bad && ((uintptr_t)rewards_dev & 7)) bad = "rewards_dev must be 8-byte aligned";
-  else if (!bad && (advantages_dev == values_dev || returns_dev == values_dev || (returns_dev && returns_dev == advantages_dev))) bad = "advantages_dev / returns_dev must not be the same pointer as values_dev or as each other";
-  else if (!bad && rewards_dev && ((const void*)rewards_dev == (const void*)advantages_dev || (const void*)rewards_dev == (const void*)returns_dev)) bad = "advantages_dev / returns_dev must not be the same pointer as rewards_dev";
-  if (bad) { g_create_err = std::string(who) + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (K == 0 || N == 0) return 0;
-  const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
-  const float g = bg_gae_g(gamma), gl = bg_gae_gl(gamma, gae_lambda);
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-#define BG_GAE_GO(R, W) hipLaunchKernelGGL((bg_gae_kernel<R, W>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, values_dev, last_values_dev, g, gl, advantages_dev, returns_dev, rewards_dev)
-  if (returns_dev) { if (rewards_dev) BG_GAE_GO(true, true); else BG_GAE_GO(true, false); }
-  else { if (rewards_dev) BG_GAE_GO(false, true); else BG_GAE_GO(false, false); }
-#undef BG_GAE_GO
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-int bg_gae_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* values_dev, const float* last_values_dev,
-                double gamma, double gae_lambda, float* advantages_dev, float* returns_dev, float* kernel_ms_out, void* stream) {
-  return bg_gae_rows_ex(rows_dev, row_stride_bytes, K, N, values_dev, last_values_dev, gamma, gae_lambda, advantages_dev, returns_dev, nullptr, kernel_ms_out, stream);
-}
-
-int bg_episode_stats_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double* ep_return_carry_dev, int32_t* ep_len_carry_dev,
-                          double* ep_return_dev, int32_t* ep_len_dev, float* kernel_ms_out, void* stream) {
-  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
-  if (!bad && (!ep_return_carry_dev || !ep_len_carry_dev)) bad = "ep_return_carry_dev and ep_len_carry_dev must be device pointers";
-  else if (!bad && ((((uintptr_t)ep_return_carry_dev | (uintptr_t)ep_return_dev) & 7) || (((uintptr_t)ep_len_carry_dev | (uintptr_t)ep_len_dev) & 3))) bad = "float64 arrays must be 8-byte aligned, int32 arrays 4-byte aligned";
-  else if (!bad && (ep_return_dev == ep_return_carry_dev || ep_len_dev == ep_len_carry_dev)) bad = "ep_return_dev / ep_len_dev must not be the same pointer as their carry";
-  if (bad) { g_create_err = std::string("bg_episode_stats_rows: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (K == 0 || N == 0) return 0;
-  const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-#define BG_EPS_GO(R, L) hipLaunchKernelGGL((bg_episode_stats_kernel<R, L>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, ep_return_carry_dev, ep_len_carry_dev, ep_return_dev, ep_len_dev)
-  if (ep_return_dev) { if (ep_len_dev) BG_EPS_GO(true, true); else BG_EPS_GO(true, false); }
-  else { if (ep_len_dev) BG_EPS_GO(false, true); else BG_EPS_GO(false, false); }
-#undef BG_EPS_GO
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// packed records -> the ended episodes of a rollout (bg_ends.h): the report, and the curriculum's state advanced per env in step order
-int bg_episode_ends_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, int64_t* report_dev, const bg_curriculum* cur,
-                         float* kernel_ms_out, void* stream) {
-  static_assert(BG_ENDS_ENVS == BG_GAE_ENVS, "bg_scan_args bounds N by the grid of a 64-env workgroup");
-  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
-  if (!bad && (!report_dev || ((uintptr_t)report_dev & 7))) bad = "report_dev must be an 8-byte aligned device pointer to int64 [BG_ENDS_WORDS]";
-  else if (!bad && cur) {
-    if (!cur->cap_dev || !cur->hist_dev || !cur->count_dev || !cur->at_level_dev || !cur->raised_dev) bad = "cur: cap_dev, hist_dev, count_dev, at_level_dev and raised_dev must all be device pointers";
-    else if ((((uintptr_t)cur->cap_dev | (uintptr_t)cur->at_level_dev) & 3) || ((uintptr_t)cur->hist_dev & 1) || ((uintptr_t)cur->count_dev & 7)) bad = "cur: int32 arrays must be 4-byte aligned, hist_dev 2-byte, count_dev 8-byte";
-    else if (cur->window < 1) bad = "cur: window must be >= 1";
-    else if (cur->increment < 1 || cur->increment > BG_ENDS_CAP_MAX) bad = "cur: increment must be in 1..255";
-    else if (!std::isfinite(cur->threshold)) bad = "cur: threshold must be finite";
-  }
-  if (bad) { g_create_err = std::string("bg_episode_ends_rows: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  hipStream_t s = (hipStream_t)stream;
-  BG_HIP0(hipMemsetAsync(report_dev, 0, BG_ENDS_WORDS * sizeof(int64_t), s));
-  if (K == 0 || N == 0) {
-    if (cur && N > 0) BG_HIP0(hipMemsetAsync(cur->raised_dev, 0, (size_t)N, s));   // (no step: no cap rose)
-    return 0;
-  }
-  const unsigned grid = (unsigned)((N + BG_ENDS_ENVS - 1) / BG_ENDS_ENVS);
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (cur) hipLaunchKernelGGL((bg_episode_ends_kernel<true>), dim3(grid), dim3(BG_ENDS_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, (unsigned long long*)report_dev, *cur);
-  else hipLaunchKernelGGL((bg_episode_ends_kernel<false>), dim3(grid), dim3(BG_ENDS_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, (unsigned long long*)report_dev, bg_curriculum{});
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// packed records -> VecNormalize (bg_norm.h).  Workspace, in doubles: [K * chunks * 306] partial (mean, M2) per (step, 256-env chunk), [K * 306] batch
-// moments (when the caller does not take them), [K * 306] (mean, sqrt(var + epsilon)) per step for the normalising pass.  The reward call's needs -- 2 per
-// (step, 64-env chunk), 2 + 1 per step -- are smaller at every shape.
-static uint64_t bg_norm_chunks(int64_t N) { return ((uint64_t)N + BG_NORM_CHUNK - 1) / BG_NORM_CHUNK; }
-static uint64_t bg_norm_rchunks(int64_t N) { return ((uint64_t)N + BG_NORM_RBLOCK - 1) / BG_NORM_RBLOCK; }
-uint64_t bg_norm_workspace_bytes(int K, int64_t N) {
-  if (K <= 0 || N <= 0) return 0;
-  return ((uint64_t)K * bg_norm_chunks(N) + 2u * (uint64_t)K) * (2u * BG_NORM_COLS) * sizeof(double);
-}
-static_assert(2 * (BG_NORM_CHUNK / BG_NORM_RBLOCK) + 3 <= 2 * BG_NORM_COLS, "the reward call fits the workspace of the observation call");
-
-int bg_norm_obs_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, int layout, int out_dtype, double* mean_dev, double* var_dev,
-                     double* count_dev, int update, double epsilon, double clip_obs, void* out_dev, uint64_t out_stride_elems, double* moments_dev,
-                     void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
-  const int D = layout == BG_ENC_PRODUCED || layout == BG_ENC_FIXED ? bg_enc_cols(layout) : -1;
-  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
-  if (bad) {}
-  else if (D < 0) bad = "layout must be BG_ENC_PRODUCED or BG_ENC_FIXED (VecNormalize wraps the env's keys, not the extractor's tensors)";
-  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if ((uint64_t)K * (uint64_t)N > (uint64_t)BG_ENC_RECS * 0x7fffffffull) bad = "K * N out of range";
-  else if (!mean_dev || !var_dev || !count_dev || (((uintptr_t)mean_dev | (uintptr_t)var_dev | (uintptr_t)count_dev | (uintptr_t)moments_dev) & 7)) bad = "mean_dev, var_dev and count_dev must be 8-byte aligned device pointers (moments_dev 8-byte aligned)";
-  else if (mean_dev == var_dev || mean_dev == count_dev || var_dev == count_dev) bad = "mean_dev, var_dev and count_dev must not be the same pointer";
-  else if (const char* r = bg_enc_out_args(out_dev, out_stride_elems, es, D, true)) bad = r;
-  else if (!update && moments_dev) bad = "moments_dev must be NULL when update == 0 (no batch moments are taken)";
-  else if (!update && !out_dev) bad = "update == 0 with out_dev NULL asks for nothing";
-  else if (!(epsilon == epsilon) || !(clip_obs == clip_obs)) bad = "epsilon and clip_obs must not be NaN";
-  else if (K > 0 && N > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_norm_workspace_bytes(K, N))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_norm_workspace_bytes(K, N) bytes";
-  else if (out_dev && ((void*)mean_dev == out_dev || (void*)var_dev == out_dev || (void*)moments_dev == out_dev || workspace_dev == out_dev || (const void*)rows_dev == out_dev)) bad = "out_dev must not be the same pointer as an input or another output";
-  if (bad) { g_create_err = std::string("bg_norm_obs_rows: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (K == 0 || N == 0) return 0;
-  const uint64_t chunks = bg_norm_chunks(N);
-  double* const part = (double*)workspace_dev;
-  double* const mom_ws = part + (uint64_t)K * chunks * (2 * BG_NORM_COLS);
-  double* const stat = mom_ws + (uint64_t)K * (2 * BG_NORM_COLS);
-  double* const mom = moments_dev ? moments_dev : mom_ws;
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (update) {
-    hipLaunchKernelGGL(bg_norm_obs_partials, dim3((unsigned)(chunks * (uint64_t)K)), dim3(BG_NORM_PBLOCK), 0, s, rows_dev, row_stride_bytes, (long long)N, (long long)chunks, part);
-    hipLaunchKernelGGL(bg_norm_obs_combine, dim3((unsigned)K), dim3(BG_NORM_PBLOCK), 0, s, part, (long long)N, (long long)chunks, mom);
-    hipLaunchKernelGGL((bg_norm_obs_chain<true>), dim3(1), dim3(BG_NORM_PBLOCK), 0, s, mom, K, (double)N, epsilon, mean_dev, var_dev, count_dev, stat);
-  } else if (out_dev)
-    hipLaunchKernelGGL((bg_norm_obs_chain<false>), dim3(1), dim3(BG_NORM_PBLOCK), 0, s, mom, K, (double)N, epsilon, mean_dev, var_dev, count_dev, stat);
-  if (out_dev) {
-    const long long m = (long long)K * (long long)N;
-    const int st = bg_enc_store_path(out_dev, out_stride_elems, es, D);
-    const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
-    const size_t sstride = update ? 2 * BG_NORM_COLS : 0;
-    bg_enc_dispatch<BG_ENC_FIXED>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
-      hipLaunchKernelGGL((bg_norm_obs_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, m, (long long)N, stat, sstride, clip_obs, out_dev, out_stride_elems);
-    });
-  }
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// bg_encode_rows / frozen bg_norm_obs_rows for the rows a minibatch names: the GATHER variants of their kernels (bg_encode.h, bg_norm.h).  Without an
-// index and without statistics it IS bg_encode_rows; statistics without an index run the GATHER variant with the identity (no workspace to hold
-// sqrt(var + epsilon): the workgroups take the roots themselves).
-int bg_encode_rows_ex(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout, int out_dtype,
-                      const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, void* out_dev, uint64_t out_stride_elems,
-                      float* kernel_ms_out, void* stream) {
-  const int D = bg_enc_cols(layout);
-  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const bool norm = mean_dev || var_dev;
-  const char* bad = nullptr;
-  if (D < 0) bad = "layout must be BG_ENC_PRODUCED, BG_ENC_FIXED or BG_ENC_EXTRACTOR";
-  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (m < 0 || m > (int64_t)BG_ENC_RECS * 0x7fffffffll) bad = "m out of range";
-  else if (store_rows < 0) bad = "store_rows must be >= 0";
-  else if (index_dev && store_rows > 0x7fffffffll) bad = "store_rows must be in [0, 2**31) when index_dev is given";
-  else if (!index_dev && m > store_rows) bad = "m must be <= store_rows when index_dev is NULL";
-  else if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) bad = r;
-  else if ((uintptr_t)index_dev & 3) bad = "index_dev must be 4-byte aligned";
-  else if (norm && (!mean_dev || !var_dev)) bad = "mean_dev and var_dev go together: both or neither";
-  else if (norm && layout == BG_ENC_EXTRACTOR) bad = "statistics need layout BG_ENC_PRODUCED or BG_ENC_FIXED (VecNormalize wraps the env's keys, not the extractor's tensors)";
-  else if (norm && (((uintptr_t)mean_dev | (uintptr_t)var_dev) & 7)) bad = "mean_dev and var_dev must be 8-byte aligned";
-  else if (norm && mean_dev == var_dev) bad = "mean_dev and var_dev must not be the same pointer";
-  else if (norm && !(epsilon >= 0.0 && epsilon <= 1.7976931348623157e308 && clip_obs >= 0.0 && clip_obs <= 1.7976931348623157e308)) bad = "epsilon and clip_obs must be finite and >= 0 when statistics are given";
-  else if (const char* r = bg_enc_out_args(out_dev, out_stride_elems, es, D, false)) bad = r;
-  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev) bad = "out_dev must not be the same pointer as an input";
-  if (bad) { g_create_err = std::string("bg_encode_rows_ex: ") + bad; return BG_E_ARG; }
-  if (!index_dev && !norm) return bg_encode_rows(rows_dev, row_stride_bytes, m, layout, out_dtype, out_dev, out_stride_elems, kernel_ms_out, stream);
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  const int st = bg_enc_store_path(out_dev, out_stride_elems, es, D);
-  const unsigned grid = (unsigned)((m + BG_ENC_RECS - 1) / BG_ENC_RECS);
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (norm)
-    bg_enc_dispatch<BG_ENC_FIXED>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
-      hipLaunchKernelGGL((bg_norm_obs_gather_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, out_dev, out_stride_elems);
-    });
-  else
-    bg_enc_dispatch<BG_ENC_EXTRACTOR>(layout, out_dtype, st, [&](auto L, auto T, auto S) {
-      hipLaunchKernelGGL((bg_encode_gather_kernel<L(), T(), S()>), dim3(grid), dim3(BG_ENC_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, out_dev, out_stride_elems);
-    });
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-int bg_norm_reward_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double* returns_carry_dev, double* ret_stats_dev, int update,
-                        double gamma, double epsilon, double clip_reward, double* rewards_dev, double* moments_dev, void* workspace_dev,
-                        uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
-  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
-  if (bad) {}
-  else if ((uint64_t)K * (uint64_t)N > 256ull * 0x7fffffffull) bad = "K * N out of range";
-  else if (!ret_stats_dev || (update && !returns_carry_dev)) bad = "ret_stats_dev (and, with update != 0, returns_carry_dev) must be device pointers";
-  else if (((uintptr_t)returns_carry_dev | (uintptr_t)ret_stats_dev | (uintptr_t)rewards_dev | (uintptr_t)moments_dev) & 7) bad = "float64 arrays must be 8-byte aligned";
-  else if (!update && moments_dev) bad = "moments_dev must be NULL when update == 0 (no batch moments are taken)";
-  else if (!update && !rewards_dev) bad = "update == 0 with rewards_dev NULL asks for nothing";
-  else if (!(gamma == gamma) || !(epsilon == epsilon) || !(clip_reward == clip_reward)) bad = "gamma, epsilon and clip_reward must not be NaN";
-  else if (K > 0 && N > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_norm_workspace_bytes(K, N))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_norm_workspace_bytes(K, N) bytes";
-  else if (rewards_dev && (rewards_dev == returns_carry_dev || rewards_dev == ret_stats_dev || rewards_dev == moments_dev || (void*)rewards_dev == workspace_dev || returns_carry_dev == ret_stats_dev)) bad = "outputs must not be the same pointer as an input or as each other";
-  if (bad) { g_create_err = std::string("bg_norm_reward_rows: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (K == 0 || N == 0) return 0;
-  const uint64_t chunks = bg_norm_rchunks(N);
-  double* const part = (double*)workspace_dev;
-  double* const mom_ws = part + (uint64_t)K * chunks * 2;
-  double* const denom = mom_ws + (uint64_t)K * 2;
-  double* const mom = moments_dev ? moments_dev : mom_ws;
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (update) {
-    hipLaunchKernelGGL(bg_norm_ret_partials, dim3((unsigned)chunks), dim3(BG_NORM_RBLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, (long long)chunks, gamma, returns_carry_dev, part);
-    hipLaunchKernelGGL(bg_norm_ret_combine, dim3((unsigned)K), dim3(BG_NORM_RBLOCK), 0, s, part, (long long)N, (long long)chunks, mom);
-    hipLaunchKernelGGL((bg_norm_ret_chain<true>), dim3(1), dim3(64), 0, s, mom, K, (double)N, epsilon, ret_stats_dev, denom);
-  } else
-    hipLaunchKernelGGL((bg_norm_ret_chain<false>), dim3(1), dim3(64), 0, s, mom, K, (double)N, epsilon, ret_stats_dev, denom);
-  if (rewards_dev) {
-    const long long m = (long long)K * (long long)N;
-    hipLaunchKernelGGL(bg_norm_reward_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, s, rows_dev, row_stride_bytes, m, (long long)N, denom, update ? 1 : 0, clip_reward, rewards_dev);
-  }
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// logits + action masks -> the policy head (bg_head.h).  The load paths follow the alignment of the caller's matrices.
-static int bg_head_call(const char* who, int mode, const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev,
-                        uint64_t mask_stride_bytes, int64_t m, uint64_t seed, uint64_t index0, uint64_t t, const int32_t* actions_in, int32_t* actions_out,
-                        float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream, float epsilon = 0.0f) {
-  const bool bf16 = logits_dtype == BG_HEAD_BF16;
-  const uint64_t es = bf16 ? 2u : 4u;
-  const void* const act = mode == BG_HEAD_EVALUATE ? (const void*)actions_in : (const void*)actions_out;
-  const char* bad = nullptr;
-  if (logits_dtype != BG_HEAD_F32 && logits_dtype != BG_HEAD_BF16) bad = "logits_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
-  else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
-  else if (!logits_dev || ((uintptr_t)logits_dev & (es - 1))) bad = "logits_dev must be a device pointer aligned to its element type";
-  else if (logits_stride_elems < BG_HEAD_ACTIONS || logits_stride_elems > 0xffffffffull) bad = "logits_stride_elems must be >= 60";
-  else if (mask_dev && (((uintptr_t)mask_dev & 3) || mask_stride_bytes < BG_HEAD_ACTIONS || (mask_stride_bytes & 3) || mask_stride_bytes > 0xffffffffull)) bad = "mask_dev must be 4-byte aligned and mask_stride_bytes a multiple of 4, >= 60";
-  else if (!act || ((uintptr_t)act & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
-  else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "log_prob_dev / entropy_dev must be 4-byte aligned";
-  else if ((log_prob_dev && log_prob_dev == entropy_dev) || (const void*)log_prob_dev == act || (const void*)entropy_dev == act) bad = "actions_dev, log_prob_dev and entropy_dev must not be the same pointer";
-  else if (act == logits_dev || act == (const void*)mask_dev || (log_prob_dev && ((const void*)log_prob_dev == logits_dev || (const void*)log_prob_dev == (const void*)mask_dev)) ||
-           (entropy_dev && ((const void*)entropy_dev == logits_dev || (const void*)entropy_dev == (const void*)mask_dev))) bad = "outputs must not alias the logits or the masks";
-  if (bad) { g_create_err = std::string(who) + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  const bool l16 = ((uintptr_t)logits_dev & 15) == 0;
-  int lld;
-  if (l16 && (logits_stride_elems * es) % 16 == 0) lld = BG_HEAD_LD_ROWS16;
-  else if (bf16 && l16 && logits_stride_elems == BG_HEAD_ACTIONS) lld = BG_HEAD_LD_FLAT16;
-  else if (!bf16 || (((uintptr_t)logits_dev & 3) == 0 && logits_stride_elems % 2 == 0)) lld = BG_HEAD_LD_WORD;
-  else lld = BG_HEAD_LD_HALF;
-  int mld = BG_HEAD_LD_NONE;
-  if (mask_dev) {
-    const bool m16 = ((uintptr_t)mask_dev & 15) == 0;
-    mld = m16 && mask_stride_bytes % 16 == 0 ? BG_HEAD_LD_ROWS16 : m16 && mask_stride_bytes == BG_HEAD_ACTIONS ? BG_HEAD_LD_FLAT16 : BG_HEAD_LD_WORD;
-  }
-  const unsigned grid = (unsigned)((m + BG_HEAD_ROWS - 1) / BG_HEAD_ROWS);
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-#define BG_HEAD_GO(M) hipLaunchKernelGGL((bg_head_kernel<M>), dim3(grid), dim3(BG_HEAD_BLOCK), 0, s, logits_dev, bf16 ? 1 : 0, lld, logits_stride_elems, mask_dev, mld, mask_stride_bytes, (long long)m, seed, index0, t, actions_in, actions_out, log_prob_dev, entropy_dev)
-  if (mode == BG_HEAD_EPS) hipLaunchKernelGGL(bg_head_eps_kernel, dim3(grid), dim3(BG_HEAD_BLOCK), 0, s, logits_dev, bf16 ? 1 : 0, lld, logits_stride_elems, mask_dev, mld, mask_stride_bytes, (long long)m, seed, index0, t, epsilon, actions_out);
-  else if (mode == BG_HEAD_SAMPLE) BG_HEAD_GO(BG_HEAD_SAMPLE); else if (mode == BG_HEAD_ARGMAX) BG_HEAD_GO(BG_HEAD_ARGMAX); else BG_HEAD_GO(BG_HEAD_EVALUATE);
-#undef BG_HEAD_GO
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-int bg_sample_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
-                      uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, int32_t* actions_dev, float* log_prob_dev, float* entropy_dev,
-                      float* kernel_ms_out, void* stream) {
-  if (flags & ~BG_HEAD_DETERMINISTIC) { g_create_err = "bg_sample_actions: flags must be 0 or BG_HEAD_DETERMINISTIC"; return BG_E_ARG; }
-  return bg_head_call("bg_sample_actions: ", flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE, logits_dev, logits_dtype, logits_stride_elems, mask_dev,
-                      mask_stride_bytes, m, seed, index0, t, nullptr, actions_dev, log_prob_dev, entropy_dev, kernel_ms_out, stream);
-}
-int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
-                        const int32_t* actions_dev, float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream) {
-  return bg_head_call("bg_evaluate_actions: ", BG_HEAD_EVALUATE, logits_dev, logits_dtype, logits_stride_elems, mask_dev, mask_stride_bytes, m, 0, 0, 0, actions_dev,
-                      nullptr, log_prob_dev, entropy_dev, kernel_ms_out, stream);
-}
-
-// logits + the stored arrays of a rollout -> PPO's loss, diagnostics and gradient (bg_ppo.h).  Workspace: BG_PPO_WS_HEAD bytes (mean, std, apply), one
-// (n, mean, M2) triple per 256 rows, six float64 sums per 64 rows.
-uint64_t bg_ppo_loss_workspace_bytes(int64_t m) {
-  if (m <= 0) return 0;
-  return BG_PPO_WS_HEAD + bg_ppo_stat_parts(m) * sizeof(BgPpoMoments) + bg_ppo_row_parts(m) * (BG_PPO_SUMS * sizeof(double));
-}
-
-int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes,
-                const int32_t* actions_dev, const float* old_log_prob_dev, const float* advantages_dev, const float* values_dev, const float* returns_dev,
-                const int32_t* index_dev, int64_t store_rows, int64_t m, float clip_range, float ent_coef, float vf_coef, uint32_t flags, void* dlogits_dev,
-                uint64_t dlogits_stride_elems, float* dvalues_dev, float* log_prob_dev, float* entropy_dev, float* stats_dev, void* workspace_dev,
-                uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
-  const bool bf16 = logits_dtype == BG_HEAD_BF16;
-  const uint64_t es = bf16 ? 2u : 4u;
-  const void* const ins[] = {logits_dev, mask_dev, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev};
-  const void* const outs[] = {dlogits_dev, dvalues_dev, log_prob_dev, entropy_dev, stats_dev, workspace_dev};
-  bool alias = false;
-  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
-  }
-  const char* bad = nullptr;
-  if (logits_dtype != BG_HEAD_F32 && logits_dtype != BG_HEAD_BF16) bad = "logits_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
-  else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
-  else if (flags & ~BG_PPO_NORMALIZE_ADV) bad = "flags must be 0 or BG_PPO_NORMALIZE_ADV";
-  else if (!(clip_range > 0.0f && clip_range < 1.0f)) bad = "clip_range must be in (0, 1)";
-  else if (!bg_ppo_finite(ent_coef) || !bg_ppo_finite(vf_coef)) bad = "ent_coef and vf_coef must be finite";
-  else if (!logits_dev || ((uintptr_t)logits_dev & (es - 1))) bad = "logits_dev must be a device pointer aligned to its element type";
-  else if (logits_stride_elems < BG_HEAD_ACTIONS || logits_stride_elems > 0xffffffffull) bad = "logits_stride_elems must be >= 60";
-  else if (!dlogits_dev || ((uintptr_t)dlogits_dev & (es - 1))) bad = "dlogits_dev must be a device pointer aligned to its element type";
-  else if (dlogits_stride_elems < BG_HEAD_ACTIONS || dlogits_stride_elems > 0xffffffffull) bad = "dlogits_stride_elems must be >= 60";
-  else if (mask_dev && (((uintptr_t)mask_dev & 3) || mask_stride_bytes < BG_HEAD_ACTIONS || (mask_stride_bytes & 3) || mask_stride_bytes > 0xffffffffull)) bad = "mask_dev must be 4-byte aligned and mask_stride_bytes a multiple of 4, >= 60";
-  else if (!actions_dev || !old_log_prob_dev || !advantages_dev || (((uintptr_t)actions_dev | (uintptr_t)old_log_prob_dev | (uintptr_t)advantages_dev) & 3)) bad = "actions_dev, old_log_prob_dev and advantages_dev must be 4-byte aligned device pointers";
-  else if ((values_dev == nullptr) != (returns_dev == nullptr)) bad = "values_dev and returns_dev go together: both or neither";
-  else if (((uintptr_t)values_dev | (uintptr_t)returns_dev | (uintptr_t)index_dev | (uintptr_t)dvalues_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "values_dev, returns_dev, index_dev, dvalues_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
-  else if (dvalues_dev && !values_dev) bad = "dvalues_dev needs values_dev and returns_dev";
-  else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
-  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_PPO_STATS floats";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_ppo_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_ppo_loss_workspace_bytes(m) bytes";
-  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
-  if (bad) { g_create_err = std::string("bg_ppo_loss: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  hipStream_t s = (hipStream_t)stream;
-  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_PPO_STATS * sizeof(float), s)); return 0; }
-  BgPpoArgs A;
-  A.logits = logits_dev; A.lstride = logits_stride_elems;
-  const bool l16 = ((uintptr_t)logits_dev & 15) == 0;
-  if (l16 && (logits_stride_elems * es) % 16 == 0) A.lld = BG_HEAD_LD_ROWS16;
-  else if (bf16 && l16 && logits_stride_elems == BG_HEAD_ACTIONS) A.lld = BG_HEAD_LD_FLAT16;
-  else if (!bf16 || (((uintptr_t)logits_dev & 3) == 0 && logits_stride_elems % 2 == 0)) A.lld = BG_HEAD_LD_WORD;
-  else A.lld = BG_HEAD_LD_HALF;
-  const bool d16 = ((uintptr_t)dlogits_dev & 15) == 0;
-  if (d16 && (dlogits_stride_elems * es) % 16 == 0) A.dst = BG_HEAD_LD_ROWS16;
-  else if (bf16 && d16 && dlogits_stride_elems == BG_HEAD_ACTIONS) A.dst = BG_HEAD_LD_FLAT16;
-  else if (!bf16 || (((uintptr_t)dlogits_dev & 3) == 0 && dlogits_stride_elems % 2 == 0)) A.dst = BG_HEAD_LD_WORD;
-  else A.dst = BG_HEAD_LD_HALF;
-  A.mask = mask_dev; A.mstride = mask_stride_bytes; A.mld = BG_HEAD_LD_NONE;
-  if (mask_dev) {
-    const bool m16 = ((uintptr_t)mask_dev & 15) == 0;
-    A.mld = m16 && mask_stride_bytes % 16 == 0 ? BG_HEAD_LD_ROWS16 : !index_dev && m16 && mask_stride_bytes == BG_HEAD_ACTIONS ? BG_HEAD_LD_FLAT16 : BG_HEAD_LD_WORD;
-  }
-  A.actions = actions_dev; A.old_lp = old_log_prob_dev; A.adv = advantages_dev; A.values = values_dev; A.returns = returns_dev;
-  A.index = index_dev; A.store_rows = (long long)store_rows; A.m = (long long)m;
-  A.c.clip = clip_range; A.c.lo = 1.0f - clip_range; A.c.hi = 1.0f + clip_range; A.c.ent_coef = ent_coef; A.c.vf_coef = vf_coef; A.c.fm = (float)m;
-  A.normalize = flags & BG_PPO_NORMALIZE_ADV ? 1 : 0;
-  A.dlogits = dlogits_dev; A.dstride = dlogits_stride_elems; A.dvalues = dvalues_dev; A.log_prob = log_prob_dev; A.entropy = entropy_dev;
-  float* const head = (float*)workspace_dev;
-  BgPpoMoments* const mom = (BgPpoMoments*)((uint8_t*)workspace_dev + BG_PPO_WS_HEAD);
-  const uint64_t SP = bg_ppo_stat_parts(m), RP = bg_ppo_row_parts(m);
-  A.head = head; A.partials = (double*)(mom + SP);
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (A.normalize) {
-    hipLaunchKernelGGL(bg_ppo_adv_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, advantages_dev, index_dev, (long long)store_rows, (long long)m, mom);
-    hipLaunchKernelGGL(bg_ppo_adv_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, mom, (long long)SP, head);
-  }
-  if (bf16) hipLaunchKernelGGL((bg_ppo_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-  else hipLaunchKernelGGL((bg_ppo_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-  hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// epsilon-greedy over the masked head (bg_dqn.h): bg_sample_actions' arguments and checks, plus epsilon; no log_prob / entropy
-int bg_sample_actions_eps(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
-                          uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, float epsilon, int32_t* actions_dev, float* log_prob_dev,
-                          float* entropy_dev, float* kernel_ms_out, void* stream) {
-  if (flags) { g_create_err = "bg_sample_actions_eps: flags must be 0"; return BG_E_ARG; }
-  if (!(epsilon >= 0.0f && epsilon <= 1.0f)) { g_create_err = "bg_sample_actions_eps: epsilon must be in [0, 1]"; return BG_E_ARG; }
-  if (log_prob_dev || entropy_dev) { g_create_err = "bg_sample_actions_eps: log_prob_dev and entropy_dev must be NULL (an epsilon-greedy action has no categorical log-probability)"; return BG_E_ARG; }
-  return bg_head_call("bg_sample_actions_eps: ", BG_HEAD_EPS, logits_dev, logits_dtype, logits_stride_elems, mask_dev, mask_stride_bytes, m, seed, index0, t, nullptr,
-                      actions_dev, nullptr, nullptr, kernel_ms_out, stream, epsilon);
-}
-
-// Q values + the ring of records -> DQN's TD loss, diagnostics and gradient (bg_dqn.h).  Workspace: seven float64 values per 64 rows.
-uint64_t bg_dqn_loss_workspace_bytes(int64_t m) {
-  if (m <= 0) return 0;
-  return bg_dqn_row_parts(m) * (BG_DQN_SUMS * sizeof(double));
-}
-
-static int bg_dqn_path(const void* p, uint64_t stride, bool bf16) {
-  const uint64_t es = bf16 ? 2u : 4u;
-  const bool a16 = ((uintptr_t)p & 15) == 0;
-  if (a16 && (stride * es) % 16 == 0) return BG_HEAD_LD_ROWS16;
-  if (bf16 && a16 && stride == BG_HEAD_ACTIONS) return BG_HEAD_LD_FLAT16;
-  if (!bf16 || (((uintptr_t)p & 3) == 0 && stride % 2 == 0)) return BG_HEAD_LD_WORD;
-  return BG_HEAD_LD_HALF;
-}
-
-int bg_dqn_loss(const void* q_dev, uint64_t q_stride_elems, const void* q_next_dev, uint64_t q_next_stride_elems, const void* q_next_online_dev,
-                uint64_t q_next_online_stride_elems, int q_dtype, const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
-                const int32_t* next_index_dev, const float* rewards_dev, int64_t m, float gamma, uint32_t flags, void* dq_dev, uint64_t dq_stride_elems,
-                float* td_dev, float* stats_dev, void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
-  const bool bf16 = q_dtype == BG_HEAD_BF16;
-  const uint64_t es = bf16 ? 2u : 4u;
-  const void* const ins[] = {q_dev, q_next_dev, q_next_online_dev, rows_dev, next_index_dev, rewards_dev};
-  const void* const outs[] = {dq_dev, td_dev, stats_dev, workspace_dev};
-  bool alias = false;
-  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
-  }
-  auto bad_matrix = [&](const void* p, uint64_t stride) { return !p || ((uintptr_t)p & (es - 1)) || stride < BG_HEAD_ACTIONS || stride > 0xffffffffull; };
-  const char* bad = nullptr;
-  if (q_dtype != BG_HEAD_F32 && q_dtype != BG_HEAD_BF16) bad = "q_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
-  else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
-  else if (flags & ~(BG_DQN_MASK_NEXT | BG_DQN_MSE | BG_DQN_TIMEOUT_EXCLUDE)) bad = "flags must be a combination of BG_DQN_MASK_NEXT, BG_DQN_MSE and BG_DQN_TIMEOUT_EXCLUDE";
-  else if (!(gamma >= 0.0f && gamma <= 1.0f)) bad = "gamma must be in [0, 1]";
-  else if (bad_matrix(q_dev, q_stride_elems)) bad = "q_dev must be a device pointer aligned to its element type, q_stride_elems >= 60";
-  else if (bad_matrix(q_next_dev, q_next_stride_elems)) bad = "q_next_dev must be a device pointer aligned to its element type, q_next_stride_elems >= 60";
-  else if (q_next_online_dev && bad_matrix(q_next_online_dev, q_next_online_stride_elems)) bad = "q_next_online_dev must be aligned to its element type, q_next_online_stride_elems >= 60";
-  else if (bad_matrix(dq_dev, dq_stride_elems)) bad = "dq_dev must be a device pointer aligned to its element type, dq_stride_elems >= 60";
-  else if (!rows_dev || ((uintptr_t)rows_dev & 15)) bad = "rows_dev must be a 16-byte aligned device pointer";
-  else if (row_stride_bytes < BG_ROW_BYTES || (row_stride_bytes & 15) || row_stride_bytes > 0xffffffffull) bad = "row_stride_bytes must be a multiple of 16, >= BG_ROW_BYTES";
-  else if (store_rows < 0 || store_rows > 0x7fffffffll) bad = "store_rows must be in [0, 2**31)";
-  else if (!next_index_dev || ((uintptr_t)next_index_dev & 3)) bad = "next_index_dev must be a 4-byte aligned device pointer";
-  else if (((uintptr_t)rewards_dev | (uintptr_t)td_dev) & 3) bad = "rewards_dev and td_dev must be 4-byte aligned";
-  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_DQN_STATS floats";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_dqn_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_dqn_loss_workspace_bytes(m) bytes";
-  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
-  if (bad) { g_create_err = std::string("bg_dqn_loss: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  hipStream_t s = (hipStream_t)stream;
-  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_DQN_STATS * sizeof(float), s)); return 0; }
-  BgDqnArgs A;
-  A.q = q_dev; A.qstride = q_stride_elems;
-  A.qn = q_next_dev; A.nstride = q_next_stride_elems; A.nld = bg_dqn_path(q_next_dev, q_next_stride_elems, bf16);
-  A.qo = q_next_online_dev; A.ostride = q_next_online_stride_elems; A.old = q_next_online_dev ? bg_dqn_path(q_next_online_dev, q_next_online_stride_elems, bf16) : BG_HEAD_LD_NONE;
-  A.rows = rows_dev; A.rstride = row_stride_bytes; A.store_rows = (long long)store_rows;
-  A.next_index = next_index_dev; A.rewards = rewards_dev; A.m = (long long)m;
-  A.gamma = gamma; A.fm = (float)m; A.flags = flags;
-  A.dq = dq_dev; A.dstride = dq_stride_elems; A.dst = bg_dqn_path(dq_dev, dq_stride_elems, bf16);
-  A.td = td_dev; A.partials = (double*)workspace_dev;
-  const uint64_t RP = bg_dqn_row_parts(m);
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  if (q_next_online_dev) {
-    if (bf16) hipLaunchKernelGGL((bg_dqn_kernel<true, true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL((bg_dqn_kernel<false, true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-  } else {
-    if (bf16) hipLaunchKernelGGL((bg_dqn_kernel<true, false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL((bg_dqn_kernel<false, false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-  }
-  hipLaunchKernelGGL(bg_dqn_finish, dim3(1), dim3(BG_DQN_LANES), 0, s, A.partials, (long long)RP, (long long)m, stats_dev);
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-// packed records -> the first layer of the network and its weight / bias gradient (bg_linear.h): the features of bg_encode_rows_ex are built in LDS
-// and consumed by the matrix cores in the same launch.
-static const char* bg_linear_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
-                                         const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, int H, int activation) {
-  const bool norm = mean_dev || var_dev;
-  if (layout == BG_ENC_EXTRACTOR) return "layout BG_ENC_EXTRACTOR is not supported (its 416 one-hot columns want an embedding gather): BG_ENC_PRODUCED or BG_ENC_FIXED";
-  if (layout != BG_ENC_PRODUCED && layout != BG_ENC_FIXED) return "layout must be BG_ENC_PRODUCED or BG_ENC_FIXED";
-  if (H < 32 || H > 4096 || H % 32) return "H must be a multiple of 32 in [32, 4096]";
-  if (activation != BG_LIN_NONE && activation != BG_LIN_RELU) return "activation must be BG_LIN_NONE or BG_LIN_RELU";
-  if (m < 0 || m > (int64_t)BG_LIN_ROWS * 0x7fffffffll) return "m out of range";
-  if (store_rows < 0) return "store_rows must be >= 0";
-  if (index_dev && store_rows > 0x7fffffffll) return "store_rows must be in [0, 2**31) when index_dev is given";
-  if (!index_dev && m > store_rows) return "m must be <= store_rows when index_dev is NULL";
-  if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) return r;
-  if ((uintptr_t)index_dev & 3) return "index_dev must be 4-byte aligned";
-  if (norm && (!mean_dev || !var_dev)) return "mean_dev and var_dev go together: both or neither";
-  if (norm && (((uintptr_t)mean_dev | (uintptr_t)var_dev) & 7)) return "mean_dev and var_dev must be 8-byte aligned";
-  if (norm && mean_dev == var_dev) return "mean_dev and var_dev must not be the same pointer";
-  if (norm && !(epsilon >= 0.0 && epsilon <= 1.7976931348623157e308 && clip_obs >= 0.0 && clip_obs <= 1.7976931348623157e308)) return "epsilon and clip_obs must be finite and >= 0 when statistics are given";
-  return nullptr;
-}
-
-int bg_linear_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
-                   const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, const void* weight_dev, uint64_t weight_stride_elems,
-                   const float* bias_dev, int H, int activation, int out_dtype, void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream) {
-  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const char* bad = bg_linear_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, layout, mean_dev, var_dev, epsilon, clip_obs, H, activation);
-  if (bad) {}
-  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (!weight_dev || ((uintptr_t)weight_dev & 1)) bad = "weight_dev must be a 2-byte aligned device pointer";
-  else if (weight_stride_elems < (uint64_t)BG_LIN_K || weight_stride_elems > 0x1000000ull) bad = "weight_stride_elems must be in [153, 2**24]";
-  else if ((uintptr_t)bias_dev & 3) bad = "bias_dev must be 4-byte aligned";
-  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
-  else if (out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= H";
-  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev ||
-           out_dev == weight_dev || out_dev == (const void*)bias_dev) bad = "out_dev must not be the same pointer as an input";
-  if (bad) { g_create_err = std::string("bg_linear_rows: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  const unsigned gx = (unsigned)bg_lin_blocks(m);
-  const unsigned nchunks = (unsigned)((H + BG_LIN_WCHUNK - 1) / BG_LIN_WCHUNK);
-  unsigned ys = 1;
-  while ((uint64_t)gx * ys < 512u && ys * 2u <= nchunks) ys *= 2u;   // a short call: the chunks of H over more workgroups (a function of m and H alone)
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-  const int relu = activation == BG_LIN_RELU;
-#define BG_LIN_GO(NORM, T) hipLaunchKernelGGL((bg_linear_rows_kernel<NORM, T>), dim3(gx, ys), dim3(BG_LIN_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, (const uint16_t*)weight_dev, weight_stride_elems, bias_dev, H, relu, out_dev, out_stride_elems)
-  if (mean_dev) { if (out_dtype == BG_ENC_F32) BG_LIN_GO(true, BG_ENC_F32); else BG_LIN_GO(true, BG_ENC_BF16); }
-  else { if (out_dtype == BG_ENC_F32) BG_LIN_GO(false, BG_ENC_F32); else BG_LIN_GO(false, BG_ENC_BF16); }
-#undef BG_LIN_GO
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-uint64_t bg_linear_rows_workspace_bytes(int64_t m, int H) {
-  if (m <= 0 || H < 32 || H > 4096 || H % 32) return 0;
-  return (uint64_t)bg_lin_groups(m, H) * BG_LIN_PART_ROWS * (uint64_t)H * sizeof(float);
-}
-
-int bg_linear_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
-                        const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, const void* dout_dev, int dout_dtype,
-                        uint64_t dout_stride_elems, const void* out_dev, int out_dtype, uint64_t out_stride_elems, int H, int activation,
-                        float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev, void* workspace_dev, uint64_t workspace_bytes,
-                        float* kernel_ms_out, void* stream) {
-  const uint64_t ds = dout_dtype == BG_ENC_F32 ? 4u : 2u, os = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const bool relu = activation == BG_LIN_RELU;
-  const char* bad = bg_linear_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, layout, mean_dev, var_dev, epsilon, clip_obs, H, activation);
-  if (bad) {}
-  else if (dout_dtype != BG_ENC_F32 && dout_dtype != BG_ENC_BF16) bad = "dout_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (!dout_dev || ((uintptr_t)dout_dev & (ds - 1))) bad = "dout_dev must be a device pointer aligned to its element type";
-  else if (dout_stride_elems < (uint64_t)H || dout_stride_elems > 0xffffffffull) bad = "dout_stride_elems must be >= H";
-  else if (relu != (out_dev != nullptr)) bad = "out_dev (the forward's output) is required with BG_LIN_RELU and must be NULL without it";
-  else if (relu && out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (relu && (((uintptr_t)out_dev & (os - 1)) || out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull)) bad = "out_dev must be aligned to its element type and out_stride_elems >= H";
-  else if (!dweight_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev must be a 4-byte aligned device pointer (dbias_dev 4-byte aligned)";
-  else if (dweight_stride_elems < (uint64_t)BG_LIN_K || dweight_stride_elems > 0xffffffffull) bad = "dweight_stride_elems must be >= 153";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_linear_rows_workspace_bytes(m, H))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_linear_rows_workspace_bytes(m, H) bytes";
-  else if ((const void*)dweight_dev == dout_dev || (const void*)dweight_dev == out_dev || (const void*)dweight_dev == (const void*)rows_dev || dweight_dev == dbias_dev ||
-           (void*)dweight_dev == workspace_dev || (dbias_dev && ((void*)dbias_dev == workspace_dev || (const void*)dbias_dev == dout_dev || (const void*)dbias_dev == out_dev)) ||
-           workspace_dev == dout_dev || (workspace_dev && workspace_dev == out_dev)) bad = "outputs and the workspace must not be the same pointer as an input or as each other";
-  if (bad) { g_create_err = std::string("bg_linear_rows_grad: ") + bad; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  const long long per = bg_lin_blocks_per_group(m, H), groups = bg_lin_groups(m, H);
-  hipStream_t s = (hipStream_t)stream;
-  BgOpTimer tm;
-  int rc = tm.begin(kernel_ms_out, s);
-  if (rc) return rc;
-#define BG_LIN_GO(NORM) hipLaunchKernelGGL((bg_linear_rows_grad_kernel<NORM>), dim3((unsigned)groups, (unsigned)bg_lin_spans(H)), dim3(BG_LIN_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, mean_dev, var_dev, epsilon, clip_obs, dout_dev, (int)(dout_dtype == BG_ENC_BF16), dout_stride_elems, out_dev, (int)(out_dtype == BG_ENC_BF16), out_stride_elems, H, per, (float*)workspace_dev)
-  if (mean_dev) BG_LIN_GO(true); else BG_LIN_GO(false);
-#undef BG_LIN_GO
-  const long long items = (long long)BG_LIN_PART_ROWS * H;
-  hipLaunchKernelGGL(bg_linear_reduce_kernel, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)workspace_dev, groups, H, dweight_dev, dweight_stride_elems, dbias_dev);
-  tm.mark(s);
-  BG_HIP0(hipGetLastError());
-  return tm.end(kernel_ms_out);
-}
-
-static int bg_batch_dev(BgDev& d, int m, uint32_t** scratch_out);
-
-int bg_score_hand_batch_ex(const int32_t* cases_dev, int64_t* out_dev, int m, int lanes_per_case, float* kernel_ms_out, void* stream) {
-  if (!cases_dev || !out_dev || m < 0 || (lanes_per_case != 1 && lanes_per_case != 8)) { g_create_err = "bg_score_hand_batch: bad arguments (lanes_per_case 1 or 8)"; return BG_E_ARG; }
-  if (kernel_ms_out) *kernel_ms_out = 0.f;
-  if (m == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  BgDev d;
-  uint32_t* scratch = nullptr; // two MT19937 blocks per case + the error word
-  int rc = bg_batch_dev(d, m, &scratch);
-  if (rc) return rc;
-  BgOpTimer tm;
-  hipError_t e = hipMemsetAsync(d.err, 0, 4 * sizeof(uint32_t), s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(bg_score_seed_kernel, dim3((m + BG_BLOCK - 1) / BG_BLOCK), dim3(BG_BLOCK), 0, s, d, cases_dev); // random.seed(gseed) per case
-    rc = tm.begin(kernel_ms_out, s);
-    if (lanes_per_case == 1)
-      hipLaunchKernelGGL(bg_score_hand_batch_kernel, dim3((m + BG_BLOCK - 1) / BG_BLOCK), dim3(BG_BLOCK), 0, s, d, cases_dev, out_dev);
-    else
-      hipLaunchKernelGGL(bg_score_hand_batch_l8_kernel, dim3((m + BG_BLOCK / 8 - 1) / (BG_BLOCK / 8)), dim3(BG_BLOCK), 0, s, d, cases_dev, out_dev);
-    tm.mark(s);
-    e = hipGetLastError();
-  }
-  uint32_t errw = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&errw, d.err, sizeof(errw), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  if (e == hipSuccess && rc == 0) rc = tm.end(kernel_ms_out);
-  (void)hipFree(scratch);
-  if (e != hipSuccess) { g_create_err = std::string("bg_score_hand_batch: ") + hipGetErrorString(e); return BG_E_HIP; }
-  if (rc) return rc;
-  if (errw) { g_create_err = "bg_score_hand_batch: a case drew more than two blocks of the global stream"; return BG_E_INTERNAL; }
-  return 0;
-}
-int bg_score_hand_batch(const int32_t* cases_dev, int64_t* out_dev, int m, void* stream) {
-  return bg_score_hand_batch_ex(cases_dev, out_dev, m, 1, nullptr, stream);
-}
-
-// scratch of a batch op that draws from a per-case global stream: two MT19937 blocks per case + the device error word
-static int bg_batch_dev(BgDev& d, int m, uint32_t** scratch_out) {
-  memset(&d, 0, sizeof(d));
-  d.N = m; d.flags = BG_FLAG_SCORER_JOKERS; d.KG = 2; d.KS = 2; d.KD = 1;
-  uint32_t* scratch = nullptr;
-  BG_HIP0(hipMalloc((void**)&scratch, ((size_t)m * 2 * BG_MTS + 4) * sizeof(uint32_t)));
-  d.gblk = scratch; d.err = scratch + (size_t)m * 2 * BG_MTS;
-  *scratch_out = scratch;
-  return 0;
-}
-
-int bg_sim_evaluate_batch(const int32_t* hands_dev, const int32_t* n_dev, const int32_t* flags_dev, int8_t* out_dev, int m, void* stream) {
-  if (!hands_dev || !n_dev || !flags_dev || !out_dev || m < 0) { g_create_err = "bg_sim_evaluate_batch: bad arguments"; return BG_E_ARG; }
-  if (m == 0) return 0;
-  hipLaunchKernelGGL(bg_sim_evaluate_batch_kernel, dim3((m + BG_BLOCK - 1) / BG_BLOCK), dim3(BG_BLOCK), 0, (hipStream_t)stream, hands_dev, n_dev, flags_dev, out_dev, m);
-  BG_HIP0(hipGetLastError());
-  return 0;
-}
-
-int bg_sim_score_batch(const int32_t* cases_dev, int64_t* out_dev, int m, void* stream) {
-  if (!cases_dev || !out_dev || m < 0) { g_create_err = "bg_sim_score_batch: bad arguments"; return BG_E_ARG; }
-  if (m == 0) return 0;
-  hipStream_t s = (hipStream_t)stream;
-  BgDev d;
-  uint32_t* scratch = nullptr;
-  int rc = bg_batch_dev(d, m, &scratch);
-  if (rc) return rc;
-  hipError_t e = hipMemsetAsync(d.err, 0, 4 * sizeof(uint32_t), s);
-  if (e == hipSuccess) {
-    hipLaunchKernelGGL(bg_sim_score_batch_kernel, dim3((m + BG_BLOCK - 1) / BG_BLOCK), dim3(BG_BLOCK), 0, s, d, cases_dev, out_dev);
-    e = hipGetLastError();
-  }
-  uint32_t errw = 0;
-  if (e == hipSuccess) e = hipMemcpyAsync(&errw, d.err, sizeof(errw), hipMemcpyDeviceToHost, s);
-  if (e == hipSuccess) e = hipStreamSynchronize(s);
-  (void)hipFree(scratch);
-  if (e != hipSuccess) { g_create_err = std::string("bg_sim_score_batch: ") + hipGetErrorString(e); return BG_E_HIP; }
-  if (errw) { g_create_err = "bg_sim_score_batch: a case drew more than two blocks of the global stream"; return BG_E_INTERNAL; }
-  return 0;
-}
+#include "bg_rows_api.h" // the stateless entry points (no handle): the measurement hooks, the batch operators and the record learners
 
 } // extern "C"

@@ -15,6 +15,10 @@ import numpy as np
 import torch
 
 from . import _native as nat
+# the learner's calls over records and logits live in rows.py; every name that used to be defined here stays importable from here
+from .rows import (DqnStats, EpisodeLimits, EpisodeStats, PpoStats, ProgressionRewards, RowCurriculum, RowLinear, RowNormalizer,  # noqa: F401
+                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, dqn_loss, encode_rows, episode_ends, evaluate_actions,
+                   gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
 
 _TORCH_DT = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
              "float32": torch.float32, "float64": torch.float64, "uint8": torch.uint8, "uint32": torch.uint32}
@@ -812,1291 +816,6 @@ def classify_batch(cards: torch.Tensor, n: torch.Tensor, lanes_per_case: int = 1
     if rc != 0:
         raise nat.NativeError(f"bg_classify_batch failed ({rc}): {L.bg_last_error(None).decode()}")
     return (out, float(ms.value)) if timing else out
-
-
-def _check_index(index, shape: Optional[tuple], device: torch.device) -> None:
-    """The `index=` of ppo_loss and encode_rows (SB3's `RolloutBuffer.get` permutation): contiguous int32 on `device`, of `shape` (None: any [m])."""
-    if not isinstance(index, torch.Tensor) or index.dtype != torch.int32 or (tuple(index.shape) != shape if shape is not None else index.dim() != 1) \
-            or not index.is_contiguous() or index.device != device:
-        raise ValueError(f"index must be a contiguous torch.int32 tensor of shape {list(shape) if shape is not None else '[m]'} on {device}")
-
-
-def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
-                timing: bool = False, *, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None):
-    """Packed records -> the float matrix a policy network reads, in one launch (bg_encode_rows).  rows: a contiguous uint8 device tensor
-    [..., stride] of records as `rollout` / `step_many` / an obs_layout="rows" env write them (`RowBuffers.rows`, `env.obs_rows`).
-    layout: "produced" -- the 31 observation keys in the reference's key order, every element as float (153 columns: what SB3's
-    CombinedExtractor concatenates); "fixed" -- those followed by the 475 zeros of BalatroEnvFixed's never-filled keys (628);
-    "extractor" -- what BalatroFeaturesExtractor.forward builds: hand one-hot, joker ids, 21 normalised state features (447).
-    `_native.ENC_COLUMNS[layout]` names the column ranges.  dtype: torch.float32 or torch.bfloat16 (round to nearest even).
-    out: optional [..., >= D] tensor of `dtype` on the same device with the same leading shape, last dimension contiguous and the leading
-    dimensions dense over its row pitch (e.g. a column slice of a wider matrix): columns beyond D are left untouched.
-    Returns the [..., D] matrix (a view of `out` when given); timing=True returns (matrix, kernel milliseconds).
-    index: int32 [m] on the rows' device -- the tensor `ppo_loss(index=)` takes (`RowBuffers.minibatches`): the result (and `out`) is [m, D], row i
-    made from record index[i] of the flattened rows (t * N + e names record (t, e)), gathered inside the launch (bg_encode_rows_ex); a row whose index
-    is out of range is zeros, the row `ppo_loss` excludes.  norm: a `RowNormalizer`: the rows as its `normalize_obs` gives them with the statistics
-    frozen ("produced" / "fixed"); its statistics, epsilon and clip_obs are read, never updated.  Without index and norm the call is bg_encode_rows."""
-    if layout not in nat.ENC_LAYOUTS:
-        raise ValueError(f"layout must be one of {sorted(nat.ENC_LAYOUTS)} (got {layout!r})")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 1 or not rows.is_contiguous():
-        raise ValueError("rows must be a contiguous uint8 tensor [..., stride] of packed records")
-    stride = int(rows.shape[-1])
-    if stride < nat.ROW_BYTES or stride % 16:
-        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
-    D = nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]
-    lead = tuple(rows.shape[:-1])
-    store_rows = int(np.prod(lead, dtype=np.int64))
-    if index is not None:
-        _check_index(index, None, rows.device)
-        if store_rows >= 2 ** 31:
-            raise ValueError("the stored records hold at most 2**31 - 1 rows")
-        lead = (int(index.shape[0]),)
-    if norm is not None:
-        if not isinstance(norm, RowNormalizer):
-            raise ValueError("norm must be a RowNormalizer")
-        if not norm.norm_obs:
-            raise ValueError("this RowNormalizer was made with norm_obs=False: use encode_rows without norm")
-        if layout not in ("produced", "fixed"):
-            raise ValueError(f"layout must be 'produced' or 'fixed' with norm (got {layout!r}): VecNormalize wraps the env's keys, not the extractor's tensors")
-        if norm.device != rows.device:
-            raise ValueError(f"norm holds its statistics on {norm.device}, rows are on {rows.device}")
-        if not (np.isfinite(norm.epsilon) and norm.epsilon >= 0.0 and np.isfinite(norm.clip_obs) and norm.clip_obs >= 0.0):
-            raise ValueError("norm.epsilon and norm.clip_obs must be finite and >= 0")
-    m = int(np.prod(lead, dtype=np.int64))
-    if out is not None:
-        if not isinstance(out, torch.Tensor) or out.dtype != dtype or out.device != rows.device:
-            raise ValueError(f"out must be a {dtype} tensor on {rows.device}")
-        if tuple(out.shape[:-1]) != lead or out.shape[-1] < D:
-            raise ValueError(f"out must have shape {lead + ('>= %d' % D,)} (got {tuple(out.shape)})")
-        pitch = int(out.stride(-2)) if out.dim() >= 2 else int(out.shape[-1])
-        dense = out.stride(-1) == 1 and pitch >= out.shape[-1]
-        for d in range(out.dim() - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
-            dense = dense and out.stride(d - 1) == out.stride(d) * out.shape[d]
-        if not dense:
-            raise ValueError("out must have a contiguous last dimension and leading dimensions that are dense over its row pitch")
-    if not rows.is_cuda:
-        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-    if rows.data_ptr() % 16:
-        raise ValueError("rows must be 16-byte aligned")
-    if out is None:
-        out = torch.empty(lead + (D,), dtype=dtype, device=rows.device)
-        pitch = D
-    if m == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
-        return (out[..., :D], 0.0) if timing else out[..., :D]
-    L = nat.load()
-    ms = C.c_float(0.0)
-    odt = nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16
-    tail = (C.c_void_p(out.data_ptr()), C.c_uint64(pitch), C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
-    with torch.cuda.device(rows.device):
-        if index is None and norm is None:
-            name = "bg_encode_rows"
-            rc = L.bg_encode_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(m), nat.ENC_LAYOUTS[layout], odt, *tail)
-        else:
-            name = "bg_encode_rows_ex"
-            rc = L.bg_encode_rows_ex(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(store_rows),
-                                     C.c_void_p(index.data_ptr()) if index is not None else None, C.c_int64(m), nat.ENC_LAYOUTS[layout], odt,
-                                     C.c_void_p(norm.obs_mean.data_ptr()) if norm is not None else None,
-                                     C.c_void_p(norm.obs_var.data_ptr()) if norm is not None else None,
-                                     C.c_double(norm.epsilon if norm is not None else 0.0), C.c_double(norm.clip_obs if norm is not None else 0.0), *tail)
-    if rc != 0:
-        raise nat.NativeError(f"{name} failed ({rc}): {L.bg_last_error(None).decode()}")
-    res = out[..., :D]
-    return (res, float(ms.value)) if timing else res
-
-
-def _linear_common(rows, index, norm, layout, activation):
-    """The arguments linear_rows and its gradient share -> (stride, store_rows, m).  Every refusal is a ValueError before the library is loaded."""
-    if layout not in ("produced", "fixed"):
-        raise ValueError(f"layout must be 'produced' or 'fixed' (got {layout!r}): the extractor's one-hot columns want an embedding gather, not this layer")
-    if activation not in nat.LIN_ACTIVATIONS:
-        raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 1 or not rows.is_contiguous():
-        raise ValueError("rows must be a contiguous uint8 tensor [..., stride] of packed records")
-    stride = int(rows.shape[-1])
-    if stride < nat.ROW_BYTES or stride % 16:
-        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
-    store_rows = int(np.prod(tuple(rows.shape[:-1]), dtype=np.int64))
-    m = store_rows
-    if index is not None:
-        _check_index(index, None, rows.device)
-        if store_rows >= 2 ** 31:
-            raise ValueError("the stored records hold at most 2**31 - 1 rows")
-        m = int(index.shape[0])
-    if norm is not None:
-        if not isinstance(norm, RowNormalizer):
-            raise ValueError("norm must be a RowNormalizer")
-        if not norm.norm_obs:
-            raise ValueError("this RowNormalizer was made with norm_obs=False: call without norm")
-        if norm.device != rows.device:
-            raise ValueError(f"norm holds its statistics on {norm.device}, rows are on {rows.device}")
-        if not (np.isfinite(norm.epsilon) and norm.epsilon >= 0.0 and np.isfinite(norm.clip_obs) and norm.clip_obs >= 0.0):
-            raise ValueError("norm.epsilon and norm.clip_obs must be finite and >= 0")
-    return stride, store_rows, m
-
-
-def _linear_matrix(name: str, t, dtypes: tuple, m: int, H: int, device: torch.device) -> int:
-    """A [m, >= H] matrix with a contiguous last dimension -> its row pitch in elements."""
-    if not isinstance(t, torch.Tensor) or t.dtype not in dtypes or t.device != device or t.dim() != 2 or t.shape[0] != m or t.shape[1] < H \
-            or t.stride(1) != 1 or (m > 1 and t.stride(0) < t.shape[1]):
-        raise ValueError(f"{name} must be a {' / '.join(str(d) for d in dtypes)} tensor [{m}, >= {H}] on {device} with a contiguous last dimension")
-    return int(t.stride(0)) if m > 1 else int(t.shape[1])
-
-
-def _linear_weight(weight) -> int:
-    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.bfloat16 or weight.dim() != 2 or weight.shape[1] not in (nat.LIN_K, nat.ENC_COLS[nat.ENC_FIXED]) \
-            or not weight.is_contiguous():
-        raise ValueError("weight must be a contiguous torch.bfloat16 tensor [H, 153] or [H, 628] (nn.Linear.weight's orientation)")
-    H = int(weight.shape[0])
-    if H < 32 or H > 4096 or H % 32:
-        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
-    return H
-
-
-def _linear_rows_args(rows, index, norm):
-    return (C.c_void_p(norm.obs_mean.data_ptr()) if norm is not None else None, C.c_void_p(norm.obs_var.data_ptr()) if norm is not None else None,
-            C.c_double(norm.epsilon if norm is not None else 0.0), C.c_double(norm.clip_obs if norm is not None else 0.0))
-
-
-def linear_rows(rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, index: Optional[torch.Tensor] = None,
-                norm: Optional["RowNormalizer"] = None, layout: str = "fixed", activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16,
-                out: Optional[torch.Tensor] = None, timing: bool = False):
-    """The network's first layer straight from packed records, on the matrix cores, in one launch (bg_linear_rows):
-    act(x @ weight[:, :153].T + bias), x the bfloat16 rows `encode_rows(rows, layout, torch.bfloat16, index=index, norm=norm)` gives -- which are never
-    written.  weight: torch.bfloat16 [H, 153] or [H, 628] (nn.Linear.weight's orientation; of 628 columns only the first 153 are read: the others meet the
-    475 zeros of the "fixed" layout), H a multiple of 32 in [32, 4096]; bias: float32 [H] or None; activation: None or "relu".  layout "fixed" or
-    "produced": the same result.  index / norm: as `encode_rows`; a row whose index is out of range is act(bias).  dtype: torch.bfloat16 or
-    torch.float32 (float32 accumulation either way, one rounding).  out: optional [m, >= H] tensor of `dtype`; columns beyond H are left untouched.
-    Returns the [m, H] matrix (m = all records flattened, or len(index)); timing=True returns (matrix, kernel milliseconds).  There is no CPU path."""
-    stride, store_rows, m = _linear_common(rows, index, norm, layout, activation)
-    H = _linear_weight(weight)
-    if weight.device != rows.device:
-        raise ValueError(f"weight must be on {rows.device}")
-    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (H,) or not bias.is_contiguous()
-                             or bias.device != rows.device):
-        raise ValueError(f"bias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-    pitch = _linear_matrix("out", out, (dtype,), m, H, rows.device) if out is not None else H
-    if not rows.is_cuda:
-        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-    if rows.data_ptr() % 16:
-        raise ValueError("rows must be 16-byte aligned")
-    if out is None:
-        out = torch.empty((m, H), dtype=dtype, device=rows.device)
-    if m == 0:
-        return (out[:, :H], 0.0) if timing else out[:, :H]
-    L = nat.load()
-    ms = C.c_float(0.0)
-    with torch.cuda.device(rows.device):
-        rc = L.bg_linear_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(store_rows), C.c_void_p(index.data_ptr()) if index is not None else None,
-                              C.c_int64(m), nat.ENC_LAYOUTS[layout], *_linear_rows_args(rows, index, norm), C.c_void_p(weight.data_ptr()),
-                              C.c_uint64(int(weight.shape[1])), C.c_void_p(bias.data_ptr()) if bias is not None else None, H, nat.LIN_ACTIVATIONS[activation],
-                              nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(out.data_ptr()), C.c_uint64(pitch),
-                              C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
-    if rc != 0:
-        raise nat.NativeError(f"bg_linear_rows failed ({rc}): {L.bg_last_error(None).decode()}")
-    return (out[:, :H], float(ms.value)) if timing else out[:, :H]
-
-
-def linear_rows_grad(rows: torch.Tensor, dout: torch.Tensor, *, out: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None,
-                     norm: Optional["RowNormalizer"] = None, layout: str = "fixed", activation: Optional[str] = None, dweight: Optional[torch.Tensor] = None,
-                     bias: bool = True, workspace: Optional[torch.Tensor] = None, timing: bool = False):
-    """The weight and bias gradient of `linear_rows`, straight from the records (bg_linear_rows_grad): dweight[n, k] = sum_i dp[i, n] * x[i, k],
-    dbias[n] = sum_i dp[i, n], dp = bfloat16(dout), under activation="relu" masked where the forward's `out` (required then) is not > 0.  dout: float32 or
-    bfloat16 [m, >= H].  dweight: optional float32 [H, 153] or [H, 628] (columns beyond 153 are not written); without one a zero-filled [H, 628] ("fixed")
-    or [H, 153] ("produced") is made, so the columns beyond 153 carry their exact gradient, zero.  Returns (dweight, dbias or None) -- with timing=True
-    (dweight, dbias, kernel milliseconds).  Sums over rows are deterministic (no atomics)."""
-    stride, store_rows, m = _linear_common(rows, index, norm, layout, activation)
-    if not isinstance(dout, torch.Tensor) or dout.dim() != 2:
-        raise ValueError("dout must be a float32 / bfloat16 tensor [m, H]")
-    H = int(dweight.shape[0]) if isinstance(dweight, torch.Tensor) and dweight.dim() == 2 else int(dout.shape[1])
-    if H < 32 or H > 4096 or H % 32:
-        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
-    dpitch = _linear_matrix("dout", dout, (torch.float32, torch.bfloat16), m, H, rows.device)
-    relu = activation == "relu"
-    if relu != (out is not None):
-        raise ValueError("out (the forward's output) is required with activation='relu' and must be None without it")
-    opitch = _linear_matrix("out", out, (torch.float32, torch.bfloat16), m, H, rows.device) if relu else 0
-    if dweight is not None and (not isinstance(dweight, torch.Tensor) or dweight.dtype != torch.float32 or dweight.dim() != 2 or dweight.shape[1] < nat.LIN_K
-                                or not dweight.is_contiguous() or dweight.device != rows.device):
-        raise ValueError(f"dweight must be a contiguous torch.float32 tensor [H, >= {nat.LIN_K}] on {rows.device}")
-    if not rows.is_cuda:
-        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-    if rows.data_ptr() % 16:
-        raise ValueError("rows must be 16-byte aligned")
-    if dweight is None:
-        dweight = torch.zeros((H, nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]), dtype=torch.float32, device=rows.device)
-    dbias = torch.zeros(H, dtype=torch.float32, device=rows.device) if bias else None
-    if m == 0:
-        dweight[:, :nat.LIN_K] = 0.0
-        return (dweight, dbias, 0.0) if timing else (dweight, dbias)
-    L = nat.load()
-    need = int(L.bg_linear_rows_workspace_bytes(C.c_int64(m), H))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
-    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != rows.device or not workspace.is_contiguous() \
-            or workspace.numel() < need:
-        raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {rows.device}")
-    ms = C.c_float(0.0)
-    with torch.cuda.device(rows.device):
-        rc = L.bg_linear_rows_grad(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), C.c_int64(store_rows), C.c_void_p(index.data_ptr()) if index is not None else None,
-                                   C.c_int64(m), nat.ENC_LAYOUTS[layout], *_linear_rows_args(rows, index, norm), C.c_void_p(dout.data_ptr()),
-                                   nat.ENC_F32 if dout.dtype == torch.float32 else nat.ENC_BF16, C.c_uint64(dpitch),
-                                   C.c_void_p(out.data_ptr()) if relu else None, (nat.ENC_F32 if out.dtype == torch.float32 else nat.ENC_BF16) if relu else 0,
-                                   C.c_uint64(opitch), H, nat.LIN_ACTIVATIONS[activation], C.c_void_p(dweight.data_ptr()), C.c_uint64(int(dweight.shape[1])),
-                                   C.c_void_p(dbias.data_ptr()) if bias else None, C.c_void_p(workspace.data_ptr()), C.c_uint64(workspace.numel()),
-                                   C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(rows.device).cuda_stream))
-    if rc != 0:
-        raise nat.NativeError(f"bg_linear_rows_grad failed ({rc}): {L.bg_last_error(None).decode()}")
-    return (dweight, dbias, float(ms.value)) if timing else (dweight, dbias)
-
-
-class _RowLinearFn(torch.autograd.Function):
-    """out = linear_rows(records); backward = ONE bg_linear_rows_grad call.  The records carry no gradient."""
-
-    @staticmethod
-    def forward(ctx, weight, bias, rows, index, norm, layout, activation, dtype):
-        out = linear_rows(rows, weight.detach().to(torch.bfloat16), bias.detach() if bias is not None else None, index=index, norm=norm, layout=layout,
-                          activation=activation, dtype=dtype)
-        ctx.save_for_backward(out)
-        ctx.call = (rows, index, norm, layout, activation, tuple(weight.shape), bias is not None)
-        return out
-
-    @staticmethod
-    def backward(ctx, grad):
-        rows, index, norm, layout, activation, wshape, has_bias = ctx.call
-        out, = ctx.saved_tensors
-        dout = grad if grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.stride(1) == 1 and (grad.shape[0] <= 1 or grad.stride(0) >= grad.shape[1]) \
-            else grad.to(torch.float32).contiguous()
-        dweight = torch.zeros(wshape, dtype=torch.float32, device=rows.device)   # columns at or beyond 153: zero, their exact gradient
-        dweight, dbias = linear_rows_grad(rows, dout, out=out if activation == "relu" else None, index=index, norm=norm, layout=layout, activation=activation,
-                                          dweight=dweight, bias=has_bias)
-        return dweight, dbias, None, None, None, None, None, None
-
-
-class RowLinear(torch.nn.Module):
-    """The first `nn.Linear` of a policy over packed records: `forward(rows)` is `linear_rows` and its backward one `linear_rows_grad` call, so neither pass
-    materialises the feature matrix.  Parameters are float32 -- weight [out_features, 628] ("fixed": SB3's MultiInputPolicy over BalatroEnvFixed) or
-    [out_features, 153] ("produced"), bias [out_features] -- initialised as nn.Linear; `from_linear` / `to_linear` move them to and from an nn.Linear, so a
-    policy trained here loads into SB3's module and back.  The weight is cast to bfloat16 for every call (the master copy stays float32); columns at or
-    beyond 153 of a 628-wide weight get a zero gradient, which is their exact gradient: their inputs are zero."""
-
-    def __init__(self, out_features: int, in_layout: str = "fixed", activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16, device=None):
-        super().__init__()
-        if in_layout not in ("produced", "fixed"):
-            raise ValueError(f"in_layout must be 'produced' or 'fixed' (got {in_layout!r})")
-        if activation not in nat.LIN_ACTIVATIONS:
-            raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-        out_features = int(out_features)
-        if out_features < 32 or out_features > 4096 or out_features % 32:
-            raise ValueError(f"out_features must be a multiple of 32 in [32, 4096] (got {out_features})")
-        self.out_features, self.in_layout, self.activation, self.dtype = out_features, in_layout, activation, dtype
-        self.in_features = nat.ENC_COLS[nat.ENC_LAYOUTS[in_layout]]
-        lin = torch.nn.Linear(self.in_features, out_features, device=device)   # nn.Linear's own initialisation
-        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
-        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
-
-    @classmethod
-    def from_linear(cls, linear: torch.nn.Linear, activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16) -> "RowLinear":
-        if not isinstance(linear, torch.nn.Linear) or linear.in_features not in (nat.LIN_K, nat.ENC_COLS[nat.ENC_FIXED]) or linear.bias is None:
-            raise ValueError("from_linear takes an nn.Linear with bias and 153 ('produced') or 628 ('fixed') inputs")
-        layer = cls(linear.out_features, "produced" if linear.in_features == nat.LIN_K else "fixed", activation, dtype, device=linear.weight.device)
-        with torch.no_grad():
-            layer.weight.copy_(linear.weight)
-            layer.bias.copy_(linear.bias)
-        return layer
-
-    def to_linear(self) -> torch.nn.Linear:
-        lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
-        with torch.no_grad():
-            lin.weight.copy_(self.weight)
-            lin.bias.copy_(self.bias)
-        return lin
-
-    def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None) -> torch.Tensor:
-        _linear_common(rows, index, norm, self.in_layout, self.activation)
-        if not rows.is_cuda or self.weight.device != rows.device:
-            raise ValueError("rows and the layer must be on the same GPU (there is no CPU fallback)")
-        return _RowLinearFn.apply(self.weight, self.bias, rows, index, norm, self.in_layout, self.activation, self.dtype)
-
-    def extra_repr(self) -> str:
-        return f"in_layout={self.in_layout!r}, out_features={self.out_features}, activation={self.activation!r}, dtype={self.dtype}"
-
-
-def _head_logits(logits) -> tuple:
-    """logits of sample_actions / evaluate_actions: float32 / bfloat16 [..., 60] with a contiguous last dimension and leading dimensions dense over the
-    row pitch (e.g. 60 columns of a wider matrix) -> (leading shape, m, row pitch in elements)."""
-    if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16) or logits.dim() < 1 or logits.shape[-1] != 60:
-        raise ValueError("logits must be a float32 or bfloat16 tensor [..., 60]")
-    pitch = int(logits.stride(-2)) if logits.dim() >= 2 else 60
-    dense = logits.stride(-1) == 1 and pitch >= 60
-    for d in range(logits.dim() - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
-        dense = dense and logits.stride(d - 1) == logits.stride(d) * logits.shape[d]
-    if not dense:
-        raise ValueError("logits must have a contiguous last dimension and leading dimensions that are dense over its row pitch")
-    lead = tuple(logits.shape[:-1])
-    return lead, int(np.prod(lead, dtype=np.int64)), pitch
-
-
-def _head_mask(mask, lead: tuple, device: torch.device) -> tuple:
-    """mask of sample_actions / evaluate_actions -> (tensor to keep alive, byte offset of the first row's mask, row pitch in bytes): packed records
-    (a contiguous uint8 tensor [..., stride], recognised as encode_rows recognises them), an int8 [..., 60] matrix, or None."""
-    if mask is None:
-        return None, 0, 0
-    if not isinstance(mask, torch.Tensor) or mask.dim() < 1:
-        raise ValueError("mask must be a uint8 tensor [..., stride] of packed records, an int8 tensor [..., 60] or None")
-    if mask.dtype == torch.uint8:
-        stride = int(mask.shape[-1])
-        if not mask.is_contiguous() or stride < nat.ROW_BYTES or stride % 16:
-            raise ValueError(f"a uint8 mask is a contiguous tensor [..., stride] of packed records: stride a multiple of 16, >= {nat.ROW_BYTES}")
-        off = nat.ROW_OFFSETS["action_mask"]
-    elif mask.dtype == torch.int8 and mask.shape[-1] == 60:
-        stride = int(mask.stride(-2)) if mask.dim() >= 2 else 60
-        dense = mask.stride(-1) == 1 and stride >= 60
-        for d in range(mask.dim() - 2, 0, -1):
-            dense = dense and mask.stride(d - 1) == mask.stride(d) * mask.shape[d]
-        if not dense or stride % 4:
-            raise ValueError("an int8 mask must have a contiguous last dimension and leading dimensions dense over a row pitch that is a multiple of 4")
-        off = 0
-    else:
-        raise ValueError("mask must be a uint8 tensor [..., stride] of packed records, an int8 tensor [..., 60] or None")
-    if tuple(mask.shape[:-1]) != lead:
-        raise ValueError(f"mask must have the leading shape of logits {list(lead)} (got {list(mask.shape[:-1])})")
-    if mask.device != device:
-        raise ValueError(f"mask must be on {device}")
-    return mask, off, stride
-
-
-def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: int, t: int, actions, log_prob, entropy, timing: bool,
-               epsilon: Optional[float] = None):
-    lead, m, pitch = _head_logits(logits)
-    dev = logits.device
-    mask, moff, mstride = _head_mask(mask, lead, dev)
-    if epsilon is not None:
-        return _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, index0, t, actions, log_prob, entropy, timing, epsilon)
-    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
-            raise ValueError(f"{what} must be an integer in [0, 2**64)")
-    if given is not None:
-        _check_scan_tensor("actions", given, torch.int32, lead, dev)
-    for what, tt, dt in (("actions", actions, torch.int32), ("log_prob", log_prob, torch.float32), ("entropy", entropy, torch.float32)):
-        if tt is not None:
-            _check_scan_tensor(what, tt, dt, lead, dev)
-    if not logits.is_cuda:
-        raise ValueError("logits must be a device tensor (there is no CPU fallback)")
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
-    if given is None and actions is None:
-        actions = torch.empty(lead, dtype=torch.int32, device=dev)
-    if log_prob is None:
-        log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
-    if entropy is None:
-        entropy = torch.empty(lead, dtype=torch.float32, device=dev)
-    res = (log_prob, entropy) if given is not None else (actions, log_prob, entropy)
-    if m == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
-        return res + (0.0,) if timing else res
-    outs = [x.data_ptr() for x in res]
-    ins = [logits.data_ptr()] + ([mask.data_ptr()] if mask is not None else []) + ([given.data_ptr()] if given is not None else [])
-    if len(set(outs)) != len(outs) or set(outs) & set(ins):
-        raise ValueError("outputs must not share memory with the inputs or with each other")
-    L = nat.load()
-    ms = C.c_float(0.0)
-    with torch.cuda.device(dev):
-        head = (C.c_void_p(logits.data_ptr()), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
-                C.c_void_p(mask.data_ptr() + moff) if mask is not None else None, C.c_uint64(mstride), C.c_int64(m))
-        tail = (C.c_void_p(log_prob.data_ptr()), C.c_void_p(entropy.data_ptr()), C.byref(ms) if timing else None,
-                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if given is None:
-            rc = L.bg_sample_actions(*head, C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)),
-                                     C.c_void_p(actions.data_ptr()), *tail)
-        else:
-            rc = L.bg_evaluate_actions(*head, C.c_void_p(given.data_ptr()), *tail)
-    if rc != 0:
-        raise nat.NativeError(f"{name} failed ({rc}): {L.bg_last_error(None).decode()}")
-    return res + (float(ms.value),) if timing else res
-
-
-def _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, index0, t, actions, log_prob, entropy, timing, epsilon):
-    """bg_sample_actions_eps: the checks of `_head_call` for the sampling form, then the epsilon-greedy launch -> (actions, None, None)."""
-    dev = logits.device
-    if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
-        raise ValueError("epsilon must be a number in [0, 1] (or None: the categorical head)")
-    if flags:
-        raise ValueError("epsilon and deterministic=True exclude each other (epsilon=0.0 is the greedy rule)")
-    if log_prob is not None or entropy is not None:
-        raise ValueError("an epsilon-greedy action has no categorical log_prob / entropy: pass neither with epsilon")
-    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
-            raise ValueError(f"{what} must be an integer in [0, 2**64)")
-    if actions is not None:
-        _check_scan_tensor("actions", actions, torch.int32, lead, dev)
-    if not logits.is_cuda:
-        raise ValueError("logits must be a device tensor (there is no CPU fallback)")
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
-    if actions is None:
-        actions = torch.empty(lead, dtype=torch.int32, device=dev)
-    res = (actions, None, None)
-    if m == 0:
-        return res + (0.0,) if timing else res
-    if actions.data_ptr() in {logits.data_ptr()} | ({mask.data_ptr()} if mask is not None else set()):
-        raise ValueError("outputs must not share memory with the inputs or with each other")
-    L = nat.load()
-    ms = C.c_float(0.0)
-    with torch.cuda.device(dev):
-        rc = L.bg_sample_actions_eps(C.c_void_p(logits.data_ptr()), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
-                                     C.c_void_p(mask.data_ptr() + moff) if mask is not None else None, C.c_uint64(mstride), C.c_int64(m), C.c_uint32(0),
-                                     C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), C.c_float(float(epsilon)),
-                                     C.c_void_p(actions.data_ptr()), None, None, C.byref(ms) if timing else None,
-                                     C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise nat.NativeError(f"bg_sample_actions_eps failed ({rc}): {L.bg_last_error(None).decode()}")
-    return res + (float(ms.value),) if timing else res
-
-
-def sample_actions(logits: torch.Tensor, mask: Optional[torch.Tensor] = None, *, seed: int, t: int, index0: int = 0, deterministic: bool = False,
-                   actions: Optional[torch.Tensor] = None, log_prob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None,
-                   timing: bool = False, epsilon: Optional[float] = None):
-    """The masked categorical policy head in one launch (bg_sample_actions): logits float32 / bfloat16 [..., 60] -> (actions int32, log_prob float32,
-    entropy float32), each [...].  mask: packed records (a contiguous uint8 tensor [..., stride]: `RowBuffers.rows[t]`, `env.obs_rows` -- their
-    action_mask field is read in place), an int8 [..., 60] matrix (`obs["action_mask"]`) or None (every action valid).  A masked action is never
-    drawn; a row with no valid action (or a NaN / +inf valid logit) gives action -1 and NaN.  Row i draws with the counter hash of (seed, index0 + i,
-    t), the rollout's: the same arguments give the same bits, whatever the batch shape or sharding (a shard passes its first global env as index0).
-    deterministic=True takes the first valid maximum instead (SB3's `mode()`).  A record's mask is the mask AFTER its step: it goes with the logits
-    computed from that record.  actions / log_prob / entropy: optional contiguous tensors to write into.  timing=True appends kernel milliseconds.
-    epsilon (None: the categorical head above, untouched): epsilon-greedy over the logits as Q values (bg_sample_actions_eps) -> (actions, None,
-    None).  Row i explores when its uniform draw u -- the one the categorical head would use -- is below epsilon, and then takes a uniformly drawn
-    valid action from a second hash; otherwise the first valid maximum.  The decision is PER ENV (SB3's DQN draws once for the whole batch, which
-    at 65 536 envs would make every env explore together).  epsilon excludes deterministic=True, log_prob and entropy."""
-    return _head_call("bg_sample_actions", logits, mask, None, nat.HEAD_DETERMINISTIC if deterministic else 0, seed, index0, t, actions, log_prob,
-                      entropy, timing, epsilon)
-
-
-def evaluate_actions(logits: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None, *, log_prob: Optional[torch.Tensor] = None,
-                     entropy: Optional[torch.Tensor] = None, timing: bool = False):
-    """(log_prob, entropy) float32 [...] of given int32 actions [...] under the masked distribution of `sample_actions` (bg_evaluate_actions; a
-    forward pass -- `ppo_loss` is the call that takes part in autograd): bit for bit what the sampler returned for the actions it drew.  A masked
-    action has log_prob -inf, one outside [0, 60) NaN."""
-    if not isinstance(actions, torch.Tensor):
-        raise ValueError("actions must be an int32 tensor with the leading shape of logits")
-    return _head_call("bg_evaluate_actions", logits, mask, actions, 0, 0, 0, 0, None, log_prob, entropy, timing)
-
-
-class PpoStats:
-    """What `ppo_loss` returns beside the loss: the scalars of `_native.PPO_STATS` as 0-dim float32 device tensors (views of `raw`, no host
-    synchronisation), `log_prob` / `entropy` [...] of the minibatch rows (bit for bit `evaluate_actions`'), and the gradient the call produced --
-    `dlogits` [..., 60] in the dtype of the logits, `dvalues` [...] or None.  `kernel_ms` with timing=True."""
-
-    def __init__(self, raw, log_prob, entropy, dlogits, dvalues, kernel_ms=None):
-        self.raw, self.log_prob, self.entropy, self.dlogits, self.dvalues, self.kernel_ms = raw, log_prob, entropy, dlogits, dvalues, kernel_ms
-        for k, name in enumerate(nat.PPO_STATS):
-            setattr(self, name, raw[k])
-
-    def __repr__(self):
-        return "PpoStats(" + ", ".join(nat.PPO_STATS) + ", log_prob, entropy, dlogits, dvalues)"
-
-
-class _PpoLossGrad(torch.autograd.Function):
-    """The node `ppo_loss` hangs on its loss: the forward pass already produced the gradient, the backward is one multiplication."""
-
-    @staticmethod
-    def forward(ctx, loss, dlogits, dvalues, logits, values):
-        ctx.save_for_backward(dlogits, dvalues if dvalues is not None else dlogits.new_empty(0))
-        ctx.has_values = dvalues is not None
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, grad):
-        dlogits, dvalues = ctx.saved_tensors
-        gl = (dlogits * grad).to(dlogits.dtype) if ctx.needs_input_grad[3] else None
-        gv = dvalues * grad if ctx.has_values and ctx.needs_input_grad[4] else None
-        return None, None, None, gl, gv
-
-
-_ppo_workspaces: dict = {}
-
-
-def _ppo_workspace(L, dev: torch.device, m: int) -> torch.Tensor:
-    need = int(L.bg_ppo_loss_workspace_bytes(C.c_int64(m)))
-    key = (dev, need)
-    if key not in _ppo_workspaces:
-        _ppo_workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return _ppo_workspaces[key]
-
-
-def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Tensor, advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
-             values: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None,
-             clip_range: float = 0.2, ent_coef: float = 0.0, vf_coef: float = 0.5, normalize_advantage: bool = True, timing: bool = False):
-    """SB3's `PPO.train` loss over the masked head of `sample_actions`, its diagnostics and its gradient, in one pass over the logits (bg_ppo_loss):
-    -> (loss, stats).  loss: 0-dim float32; when `logits` (or `values`) require grad it carries an autograd node whose backward is
-    grad_output * stats.dlogits (and * stats.dvalues) -- `loss.backward()` drives the network's own backward with nothing recomputed.  stats: `PpoStats`.
-    logits float32 / bfloat16 [..., 60] and values float32 [...] are the network's outputs for the minibatch.  Without `index`, actions int32,
-    old_log_prob / advantages / returns float32 and the mask (forms of `sample_actions`) have the leading shape of logits.  With `index` (int32 [...],
-    SB3's `RolloutBuffer.get` permutation) they are the STORED arrays of the whole rollout, one common shape, read at row index[i]: the minibatch is
-    gathered inside the launch, a record's mask in place.  A row that cannot take part (degenerate mask, masked or out-of-range action, non-finite
-    input, index out of range) is excluded: zero gradient, counted in stats.excluded, the divisor stays m.  values / returns: both or neither."""
-    lead, m, pitch = _head_logits(logits)
-    dev = logits.device
-    if index is not None:
-        _check_index(index, lead, dev)
-        if not isinstance(actions, torch.Tensor):
-            raise ValueError("actions must be an int32 tensor")
-        store = tuple(actions.shape)
-    else:
-        store = lead
-    store_rows = int(np.prod(store, dtype=np.int64))
-    if store_rows >= 2 ** 31:
-        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
-    mask, moff, mstride = _head_mask(mask, store, dev)
-    _check_scan_tensor("actions", actions, torch.int32, store, dev)
-    _check_scan_tensor("old_log_prob", old_log_prob, torch.float32, store, dev)
-    _check_scan_tensor("advantages", advantages, torch.float32, store, dev)
-    if (values is None) != (returns is None):
-        raise ValueError("values and returns go together: both or neither")
-    if values is not None:
-        _check_scan_tensor("values", values, torch.float32, lead, dev)
-        _check_scan_tensor("returns", returns, torch.float32, store, dev)
-    for what, v in (("clip_range", clip_range), ("ent_coef", ent_coef), ("vf_coef", vf_coef)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"{what} must be a finite number")
-    if not 0.0 < float(np.float32(clip_range)) < 1.0:
-        raise ValueError("clip_range must be in (0, 1)")
-    if not logits.is_cuda:
-        raise ValueError("logits must be a device tensor (there is no CPU fallback)")
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
-    lg = logits.detach()
-    vals = values.detach() if values is not None else None
-    raw = torch.zeros(len(nat.PPO_STATS), dtype=torch.float32, device=dev)
-    dlogits = torch.empty(lead + (60,), dtype=logits.dtype, device=dev)
-    dvalues = torch.empty(lead, dtype=torch.float32, device=dev) if values is not None else None
-    log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
-    entropy = torch.empty(lead, dtype=torch.float32, device=dev)
-    ms = C.c_float(0.0)
-    if m > 0:
-        L = nat.load()
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(dev):
-            ws = _ppo_workspace(L, dev, m)
-            rc = L.bg_ppo_loss(ptr(lg), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
-                               C.c_void_p(mask.data_ptr() + moff) if mask is not None else None, C.c_uint64(mstride), ptr(actions), ptr(old_log_prob),
-                               ptr(advantages), ptr(vals), ptr(returns), ptr(index), C.c_int64(store_rows), C.c_int64(m), C.c_float(clip_range),
-                               C.c_float(ent_coef), C.c_float(vf_coef), C.c_uint32(nat.PPO_NORMALIZE_ADV if normalize_advantage else 0), ptr(dlogits),
-                               C.c_uint64(60), ptr(dvalues), ptr(log_prob), ptr(entropy), ptr(raw), ptr(ws), C.c_uint64(ws.numel()),
-                               C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise nat.NativeError(f"bg_ppo_loss failed ({rc}): {L.bg_last_error(None).decode()}")
-    stats = PpoStats(raw, log_prob, entropy, dlogits, dvalues, float(ms.value) if timing else None)
-    loss = raw[0]
-    if torch.is_grad_enabled() and (logits.requires_grad or (values is not None and values.requires_grad)):
-        loss = _PpoLossGrad.apply(loss, dlogits, dvalues, logits, values)
-    return loss, stats
-
-
-class DqnStats:
-    """What `dqn_loss` returns beside the loss: the scalars of `_native.DQN_STATS` as 0-dim float32 device tensors (views of `raw`, no host
-    synchronisation), `td` float32 [...] (q[a] - y per row, NaN on an excluded row: for prioritised replay), and the gradient the call produced --
-    `dq` [..., 60] in the dtype of q.  `kernel_ms` with timing=True."""
-
-    def __init__(self, raw, td, dq, kernel_ms=None):
-        self.raw, self.td, self.dq, self.kernel_ms = raw, td, dq, kernel_ms
-        for k, name in enumerate(nat.DQN_STATS):
-            setattr(self, name, raw[k])
-
-    def __repr__(self):
-        return "DqnStats(" + ", ".join(nat.DQN_STATS) + ", td, dq)"
-
-
-class _DqnLossGrad(torch.autograd.Function):
-    """The node `dqn_loss` hangs on its loss (`_PpoLossGrad`'s pattern): the forward pass already produced the gradient."""
-
-    @staticmethod
-    def forward(ctx, loss, dq, q):
-        ctx.save_for_backward(dq)
-        return loss.clone()
-
-    @staticmethod
-    def backward(ctx, grad):
-        dq, = ctx.saved_tensors
-        return None, None, (dq * grad).to(dq.dtype) if ctx.needs_input_grad[2] else None
-
-
-_dqn_workspaces: dict = {}
-
-
-def _dqn_workspace(L, dev: torch.device, m: int) -> torch.Tensor:
-    need = int(L.bg_dqn_loss_workspace_bytes(C.c_int64(m)))
-    key = (dev, need)
-    if key not in _dqn_workspaces:
-        _dqn_workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-    return _dqn_workspaces[key]
-
-
-def dqn_loss(q: torch.Tensor, q_next: torch.Tensor, rows: torch.Tensor, next_index: torch.Tensor, *, q_next_online: Optional[torch.Tensor] = None,
-             rewards: Optional[torch.Tensor] = None, gamma: float = 0.99, mask_next: bool = True, loss: str = "huber", timeouts: str = "exclude",
-             timing: bool = False):
-    """SB3's `DQN.train` loss over a store of packed records, its diagnostics and its gradient with respect to q, in one pass (bg_dqn_loss):
-    -> (loss, stats).  loss: 0-dim float32; when `q` requires grad it carries an autograd node whose backward is grad_output * stats.dq -- nothing
-    is recomputed.  stats: `DqnStats`.
-    q float32 / bfloat16 [..., 60]: the online network at the OBSERVATION records (`encode_rows(store, index=index)`); q_next, same dtype and leading
-    shape: the target network at the NEXT records (`index=next_index`); q_next_online: the online network there -- given, it selects double DQN.
-    rows: the store, a contiguous uint8 [..., stride] tensor of records (`RowReplay.store`).  next_index int32 [...]: the flat row of each transition's
-    next record -- the record that holds the step's action, reward, terminated byte and end flags and the mask of the next decision, all read in
-    place.  rewards: float32 with the store's leading shape, read at next_index instead of the records' rewards (normalised rewards).
-    mask_next: the maximum over the next record's valid actions only.  loss: "huber" (SB3's smooth_l1) or "mse".  timeouts: "exclude" leaves out rows
-    that only the step limit ended (SB3 bootstraps them from a terminal observation the store does not hold); "terminal" treats them as ordinary done
-    rows.  mask_next=False, loss="huber", timeouts="terminal" is SB3's rule literally.  A row that cannot take part (next_index or action out of
-    range, non-finite reward, q[a] or target, no valid next action) is excluded: zero gradient, NaN td, counted in stats.excluded, the divisor stays m."""
-    lead, m, pitch = _head_logits(q)
-    dev = q.device
-    if not isinstance(q_next, torch.Tensor) or q_next.dtype != q.dtype:
-        raise ValueError("q_next must be a tensor [..., 60] of the dtype of q")
-    nlead, _, npitch = _head_logits(q_next)
-    if nlead != lead or q_next.device != dev:
-        raise ValueError(f"q_next must have the leading shape of q {list(lead)} on {dev}")
-    opitch = 0
-    if q_next_online is not None:
-        if not isinstance(q_next_online, torch.Tensor) or q_next_online.dtype != q.dtype:
-            raise ValueError("q_next_online must be a tensor [..., 60] of the dtype of q")
-        olead, _, opitch = _head_logits(q_next_online)
-        if olead != lead or q_next_online.device != dev:
-            raise ValueError(f"q_next_online must have the leading shape of q {list(lead)} on {dev}")
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() < 2 or not rows.is_contiguous() or rows.device != dev:
-        raise ValueError(f"rows must be a contiguous uint8 tensor [..., stride] of packed records on {dev}")
-    stride = int(rows.shape[-1])
-    if stride < nat.ROW_BYTES or stride % 16:
-        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
-    store = tuple(rows.shape[:-1])
-    store_rows = int(np.prod(store, dtype=np.int64))
-    if store_rows >= 2 ** 31:
-        raise ValueError("the store holds at most 2**31 - 1 records")
-    if not isinstance(next_index, torch.Tensor) or next_index.dtype != torch.int32 or tuple(next_index.shape) != lead or not next_index.is_contiguous() \
-            or next_index.device != dev:
-        raise ValueError(f"next_index must be a contiguous torch.int32 tensor of shape {list(lead)} on {dev}")
-    if rewards is not None:
-        _check_scan_tensor("rewards", rewards, torch.float32, store, dev)
-    if isinstance(gamma, bool) or not isinstance(gamma, (int, float, np.integer, np.floating)) or not 0.0 <= float(gamma) <= 1.0:
-        raise ValueError("gamma must be a number in [0, 1]")
-    if loss not in ("huber", "mse"):
-        raise ValueError("loss must be 'huber' or 'mse'")
-    if timeouts not in ("exclude", "terminal"):
-        raise ValueError("timeouts must be 'exclude' or 'terminal'")
-    if not q.is_cuda:
-        raise ValueError("q must be a device tensor (there is no CPU fallback)")
-    if rows.data_ptr() % 16:
-        raise ValueError("rows must be 16-byte aligned")
-    flags = (nat.DQN_MASK_NEXT if mask_next else 0) | (nat.DQN_MSE if loss == "mse" else 0) | (nat.DQN_TIMEOUT_EXCLUDE if timeouts == "exclude" else 0)
-    qd, qn = q.detach(), q_next.detach()
-    qo = q_next_online.detach() if q_next_online is not None else None
-    raw = torch.zeros(len(nat.DQN_STATS), dtype=torch.float32, device=dev)
-    dq = torch.empty(lead + (60,), dtype=q.dtype, device=dev)
-    td = torch.empty(lead, dtype=torch.float32, device=dev)
-    ms = C.c_float(0.0)
-    if m > 0:
-        L = nat.load()
-
-        def ptr(t):
-            return C.c_void_p(t.data_ptr()) if t is not None else None
-        with torch.cuda.device(dev):
-            ws = _dqn_workspace(L, dev, m)
-            rc = L.bg_dqn_loss(ptr(qd), C.c_uint64(pitch), ptr(qn), C.c_uint64(npitch), ptr(qo), C.c_uint64(opitch),
-                               nat.HEAD_F32 if q.dtype == torch.float32 else nat.HEAD_BF16, ptr(rows), C.c_uint64(stride), C.c_int64(store_rows),
-                               ptr(next_index), ptr(rewards), C.c_int64(m), C.c_float(float(gamma)), C.c_uint32(flags), ptr(dq), C.c_uint64(60), ptr(td),
-                               ptr(raw), ptr(ws), C.c_uint64(ws.numel()), C.byref(ms) if timing else None,
-                               C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        if rc != 0:
-            raise nat.NativeError(f"bg_dqn_loss failed ({rc}): {L.bg_last_error(None).decode()}")
-    stats = DqnStats(raw, td, dq, float(ms.value) if timing else None)
-    out = raw[0]
-    if torch.is_grad_enabled() and q.requires_grad:
-        out = _DqnLossGrad.apply(out, dq, q)
-    return out, stats
-
-
-class RowReplay:
-    """DQN's replay buffer as a ring of packed records: `capacity_steps` slots of `n` records, [C, N, stride] uint8, 128-byte aligned.  A record
-    already carries the observation and action mask of one decision and the action, reward, terminated byte and end flags of the step that led to
-    it, so consecutive slots (s, s + 1) of one env ARE a transition and nothing is stored twice (SB3's DictReplayBuffer keeps obs and next_obs).
-    `store` goes to `encode_rows(index=)` / `RowLinear(index=)` / `dqn_loss` as it is.
-    The ring holds ONE unbroken chain of steps: `start(env.obs_rows)` writes the record before the first step, every `add(buf.rows)` the K records
-    of a `step_many` call that continues from the last record added.  Auto-reset envs never break the chain (a record whose terminated byte is set
-    already shows the new episode, and `dqn_loss` does not bootstrap across it); a caller who resets envs by hand calls `clear()` and `start()`
-    again.  Writing `step_many`'s records into the ring in place is out of scope: `add` is one device copy (two where the ring wraps)."""
-
-    def __init__(self, capacity_steps: int, n: int, device, row_stride: int = 384):
-        C_, N, stride = int(capacity_steps), int(n), int(row_stride)
-        if C_ < 2 or N < 1:
-            raise ValueError("capacity_steps must be >= 2 (a transition is two records) and n >= 1")
-        if stride < nat.ROW_BYTES or stride % 16:
-            raise ValueError(f"row_stride must be a multiple of 16 and >= the {nat.ROW_BYTES}-byte record")
-        if C_ * N >= 2 ** 31:
-            raise ValueError("capacity_steps * n must be below 2**31 (int32 row indices)")
-        self.capacity_steps, self.n, self.row_stride = C_, N, stride
-        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
-        nbytes = C_ * N * stride
-        self._flat = torch.zeros(nbytes + 128, dtype=torch.uint8, device=self.device)
-        off = (-self._flat.data_ptr()) % 128
-        self.store = self._flat[off:off + nbytes].view(C_, N, stride)
-        self._head = 0      # the slot the next record goes to (the write head)
-        self._filled = 0    # slots that hold a record
-
-    def __len__(self) -> int:
-        """Valid transitions: (filled slots - 1) * n."""
-        return max(self._filled - 1, 0) * self.n
-
-    def clear(self) -> None:
-        self._head, self._filled = 0, 0
-
-    def _check_records(self, what: str, t, dims: int):
-        if not isinstance(t, torch.Tensor) or t.dtype != torch.uint8 or t.dim() != dims or tuple(t.shape[-2:]) != (self.n, self.row_stride) \
-                or t.device != self.device:
-            lead = "[K, " if dims == 3 else "["
-            raise ValueError(f"{what} must be a uint8 tensor {lead}{self.n}, {self.row_stride}] of packed records on {self.device}")
-
-    def start(self, obs_rows: torch.Tensor) -> None:
-        """Begin a chain: the record BEFORE the first step (`env.obs_rows`, [N, stride]).  Whatever the ring held is dropped."""
-        self._check_records("obs_rows", obs_rows, 2)
-        self.store[0].copy_(obs_rows)
-        self._head, self._filled = 1 % self.capacity_steps, 1
-
-    def add(self, rows_kn: torch.Tensor) -> None:
-        """Append the K step records of one `step_many` call ([K, N, stride], `RowBuffers.rows`), wrapping."""
-        self._check_records("rows_kn", rows_kn, 3)
-        K, C_ = int(rows_kn.shape[0]), self.capacity_steps
-        if K >= C_:
-            raise ValueError(f"K = {K} step records do not fit a ring of {C_} slots beside the record they continue from (K < capacity_steps)")
-        if self._filled == 0:
-            raise ValueError("start(obs_rows) writes the record before the first step; add() continues from it")
-        first = min(K, C_ - self._head)
-        self.store[self._head:self._head + first].copy_(rows_kn[:first])
-        if first < K:
-            self.store[:K - first].copy_(rows_kn[first:])
-        self._head = (self._head + K) % C_
-        self._filled = min(self._filled + K, C_)
-
-    def sample(self, m: int, generator: Optional[torch.Generator] = None):
-        """(index, next_index): int32 [m] device tensors, drawn on the device with no host synchronisation.  The slot s is uniform over the slots
-        whose successor (s + 1) % C is also filled and is not the write head, the env uniform over n; index = s * n + env names the observation
-        record, next_index = ((s + 1) % C) * n + env the record of the step taken there."""
-        m = int(m)
-        if m < 0:
-            raise ValueError("m must be >= 0")
-        count = self._filled - 1
-        if count < 1:
-            raise ValueError("the ring holds no transition yet (start() and at least one add())")
-        C_, N = self.capacity_steps, self.n
-        oldest = self._head if self._filled == C_ else 0
-        gdev = generator.device if generator is not None else self.device
-        r = torch.randint(0, count * N, (m,), generator=generator, device=gdev, dtype=torch.int64).to(self.device)
-        j, env = r // N, r % N
-        s = (j + oldest) % C_
-        return (s * N + env).to(torch.int32), (((s + 1) % C_) * N + env).to(torch.int32)
-
-    def state_dict(self) -> dict:
-        return {"store": self.store.clone(), "head": self._head, "filled": self._filled, "capacity_steps": self.capacity_steps, "n": self.n,
-                "row_stride": self.row_stride}
-
-    def load_state_dict(self, state: dict) -> None:
-        shape = (int(state["capacity_steps"]), int(state["n"]), int(state["row_stride"]))
-        if shape != (self.capacity_steps, self.n, self.row_stride):
-            raise ValueError(f"the state is of a ring {list(shape)}, this one is {[self.capacity_steps, self.n, self.row_stride]}")
-        head, filled = int(state["head"]), int(state["filled"])
-        if not 0 <= filled <= self.capacity_steps or not 0 <= head < self.capacity_steps or (filled < self.capacity_steps and head != filled % self.capacity_steps):
-            raise ValueError("the state's head / filled do not describe a ring of this capacity")
-        self.store.copy_(state["store"])
-        self._head, self._filled = head, filled
-
-
-def _check_scan_rows(rows) -> tuple:
-    """rows of gae_rows / EpisodeStats.update: contiguous uint8 [K, N, stride] -> (K, N, stride)."""
-    if not isinstance(rows, torch.Tensor) or rows.dtype != torch.uint8 or rows.dim() != 3 or not rows.is_contiguous():
-        raise ValueError("rows must be a contiguous uint8 tensor [K, N, stride] of packed records")
-    K, N, stride = (int(x) for x in rows.shape)
-    if stride < nat.ROW_BYTES or stride % 16:
-        raise ValueError(f"the last dimension of rows is the record stride: a multiple of 16, >= {nat.ROW_BYTES} (got {stride})")
-    return K, N, stride
-
-
-def _check_scan_tensor(name: str, t, dtype: torch.dtype, shape: tuple, device: torch.device):
-    if not isinstance(t, torch.Tensor) or t.dtype != dtype or tuple(t.shape) != shape or not t.is_contiguous() or t.device != device:
-        raise ValueError(f"{name} must be a contiguous {dtype} tensor of shape {list(shape)} on {device}")
-
-
-def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor, gamma: float = 0.99, gae_lambda: float = 0.95,
-             advantages: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, timing: bool = False,
-             rewards: Optional[torch.Tensor] = None):
-    """Advantages and returns of a finished [K, N] rollout of packed records in one launch (bg_gae_rows): bit for bit SB3's
-    `RolloutBuffer.compute_returns_and_advantage` run in numpy on float32 buffers, with dones[t] = the record's terminated byte and the reward
-    rounded from the record's float64.  rows: contiguous uint8 device tensor [K, N, stride] (`RowBuffers.rows`); values float32 [K, N] (the value
-    network's output per step), last_values float32 [N] (its output on the observation after the last step).  advantages / returns: optional
-    float32 [K, N] tensors to write into; they must not share memory with values or with each other.  rewards: optional float64 [K, N] device tensor
-    to take the rewards from instead of the records (bg_gae_rows_ex; `RowNormalizer.normalize_reward`'s output), each rounded to float32 like the record's.
-    Returns (advantages, returns); timing=True returns (advantages, returns, kernel milliseconds)."""
-    K, N, stride = _check_scan_rows(rows)
-    dev = rows.device
-    _check_scan_tensor("values", values, torch.float32, (K, N), dev)
-    _check_scan_tensor("last_values", last_values, torch.float32, (N,), dev)
-    for name, t in (("advantages", advantages), ("returns", returns)):
-        if t is not None:
-            _check_scan_tensor(name, t, torch.float32, (K, N), dev)
-    if rewards is not None:
-        _check_scan_tensor("rewards", rewards, torch.float64, (K, N), dev)
-    gamma, gae_lambda = float(gamma), float(gae_lambda)
-    if not (np.isfinite(gamma) and np.isfinite(gae_lambda)):
-        raise ValueError("gamma and gae_lambda must be finite")
-    if not rows.is_cuda:
-        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-    if rows.data_ptr() % 16:
-        raise ValueError("rows must be 16-byte aligned")
-    if advantages is None:
-        advantages = torch.empty((K, N), dtype=torch.float32, device=dev)
-    if returns is None:
-        returns = torch.empty((K, N), dtype=torch.float32, device=dev)
-    ptrs = [values.data_ptr(), advantages.data_ptr(), returns.data_ptr()]
-    if K * N and len(set(ptrs)) != 3:
-        raise ValueError("advantages / returns must not share memory with values or with each other")
-    if K * N == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
-        return (advantages, returns, 0.0) if timing else (advantages, returns)
-    L = nat.load()
-    ms = C.c_float(0.0)
-    with torch.cuda.device(dev):
-        args = (C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(values.data_ptr()),
-                C.c_void_p(last_values.data_ptr()), C.c_double(gamma), C.c_double(gae_lambda), C.c_void_p(advantages.data_ptr()),
-                C.c_void_p(returns.data_ptr()))
-        tail = (C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-        rc = L.bg_gae_rows(*args, *tail) if rewards is None else L.bg_gae_rows_ex(*args, C.c_void_p(rewards.data_ptr()), *tail)
-    if rc != 0:
-        raise nat.NativeError(f"bg_gae_rows failed ({rc}): {L.bg_last_error(None).decode()}")
-    return (advantages, returns, float(ms.value)) if timing else (advantages, returns)
-
-
-class EpisodeStats:
-    """What `Monitor` reports per finished episode, for N envs on the device (bg_episode_stats_rows): owns the running reward sum (float64, a plain
-    sum in step order) and step count (int32) of every env's current episode, across calls."""
-
-    def __init__(self, n: int, device):
-        if int(n) < 0:
-            raise ValueError("n must be >= 0")
-        self.n = int(n)
-        self.device = torch.device(device)
-        self.ep_return_carry = torch.zeros(self.n, dtype=torch.float64, device=self.device)
-        self.ep_len_carry = torch.zeros(self.n, dtype=torch.int32, device=self.device)
-
-    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
-        """Forget the running episodes (of the envs where `mask` is set): for callers who `env.reset()` by hand."""
-        if mask is None:
-            self.ep_return_carry.zero_()
-            self.ep_len_carry.zero_()
-            return
-        mask = torch.as_tensor(mask)
-        if tuple(mask.shape) != (self.n,):
-            raise ValueError(f"mask must have shape [{self.n}]")
-        mask = mask.to(device=self.device, dtype=torch.bool)
-        self.ep_return_carry.masked_fill_(mask, 0.0)
-        self.ep_len_carry.masked_fill_(mask, 0)
-
-    def update(self, rows: torch.Tensor, ep_return: Optional[torch.Tensor] = None, ep_len: Optional[torch.Tensor] = None, timing: bool = False):
-        """The next K steps of every env: rows contiguous uint8 [K, N, stride] on this device.  Returns (ep_return float64 [K, N], ep_len int32
-        [K, N]): on a terminated step the finished episode's reward sum and length, 0.0 / 0 elsewhere (`ep_len.nonzero()` lists the episodes);
-        timing=True appends the kernel milliseconds.  ep_return / ep_len: optional tensors to write into."""
-        K, N, stride = _check_scan_rows(rows)
-        if N != self.n or rows.device != self.device:
-            raise ValueError(f"rows must hold records of {self.n} envs on {self.device} (got {N} envs on {rows.device})")
-        if ep_return is not None:
-            _check_scan_tensor("ep_return", ep_return, torch.float64, (K, N), self.device)
-        if ep_len is not None:
-            _check_scan_tensor("ep_len", ep_len, torch.int32, (K, N), self.device)
-        if not rows.is_cuda:
-            raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-        if rows.data_ptr() % 16:
-            raise ValueError("rows must be 16-byte aligned")
-        if ep_return is None:
-            ep_return = torch.empty((K, N), dtype=torch.float64, device=self.device)
-        if ep_len is None:
-            ep_len = torch.empty((K, N), dtype=torch.int32, device=self.device)
-        if K * N == 0:
-            return (ep_return, ep_len, 0.0) if timing else (ep_return, ep_len)
-        L = nat.load()
-        ms = C.c_float(0.0)
-        with torch.cuda.device(self.device):
-            rc = L.bg_episode_stats_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(self.ep_return_carry.data_ptr()),
-                                         C.c_void_p(self.ep_len_carry.data_ptr()), C.c_void_p(ep_return.data_ptr()), C.c_void_p(ep_len.data_ptr()),
-                                         C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise nat.NativeError(f"bg_episode_stats_rows failed ({rc}): {L.bg_last_error(None).decode()}")
-        return (ep_return, ep_len, float(ms.value)) if timing else (ep_return, ep_len)
-
-
-class EpisodeLimits:
-    """SafeBalatroEnv's episode limits for `BalatroVecEnv.step_many(actions, obs_buffers=rows, limits=...)` (bg_step_many_rows_ex): owns, on the
-    device, the per-env counters the limits need across calls (int32 [n, 4]: episode_steps, consecutive_invalid, wrapper endings in the last call,
-    0) and the buffers for the records before the resets the wrapper causes -- SB3's info["terminal_observation"]: `terminal_rows` uint8
-    [S, n, row_stride] and `terminal_step` int32 [S, n] (the step of the last call whose ending filled the slot, else -1), S =
-    steps // min(limits) + 1 slots per env for calls of up to `steps` steps.  summary=True: `step_many` turns the handle's episode summary on
-    (bg_set_episode_summary), and the record of every ended step carries the ended episode's final ante, round and score.  progression=True: sized
-    for `step_many(..., progression=)`, whose stuck endings need steps // min(limits, 301) + 1 slots (bg_progress_terminal_slots)."""
-
-    def __init__(self, n: int, device, max_invalid_actions: int = 50, max_episode_steps: int = 1000, steps: int = 1, row_stride: int = 384,
-                 summary: bool = False, progression: bool = False):
-        if not isinstance(summary, (bool, np.bool_)):
-            raise ValueError("summary must be a bool")
-        if not isinstance(progression, (bool, np.bool_)):
-            raise ValueError("progression must be a bool")
-        self.summary = bool(summary)
-        self.progression = bool(progression)
-        self.n, self.steps = int(n), int(steps)
-        self.device = torch.device(device)
-        self.max_invalid_actions, self.max_episode_steps = int(max_invalid_actions), int(max_episode_steps)
-        self.row_stride = int(row_stride) or nat.ROW_BYTES
-        if self.n < 0 or self.steps < 1:
-            raise ValueError("n must be >= 0 and steps >= 1")
-        if min(self.max_invalid_actions, self.max_episode_steps) < nat.SAFE_MIN_LIMIT or max(self.max_invalid_actions, self.max_episode_steps) >= 2 ** 31:
-            raise ValueError(f"max_invalid_actions and max_episode_steps must be >= {nat.SAFE_MIN_LIMIT} (and fit an int32)")
-        if self.row_stride < nat.ROW_BYTES or self.row_stride % 16:
-            raise ValueError("row_stride must be a multiple of 16 and >= the 352-byte record")
-        self.slots = self.steps // min(self.max_invalid_actions, self.max_episode_steps) + 1   # bg_safe_terminal_slots
-        if self.progression:
-            self.slots = self.steps // min(self.max_invalid_actions, self.max_episode_steps, nat.PROGRESS_STUCK_STEPS + 1) + 1   # bg_progress_terminal_slots
-        self.counters = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
-        self.terminal_rows = torch.zeros((self.slots, self.n, self.row_stride), dtype=torch.uint8, device=self.device)
-        self.terminal_step = torch.full((self.slots, self.n), -1, dtype=torch.int32, device=self.device)
-        self._terminal = None
-
-    def _struct(self) -> "nat.SafeLimits":
-        return nat.SafeLimits(self.max_invalid_actions, self.max_episode_steps, self.counters.data_ptr(), self.terminal_rows.data_ptr(),
-                              self.row_stride, self.terminal_step.data_ptr(), self.slots)
-
-    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
-        """Zero the counters (of the envs where `mask` is set): beside `env.reset(mask=...)`, as SafeBalatroEnv.reset does."""
-        if mask is None:
-            self.counters.zero_()
-            return
-        mask = torch.as_tensor(mask)
-        if tuple(mask.shape) != (self.n,):
-            raise ValueError(f"mask must have shape [{self.n}]")
-        self.counters.masked_fill_(mask.to(device=self.device, dtype=torch.bool).view(self.n, 1), 0)
-
-    def state_dict(self) -> dict:
-        return {"max_invalid_actions": self.max_invalid_actions, "max_episode_steps": self.max_episode_steps, "counters": self.counters.cpu().clone()}
-
-    def load_state_dict(self, state: dict) -> None:
-        if (int(state["max_invalid_actions"]), int(state["max_episode_steps"])) != (self.max_invalid_actions, self.max_episode_steps):
-            raise ValueError("the saved counters belong to other limits")
-        c = torch.as_tensor(state["counters"])
-        if tuple(c.shape) != (self.n, 4):
-            raise ValueError(f"counters must have shape [{self.n}, 4]")
-        self.counters.copy_(c.to(device=self.device, dtype=torch.int32))
-
-    def terminal(self):
-        """(index int32 [M], records uint8 [M, row_stride]) of the last call's wrapper endings: index = t * n + e, ascending (the index `minibatches` /
-        `ppo_loss(index=)` use for step t of env e); records[i] is the record of that step BEFORE the reset.  `encode_rows(records, layout)` -- with
-        `norm=` a RowNormalizer for VecNormalize's frozen statistics -- takes the [M, row_stride] tensor as it is, M = 0 included (`normalize_obs`
-        does not: it reads a 2-D tensor as ONE step of its N envs); the value network turns that matrix into `bootstrap_rewards`' terminal_values.  Made with torch on the
-        device (M is at most slots * n); the result is kept until the next call."""
-        if self._terminal is None:
-            ts = self.terminal_step.reshape(-1)
-            used = (ts >= 0).nonzero(as_tuple=False).flatten()          # slot j * n + e
-            index = ts[used].to(torch.int64) * self.n + used % self.n    # t * n + e: distinct, so the order is total
-            order = torch.argsort(index)
-            self._terminal = (index[order].to(torch.int32), self.terminal_rows.view(-1, self.row_stride)[used[order]].contiguous())
-        return self._terminal
-
-
-class ProgressionRewards:
-    """ProgressionRewardWrapper's state for `BalatroVecEnv.step_many(actions, obs_buffers=rows, limits=..., progression=...)`
-    (bg_step_many_rows_progress): owns, on the device, the per-env carry of the wrapper across calls -- int32 [n, 4]: total_steps,
-    steps_on_current_ante, (last_ante - 1) | (max_ante_reached - 1) << 16, last_round - 1, so that zeros are the state after the wrapper's reset().
-    The constants of the rule are the reference's (train_progressive.py:21-120), not parameters."""
-
-    def __init__(self, n: int, device):
-        self.n = int(n)
-        if self.n < 0:
-            raise ValueError("n must be >= 0")
-        self.device = torch.device(device)
-        self.counters = torch.zeros((self.n, 4), dtype=torch.int32, device=self.device)
-
-    def _struct(self) -> "nat.ProgressRewards":
-        return nat.ProgressRewards(self.counters.data_ptr())
-
-    def reset(self, mask: Optional[torch.Tensor] = None) -> None:
-        """Zero the carry (of the envs where `mask` is set): beside `env.reset(mask=...)`, as ProgressionRewardWrapper.reset does."""
-        if mask is None:
-            self.counters.zero_()
-            return
-        mask = torch.as_tensor(mask)
-        if tuple(mask.shape) != (self.n,):
-            raise ValueError(f"mask must have shape [{self.n}]")
-        self.counters.masked_fill_(mask.to(device=self.device, dtype=torch.bool).view(self.n, 1), 0)
-
-    def state_dict(self) -> dict:
-        return {"counters": self.counters.cpu().clone()}
-
-    def load_state_dict(self, state: dict) -> None:
-        c = torch.as_tensor(state["counters"])
-        if tuple(c.shape) != (self.n, 4):
-            raise ValueError(f"counters must have shape [{self.n}, 4]")
-        self.counters.copy_(c.to(device=self.device, dtype=torch.int32))
-
-
-def _episode_ends_call(rows, cur: Optional["nat.Curriculum"], n_expected: Optional[int], timing: bool):
-    K, N, stride = _check_scan_rows(rows)
-    if n_expected is not None and N != n_expected:
-        raise ValueError(f"rows must hold records of {n_expected} envs (got {N})")
-    if not rows.is_cuda:
-        raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-    if rows.data_ptr() % 16:
-        raise ValueError("rows must be 16-byte aligned")
-    dev = rows.device
-    if K * N == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
-        return torch.zeros(nat.ENDS_WORDS, dtype=torch.int64, device=dev), 0.0
-    report = torch.empty(nat.ENDS_WORDS, dtype=torch.int64, device=dev)
-    L = nat.load()
-    ms = C.c_float(0.0)
-    with torch.cuda.device(dev):
-        rc = L.bg_episode_ends_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(report.data_ptr()),
-                                    None if cur is None else C.byref(cur), C.byref(ms) if timing else None,
-                                    C.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
-    if rc != 0:
-        raise nat.NativeError(f"bg_episode_ends_rows failed ({rc}): {L.bg_last_error(None).decode()}")
-    return report, float(ms.value)
-
-
-def episode_ends(rows: torch.Tensor, timing: bool = False):
-    """The ended episodes of a finished [K, N] rollout of packed records in one launch (bg_episode_ends_rows): int64 [32] on the device, words by
-    `_native.ENDS_REPORT` -- ended records, of which game overs / kills / step-limit-only endings, sum and maximum of the end ante and of the end
-    chips, records without a summary -- and from `_native.ENDS_HIST` on the histogram of min(end ante, 15).  rows: contiguous uint8 device tensor
-    [K, N, stride] (`RowBuffers.rows`) of `step_many(..., limits=EpisodeLimits(..., summary=True))`.  timing=True returns (report, kernel ms)."""
-    report, ms = _episode_ends_call(rows, None, None, timing)
-    return (report, ms) if timing else report
-
-
-class RowCurriculum:
-    """`CurriculumBalatroEnv` (train_balatro_agent.py:126-170) for the packed-record path, on the device: `sb3_adapter.CurriculumTracker`'s state --
-    `cap` int32 [n], `hist` int16 [window, n] (the final antes of the last `window` episodes), `count` int64 [n], `at_level` int32 [n] -- advanced
-    by bg_episode_ends_rows from the records of `step_many(..., limits=EpisodeLimits(..., summary=True))`.  A raised cap takes effect at the call
-    boundary: episodes an env finishes later in the same rollout were played under the old cap and enter the history as played."""
-
-    def __init__(self, env: "BalatroVecEnv", initial_max_ante: int = 3, ante_increment: int = 1, success_threshold: float = 0.8, window: int = 100):
-        self.env = env
-        self.n = int(env.num_envs)
-        self.device = torch.device(env.device)
-        self.increment, self.threshold, self.window = int(ante_increment), float(success_threshold), int(window)
-        if not 1 <= int(initial_max_ante) <= nat.CURRICULUM_CAP_MAX:
-            raise ValueError(f"initial_max_ante must be in 1..{nat.CURRICULUM_CAP_MAX}")
-        if not 1 <= self.increment <= nat.CURRICULUM_CAP_MAX:
-            raise ValueError(f"ante_increment must be in 1..{nat.CURRICULUM_CAP_MAX}")
-        if self.window < 1 or self.window >= 2 ** 31:
-            raise ValueError("window must be >= 1 (and fit an int32)")
-        if not np.isfinite(self.threshold):
-            raise ValueError("success_threshold must be finite")
-        self.cap = torch.full((self.n,), int(initial_max_ante), dtype=torch.int32, device=self.device)
-        self.hist = torch.zeros((self.window, self.n), dtype=torch.int16, device=self.device)
-        self.count = torch.zeros(self.n, dtype=torch.int64, device=self.device)
-        self.at_level = torch.zeros(self.n, dtype=torch.int32, device=self.device)
-        self.raised = torch.zeros(self.n, dtype=torch.uint8, device=self.device)
-        env.set_max_ante(int(initial_max_ante))
-
-    def _struct(self) -> "nat.Curriculum":
-        return nat.Curriculum(self.cap.data_ptr(), self.hist.data_ptr(), self.count.data_ptr(), self.at_level.data_ptr(), self.raised.data_ptr(),
-                              self.window, self.increment, self.threshold)
-
-    def update(self, rows: torch.Tensor, apply: bool = True, timing: bool = False):
-        """The ended episodes of rows (contiguous uint8 [K, n, stride] on the env's device) through the rule, per env in step order.  Returns the
-        report (`episode_ends`; word `_native.ENDS_REPORT["raised"]` counts the envs whose cap rose, `self.raised` marks them); timing=True appends
-        the kernel milliseconds.  apply=True reads that word -- the call's one 8-byte synchronisation -- and, only when it is non-zero, hands the
-        raised caps to `env.set_max_ante`, which keeps the library's host mirror of the caps in step.  apply=False leaves that to the caller."""
-        if isinstance(rows, torch.Tensor) and rows.device != self.device:
-            raise ValueError(f"rows must hold records of {self.n} envs on {self.device} (got {rows.device})")
-        report, ms = _episode_ends_call(rows, self._struct(), self.n, timing)
-        if rows.shape[0] * rows.shape[1] == 0:
-            self.raised.zero_()
-        elif apply and int(report[nat.ENDS_REPORT["raised"]].item()):
-            self.env.set_max_ante(self.cap.cpu().numpy(), mask=self.raised.cpu().numpy())
-        return (report, ms) if timing else report
-
-    def state_dict(self) -> dict:
-        return {"window": self.window, "ante_increment": self.increment, "success_threshold": self.threshold, "cap": self.cap.cpu().clone(),
-                "hist": self.hist.cpu().clone(), "count": self.count.cpu().clone(), "at_level": self.at_level.cpu().clone()}
-
-    def load_state_dict(self, state: dict, apply: bool = True) -> None:
-        """Restores the rule's state; apply=True also sets the env's caps from it (`env.set_max_ante`)."""
-        if int(state["window"]) != self.window:
-            raise ValueError("the saved history belongs to another window")
-        new = {}
-        for name, dt, shape in (("cap", torch.int32, (self.n,)), ("hist", torch.int16, (self.window, self.n)), ("count", torch.int64, (self.n,)),
-                                ("at_level", torch.int32, (self.n,))):
-            t = torch.as_tensor(state[name])
-            if tuple(t.shape) != shape:
-                raise ValueError(f"{name} must have shape {list(shape)}")
-            new[name] = t.to(dtype=dt)
-        if new["cap"].numel() and (int(new["cap"].min()) < 0 or int(new["cap"].max()) > nat.CURRICULUM_CAP_MAX):
-            raise ValueError(f"cap must be in 0..{nat.CURRICULUM_CAP_MAX}")
-        self.increment, self.threshold = int(state["ante_increment"]), float(state["success_threshold"])
-        for name, t in new.items():
-            getattr(self, name).copy_(t.to(self.device))
-        if apply:
-            self.env.set_max_ante(new["cap"].numpy())
-
-
-def _norm_rows(rows) -> torch.Tensor:
-    """rows of RowNormalizer: [N, stride] (one step) or [K, N, stride] -> the [K, N, stride] view."""
-    if isinstance(rows, torch.Tensor) and rows.dim() == 2:
-        rows = rows.unsqueeze(0)
-    return rows
-
-
-class RowNormalizer:
-    """SB3's `VecNormalize(norm_obs, norm_reward)` for N envs over packed records, on the device (bg_norm_obs_rows / bg_norm_reward_rows).  Owns what
-    VecNormalize pickles -- one RunningMeanStd (mean, var float64 [153], one count) over the columns of the "produced" layout, the return statistics
-    `ret_stats` (mean, var, count) -- plus the per-env discounted return `returns` (float64 [N]) and a cached workspace, all device tensors.
-    Each of the K steps of a call is one VecNormalize step: update the statistics with the batch of N envs, then normalise with the updated statistics.
-    training=False (or `.training = False` later) freezes the statistics: only the normalisation runs.  With norm_obs / norm_reward unset the matching
-    call refuses: encode the records / read `RowBuffers.reward` instead."""
-
-    def __init__(self, n: int, device, *, gamma: float = 0.99, epsilon: float = 1e-8, clip_obs: float = 10.0, clip_reward: float = 10.0,
-                 norm_obs: bool = True, norm_reward: bool = True, training: bool = True):
-        if int(n) < 0:
-            raise ValueError("n must be >= 0")
-        for name, v in (("gamma", gamma), ("epsilon", epsilon), ("clip_obs", clip_obs), ("clip_reward", clip_reward)):
-            if not np.isfinite(float(v)):
-                raise ValueError(f"{name} must be finite")
-        self.n = int(n)
-        self.device = torch.device(device)
-        if self.device.type == "cuda" and self.device.index is None:   # "cuda" is the current device: tensors report it with its index
-            self.device = torch.device("cuda", torch.cuda.current_device())
-        self.gamma, self.epsilon, self.clip_obs, self.clip_reward = float(gamma), float(epsilon), float(clip_obs), float(clip_reward)
-        self.norm_obs, self.norm_reward, self.training = bool(norm_obs), bool(norm_reward), bool(training)
-        f64 = dict(dtype=torch.float64, device=self.device)
-        self.obs_mean = torch.zeros(nat.NORM_COLS, **f64)        # RunningMeanStd(epsilon=1e-4): mean 0, var 1, count 1e-4
-        self.obs_var = torch.ones(nat.NORM_COLS, **f64)
-        self.obs_count = torch.full((1,), 1e-4, **f64)
-        self.ret_stats = torch.tensor([0.0, 1.0, 1e-4], **f64)   # mean, var, count
-        self.returns = torch.zeros(self.n, **f64)
-        self._workspace: Optional[torch.Tensor] = None
-
-    def reset_returns(self, mask: Optional[torch.Tensor] = None) -> None:
-        """Zero the discounted returns (of the envs where `mask` is set): VecNormalize.reset() does so for all envs."""
-        if mask is None:
-            self.returns.zero_()
-            return
-        mask = torch.as_tensor(mask)
-        if tuple(mask.shape) != (self.n,):
-            raise ValueError(f"mask must have shape [{self.n}]")
-        self.returns.masked_fill_(mask.to(device=self.device, dtype=torch.bool), 0.0)
-
-    def state_dict(self) -> dict:
-        """Host copies of everything the next call depends on: the counterpart of VecNormalize's pickle.  `load_state_dict` restores it exactly."""
-        return {"obs_mean": self.obs_mean.cpu().clone(), "obs_var": self.obs_var.cpu().clone(), "obs_count": self.obs_count.cpu().clone(),
-                "ret_stats": self.ret_stats.cpu().clone(), "returns": self.returns.cpu().clone(),
-                "gamma": self.gamma, "epsilon": self.epsilon, "clip_obs": self.clip_obs, "clip_reward": self.clip_reward,
-                "norm_obs": self.norm_obs, "norm_reward": self.norm_reward, "training": self.training}
-
-    def load_state_dict(self, state: dict) -> None:
-        for name in ("obs_mean", "obs_var", "obs_count", "ret_stats", "returns"):
-            mine, t = getattr(self, name), torch.as_tensor(state[name])
-            if t.dtype != torch.float64 or tuple(t.shape) != tuple(mine.shape):
-                raise ValueError(f"{name} must be a torch.float64 tensor of shape {list(mine.shape)}")
-        for name in ("obs_mean", "obs_var", "obs_count", "ret_stats", "returns"):
-            getattr(self, name).copy_(torch.as_tensor(state[name]))
-        for name in ("gamma", "epsilon", "clip_obs", "clip_reward"):
-            if name in state:
-                setattr(self, name, float(state[name]))
-        for name in ("norm_obs", "norm_reward", "training"):
-            if name in state:
-                setattr(self, name, bool(state[name]))
-
-    def _check_rows(self, rows) -> tuple:
-        K, N, stride = _check_scan_rows(_norm_rows(rows))
-        if N != self.n or rows.device != self.device:
-            raise ValueError(f"rows must hold records of {self.n} envs on {self.device} (got {N} envs on {rows.device})")
-        return K, N, stride
-
-    def _ready(self, L, K, N) -> torch.Tensor:
-        need = int(L.bg_norm_workspace_bytes(K, C.c_int64(N)))
-        if self._workspace is None or self._workspace.numel() < need:
-            self._workspace = torch.empty(need, dtype=torch.uint8, device=self.device)
-        return self._workspace
-
-    def normalize_obs(self, rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
-                      timing: bool = False, *, index: Optional[torch.Tensor] = None, update: Optional[bool] = None):
-        """K VecNormalize steps over the observations of rows (contiguous uint8 [K, N, stride], or [N, stride] = one step): returns the normalised
-        [K, N, D] (or [N, D]) matrix of `layout` ("produced" 153 columns, "fixed" 628: the never-filled columns are 0.0) in `dtype` (torch.float32 or
-        torch.bfloat16).  out: optional contiguous tensor of that shape and dtype to write into.  timing=True appends the kernel milliseconds.
-        update: None = `self.training`; False normalises with the statistics as they stand.  index: int32 [m] (`RowBuffers.minibatches`): the
-        [m, D] matrix of records index[i], gathered inside the launch with the statistics FROZEN (`encode_rows(index=, norm=)`); a statistics update is
-        defined per step over all N envs, not over a minibatch, so update=True with an index is refused."""
-        if index is not None:
-            if update:
-                raise ValueError("update=True with an index: a statistics update is defined per step over all N envs, not over a minibatch")
-            self._check_rows(rows)
-            return encode_rows(rows, layout, dtype, out, index=index, norm=self, timing=timing)
-        if not self.norm_obs:
-            raise ValueError("this RowNormalizer was made with norm_obs=False: use encode_rows")
-        if layout not in ("produced", "fixed"):
-            raise ValueError(f"layout must be 'produced' or 'fixed' (got {layout!r}): VecNormalize wraps the env's keys, not the extractor's tensors")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-        K, N, stride = self._check_rows(rows)
-        D = nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]
-        shape = (K, N, D) if rows.dim() == 3 else (N, D)
-        if out is not None:
-            _check_scan_tensor("out", out, dtype, shape, self.device)
-        if not rows.is_cuda:
-            raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-        if rows.data_ptr() % 16:
-            raise ValueError("rows must be 16-byte aligned")
-        if out is None:
-            out = torch.empty(shape, dtype=dtype, device=self.device)
-        if K * N == 0:
-            return (out, 0.0) if timing else out
-        L = nat.load()
-        ms = C.c_float(0.0)
-        with torch.cuda.device(self.device):
-            ws = self._ready(L, K, N)
-            rc = L.bg_norm_obs_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), nat.ENC_LAYOUTS[layout],
-                                    nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, C.c_void_p(self.obs_mean.data_ptr()),
-                                    C.c_void_p(self.obs_var.data_ptr()), C.c_void_p(self.obs_count.data_ptr()), 1 if (self.training if update is None else update) else 0,
-                                    C.c_double(self.epsilon), C.c_double(self.clip_obs), C.c_void_p(out.data_ptr()), C.c_uint64(D), None,
-                                    C.c_void_p(ws.data_ptr()), C.c_uint64(ws.numel()), C.byref(ms) if timing else None,
-                                    C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise nat.NativeError(f"bg_norm_obs_rows failed ({rc}): {L.bg_last_error(None).decode()}")
-        return (out, float(ms.value)) if timing else out
-
-    def normalize_reward(self, rows: torch.Tensor, out: Optional[torch.Tensor] = None, timing: bool = False):
-        """K VecNormalize steps over the rewards of rows: returns the normalised rewards, float64 [K, N] (or [N] for [N, stride] rows), what
-        `gae_rows(..., rewards=)` takes.  out: optional contiguous float64 tensor of that shape.  timing=True appends the kernel milliseconds."""
-        if not self.norm_reward:
-            raise ValueError("this RowNormalizer was made with norm_reward=False: the records' own rewards are `RowBuffers.reward`")
-        K, N, stride = self._check_rows(rows)
-        shape = (K, N) if rows.dim() == 3 else (N,)
-        if out is not None:
-            _check_scan_tensor("out", out, torch.float64, shape, self.device)
-        if not rows.is_cuda:
-            raise ValueError("rows must be a device tensor (there is no CPU fallback)")
-        if rows.data_ptr() % 16:
-            raise ValueError("rows must be 16-byte aligned")
-        if out is None:
-            out = torch.empty(shape, dtype=torch.float64, device=self.device)
-        if K * N == 0:
-            return (out, 0.0) if timing else out
-        L = nat.load()
-        ms = C.c_float(0.0)
-        with torch.cuda.device(self.device):
-            ws = self._ready(L, K, N)
-            rc = L.bg_norm_reward_rows(C.c_void_p(rows.data_ptr()), C.c_uint64(stride), K, C.c_int64(N), C.c_void_p(self.returns.data_ptr()),
-                                       C.c_void_p(self.ret_stats.data_ptr()), 1 if self.training else 0, C.c_double(self.gamma), C.c_double(self.epsilon),
-                                       C.c_double(self.clip_reward), C.c_void_p(out.data_ptr()), None, C.c_void_p(ws.data_ptr()), C.c_uint64(ws.numel()),
-                                       C.byref(ms) if timing else None, C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream))
-        if rc != 0:
-            raise nat.NativeError(f"bg_norm_reward_rows failed ({rc}): {L.bg_last_error(None).decode()}")
-        return (out, float(ms.value)) if timing else out
 
 
 def score_hand_batch(cases: torch.Tensor, lanes_per_case: int = 1, timing: bool = False):
