@@ -78,6 +78,7 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_sample_actions", "bg_evaluate_actions", "bg_ppo_loss", "bg_ppo_loss_workspace_bytes", "bg_encode_rows_ex",
            "bg_step_many_rows_ex", "bg_safe_terminal_slots",
            "bg_linear_rows", "bg_linear_rows_workspace_bytes", "bg_linear_rows_grad",
+           "bg_extractor_rows", "bg_extractor_rows_workspace_bytes", "bg_extractor_rows_grad",
            "bg_get_states", "bg_set_states", "bg_copy_states",
            "bg_set_episode_summary", "bg_episode_ends_rows",
            "bg_step_many_rows_progress", "bg_progress_terminal_slots",
@@ -103,6 +104,8 @@ DQN_MASK_NEXT, DQN_MSE, DQN_TIMEOUT_EXCLUDE = 1, 2, 4
 LIN_NONE, LIN_RELU = 0, 1   # bg_linear_rows / bg_linear_rows_grad (BG_LIN_*)
 LIN_ACTIVATIONS = {None: LIN_NONE, "relu": LIN_RELU}
 LIN_K = 153                 # the columns of a first-layer weight that are read: the "produced" ones
+EXT_K = 447                 # bg_extractor_rows: the columns of the "extractor" layout (416 one-hot, 10 joker ids, 21 state features)
+EXT_SPLITS = (416, 10, 21)  # the inputs of the reference's hand_net / joker_net / game_state_net first layers, in column order
 NORM_COLS = 153   # BG_NORM_COLS: VecNormalize's statistics are one (mean, var) per column of the "produced" layout
 # the keys BalatroEnvFixed zero-fills (train_balatro_fixed.py:125-207), in the order of its observation space, with their element counts
 ENC_ZERO_KEYS = [("hand_one_hot", 416), ("hand_suits", 8), ("hand_ranks", 8), ("rank_counts", 13), ("suit_counts", 4), ("straight_potential", 1),
@@ -316,5 +319,9 @@ def load(build_if_missing: bool = True):
     L.bg_linear_rows_workspace_bytes.argtypes = [i64, i32]
     L.bg_linear_rows_grad.argtypes = [vp, u64, i64, vp, i64, i32, vp, vp, C.c_double, C.c_double, vp, i32, u64, vp, i32, u64, i32, i32, vp, u64, vp, vp, u64,
                                       C.POINTER(C.c_float), vp]
+    L.bg_extractor_rows.argtypes = [vp, u64, i64, vp, i64, vp, u64, vp, i32, i32, i32, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_extractor_rows_workspace_bytes.restype = u64
+    L.bg_extractor_rows_workspace_bytes.argtypes = [i64, i32]
+    L.bg_extractor_rows_grad.argtypes = [vp, u64, i64, vp, i64, vp, i32, u64, vp, i32, u64, i32, i32, vp, u64, vp, vp, u64, C.POINTER(C.c_float), vp]
     _lib = L
     return L

@@ -754,3 +754,92 @@ int bg_sim_score_batch(const int32_t* cases_dev, int64_t* out_dev, int m, void* 
 }
 
 #endif  // BG_ROWS_API_H
+
+// packed records -> the first layer behind BalatroFeaturesExtractor's 447-column input and its weight / bias gradient (bg_extractor.h): entry points of
+// their own, so bg_linear_rows keeps refusing the layout.  The header is read here, behind every other kernel of the library, and its kernels are all
+// templates: the compiler numbers a function's labels by its place in the module, so kernels added at the end leave the text of the others as it was
+// (tools/isa_diff.py).
+extern "C++" {
+#include "bg_extractor.h"
+}
+static const char* bg_extractor_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int H,
+                                            int activation) {
+  if (H < 32 || H > 4096 || H % 32) return "H must be a multiple of 32 in [32, 4096]";
+  if (activation != BG_LIN_NONE && activation != BG_LIN_RELU) return "activation must be BG_LIN_NONE or BG_LIN_RELU";
+  if (m < 0 || m > (int64_t)BG_LIN_ROWS * 0x7fffffffll) return "m out of range";
+  if (store_rows < 0) return "store_rows must be >= 0";
+  if (index_dev && store_rows > 0x7fffffffll) return "store_rows must be in [0, 2**31) when index_dev is given";
+  if (!index_dev && m > store_rows) return "m must be <= store_rows when index_dev is NULL";
+  if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) return r;
+  if ((uintptr_t)index_dev & 3) return "index_dev must be 4-byte aligned";
+  return nullptr;
+}
+
+int bg_extractor_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, const void* weight_dev,
+                      uint64_t weight_stride_elems, const float* bias_dev, int H, int activation, int out_dtype, void* out_dev, uint64_t out_stride_elems,
+                      float* kernel_ms_out, void* stream) {
+  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const char* bad = bg_extractor_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation);
+  if (bad) {}
+  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (!weight_dev || ((uintptr_t)weight_dev & 1)) bad = "weight_dev must be a 2-byte aligned device pointer";
+  else if (weight_stride_elems < (uint64_t)BG_EXT_K || weight_stride_elems > 0x1000000ull) bad = "weight_stride_elems must be in [447, 2**24]";
+  else if ((uintptr_t)bias_dev & 3) bad = "bias_dev must be 4-byte aligned";
+  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
+  else if (out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= H";
+  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == weight_dev || out_dev == (const void*)bias_dev)
+    bad = "out_dev must not be the same pointer as an input";
+  if (int rc = bg_op_begin("bg_extractor_rows: ", bad, kernel_ms_out)) return rc;
+  if (m == 0) return 0;
+  const unsigned gx = (unsigned)bg_lin_blocks(m);
+  const unsigned nchunks = (unsigned)((H + BG_LIN_WCHUNK - 1) / BG_LIN_WCHUNK);
+  unsigned ys = 1;
+  while ((uint64_t)gx * ys < 512u && ys * 2u <= nchunks) ys *= 2u;   // a short call: the chunks of H over more workgroups (a function of m and H alone)
+  hipStream_t s = (hipStream_t)stream;
+  const int relu = activation == BG_LIN_RELU;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    auto go = [&](auto F32) {
+      hipLaunchKernelGGL((bg_extractor_rows_kernel<F32() ? BG_ENC_F32 : BG_ENC_BF16>), dim3(gx, ys), dim3(BG_LIN_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, (const uint16_t*)weight_dev, weight_stride_elems, bias_dev, H, relu, out_dev, out_stride_elems);
+    };
+    if (out_dtype == BG_ENC_F32) go(std::true_type{}); else go(std::false_type{});
+  });
+}
+
+uint64_t bg_extractor_rows_workspace_bytes(int64_t m, int H) { return bg_ext_workspace_bytes(m, H); }
+
+int bg_extractor_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, const void* dout_dev,
+                           int dout_dtype, uint64_t dout_stride_elems, const void* out_dev, int out_dtype, uint64_t out_stride_elems, int H, int activation,
+                           float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev, void* workspace_dev, uint64_t workspace_bytes,
+                           float* kernel_ms_out, void* stream) {
+  const uint64_t ds = dout_dtype == BG_ENC_F32 ? 4u : 2u, os = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const bool relu = activation == BG_LIN_RELU;
+  const char* bad = bg_extractor_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation);
+  if (bad) {}
+  else if (dout_dtype != BG_ENC_F32 && dout_dtype != BG_ENC_BF16) bad = "dout_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (!dout_dev || ((uintptr_t)dout_dev & (ds - 1))) bad = "dout_dev must be a device pointer aligned to its element type";
+  else if (dout_stride_elems < (uint64_t)H || dout_stride_elems > 0xffffffffull) bad = "dout_stride_elems must be >= H";
+  else if (relu != (out_dev != nullptr)) bad = "out_dev (the forward's output) is required with BG_LIN_RELU and must be NULL without it";
+  else if (relu && out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (relu && (((uintptr_t)out_dev & (os - 1)) || out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull)) bad = "out_dev must be aligned to its element type and out_stride_elems >= H";
+  else if (!dweight_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev must be a 4-byte aligned device pointer (dbias_dev 4-byte aligned)";
+  else if (dweight_stride_elems < (uint64_t)BG_EXT_K || dweight_stride_elems > 0xffffffffull) bad = "dweight_stride_elems must be >= 447";
+  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_ext_workspace_bytes(m, H))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_extractor_rows_workspace_bytes(m, H) bytes";
+  else if ((const void*)dweight_dev == dout_dev || (const void*)dweight_dev == out_dev || (const void*)dweight_dev == (const void*)rows_dev || dweight_dev == dbias_dev ||
+           (void*)dweight_dev == workspace_dev || (dbias_dev && ((void*)dbias_dev == workspace_dev || (const void*)dbias_dev == dout_dev || (const void*)dbias_dev == out_dev)) ||
+           workspace_dev == dout_dev || (workspace_dev && workspace_dev == out_dev)) bad = "outputs and the workspace must not be the same pointer as an input or as each other";
+  if (int rc = bg_op_begin("bg_extractor_rows_grad: ", bad, kernel_ms_out)) return rc;
+  if (m == 0) return 0;
+  const long long per = bg_ext_blocks_per_group(m, H), groups = bg_ext_groups(m, H);
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    const int outk = !relu ? 0 : out_dtype == BG_ENC_F32 ? 1 : 2;
+    bg_enc_pick<0, 1, 2>(outk, [&](auto OUTK) {
+      auto go = [&](auto DBF16) {
+        hipLaunchKernelGGL((bg_extractor_rows_grad_kernel<DBF16(), OUTK()>), dim3((unsigned)groups, (unsigned)bg_lin_spans(H), BG_EXT_KSPANS), dim3(BG_LIN_BLOCK), 0, s, rows_dev, row_stride_bytes, index_dev, (long long)store_rows, (long long)m, dout_dev, dout_stride_elems, out_dev, out_stride_elems, H, per, (float*)workspace_dev);
+      };
+      if (dout_dtype == BG_ENC_BF16) go(std::true_type{}); else go(std::false_type{});
+    });
+    const long long items = (long long)BG_EXT_PART_ROWS * H;
+    hipLaunchKernelGGL((bg_extractor_reduce_kernel<BG_EXT_K>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)workspace_dev, groups, H, dweight_dev, dweight_stride_elems, dbias_dev);
+  });
+}

@@ -340,6 +340,219 @@ class RowLinear(torch.nn.Module):
         return f"in_layout={self.in_layout!r}, out_features={self.out_features}, activation={self.activation!r}, dtype={self.dtype}"
 
 
+def _extractor_common(rows, index, activation):
+    """The arguments extractor_rows and its gradient share -> (stride, store_rows, m).  Every refusal is a ValueError before the library is loaded."""
+    if activation not in nat.LIN_ACTIVATIONS:
+        raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
+    lead, stride = _check_records(rows)
+    store_rows = int(np.prod(lead, dtype=np.int64))
+    m = store_rows
+    if index is not None:
+        _check_index(index, None, rows.device)
+        if store_rows >= 2 ** 31:
+            raise ValueError("the stored records hold at most 2**31 - 1 rows")
+        m = int(index.shape[0])
+    return stride, store_rows, m
+
+
+def _extractor_weight(weight) -> tuple:
+    """-> (H, row pitch in elements).  A [H, 447] view of a wider matrix (e.g. of a 16-byte aligned [H, 448] one, which the kernel stages fastest) passes."""
+    if not isinstance(weight, torch.Tensor) or weight.dtype != torch.bfloat16 or weight.dim() != 2 or weight.shape[1] != nat.EXT_K or weight.stride(1) != 1 \
+            or (weight.shape[0] > 1 and weight.stride(0) < nat.EXT_K):
+        raise ValueError(f"weight must be a torch.bfloat16 tensor [H, {nat.EXT_K}] with a contiguous last dimension (nn.Linear.weight's orientation)")
+    H = int(weight.shape[0])
+    if H < 32 or H > 4096 or H % 32:
+        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
+    return H, int(weight.stride(0))
+
+
+def extractor_rows(rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, *, index: Optional[torch.Tensor] = None,
+                   activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16, out: Optional[torch.Tensor] = None, timing: bool = False):
+    """The first layer behind BalatroFeaturesExtractor's input (train_balatro_agent.py:84-119) straight from packed records, on the matrix cores, in
+    one launch (bg_extractor_rows): act(x @ weight.T + bias), x the bfloat16 rows `encode_rows(rows, "extractor", torch.bfloat16, index=index)` gives --
+    416 one-hot hand columns, 10 joker ids, 21 scaled state features -- which are never written.  weight: torch.bfloat16 [H, 447] (nn.Linear.weight's
+    orientation; rows may be a view with a wider pitch), H a multiple of 32 in [32, 4096]; bias: float32 [H] or None; activation: None or "relu".
+    index: as `encode_rows`; a row whose index is out of range is act(bias).  There is no norm=: VecNormalize wraps the env's keys, not these tensors.
+    dtype: torch.bfloat16 or torch.float32 (float32 accumulation either way, one rounding).  out: optional [m, >= H] tensor of `dtype`; columns beyond H
+    are left untouched.  Returns the [m, H] matrix; timing=True returns (matrix, kernel milliseconds).  There is no CPU path.
+    The reference's constructor declares `joker_dim = 160` and `game_state_dim = 32`, but its `forward` builds 10 and 21 columns, so that class raises a
+    shape error on its first batch as written.  The "extractor" layout, and therefore this layer, follow `forward`: 416 + 10 + 21 = 447."""
+    stride, store_rows, m = _extractor_common(rows, index, activation)
+    H, wpitch = _extractor_weight(weight)
+    if weight.device != rows.device:
+        raise ValueError(f"weight must be on {rows.device}")
+    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (H,) or not bias.is_contiguous()
+                             or bias.device != rows.device):
+        raise ValueError(f"bias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+    pitch = _linear_matrix("out", out, (dtype,), m, H, rows.device) if out is not None else H
+    _check_device(rows)
+    if out is None:
+        out = torch.empty((m, H), dtype=dtype, device=rows.device)
+    args = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), _ptr(weight), C.c_uint64(wpitch), _ptr(bias), H,
+            nat.LIN_ACTIVATIONS[activation], nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, _ptr(out), C.c_uint64(pitch))
+    return _native_call("bg_extractor_rows", rows.device, args, out[:, :H], timing, empty=m == 0)
+
+
+def extractor_rows_grad(rows: torch.Tensor, dout: torch.Tensor, *, out: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None,
+                        activation: Optional[str] = None, dweight: Optional[torch.Tensor] = None, dbias: Optional[torch.Tensor] = None, timing: bool = False):
+    """The weight and bias gradient of `extractor_rows`, straight from the records (bg_extractor_rows_grad): dweight[n, k] = sum_i dp[i, n] * x[i, k],
+    dbias[n] = sum_i dp[i, n], dp = bfloat16(dout), under activation="relu" masked where the forward's `out` (required then) is not > 0.  dout: float32 or
+    bfloat16 [m, >= H].  dweight: optional float32 [H, >= 447] with a contiguous last dimension (columns at or beyond 447 are not written); dbias: optional
+    contiguous float32 [H]; without them new tensors are made.  Returns (dweight, dbias) -- with timing=True (dweight, dbias, kernel milliseconds).
+    Sums over rows are deterministic (no atomics)."""
+    stride, store_rows, m = _extractor_common(rows, index, activation)
+    if not isinstance(dout, torch.Tensor) or dout.dim() != 2:
+        raise ValueError("dout must be a float32 / bfloat16 tensor [m, H]")
+    H = int(dweight.shape[0]) if isinstance(dweight, torch.Tensor) and dweight.dim() == 2 else int(dout.shape[1])
+    if H < 32 or H > 4096 or H % 32:
+        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
+    dpitch = _linear_matrix("dout", dout, (torch.float32, torch.bfloat16), m, H, rows.device)
+    relu = activation == "relu"
+    if relu != (out is not None):
+        raise ValueError("out (the forward's output) is required with activation='relu' and must be None without it")
+    opitch = _linear_matrix("out", out, (torch.float32, torch.bfloat16), m, H, rows.device) if relu else 0
+    if dweight is not None and (not isinstance(dweight, torch.Tensor) or dweight.dtype != torch.float32 or dweight.dim() != 2 or dweight.shape[1] < nat.EXT_K
+                                or dweight.stride(1) != 1 or dweight.stride(0) < dweight.shape[1] or dweight.device != rows.device):
+        raise ValueError(f"dweight must be a torch.float32 tensor [H, >= {nat.EXT_K}] on {rows.device} with a contiguous last dimension")
+    if dbias is not None and (not isinstance(dbias, torch.Tensor) or dbias.dtype != torch.float32 or tuple(dbias.shape) != (H,) or not dbias.is_contiguous()
+                              or dbias.device != rows.device):
+        raise ValueError(f"dbias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
+    _check_device(rows)
+    if dweight is None:
+        dweight = torch.zeros((H, nat.EXT_K), dtype=torch.float32, device=rows.device)
+    if dbias is None:
+        dbias = torch.zeros(H, dtype=torch.float32, device=rows.device)
+    if m == 0:
+        dweight[:, :nat.EXT_K] = 0.0
+        dbias.zero_()
+        return _native_call("bg_extractor_rows_grad", rows.device, (), (dweight, dbias), timing, empty=True)
+    need = int(nat.load().bg_extractor_rows_workspace_bytes(C.c_int64(m), H))
+    workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    args = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), _ptr(dout),
+            nat.ENC_F32 if dout.dtype == torch.float32 else nat.ENC_BF16, C.c_uint64(dpitch), _ptr(out),
+            (nat.ENC_F32 if out.dtype == torch.float32 else nat.ENC_BF16) if relu else 0, C.c_uint64(opitch), H, nat.LIN_ACTIVATIONS[activation],
+            _ptr(dweight), C.c_uint64(int(dweight.stride(0))), _ptr(dbias), _ptr(workspace), C.c_uint64(workspace.numel()))
+    return _native_call("bg_extractor_rows_grad", rows.device, args, (dweight, dbias), timing)
+
+
+class _RowExtractorFn(torch.autograd.Function):
+    """out = extractor_rows(records); backward = ONE bg_extractor_rows_grad call.  The records carry no gradient."""
+
+    @staticmethod
+    def forward(ctx, weight, bias, rows, index, activation, dtype, mask):
+        wb = torch.empty((weight.shape[0], nat.EXT_K + 1), dtype=torch.bfloat16, device=weight.device)[:, :nat.EXT_K]   # pitch 448: 16-byte lines
+        wb.copy_(weight.detach())
+        out = extractor_rows(rows, wb, bias.detach(), index=index, activation=activation, dtype=dtype)
+        ctx.save_for_backward(out)
+        ctx.call = (rows, index, activation, mask)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad):
+        rows, index, activation, mask = ctx.call
+        out, = ctx.saved_tensors
+        dout = grad if grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.stride(1) == 1 and (grad.shape[0] <= 1 or grad.stride(0) >= grad.shape[1]) \
+            else grad.to(torch.float32).contiguous()
+        dweight, dbias = extractor_rows_grad(rows, dout, out=out if activation == "relu" else None, index=index, activation=activation)
+        if mask is not None:
+            dweight.mul_(mask)
+        return dweight, dbias, None, None, None, None, None
+
+
+class RowExtractor(torch.nn.Module):
+    """The first layer of a network over BalatroFeaturesExtractor's input (train_balatro_agent.py:84-119), from packed records: `forward(rows)` is
+    `extractor_rows` and its backward one `extractor_rows_grad` call, so neither pass materialises the [m, 447] matrix.  Parameters are float32 --
+    weight [out_features, 447], bias [out_features] -- initialised as nn.Linear(447, out_features); `from_linear` / `to_linear` move them to and from an
+    nn.Linear.  The weight is cast to bfloat16 for every call (the master copy stays float32).
+    `from_linears(hand, joker, state)` stacks the first layers of the reference's `hand_net`, `joker_net` and `game_state_net` (416, 10 and 21 inputs)
+    as ONE block-structured [h + j + s, 447] weight: `.splits == (h, j, s)`, so `out.split(layer.splits, dim=1)` gives the three sub-networks'
+    activations; the block mask is a buffer and multiplies dweight in backward, so off-block weights stay exactly zero under any optimiser;
+    `to_linears()` returns the three layers.
+    The reference's constructor declares `joker_dim = 160` and `game_state_dim = 32`, but its `forward` builds 10 and 21 columns, so that class raises a
+    shape error on its first batch as written.  The "extractor" layout, and therefore this layer, follow `forward`: 416 + 10 + 21 = 447."""
+
+    def __init__(self, out_features: int, activation: Optional[str] = "relu", dtype: torch.dtype = torch.bfloat16, device=None):
+        super().__init__()
+        if activation not in nat.LIN_ACTIVATIONS:
+            raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        out_features = int(out_features)
+        if out_features < 32 or out_features > 4096 or out_features % 32:
+            raise ValueError(f"out_features must be a multiple of 32 in [32, 4096] (got {out_features})")
+        self.out_features, self.in_features, self.activation, self.dtype = out_features, nat.EXT_K, activation, dtype
+        self.splits = (out_features,)
+        lin = torch.nn.Linear(self.in_features, out_features, device=device)   # nn.Linear's own initialisation
+        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
+        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+        self.register_buffer("block_mask", None)
+
+    @classmethod
+    def from_linear(cls, linear: torch.nn.Linear, activation: Optional[str] = "relu", dtype: torch.dtype = torch.bfloat16) -> "RowExtractor":
+        if not isinstance(linear, torch.nn.Linear) or linear.in_features != nat.EXT_K or linear.bias is None:
+            raise ValueError(f"from_linear takes an nn.Linear with bias and {nat.EXT_K} inputs")
+        layer = cls(linear.out_features, activation, dtype, device=linear.weight.device)
+        with torch.no_grad():
+            layer.weight.copy_(linear.weight)
+            layer.bias.copy_(linear.bias)
+        return layer
+
+    def to_linear(self) -> torch.nn.Linear:
+        lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
+        with torch.no_grad():
+            lin.weight.copy_(self.weight)
+            lin.bias.copy_(self.bias)
+        return lin
+
+    @classmethod
+    def from_linears(cls, hand: torch.nn.Linear, joker: torch.nn.Linear, state: torch.nn.Linear, activation: Optional[str] = "relu",
+                     dtype: torch.dtype = torch.bfloat16) -> "RowExtractor":
+        parts = (hand, joker, state)
+        for lin, cols, name in zip(parts, nat.EXT_SPLITS, ("hand", "joker", "state")):
+            if not isinstance(lin, torch.nn.Linear) or lin.in_features != cols or lin.bias is None:
+                raise ValueError(f"from_linears: {name} must be an nn.Linear with bias and in_features {cols} (the reference's forward builds 416, 10 and 21 columns)")
+        splits = tuple(int(lin.out_features) for lin in parts)
+        if sum(splits) % 32:
+            raise ValueError(f"from_linears: the out_features {splits} must sum to a multiple of 32 (got {sum(splits)})")
+        layer = cls(sum(splits), activation, dtype, device=hand.weight.device)
+        layer.splits = splits
+        mask = torch.zeros_like(layer.weight)
+        with torch.no_grad():
+            layer.weight.zero_()
+            r = c = 0
+            for lin, cols in zip(parts, nat.EXT_SPLITS):
+                layer.weight[r:r + lin.out_features, c:c + cols] = lin.weight
+                layer.bias[r:r + lin.out_features] = lin.bias
+                mask[r:r + lin.out_features, c:c + cols] = 1.0
+                r, c = r + lin.out_features, c + cols
+        layer.block_mask = mask
+        return layer
+
+    def to_linears(self) -> tuple:
+        if len(self.splits) != 3:
+            raise ValueError("to_linears needs a layer made by from_linears")
+        out, r, c = [], 0, 0
+        for width, cols in zip(self.splits, nat.EXT_SPLITS):
+            lin = torch.nn.Linear(cols, width, device=self.weight.device)
+            with torch.no_grad():
+                lin.weight.copy_(self.weight[r:r + width, c:c + cols])
+                lin.bias.copy_(self.bias[r:r + width])
+            out.append(lin)
+            r, c = r + width, c + cols
+        return tuple(out)
+
+    def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        _extractor_common(rows, index, self.activation)
+        if not rows.is_cuda or self.weight.device != rows.device:
+            raise ValueError("rows and the layer must be on the same GPU (there is no CPU fallback)")
+        return _RowExtractorFn.apply(self.weight, self.bias, rows, index, self.activation, self.dtype, self.block_mask)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features={self.out_features}, splits={self.splits}, activation={self.activation!r}, dtype={self.dtype}"
+
+
 def _head_logits(logits) -> tuple:
     """logits of sample_actions / evaluate_actions: float32 / bfloat16 [..., 60] with a contiguous last dimension and leading dimensions dense over the
     row pitch (e.g. 60 columns of a wider matrix) -> (leading shape, m, row pitch in elements)."""

@@ -16,9 +16,9 @@ import torch
 
 from . import _native as nat
 # the learner's calls over records and logits live in rows.py; every name that used to be defined here stays importable from here
-from .rows import (DqnStats, EpisodeLimits, EpisodeStats, PpoStats, ProgressionRewards, RowCurriculum, RowLinear, RowNormalizer,  # noqa: F401
+from .rows import (DqnStats, EpisodeLimits, EpisodeStats, PpoStats, ProgressionRewards, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
                    RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, dqn_loss, encode_rows, episode_ends, evaluate_actions,
-                   gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
+                   extractor_rows, extractor_rows_grad, gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
 
 _TORCH_DT = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
              "float32": torch.float32, "float64": torch.float64, "uint8": torch.uint8, "uint32": torch.uint32}
@@ -146,6 +146,11 @@ class RowBuffers:
         """The first layer of the network over these records, [steps * n, H] or with `index` [m, H] (`RowLinear.forward`: bg_linear_rows, and
         bg_linear_rows_grad under autograd): the feature matrix is never written."""
         return layer(self.rows, index, norm)
+
+    def extractor(self, layer: "RowExtractor", index: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The first layer behind BalatroFeaturesExtractor's input over these records, [steps * n, H] or with `index` [m, H] (`RowExtractor.forward`:
+        bg_extractor_rows, and bg_extractor_rows_grad under autograd): the [m, 447] matrix is never written."""
+        return layer(self.rows, index)
 
     def normalize_reward(self, norm: "RowNormalizer", out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The records' rewards as VecNormalize would hand them to the learner, float64 [steps, n] (`RowNormalizer.normalize_reward`)."""

@@ -927,6 +927,55 @@ int bg_linear_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int6
                         float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev /*nullable*/,
                         void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* The first layer behind BalatroFeaturesExtractor's input, straight from the stored records, forward and backward -- the counterpart of bg_linear_rows
+ * for the one layout it refuses.  The arithmetic and the tile shapes are csrc/bg_extractor.h.
+ * Replaces: the tensors `BalatroFeaturesExtractor.forward` builds (train_balatro_agent.py:84-119: the hand one-hot :86-93, `joker_ids.float()` :98,
+ * `game_features` :102-113) plus the first `nn.Linear` of `hand_net`, `joker_net` and `game_state_net`, which PPO, DQN and A2C of that script
+ * (:326-377) all run, and the autograd backward of those layers.  The three layers are ONE call on a block-structured [h + j + s, 447] weight.
+ *
+ * bg_extractor_rows:       out[i, n] = act( sum over k < 447 of x[i, k] * w[n, k]  +  b[n] )
+ * x[i, :] = the row bg_encode_rows_ex writes with layout BG_ENC_EXTRACTOR and out_dtype BG_ENC_BF16 for the same rows_dev, row_stride_bytes,
+ * store_rows, index_dev, m -- bit for bit, and never written: column 52 slot + card is 1.0 where hand byte `slot` equals `card` (card in 0..51; the
+ * bytes -1, 52..127 and negative values match no column; the same card in two slots sets two columns), the other 31 columns are the float32 values
+ * rounded to nearest even to bfloat16.  An index outside [0, store_rows) reads nothing and gives x = +0.0, so out = act(b).  There are no VecNormalize
+ * statistics: every call refuses them for this layout, and this one does not take them.
+ * weight_dev: bfloat16 in torch's `nn.Linear.weight` orientation, [H, weight_stride_elems >= 447] (at most 2**24); 2-byte alignment is all that is
+ * required (a 16-byte aligned matrix with a pitch that is a multiple of 8, e.g. 448, is staged fastest).  bias_dev: float32 [H] or NULL.  activation:
+ * BG_LIN_NONE or BG_LIN_RELU, as bg_linear_rows.  out_dtype BG_ENC_F32 or BG_ENC_BF16, out_stride_elems >= H; columns at or beyond H and rows at or
+ * beyond m are not touched.  H: a multiple of 32 in [32, 4096].
+ * Products are bfloat16 x bfloat16 (exact in float32), accumulated in float32 by __builtin_amdgcn_mfma_f32_32x32x16_bf16 over the reduction padded to
+ * 448 with a zero; the bias is added in float32 behind the sum, then the activation, then ONE rounding to the output dtype: a bfloat16 output is the
+ * round-to-nearest-even of the float32 output of the same arithmetic.  Two calls give the same bits.
+ *
+ * bg_extractor_rows_grad:  dweight[n, k] = sum over i of dp[i, n] * x[i, k]  (k < 447);    dbias[n] = sum over i of dp[i, n]
+ * dp, dout_*, out_* as bg_linear_rows_grad: dp = bfloat16(dout), +0.0 where BG_LIN_RELU's forward output is not > 0 (out_dev required exactly then).
+ * dweight_dev: float32 [H, dweight_stride_elems >= 447], columns at or beyond 447 untouched; dbias_dev: float32 [H] or NULL.  The rows are cut into
+ * groups of consecutive 128-row blocks, the units into spans of 256 and k into 3 spans of 160, 160 and 128 columns; a workgroup keeps float32
+ * matrix-core accumulators over the rows of its group, the groups' partials ([449, H] float32 each: dweight^T and the dbias row) go to workspace_dev
+ * and a second launch adds them in index order in float64, rounding once.  There are no atomics: two calls give the same bits.
+ * bg_extractor_rows_workspace_bytes(m, H) = groups * 449 * H * 4 bytes, groups = ceil(B / ceil(B / max(1, 256 / (3 * ceil(H / 256))))) with
+ * B = ceil(m / 128): at most 256 workgroups, 39 MB at the most; a group holds 128 * ceil(B / groups) rows at most.  workspace_dev: 16-byte aligned.
+ *
+ * Both calls run on the current device, need no handle, return BG_E_ARG (text "bg_extractor_rows: ..." / "bg_extractor_rows_grad: ..." in
+ * bg_last_error(NULL)) before anything is launched, treat m == 0 as a no-op and never synchronise unless timing is asked for; kernel_ms_out as in
+ * bg_classify_batch_ex.  All record addressing is 64-bit.
+ * Out of scope: the second layers of the three sub-networks and `combined_net`, skipping the structurally zero blocks of a block-structured weight,
+ * tanh, a gradient with respect to the records, and the optimiser. */
+int bg_extractor_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                      const int32_t* index_dev /*nullable*/, int64_t m,
+                      const void* weight_dev, uint64_t weight_stride_elems, const float* bias_dev /*nullable*/,
+                      int H, int activation, int out_dtype, void* out_dev, uint64_t out_stride_elems,
+                      float* kernel_ms_out, void* stream);
+uint64_t bg_extractor_rows_workspace_bytes(int64_t m, int H);
+int bg_extractor_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows,
+                           const int32_t* index_dev /*nullable*/, int64_t m,
+                           const void* dout_dev, int dout_dtype, uint64_t dout_stride_elems,
+                           const void* out_dev /*nullable*/, int out_dtype, uint64_t out_stride_elems,
+                           int H, int activation,
+                           float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev /*nullable*/,
+                           void* workspace_dev, uint64_t workspace_bytes,
+                           float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -80,6 +80,10 @@ def split(asm: str) -> tuple[dict[str, list[str]], set[str]]:
     tail = next((i for i, ln in enumerate(lines) if ln.startswith("\t.amdgpu_metadata") or ".AMDGPU.gpr_maximums" in ln), len(lines))
     if starts and tail < starts[-1][0]:
         tail = len(lines)
+    # the module's end-of-text padding (`.text`, `.p2alignl`, `.fill`) stands behind whichever function is last: it belongs to the tail, not to that
+    # function, or a kernel appended to the module would make the previously last one differ by three lines that are no instruction
+    while starts and tail > starts[-1][0] and lines[tail - 1].strip().startswith((".text", ".p2alignl", ".fill")):
+        tail -= 1
     pieces: dict[str, list[str]] = {"(head)": lines[:starts[0][0]] if starts else lines}
     for k, (j, name) in enumerate(starts):
         end = starts[k + 1][0] if k + 1 < len(starts) else tail
