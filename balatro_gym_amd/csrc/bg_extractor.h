@@ -38,7 +38,6 @@
 #define BG_EXT_SPAN_TILES 5 /* k-tiles of one workgroup of the gradient: the wave shape of bg_linear_rows_grad_kernel (2 x 5 accumulator tiles) */
 #define BG_EXT_KSPANS 3     /* spans of k over the gradient's grid: tiles 0..4, 5..9, 10..13 */
 #define BG_EXT_PART_ROWS (BG_EXT_KPAD + 1) /* rows of a gradient partial: [448][H] of dweight^T, then [H] of dbias */
-#define BG_EXT_MAX_WG 256   /* bound on row groups x unit spans x k spans of the gradient: one workgroup per CU */
 
 // ---- the one-hot columns ----
 BG_EXT_FN int bg_ext_slot(int k) { return k / BG_EXT_CARDS; }   // one-hot column k = 52 slot + card
@@ -59,19 +58,11 @@ BG_EXT_FN int bg_ext_tile_k(int tile, int lane) { return BG_LIN_TILE * tile + bg
 // ---- the gradient's split: m rows into blocks of 128, `per` consecutive blocks per row group; H into spans of 256 units; k into 3 spans of tiles ----
 BG_EXT_FN int bg_ext_span_tile0(int z) { return BG_EXT_SPAN_TILES * z; }
 BG_EXT_FN int bg_ext_span_tiles(int z) { return BG_EXT_KTILES - bg_ext_span_tile0(z) < BG_EXT_SPAN_TILES ? BG_EXT_KTILES - bg_ext_span_tile0(z) : BG_EXT_SPAN_TILES; }
-BG_EXT_FN int64_t bg_ext_blocks_per_group(int64_t m, int H) {
-  const int64_t wg = BG_EXT_KSPANS * bg_lin_spans(H), cap = BG_EXT_MAX_WG / wg > 0 ? BG_EXT_MAX_WG / wg : 1;
-  return (bg_lin_blocks(m) + cap - 1) / cap;
-}
-BG_EXT_FN int64_t bg_ext_groups(int64_t m, int H) {
-  const int64_t per = bg_ext_blocks_per_group(m, H);
-  return (bg_lin_blocks(m) + per - 1) / per;
-}
+// bg_linear.h's split with BG_EXT_KSPANS workgroups per unit span
+BG_EXT_FN int64_t bg_ext_blocks_per_group(int64_t m, int H) { return bg_lin_blocks_per_group(m, H, BG_EXT_KSPANS); }
+BG_EXT_FN int64_t bg_ext_groups(int64_t m, int H) { return bg_lin_groups(m, H, BG_EXT_KSPANS); }
 // bg_extractor_rows_workspace_bytes: groups partials of [449][H] float32
-BG_EXT_FN uint64_t bg_ext_workspace_bytes(int64_t m, int H) {
-  if (m <= 0 || H < 32 || H > 4096 || H % 32) return 0;
-  return (uint64_t)bg_ext_groups(m, H) * BG_EXT_PART_ROWS * (uint64_t)H * sizeof(float);
-}
+BG_EXT_FN uint64_t bg_ext_workspace_bytes(int64_t m, int H) { return bg_lin_workspace_bytes(m, H, BG_EXT_KSPANS, BG_EXT_PART_ROWS); }
 
 #ifndef BG_EXT_HOST
 // ---- the kernels ----
@@ -130,7 +121,8 @@ __device__ __forceinline__ void bg_ext_load_hands(const uint8_t* __restrict__ ro
 }
 
 // the 31 dense columns of the BG_LIN_ROWS records from rec0 as bfloat16 into `x`: [row][c] of BG_EXT_DPITCH (TRANSPOSED false) or [c][row] of
-// BG_LIN_TPITCH; rows at or beyond m and column 31 are +0.0.  Ends behind a barrier.
+// BG_LIN_TPITCH; rows at or beyond m and column 31 are +0.0.  Ends behind a barrier.  (The twin of bg_lin_build_x, bg_linear.h: one function over the
+// converter, the columns and the pitch moved a kernel's text -- DESIGN.md, "Source-only changes to the engines".)
 template <bool TRANSPOSED>
 __device__ __forceinline__ void bg_ext_build_dense(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index, long long store_rows,
                                                    long long m, long long rec0, long long* src, uint32_t* stage, uint16_t* x) {
@@ -255,13 +247,7 @@ __global__ __launch_bounds__(BG_LIN_BLOCK, 2) void bg_extractor_rows_kernel(cons
 #pragma unroll
       for (int g = 0; g < 16; g++) {
         const long long r = row_base + bg_lin_acc_row(lane, g);
-        if (r < m) {
-          float v = bias ? acc[g] + bv : acc[g];
-          if (relu) v = bg_lin_relu(v);
-          const size_t at = (size_t)r * ostride + (size_t)col;
-          if (ODT == BG_ENC_F32) reinterpret_cast<float*>(out)[at] = v;
-          else reinterpret_cast<uint16_t*>(out)[at] = bg_enc_bf16(__float_as_uint(v));
-        }
+        if (r < m) bg_lin_emit<ODT>(out, (size_t)r * ostride + (size_t)col, bias ? acc[g] + bv : acc[g], relu);
       }
     }
   }
@@ -298,6 +284,7 @@ __global__ __launch_bounds__(BG_LIN_BLOCK) void bg_extractor_rows_grad_kernel(co
   constexpr int KT = BG_EXT_SPAN_TILES, NT = BG_LIN_NSPAN / BG_LIN_TILE / (BG_LIN_BLOCK / 64);   // 5 tiles of k; 2 unit tiles per wave
   const int tile0 = bg_ext_span_tile0(blockIdx.z), ntile = bg_ext_span_tiles(blockIdx.z);
   const bool dense = tile0 + ntile > BG_EXT_HOT_TILES;   // this span holds the dense tile (its last)
+  // (ncol / acc / dbsum, the block range and the write-out of the partial are bg_linear_rows_grad_kernel's: shared helpers moved both kernels' text)
   int ncol[NT];      // the lane's unit in tile t, or -1: the tile is beyond H (uniform over the wave)
   int card[KT], hoff[KT];   // the card of the lane's column in k-tile kt and where its slot's bytes of the lane's 8 records start in HB
   bg_lin_c16 acc[NT][KT];
@@ -401,18 +388,11 @@ __global__ __launch_bounds__(BG_LIN_BLOCK) void bg_extractor_rows_grad_kernel(co
   }
 }
 
-// dweight[n][k] (k < KCOLS) / dbias[n] = the partials' elements summed in index order in float64, rounded once
+// bg_linear.h's reduce over partials of [449][H] (a template, as every kernel here: see above)
 template <int KCOLS>
 __global__ __launch_bounds__(256) void bg_extractor_reduce_kernel(const float* __restrict__ part, long long groups, int H, float* __restrict__ dweight, uint64_t dwstride,
                                                                   float* __restrict__ dbias) {
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (item >= (long long)BG_EXT_PART_ROWS * H) return;
-  const int k = (int)(item / H), n = (int)(item - (long long)k * H);
-  if (k >= KCOLS && (k != BG_EXT_KPAD || !dbias)) return;
-  double s = 0.0;
-  for (long long p = 0; p < groups; p++) s = s + (double)part[(size_t)p * BG_EXT_PART_ROWS * (size_t)H + (size_t)item];
-  if (k < KCOLS) dweight[(size_t)n * dwstride + k] = (float)s;
-  else dbias[n] = (float)s;
+  bg_lin_reduce<KCOLS, BG_EXT_KPAD>(part, groups, H, dweight, dwstride, dbias);
 }
 #endif  // BG_EXT_HOST
 #endif

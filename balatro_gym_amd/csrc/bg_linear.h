@@ -25,7 +25,7 @@
 #define BG_LIN_ROWS 128 /* records of one pass of a workgroup: four sub-tiles of 32, as bg_encode_kernel stages them */
 #define BG_LIN_NSPAN 256 /* output units of one workgroup of the gradient: two accumulator tiles per wave */
 #define BG_LIN_PART_ROWS (BG_LIN_KPAD + 1) /* rows of a gradient partial: [160][H] of dweight^T, then [H] of dbias */
-#define BG_LIN_MAX_GROUPS 256 /* bound on row groups x unit spans of the gradient: one partial per CU */
+#define BG_LIN_MAX_WG 256 /* bound on the workgroups of a gradient (row groups x unit spans x, in bg_extractor.h, k spans): one per CU */
 
 // ---- v_mfma_f32_32x32x16_bf16: D[32][32] += A[32][16] * B[16][32], one wave of 64 lanes ----
 // Lane l holds 8 consecutive k of ONE row of A and of ONE column of B; its 16 accumulator registers are 16 rows of ONE column of D.
@@ -36,16 +36,22 @@ BG_LIN_FN int bg_lin_acc_col(int lane) { return lane & 31; }
 // element offset of the lane's fragment (8 consecutive elements) in an image [row of A | column of B][reduction index] of `pitch` elements per line
 BG_LIN_FN int bg_lin_frag_off(int lane, int step, int pitch) { return bg_lin_frag_rc(lane) * pitch + bg_lin_frag_k(lane, step, 0); }
 
-// the gradient's split of m rows: blocks of BG_LIN_ROWS rows, `per` consecutive blocks per row group, `groups` groups (= partials)
+// a gradient's split of m rows (this layer's and bg_extractor.h's): blocks of BG_LIN_ROWS rows, `per` consecutive blocks per row group, `groups` groups
+// (= partials), for a grid of bg_lin_spans(H) x `kspans` workgroups per row group: kspans is 1 here, the k spans there
 BG_LIN_FN int64_t bg_lin_blocks(int64_t m) { return (m + BG_LIN_ROWS - 1) / BG_LIN_ROWS; }
 BG_LIN_FN int64_t bg_lin_spans(int H) { return (H + BG_LIN_NSPAN - 1) / BG_LIN_NSPAN; }
-BG_LIN_FN int64_t bg_lin_blocks_per_group(int64_t m, int H) {
-  const int64_t cap = BG_LIN_MAX_GROUPS / bg_lin_spans(H) > 0 ? BG_LIN_MAX_GROUPS / bg_lin_spans(H) : 1;
+BG_LIN_FN int64_t bg_lin_blocks_per_group(int64_t m, int H, int kspans = 1) {
+  const int64_t wg = kspans * bg_lin_spans(H), cap = BG_LIN_MAX_WG / wg > 0 ? BG_LIN_MAX_WG / wg : 1;
   return (bg_lin_blocks(m) + cap - 1) / cap;
 }
-BG_LIN_FN int64_t bg_lin_groups(int64_t m, int H) {
-  const int64_t per = bg_lin_blocks_per_group(m, H);
+BG_LIN_FN int64_t bg_lin_groups(int64_t m, int H, int kspans = 1) {
+  const int64_t per = bg_lin_blocks_per_group(m, H, kspans);
   return (bg_lin_blocks(m) + per - 1) / per;
+}
+// the workspace of such a gradient: groups partials of [part_rows][H] float32; 0 where nothing is launched
+BG_LIN_FN uint64_t bg_lin_workspace_bytes(int64_t m, int H, int kspans, int part_rows) {
+  if (m <= 0 || H < 32 || H > 4096 || H % 32) return 0;
+  return (uint64_t)bg_lin_groups(m, H, kspans) * (uint64_t)part_rows * (uint64_t)H * sizeof(float);
 }
 // max(v, +0.0) with a NaN kept
 BG_LIN_FN float bg_lin_relu(float v) { return v > 0.f ? v : v != v ? v : 0.f; }
@@ -182,6 +188,14 @@ __device__ __forceinline__ void bg_lin_stage_w(const uint16_t* __restrict__ weig
   }
 }
 
+// one element of a forward's output: the activation, then the store as float32 or rounded to bfloat16
+template <int ODT>
+__device__ __forceinline__ void bg_lin_emit(void* out, size_t at, float v, int relu) {
+  if (relu) v = bg_lin_relu(v);
+  if (ODT == BG_ENC_F32) reinterpret_cast<float*>(out)[at] = v;
+  else reinterpret_cast<uint16_t*>(out)[at] = bg_enc_bf16(__float_as_uint(v));
+}
+
 template <bool NORM, int ODT>
 __global__ __launch_bounds__(BG_LIN_BLOCK, 2) void bg_linear_rows_kernel(const uint8_t* __restrict__ rows, uint64_t row_stride, const int32_t* __restrict__ index,
                                                                       long long store_rows, long long m, const double* __restrict__ mean,
@@ -224,13 +238,7 @@ __global__ __launch_bounds__(BG_LIN_BLOCK, 2) void bg_linear_rows_kernel(const u
 #pragma unroll
       for (int g = 0; g < 16; g++) {
         const long long row = row_base + bg_lin_acc_row(lane, g);
-        if (row < m) {
-          float v = bias ? acc[g] + bv : acc[g];
-          if (relu) v = bg_lin_relu(v);
-          const size_t at = (size_t)row * ostride + (size_t)col;
-          if (ODT == BG_ENC_F32) reinterpret_cast<float*>(out)[at] = v;
-          else reinterpret_cast<uint16_t*>(out)[at] = bg_enc_bf16(__float_as_uint(v));
-        }
+        if (row < m) bg_lin_emit<ODT>(out, (size_t)row * ostride + (size_t)col, bias ? acc[g] + bv : acc[g], relu);
       }
     }
   }
@@ -320,17 +328,23 @@ __global__ __launch_bounds__(BG_LIN_BLOCK) void bg_linear_rows_grad_kernel(const
   }
 }
 
-// dweight[n][k] / dbias[n] = the partials' elements summed in index order in float64, rounded once
+// dweight[n][k] (k < K) / dbias[n] = the elements of the partials [KPAD + 1][H] summed in index order in float64, rounded once: the body of this layer's
+// reduce kernel and of bg_extractor.h's
+template <int K, int KPAD>
+__device__ __forceinline__ void bg_lin_reduce(const float* __restrict__ part, long long groups, int H, float* __restrict__ dweight, uint64_t dwstride,
+                                              float* __restrict__ dbias) {
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (item >= (long long)(KPAD + 1) * H) return;
+  const int k = (int)(item / H), n = (int)(item - (long long)k * H);
+  if (k >= K && (k != KPAD || !dbias)) return;
+  double s = 0.0;
+  for (long long p = 0; p < groups; p++) s = s + (double)part[(size_t)p * (KPAD + 1) * (size_t)H + (size_t)item];
+  if (k < K) dweight[(size_t)n * dwstride + k] = (float)s;
+  else dbias[n] = (float)s;
+}
 __global__ __launch_bounds__(256) void bg_linear_reduce_kernel(const float* __restrict__ part, long long groups, int H, float* __restrict__ dweight, uint64_t dwstride,
                                                                float* __restrict__ dbias) {
-  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (item >= (long long)BG_LIN_PART_ROWS * H) return;
-  const int k = (int)(item / H), n = (int)(item - (long long)k * H);
-  if (k >= BG_LIN_K && (k != BG_LIN_KPAD || !dbias)) return;
-  double s = 0.0;
-  for (long long p = 0; p < groups; p++) s = s + (double)part[(size_t)p * BG_LIN_PART_ROWS * (size_t)H + (size_t)item];
-  if (k < BG_LIN_K) dweight[(size_t)n * dwstride + k] = (float)s;
-  else dbias[n] = (float)s;
+  bg_lin_reduce<BG_LIN_K, BG_LIN_KPAD>(part, groups, H, dweight, dwstride, dbias);
 }
 #endif  // BG_LIN_HOST
 #endif

@@ -584,13 +584,22 @@ int bg_dqn_loss(const void* q_dev, uint64_t q_stride_elems, const void* q_next_d
   });
 }
 
-// packed records -> the first layer of the network and its weight / bias gradient (bg_linear.h): the features of bg_encode_rows_ex are built in LDS
-// and consumed by the matrix cores in the same launch.
-static const char* bg_linear_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
-                                         const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, int H, int activation) {
-  const bool norm = mean_dev || var_dev;
-  if (layout == BG_ENC_EXTRACTOR) return "layout BG_ENC_EXTRACTOR is not supported (its 416 one-hot columns want an embedding gather): BG_ENC_PRODUCED or BG_ENC_FIXED";
-  if (layout != BG_ENC_PRODUCED && layout != BG_ENC_FIXED) return "layout must be BG_ENC_PRODUCED or BG_ENC_FIXED";
+// packed records -> a network's first layer and its weight / bias gradient: bg_linear_rows (bg_linear.h: the features of bg_encode_rows_ex are built
+// in LDS and consumed by the matrix cores in the same launch) and, at the end of this header, bg_extractor_rows (bg_extractor.h).  The two families make
+// the same checks in the same order; a BgFirstLayer states what differs: the weight's columns, the three refusals that name them or the workspace
+// function, and that function.
+struct BgFirstLayer {
+  int K;
+  const char *bad_weight_stride, *bad_dweight_stride, *bad_workspace;
+  uint64_t (*workspace_bytes)(int64_t m, int H);
+};
+static const BgFirstLayer bg_linear_layer = {BG_LIN_K, "weight_stride_elems must be in [153, 2**24]", "dweight_stride_elems must be >= 153",
+                                             "workspace_dev must be a 16-byte aligned device buffer of bg_linear_rows_workspace_bytes(m, H) bytes",
+                                             bg_linear_rows_workspace_bytes};
+
+// what all four entry points check of the layer's shape, the records and the index
+static const char* bg_first_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int H,
+                                        int activation) {
   if (H < 32 || H > 4096 || H % 32) return "H must be a multiple of 32 in [32, 4096]";
   if (activation != BG_LIN_NONE && activation != BG_LIN_RELU) return "activation must be BG_LIN_NONE or BG_LIN_RELU";
   if (m < 0 || m > (int64_t)BG_LIN_ROWS * 0x7fffffffll) return "m out of range";
@@ -599,33 +608,72 @@ static const char* bg_linear_common_args(const uint8_t* rows_dev, uint64_t row_s
   if (!index_dev && m > store_rows) return "m must be <= store_rows when index_dev is NULL";
   if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) return r;
   if ((uintptr_t)index_dev & 3) return "index_dev must be 4-byte aligned";
+  return nullptr;
+}
+// ... with the layout in front of it and the statistics behind it: the linear calls
+static const char* bg_linear_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
+                                         const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, int H, int activation) {
+  const bool norm = mean_dev || var_dev;
+  if (layout == BG_ENC_EXTRACTOR) return "layout BG_ENC_EXTRACTOR is not supported (its 416 one-hot columns want an embedding gather): BG_ENC_PRODUCED or BG_ENC_FIXED";
+  if (layout != BG_ENC_PRODUCED && layout != BG_ENC_FIXED) return "layout must be BG_ENC_PRODUCED or BG_ENC_FIXED";
+  if (const char* r = bg_first_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation)) return r;
   if (norm && (!mean_dev || !var_dev)) return "mean_dev and var_dev go together: both or neither";
   if (norm && (((uintptr_t)mean_dev | (uintptr_t)var_dev) & 7)) return "mean_dev and var_dev must be 8-byte aligned";
   if (norm && mean_dev == var_dev) return "mean_dev and var_dev must not be the same pointer";
   if (norm && !(epsilon >= 0.0 && epsilon <= 1.7976931348623157e308 && clip_obs >= 0.0 && clip_obs <= 1.7976931348623157e308)) return "epsilon and clip_obs must be finite and >= 0 when statistics are given";
   return nullptr;
 }
+// the forward's weight, bias and out; out must be none of the inputs (mean_dev / var_dev: NULL where the call has no statistics)
+static const char* bg_first_forward_args(const BgFirstLayer& L, const uint8_t* rows_dev, const int32_t* index_dev, const double* mean_dev, const double* var_dev,
+                                         const void* weight_dev, uint64_t weight_stride_elems, const float* bias_dev, int H, int out_dtype, void* out_dev,
+                                         uint64_t out_stride_elems) {
+  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) return "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  if (!weight_dev || ((uintptr_t)weight_dev & 1)) return "weight_dev must be a 2-byte aligned device pointer";
+  if (weight_stride_elems < (uint64_t)L.K || weight_stride_elems > 0x1000000ull) return L.bad_weight_stride;
+  if ((uintptr_t)bias_dev & 3) return "bias_dev must be 4-byte aligned";
+  if (!out_dev || ((uintptr_t)out_dev & (es - 1))) return "out_dev must be a device pointer aligned to its element type";
+  if (out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull) return "out_stride_elems must be >= H";
+  if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev ||
+      out_dev == weight_dev || out_dev == (const void*)bias_dev) return "out_dev must not be the same pointer as an input";
+  return nullptr;
+}
+// the gradient's dout, out, dweight, dbias and workspace, and that no output or workspace is an input or another output
+static const char* bg_first_grad_args(const BgFirstLayer& L, const uint8_t* rows_dev, int64_t m, const void* dout_dev, int dout_dtype, uint64_t dout_stride_elems,
+                                      const void* out_dev, int out_dtype, uint64_t out_stride_elems, int H, int activation, float* dweight_dev,
+                                      uint64_t dweight_stride_elems, float* dbias_dev, void* workspace_dev, uint64_t workspace_bytes) {
+  const uint64_t ds = dout_dtype == BG_ENC_F32 ? 4u : 2u, os = out_dtype == BG_ENC_F32 ? 4u : 2u;
+  const bool relu = activation == BG_LIN_RELU;
+  if (dout_dtype != BG_ENC_F32 && dout_dtype != BG_ENC_BF16) return "dout_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  if (!dout_dev || ((uintptr_t)dout_dev & (ds - 1))) return "dout_dev must be a device pointer aligned to its element type";
+  if (dout_stride_elems < (uint64_t)H || dout_stride_elems > 0xffffffffull) return "dout_stride_elems must be >= H";
+  if (relu != (out_dev != nullptr)) return "out_dev (the forward's output) is required with BG_LIN_RELU and must be NULL without it";
+  if (relu && out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) return "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  if (relu && (((uintptr_t)out_dev & (os - 1)) || out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull)) return "out_dev must be aligned to its element type and out_stride_elems >= H";
+  if (!dweight_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) return "dweight_dev must be a 4-byte aligned device pointer (dbias_dev 4-byte aligned)";
+  if (dweight_stride_elems < (uint64_t)L.K || dweight_stride_elems > 0xffffffffull) return L.bad_dweight_stride;
+  if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < L.workspace_bytes(m, H))) return L.bad_workspace;
+  if ((const void*)dweight_dev == dout_dev || (const void*)dweight_dev == out_dev || (const void*)dweight_dev == (const void*)rows_dev || dweight_dev == dbias_dev ||
+      (void*)dweight_dev == workspace_dev || (dbias_dev && ((void*)dbias_dev == workspace_dev || (const void*)dbias_dev == dout_dev || (const void*)dbias_dev == out_dev)) ||
+      workspace_dev == dout_dev || (workspace_dev && workspace_dev == out_dev)) return "outputs and the workspace must not be the same pointer as an input or as each other";
+  return nullptr;
+}
+// the forward's grid.y: a short call spreads the chunks of H over more workgroups (a function of m and H alone)
+static unsigned bg_first_ysplit(unsigned gx, int H) {
+  const unsigned nchunks = (unsigned)((H + BG_LIN_WCHUNK - 1) / BG_LIN_WCHUNK);
+  unsigned ys = 1;
+  while ((uint64_t)gx * ys < 512u && ys * 2u <= nchunks) ys *= 2u;
+  return ys;
+}
 
 int bg_linear_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
                    const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, const void* weight_dev, uint64_t weight_stride_elems,
                    const float* bias_dev, int H, int activation, int out_dtype, void* out_dev, uint64_t out_stride_elems, float* kernel_ms_out, void* stream) {
-  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
   const char* bad = bg_linear_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, layout, mean_dev, var_dev, epsilon, clip_obs, H, activation);
-  if (bad) {}
-  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (!weight_dev || ((uintptr_t)weight_dev & 1)) bad = "weight_dev must be a 2-byte aligned device pointer";
-  else if (weight_stride_elems < (uint64_t)BG_LIN_K || weight_stride_elems > 0x1000000ull) bad = "weight_stride_elems must be in [153, 2**24]";
-  else if ((uintptr_t)bias_dev & 3) bad = "bias_dev must be 4-byte aligned";
-  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
-  else if (out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= H";
-  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == (const void*)mean_dev || out_dev == (const void*)var_dev ||
-           out_dev == weight_dev || out_dev == (const void*)bias_dev) bad = "out_dev must not be the same pointer as an input";
+  if (!bad) bad = bg_first_forward_args(bg_linear_layer, rows_dev, index_dev, mean_dev, var_dev, weight_dev, weight_stride_elems, bias_dev, H, out_dtype, out_dev, out_stride_elems);
   if (int rc = bg_op_begin("bg_linear_rows: ", bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
-  const unsigned gx = (unsigned)bg_lin_blocks(m);
-  const unsigned nchunks = (unsigned)((H + BG_LIN_WCHUNK - 1) / BG_LIN_WCHUNK);
-  unsigned ys = 1;
-  while ((uint64_t)gx * ys < 512u && ys * 2u <= nchunks) ys *= 2u;   // a short call: the chunks of H over more workgroups (a function of m and H alone)
+  const unsigned gx = (unsigned)bg_lin_blocks(m), ys = bg_first_ysplit(gx, H);
   hipStream_t s = (hipStream_t)stream;
   const int relu = activation == BG_LIN_RELU;
   return bg_op_run(kernel_ms_out, s, [&] {
@@ -635,32 +683,15 @@ int bg_linear_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t s
   });
 }
 
-uint64_t bg_linear_rows_workspace_bytes(int64_t m, int H) {
-  if (m <= 0 || H < 32 || H > 4096 || H % 32) return 0;
-  return (uint64_t)bg_lin_groups(m, H) * BG_LIN_PART_ROWS * (uint64_t)H * sizeof(float);
-}
+uint64_t bg_linear_rows_workspace_bytes(int64_t m, int H) { return bg_lin_workspace_bytes(m, H, 1, BG_LIN_PART_ROWS); }
 
 int bg_linear_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int layout,
                         const double* mean_dev, const double* var_dev, double epsilon, double clip_obs, const void* dout_dev, int dout_dtype,
                         uint64_t dout_stride_elems, const void* out_dev, int out_dtype, uint64_t out_stride_elems, int H, int activation,
                         float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev, void* workspace_dev, uint64_t workspace_bytes,
                         float* kernel_ms_out, void* stream) {
-  const uint64_t ds = dout_dtype == BG_ENC_F32 ? 4u : 2u, os = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const bool relu = activation == BG_LIN_RELU;
   const char* bad = bg_linear_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, layout, mean_dev, var_dev, epsilon, clip_obs, H, activation);
-  if (bad) {}
-  else if (dout_dtype != BG_ENC_F32 && dout_dtype != BG_ENC_BF16) bad = "dout_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (!dout_dev || ((uintptr_t)dout_dev & (ds - 1))) bad = "dout_dev must be a device pointer aligned to its element type";
-  else if (dout_stride_elems < (uint64_t)H || dout_stride_elems > 0xffffffffull) bad = "dout_stride_elems must be >= H";
-  else if (relu != (out_dev != nullptr)) bad = "out_dev (the forward's output) is required with BG_LIN_RELU and must be NULL without it";
-  else if (relu && out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (relu && (((uintptr_t)out_dev & (os - 1)) || out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull)) bad = "out_dev must be aligned to its element type and out_stride_elems >= H";
-  else if (!dweight_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev must be a 4-byte aligned device pointer (dbias_dev 4-byte aligned)";
-  else if (dweight_stride_elems < (uint64_t)BG_LIN_K || dweight_stride_elems > 0xffffffffull) bad = "dweight_stride_elems must be >= 153";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_linear_rows_workspace_bytes(m, H))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_linear_rows_workspace_bytes(m, H) bytes";
-  else if ((const void*)dweight_dev == dout_dev || (const void*)dweight_dev == out_dev || (const void*)dweight_dev == (const void*)rows_dev || dweight_dev == dbias_dev ||
-           (void*)dweight_dev == workspace_dev || (dbias_dev && ((void*)dbias_dev == workspace_dev || (const void*)dbias_dev == dout_dev || (const void*)dbias_dev == out_dev)) ||
-           workspace_dev == dout_dev || (workspace_dev && workspace_dev == out_dev)) bad = "outputs and the workspace must not be the same pointer as an input or as each other";
+  if (!bad) bad = bg_first_grad_args(bg_linear_layer, rows_dev, m, dout_dev, dout_dtype, dout_stride_elems, out_dev, out_dtype, out_stride_elems, H, activation, dweight_dev, dweight_stride_elems, dbias_dev, workspace_dev, workspace_bytes);
   if (int rc = bg_op_begin("bg_linear_rows_grad: ", bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
   const long long per = bg_lin_blocks_per_group(m, H), groups = bg_lin_groups(m, H);
@@ -762,39 +793,18 @@ int bg_sim_score_batch(const int32_t* cases_dev, int64_t* out_dev, int m, void* 
 extern "C++" {
 #include "bg_extractor.h"
 }
-static const char* bg_extractor_common_args(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, int H,
-                                            int activation) {
-  if (H < 32 || H > 4096 || H % 32) return "H must be a multiple of 32 in [32, 4096]";
-  if (activation != BG_LIN_NONE && activation != BG_LIN_RELU) return "activation must be BG_LIN_NONE or BG_LIN_RELU";
-  if (m < 0 || m > (int64_t)BG_LIN_ROWS * 0x7fffffffll) return "m out of range";
-  if (store_rows < 0) return "store_rows must be >= 0";
-  if (index_dev && store_rows > 0x7fffffffll) return "store_rows must be in [0, 2**31) when index_dev is given";
-  if (!index_dev && m > store_rows) return "m must be <= store_rows when index_dev is NULL";
-  if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) return r;
-  if ((uintptr_t)index_dev & 3) return "index_dev must be 4-byte aligned";
-  return nullptr;
-}
+static const BgFirstLayer bg_extractor_layer = {BG_EXT_K, "weight_stride_elems must be in [447, 2**24]", "dweight_stride_elems must be >= 447",
+                                                "workspace_dev must be a 16-byte aligned device buffer of bg_extractor_rows_workspace_bytes(m, H) bytes",
+                                                bg_extractor_rows_workspace_bytes};
 
 int bg_extractor_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int64_t store_rows, const int32_t* index_dev, int64_t m, const void* weight_dev,
                       uint64_t weight_stride_elems, const float* bias_dev, int H, int activation, int out_dtype, void* out_dev, uint64_t out_stride_elems,
                       float* kernel_ms_out, void* stream) {
-  const uint64_t es = out_dtype == BG_ENC_F32 ? 4u : 2u;
-  const char* bad = bg_extractor_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation);
-  if (bad) {}
-  else if (out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (!weight_dev || ((uintptr_t)weight_dev & 1)) bad = "weight_dev must be a 2-byte aligned device pointer";
-  else if (weight_stride_elems < (uint64_t)BG_EXT_K || weight_stride_elems > 0x1000000ull) bad = "weight_stride_elems must be in [447, 2**24]";
-  else if ((uintptr_t)bias_dev & 3) bad = "bias_dev must be 4-byte aligned";
-  else if (!out_dev || ((uintptr_t)out_dev & (es - 1))) bad = "out_dev must be a device pointer aligned to its element type";
-  else if (out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull) bad = "out_stride_elems must be >= H";
-  else if (out_dev == (const void*)rows_dev || out_dev == (const void*)index_dev || out_dev == weight_dev || out_dev == (const void*)bias_dev)
-    bad = "out_dev must not be the same pointer as an input";
+  const char* bad = bg_first_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation);
+  if (!bad) bad = bg_first_forward_args(bg_extractor_layer, rows_dev, index_dev, nullptr, nullptr, weight_dev, weight_stride_elems, bias_dev, H, out_dtype, out_dev, out_stride_elems);
   if (int rc = bg_op_begin("bg_extractor_rows: ", bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
-  const unsigned gx = (unsigned)bg_lin_blocks(m);
-  const unsigned nchunks = (unsigned)((H + BG_LIN_WCHUNK - 1) / BG_LIN_WCHUNK);
-  unsigned ys = 1;
-  while ((uint64_t)gx * ys < 512u && ys * 2u <= nchunks) ys *= 2u;   // a short call: the chunks of H over more workgroups (a function of m and H alone)
+  const unsigned gx = (unsigned)bg_lin_blocks(m), ys = bg_first_ysplit(gx, H);
   hipStream_t s = (hipStream_t)stream;
   const int relu = activation == BG_LIN_RELU;
   return bg_op_run(kernel_ms_out, s, [&] {
@@ -811,22 +821,9 @@ int bg_extractor_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, i
                            int dout_dtype, uint64_t dout_stride_elems, const void* out_dev, int out_dtype, uint64_t out_stride_elems, int H, int activation,
                            float* dweight_dev, uint64_t dweight_stride_elems, float* dbias_dev, void* workspace_dev, uint64_t workspace_bytes,
                            float* kernel_ms_out, void* stream) {
-  const uint64_t ds = dout_dtype == BG_ENC_F32 ? 4u : 2u, os = out_dtype == BG_ENC_F32 ? 4u : 2u;
   const bool relu = activation == BG_LIN_RELU;
-  const char* bad = bg_extractor_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation);
-  if (bad) {}
-  else if (dout_dtype != BG_ENC_F32 && dout_dtype != BG_ENC_BF16) bad = "dout_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (!dout_dev || ((uintptr_t)dout_dev & (ds - 1))) bad = "dout_dev must be a device pointer aligned to its element type";
-  else if (dout_stride_elems < (uint64_t)H || dout_stride_elems > 0xffffffffull) bad = "dout_stride_elems must be >= H";
-  else if (relu != (out_dev != nullptr)) bad = "out_dev (the forward's output) is required with BG_LIN_RELU and must be NULL without it";
-  else if (relu && out_dtype != BG_ENC_F32 && out_dtype != BG_ENC_BF16) bad = "out_dtype must be BG_ENC_F32 or BG_ENC_BF16";
-  else if (relu && (((uintptr_t)out_dev & (os - 1)) || out_stride_elems < (uint64_t)H || out_stride_elems > 0xffffffffull)) bad = "out_dev must be aligned to its element type and out_stride_elems >= H";
-  else if (!dweight_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev must be a 4-byte aligned device pointer (dbias_dev 4-byte aligned)";
-  else if (dweight_stride_elems < (uint64_t)BG_EXT_K || dweight_stride_elems > 0xffffffffull) bad = "dweight_stride_elems must be >= 447";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_ext_workspace_bytes(m, H))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_extractor_rows_workspace_bytes(m, H) bytes";
-  else if ((const void*)dweight_dev == dout_dev || (const void*)dweight_dev == out_dev || (const void*)dweight_dev == (const void*)rows_dev || dweight_dev == dbias_dev ||
-           (void*)dweight_dev == workspace_dev || (dbias_dev && ((void*)dbias_dev == workspace_dev || (const void*)dbias_dev == dout_dev || (const void*)dbias_dev == out_dev)) ||
-           workspace_dev == dout_dev || (workspace_dev && workspace_dev == out_dev)) bad = "outputs and the workspace must not be the same pointer as an input or as each other";
+  const char* bad = bg_first_common_args(rows_dev, row_stride_bytes, store_rows, index_dev, m, H, activation);
+  if (!bad) bad = bg_first_grad_args(bg_extractor_layer, rows_dev, m, dout_dev, dout_dtype, dout_stride_elems, out_dev, out_dtype, out_stride_elems, H, activation, dweight_dev, dweight_stride_elems, dbias_dev, workspace_dev, workspace_bytes);
   if (int rc = bg_op_begin("bg_extractor_rows_grad: ", bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
   const long long per = bg_ext_blocks_per_group(m, H), groups = bg_ext_groups(m, H);

@@ -158,10 +158,9 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
     return _native_call(name, rows.device, args, out[..., :D], timing, empty=m == 0)   # (empty: an empty tensor has no pointer to hand over)
 
 
-def _linear_common(rows, index, norm, layout, activation):
-    """The arguments linear_rows and its gradient share -> (stride, store_rows, m).  Every refusal is a ValueError before the library is loaded."""
-    if layout not in ("produced", "fixed"):
-        raise ValueError(f"layout must be 'produced' or 'fixed' (got {layout!r}): the extractor's one-hot columns want an embedding gather, not this layer")
+# ---------------------------------------------------------------------- the first layers: linear_rows and extractor_rows
+def _first_layer_common(rows, index, activation):
+    """The arguments every first-layer call shares -> (stride, store_rows, m).  Every refusal is a ValueError before the library is loaded."""
     if activation not in nat.LIN_ACTIVATIONS:
         raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
     lead, stride = _check_records(rows)
@@ -172,9 +171,26 @@ def _linear_common(rows, index, norm, layout, activation):
         if store_rows >= 2 ** 31:
             raise ValueError("the stored records hold at most 2**31 - 1 rows")
         m = int(index.shape[0])
+    return stride, store_rows, m
+
+
+def _linear_common(rows, index, norm, layout, activation):
+    """`_first_layer_common` with linear_rows' layout in front of it and its norm behind it."""
+    if layout not in ("produced", "fixed"):
+        raise ValueError(f"layout must be 'produced' or 'fixed' (got {layout!r}): the extractor's one-hot columns want an embedding gather, not this layer")
+    shape = _first_layer_common(rows, index, activation)
     if norm is not None:
         _check_norm(norm, rows, layout, "call without norm")
-    return stride, store_rows, m
+    return shape
+
+
+def _check_width(H: int, what: str = "the layer's width") -> None:
+    if H < 32 or H > 4096 or H % 32:
+        raise ValueError(f"{what} must be a multiple of 32 in [32, 4096] (got {H})")
+
+
+def _dtype_code(dtype: torch.dtype) -> int:
+    return nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16
 
 
 def _linear_matrix(name: str, t, dtypes: tuple, m: int, H: int, device: torch.device) -> int:
@@ -185,13 +201,108 @@ def _linear_matrix(name: str, t, dtypes: tuple, m: int, H: int, device: torch.de
     return int(t.stride(0)) if m > 1 else int(t.shape[1])
 
 
+def _check_vector(name: str, t, H: int, device: torch.device) -> None:
+    """bias / dbias: a contiguous float32 [H] on the rows' device."""
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != (H,) or not t.is_contiguous() or t.device != device:
+        raise ValueError(f"{name} must be a contiguous torch.float32 tensor [{H}] on {device}")
+
+
+def _forward_out(rows, weight, bias, H: int, dtype, out, m: int) -> tuple:
+    """What a forward checks behind its weight -- the weight's device, bias, dtype, out -- and, behind the device check, the allocation -> (out, its pitch)."""
+    if weight.device != rows.device:
+        raise ValueError(f"weight must be on {rows.device}")
+    if bias is not None:
+        _check_vector("bias", bias, H, rows.device)
+    if dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+    pitch = _linear_matrix("out", out, (dtype,), m, H, rows.device) if out is not None else H
+    _check_device(rows)
+    if out is None:
+        out = torch.empty((m, H), dtype=dtype, device=rows.device)
+    return out, pitch
+
+
+def _grad_matrices(rows, dout, out, dweight, activation, m: int) -> tuple:
+    """What a gradient checks in front of its dweight: dout, the width, out against the activation -> (H, dout's pitch, relu, out's pitch)."""
+    if not isinstance(dout, torch.Tensor) or dout.dim() != 2:
+        raise ValueError("dout must be a float32 / bfloat16 tensor [m, H]")
+    H = int(dweight.shape[0]) if isinstance(dweight, torch.Tensor) and dweight.dim() == 2 else int(dout.shape[1])
+    _check_width(H)
+    dpitch = _linear_matrix("dout", dout, (torch.float32, torch.bfloat16), m, H, rows.device)
+    relu = activation == "relu"
+    if relu != (out is not None):
+        raise ValueError("out (the forward's output) is required with activation='relu' and must be None without it")
+    opitch = _linear_matrix("out", out, (torch.float32, torch.bfloat16), m, H, rows.device) if relu else 0
+    return H, dpitch, relu, opitch
+
+
+def _grad_call(name: str, rows, head: tuple, m: int, K: int, dout, dpitch: int, out, opitch: int, H: int, activation, dweight, dbias, workspace, timing: bool):
+    """A gradient behind its checks: an empty call zeroes what it would have written; otherwise the workspace (made here unless the caller gave one) and
+    the call `name(*head, dout .. workspace)`.  Returns (dweight, dbias), with timing the kernel milliseconds behind them."""
+    if m == 0:
+        dweight[:, :K] = 0.0
+        if dbias is not None:
+            dbias.zero_()
+        return _native_call(name, rows.device, (), (dweight, dbias), timing, empty=True)
+    need = int(getattr(nat.load(), name.replace("_grad", "_workspace_bytes"))(C.c_int64(m), H))
+    if workspace is None:
+        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
+    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != rows.device or not workspace.is_contiguous() \
+            or workspace.numel() < need:
+        raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {rows.device}")
+    args = head + (_ptr(dout), _dtype_code(dout.dtype), C.c_uint64(dpitch), _ptr(out), _dtype_code(out.dtype) if out is not None else 0, C.c_uint64(opitch), H,
+                   nat.LIN_ACTIVATIONS[activation], _ptr(dweight), C.c_uint64(int(dweight.stride(0))), _ptr(dbias), _ptr(workspace), C.c_uint64(workspace.numel()))
+    return _native_call(name, rows.device, args, (dweight, dbias), timing)
+
+
+def _grad_as_dout(grad: torch.Tensor) -> torch.Tensor:
+    """autograd's gradient as a gradient call takes dout: as it is when it is a float32 / bfloat16 matrix with a contiguous last dimension, else a copy."""
+    if grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.stride(1) == 1 and (grad.shape[0] <= 1 or grad.stride(0) >= grad.shape[1]):
+        return grad
+    return grad.to(torch.float32).contiguous()
+
+
+class _RowFirstLayer(torch.nn.Module):
+    """What RowLinear and RowExtractor share: the constructor's checks, float32 parameters initialised as nn.Linear(in_features, out_features), and the
+    copies to and from an nn.Linear."""
+
+    def __init__(self, in_features: int, out_features: int, activation: Optional[str], dtype: torch.dtype, device):
+        super().__init__()
+        if activation not in nat.LIN_ACTIVATIONS:
+            raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        out_features = int(out_features)
+        _check_width(out_features, "out_features")
+        self.in_features, self.out_features, self.activation, self.dtype = in_features, out_features, activation, dtype
+        lin = torch.nn.Linear(in_features, out_features, device=device)   # nn.Linear's own initialisation
+        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
+        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+
+    def _load(self, linear: torch.nn.Linear):
+        with torch.no_grad():
+            self.weight.copy_(linear.weight)
+            self.bias.copy_(linear.bias)
+        return self
+
+    def to_linear(self) -> torch.nn.Linear:
+        lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
+        with torch.no_grad():
+            lin.weight.copy_(self.weight)
+            lin.bias.copy_(self.bias)
+        return lin
+
+    def _check_same_gpu(self, rows: torch.Tensor) -> None:
+        if not rows.is_cuda or self.weight.device != rows.device:
+            raise ValueError("rows and the layer must be on the same GPU (there is no CPU fallback)")
+
+
 def _linear_weight(weight) -> int:
     if not isinstance(weight, torch.Tensor) or weight.dtype != torch.bfloat16 or weight.dim() != 2 or weight.shape[1] not in (nat.LIN_K, nat.ENC_COLS[nat.ENC_FIXED]) \
             or not weight.is_contiguous():
         raise ValueError("weight must be a contiguous torch.bfloat16 tensor [H, 153] or [H, 628] (nn.Linear.weight's orientation)")
     H = int(weight.shape[0])
-    if H < 32 or H > 4096 or H % 32:
-        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
+    _check_width(H)
     return H
 
 
@@ -207,20 +318,9 @@ def linear_rows(rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     Returns the [m, H] matrix (m = all records flattened, or len(index)); timing=True returns (matrix, kernel milliseconds).  There is no CPU path."""
     stride, store_rows, m = _linear_common(rows, index, norm, layout, activation)
     H = _linear_weight(weight)
-    if weight.device != rows.device:
-        raise ValueError(f"weight must be on {rows.device}")
-    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (H,) or not bias.is_contiguous()
-                             or bias.device != rows.device):
-        raise ValueError(f"bias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-    pitch = _linear_matrix("out", out, (dtype,), m, H, rows.device) if out is not None else H
-    _check_device(rows)
-    if out is None:
-        out = torch.empty((m, H), dtype=dtype, device=rows.device)
+    out, pitch = _forward_out(rows, weight, bias, H, dtype, out, m)
     args = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), nat.ENC_LAYOUTS[layout], *_norm_args(norm), _ptr(weight),
-            C.c_uint64(int(weight.shape[1])), _ptr(bias), H, nat.LIN_ACTIVATIONS[activation], nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16,
-            _ptr(out), C.c_uint64(pitch))
+            C.c_uint64(int(weight.shape[1])), _ptr(bias), H, nat.LIN_ACTIVATIONS[activation], _dtype_code(dtype), _ptr(out), C.c_uint64(pitch))
     return _native_call("bg_linear_rows", rows.device, args, out[:, :H], timing, empty=m == 0)
 
 
@@ -233,16 +333,7 @@ def linear_rows_grad(rows: torch.Tensor, dout: torch.Tensor, *, out: Optional[to
     or [H, 153] ("produced") is made, so the columns beyond 153 carry their exact gradient, zero.  Returns (dweight, dbias or None) -- with timing=True
     (dweight, dbias, kernel milliseconds).  Sums over rows are deterministic (no atomics)."""
     stride, store_rows, m = _linear_common(rows, index, norm, layout, activation)
-    if not isinstance(dout, torch.Tensor) or dout.dim() != 2:
-        raise ValueError("dout must be a float32 / bfloat16 tensor [m, H]")
-    H = int(dweight.shape[0]) if isinstance(dweight, torch.Tensor) and dweight.dim() == 2 else int(dout.shape[1])
-    if H < 32 or H > 4096 or H % 32:
-        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
-    dpitch = _linear_matrix("dout", dout, (torch.float32, torch.bfloat16), m, H, rows.device)
-    relu = activation == "relu"
-    if relu != (out is not None):
-        raise ValueError("out (the forward's output) is required with activation='relu' and must be None without it")
-    opitch = _linear_matrix("out", out, (torch.float32, torch.bfloat16), m, H, rows.device) if relu else 0
+    H, dpitch, _, opitch = _grad_matrices(rows, dout, out, dweight, activation, m)
     if dweight is not None and (not isinstance(dweight, torch.Tensor) or dweight.dtype != torch.float32 or dweight.dim() != 2 or dweight.shape[1] < nat.LIN_K
                                 or not dweight.is_contiguous() or dweight.device != rows.device):
         raise ValueError(f"dweight must be a contiguous torch.float32 tensor [H, >= {nat.LIN_K}] on {rows.device}")
@@ -250,20 +341,8 @@ def linear_rows_grad(rows: torch.Tensor, dout: torch.Tensor, *, out: Optional[to
     if dweight is None:
         dweight = torch.zeros((H, nat.ENC_COLS[nat.ENC_LAYOUTS[layout]]), dtype=torch.float32, device=rows.device)
     dbias = torch.zeros(H, dtype=torch.float32, device=rows.device) if bias else None
-    if m == 0:
-        dweight[:, :nat.LIN_K] = 0.0
-        return _native_call("bg_linear_rows_grad", rows.device, (), (dweight, dbias), timing, empty=True)
-    need = int(nat.load().bg_linear_rows_workspace_bytes(C.c_int64(m), H))
-    if workspace is None:
-        workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
-    elif not isinstance(workspace, torch.Tensor) or workspace.dtype != torch.uint8 or workspace.device != rows.device or not workspace.is_contiguous() \
-            or workspace.numel() < need:
-        raise ValueError(f"workspace must be a contiguous uint8 tensor of >= {need} bytes on {rows.device}")
-    args = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), nat.ENC_LAYOUTS[layout], *_norm_args(norm), _ptr(dout),
-            nat.ENC_F32 if dout.dtype == torch.float32 else nat.ENC_BF16, C.c_uint64(dpitch), _ptr(out),
-            (nat.ENC_F32 if out.dtype == torch.float32 else nat.ENC_BF16) if relu else 0, C.c_uint64(opitch), H, nat.LIN_ACTIVATIONS[activation],
-            _ptr(dweight), C.c_uint64(int(dweight.shape[1])), _ptr(dbias), _ptr(workspace), C.c_uint64(workspace.numel()))
-    return _native_call("bg_linear_rows_grad", rows.device, args, (dweight, dbias), timing)
+    head = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), nat.ENC_LAYOUTS[layout], *_norm_args(norm))
+    return _grad_call("bg_linear_rows_grad", rows, head, m, nat.LIN_K, dout, dpitch, out, opitch, H, activation, dweight, dbias, workspace, timing)
 
 
 class _RowLinearFn(torch.autograd.Function):
@@ -281,15 +360,13 @@ class _RowLinearFn(torch.autograd.Function):
     def backward(ctx, grad):
         rows, index, norm, layout, activation, wshape, has_bias = ctx.call
         out, = ctx.saved_tensors
-        dout = grad if grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.stride(1) == 1 and (grad.shape[0] <= 1 or grad.stride(0) >= grad.shape[1]) \
-            else grad.to(torch.float32).contiguous()
         dweight = torch.zeros(wshape, dtype=torch.float32, device=rows.device)   # columns at or beyond 153: zero, their exact gradient
-        dweight, dbias = linear_rows_grad(rows, dout, out=out if activation == "relu" else None, index=index, norm=norm, layout=layout, activation=activation,
-                                          dweight=dweight, bias=has_bias)
+        dweight, dbias = linear_rows_grad(rows, _grad_as_dout(grad), out=out if activation == "relu" else None, index=index, norm=norm, layout=layout,
+                                          activation=activation, dweight=dweight, bias=has_bias)
         return dweight, dbias, None, None, None, None, None, None
 
 
-class RowLinear(torch.nn.Module):
+class RowLinear(_RowFirstLayer):
     """The first `nn.Linear` of a policy over packed records: `forward(rows)` is `linear_rows` and its backward one `linear_rows_grad` call, so neither pass
     materialises the feature matrix.  Parameters are float32 -- weight [out_features, 628] ("fixed": SB3's MultiInputPolicy over BalatroEnvFixed) or
     [out_features, 153] ("produced"), bias [out_features] -- initialised as nn.Linear; `from_linear` / `to_linear` move them to and from an nn.Linear, so a
@@ -297,62 +374,24 @@ class RowLinear(torch.nn.Module):
     beyond 153 of a 628-wide weight get a zero gradient, which is their exact gradient: their inputs are zero."""
 
     def __init__(self, out_features: int, in_layout: str = "fixed", activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16, device=None):
-        super().__init__()
         if in_layout not in ("produced", "fixed"):
             raise ValueError(f"in_layout must be 'produced' or 'fixed' (got {in_layout!r})")
-        if activation not in nat.LIN_ACTIVATIONS:
-            raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-        out_features = int(out_features)
-        if out_features < 32 or out_features > 4096 or out_features % 32:
-            raise ValueError(f"out_features must be a multiple of 32 in [32, 4096] (got {out_features})")
-        self.out_features, self.in_layout, self.activation, self.dtype = out_features, in_layout, activation, dtype
-        self.in_features = nat.ENC_COLS[nat.ENC_LAYOUTS[in_layout]]
-        lin = torch.nn.Linear(self.in_features, out_features, device=device)   # nn.Linear's own initialisation
-        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
-        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+        super().__init__(nat.ENC_COLS[nat.ENC_LAYOUTS[in_layout]], out_features, activation, dtype, device)
+        self.in_layout = in_layout
 
     @classmethod
     def from_linear(cls, linear: torch.nn.Linear, activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16) -> "RowLinear":
         if not isinstance(linear, torch.nn.Linear) or linear.in_features not in (nat.LIN_K, nat.ENC_COLS[nat.ENC_FIXED]) or linear.bias is None:
             raise ValueError("from_linear takes an nn.Linear with bias and 153 ('produced') or 628 ('fixed') inputs")
-        layer = cls(linear.out_features, "produced" if linear.in_features == nat.LIN_K else "fixed", activation, dtype, device=linear.weight.device)
-        with torch.no_grad():
-            layer.weight.copy_(linear.weight)
-            layer.bias.copy_(linear.bias)
-        return layer
-
-    def to_linear(self) -> torch.nn.Linear:
-        lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
-        with torch.no_grad():
-            lin.weight.copy_(self.weight)
-            lin.bias.copy_(self.bias)
-        return lin
+        return cls(linear.out_features, "produced" if linear.in_features == nat.LIN_K else "fixed", activation, dtype, device=linear.weight.device)._load(linear)
 
     def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None) -> torch.Tensor:
         _linear_common(rows, index, norm, self.in_layout, self.activation)
-        if not rows.is_cuda or self.weight.device != rows.device:
-            raise ValueError("rows and the layer must be on the same GPU (there is no CPU fallback)")
+        self._check_same_gpu(rows)
         return _RowLinearFn.apply(self.weight, self.bias, rows, index, norm, self.in_layout, self.activation, self.dtype)
 
     def extra_repr(self) -> str:
         return f"in_layout={self.in_layout!r}, out_features={self.out_features}, activation={self.activation!r}, dtype={self.dtype}"
-
-
-def _extractor_common(rows, index, activation):
-    """The arguments extractor_rows and its gradient share -> (stride, store_rows, m).  Every refusal is a ValueError before the library is loaded."""
-    if activation not in nat.LIN_ACTIVATIONS:
-        raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
-    lead, stride = _check_records(rows)
-    store_rows = int(np.prod(lead, dtype=np.int64))
-    m = store_rows
-    if index is not None:
-        _check_index(index, None, rows.device)
-        if store_rows >= 2 ** 31:
-            raise ValueError("the stored records hold at most 2**31 - 1 rows")
-        m = int(index.shape[0])
-    return stride, store_rows, m
 
 
 def _extractor_weight(weight) -> tuple:
@@ -361,8 +400,7 @@ def _extractor_weight(weight) -> tuple:
             or (weight.shape[0] > 1 and weight.stride(0) < nat.EXT_K):
         raise ValueError(f"weight must be a torch.bfloat16 tensor [H, {nat.EXT_K}] with a contiguous last dimension (nn.Linear.weight's orientation)")
     H = int(weight.shape[0])
-    if H < 32 or H > 4096 or H % 32:
-        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
+    _check_width(H)
     return H, int(weight.stride(0))
 
 
@@ -377,21 +415,11 @@ def extractor_rows(rows: torch.Tensor, weight: torch.Tensor, bias: Optional[torc
     are left untouched.  Returns the [m, H] matrix; timing=True returns (matrix, kernel milliseconds).  There is no CPU path.
     The reference's constructor declares `joker_dim = 160` and `game_state_dim = 32`, but its `forward` builds 10 and 21 columns, so that class raises a
     shape error on its first batch as written.  The "extractor" layout, and therefore this layer, follow `forward`: 416 + 10 + 21 = 447."""
-    stride, store_rows, m = _extractor_common(rows, index, activation)
+    stride, store_rows, m = _first_layer_common(rows, index, activation)
     H, wpitch = _extractor_weight(weight)
-    if weight.device != rows.device:
-        raise ValueError(f"weight must be on {rows.device}")
-    if bias is not None and (not isinstance(bias, torch.Tensor) or bias.dtype != torch.float32 or tuple(bias.shape) != (H,) or not bias.is_contiguous()
-                             or bias.device != rows.device):
-        raise ValueError(f"bias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
-    if dtype not in (torch.float32, torch.bfloat16):
-        raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-    pitch = _linear_matrix("out", out, (dtype,), m, H, rows.device) if out is not None else H
-    _check_device(rows)
-    if out is None:
-        out = torch.empty((m, H), dtype=dtype, device=rows.device)
+    out, pitch = _forward_out(rows, weight, bias, H, dtype, out, m)
     args = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), _ptr(weight), C.c_uint64(wpitch), _ptr(bias), H,
-            nat.LIN_ACTIVATIONS[activation], nat.ENC_F32 if dtype == torch.float32 else nat.ENC_BF16, _ptr(out), C.c_uint64(pitch))
+            nat.LIN_ACTIVATIONS[activation], _dtype_code(dtype), _ptr(out), C.c_uint64(pitch))
     return _native_call("bg_extractor_rows", rows.device, args, out[:, :H], timing, empty=m == 0)
 
 
@@ -402,39 +430,20 @@ def extractor_rows_grad(rows: torch.Tensor, dout: torch.Tensor, *, out: Optional
     bfloat16 [m, >= H].  dweight: optional float32 [H, >= 447] with a contiguous last dimension (columns at or beyond 447 are not written); dbias: optional
     contiguous float32 [H]; without them new tensors are made.  Returns (dweight, dbias) -- with timing=True (dweight, dbias, kernel milliseconds).
     Sums over rows are deterministic (no atomics)."""
-    stride, store_rows, m = _extractor_common(rows, index, activation)
-    if not isinstance(dout, torch.Tensor) or dout.dim() != 2:
-        raise ValueError("dout must be a float32 / bfloat16 tensor [m, H]")
-    H = int(dweight.shape[0]) if isinstance(dweight, torch.Tensor) and dweight.dim() == 2 else int(dout.shape[1])
-    if H < 32 or H > 4096 or H % 32:
-        raise ValueError(f"the layer's width must be a multiple of 32 in [32, 4096] (got {H})")
-    dpitch = _linear_matrix("dout", dout, (torch.float32, torch.bfloat16), m, H, rows.device)
-    relu = activation == "relu"
-    if relu != (out is not None):
-        raise ValueError("out (the forward's output) is required with activation='relu' and must be None without it")
-    opitch = _linear_matrix("out", out, (torch.float32, torch.bfloat16), m, H, rows.device) if relu else 0
+    stride, store_rows, m = _first_layer_common(rows, index, activation)
+    H, dpitch, _, opitch = _grad_matrices(rows, dout, out, dweight, activation, m)
     if dweight is not None and (not isinstance(dweight, torch.Tensor) or dweight.dtype != torch.float32 or dweight.dim() != 2 or dweight.shape[1] < nat.EXT_K
                                 or dweight.stride(1) != 1 or dweight.stride(0) < dweight.shape[1] or dweight.device != rows.device):
         raise ValueError(f"dweight must be a torch.float32 tensor [H, >= {nat.EXT_K}] on {rows.device} with a contiguous last dimension")
-    if dbias is not None and (not isinstance(dbias, torch.Tensor) or dbias.dtype != torch.float32 or tuple(dbias.shape) != (H,) or not dbias.is_contiguous()
-                              or dbias.device != rows.device):
-        raise ValueError(f"dbias must be a contiguous torch.float32 tensor [{H}] on {rows.device}")
+    if dbias is not None:
+        _check_vector("dbias", dbias, H, rows.device)
     _check_device(rows)
     if dweight is None:
         dweight = torch.zeros((H, nat.EXT_K), dtype=torch.float32, device=rows.device)
     if dbias is None:
         dbias = torch.zeros(H, dtype=torch.float32, device=rows.device)
-    if m == 0:
-        dweight[:, :nat.EXT_K] = 0.0
-        dbias.zero_()
-        return _native_call("bg_extractor_rows_grad", rows.device, (), (dweight, dbias), timing, empty=True)
-    need = int(nat.load().bg_extractor_rows_workspace_bytes(C.c_int64(m), H))
-    workspace = torch.empty(need, dtype=torch.uint8, device=rows.device)
-    args = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m), _ptr(dout),
-            nat.ENC_F32 if dout.dtype == torch.float32 else nat.ENC_BF16, C.c_uint64(dpitch), _ptr(out),
-            (nat.ENC_F32 if out.dtype == torch.float32 else nat.ENC_BF16) if relu else 0, C.c_uint64(opitch), H, nat.LIN_ACTIVATIONS[activation],
-            _ptr(dweight), C.c_uint64(int(dweight.stride(0))), _ptr(dbias), _ptr(workspace), C.c_uint64(workspace.numel()))
-    return _native_call("bg_extractor_rows_grad", rows.device, args, (dweight, dbias), timing)
+    head = (_ptr(rows), C.c_uint64(stride), C.c_int64(store_rows), _ptr(index), C.c_int64(m))
+    return _grad_call("bg_extractor_rows_grad", rows, head, m, nat.EXT_K, dout, dpitch, out, opitch, H, activation, dweight, dbias, None, timing)
 
 
 class _RowExtractorFn(torch.autograd.Function):
@@ -453,15 +462,13 @@ class _RowExtractorFn(torch.autograd.Function):
     def backward(ctx, grad):
         rows, index, activation, mask = ctx.call
         out, = ctx.saved_tensors
-        dout = grad if grad.dtype in (torch.float32, torch.bfloat16) and grad.dim() == 2 and grad.stride(1) == 1 and (grad.shape[0] <= 1 or grad.stride(0) >= grad.shape[1]) \
-            else grad.to(torch.float32).contiguous()
-        dweight, dbias = extractor_rows_grad(rows, dout, out=out if activation == "relu" else None, index=index, activation=activation)
+        dweight, dbias = extractor_rows_grad(rows, _grad_as_dout(grad), out=out if activation == "relu" else None, index=index, activation=activation)
         if mask is not None:
             dweight.mul_(mask)
         return dweight, dbias, None, None, None, None, None
 
 
-class RowExtractor(torch.nn.Module):
+class RowExtractor(_RowFirstLayer):
     """The first layer of a network over BalatroFeaturesExtractor's input (train_balatro_agent.py:84-119), from packed records: `forward(rows)` is
     `extractor_rows` and its backward one `extractor_rows_grad` call, so neither pass materialises the [m, 447] matrix.  Parameters are float32 --
     weight [out_features, 447], bias [out_features] -- initialised as nn.Linear(447, out_features); `from_linear` / `to_linear` move them to and from an
@@ -474,37 +481,15 @@ class RowExtractor(torch.nn.Module):
     shape error on its first batch as written.  The "extractor" layout, and therefore this layer, follow `forward`: 416 + 10 + 21 = 447."""
 
     def __init__(self, out_features: int, activation: Optional[str] = "relu", dtype: torch.dtype = torch.bfloat16, device=None):
-        super().__init__()
-        if activation not in nat.LIN_ACTIVATIONS:
-            raise ValueError(f"activation must be None or 'relu' (got {activation!r}): tanh stays in torch")
-        if dtype not in (torch.float32, torch.bfloat16):
-            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
-        out_features = int(out_features)
-        if out_features < 32 or out_features > 4096 or out_features % 32:
-            raise ValueError(f"out_features must be a multiple of 32 in [32, 4096] (got {out_features})")
-        self.out_features, self.in_features, self.activation, self.dtype = out_features, nat.EXT_K, activation, dtype
-        self.splits = (out_features,)
-        lin = torch.nn.Linear(self.in_features, out_features, device=device)   # nn.Linear's own initialisation
-        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
-        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+        super().__init__(nat.EXT_K, out_features, activation, dtype, device)
+        self.splits = (self.out_features,)
         self.register_buffer("block_mask", None)
 
     @classmethod
     def from_linear(cls, linear: torch.nn.Linear, activation: Optional[str] = "relu", dtype: torch.dtype = torch.bfloat16) -> "RowExtractor":
         if not isinstance(linear, torch.nn.Linear) or linear.in_features != nat.EXT_K or linear.bias is None:
             raise ValueError(f"from_linear takes an nn.Linear with bias and {nat.EXT_K} inputs")
-        layer = cls(linear.out_features, activation, dtype, device=linear.weight.device)
-        with torch.no_grad():
-            layer.weight.copy_(linear.weight)
-            layer.bias.copy_(linear.bias)
-        return layer
-
-    def to_linear(self) -> torch.nn.Linear:
-        lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
-        with torch.no_grad():
-            lin.weight.copy_(self.weight)
-            lin.bias.copy_(self.bias)
-        return lin
+        return cls(linear.out_features, activation, dtype, device=linear.weight.device)._load(linear)
 
     @classmethod
     def from_linears(cls, hand: torch.nn.Linear, joker: torch.nn.Linear, state: torch.nn.Linear, activation: Optional[str] = "relu",
@@ -544,9 +529,8 @@ class RowExtractor(torch.nn.Module):
         return tuple(out)
 
     def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
-        _extractor_common(rows, index, self.activation)
-        if not rows.is_cuda or self.weight.device != rows.device:
-            raise ValueError("rows and the layer must be on the same GPU (there is no CPU fallback)")
+        _first_layer_common(rows, index, self.activation)
+        self._check_same_gpu(rows)
         return _RowExtractorFn.apply(self.weight, self.bias, rows, index, self.activation, self.dtype, self.block_mask)
 
     def extra_repr(self) -> str:

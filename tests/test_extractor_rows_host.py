@@ -1,24 +1,22 @@
 """bg_extractor_rows / bg_extractor_rows_grad on the CPU (no GPU): the header's declarations and the library's exports; the index functions of
-csrc/bg_extractor.h compiled with g++ under BG_EXT_HOST and driven through a scalar model of v_mfma_f32_32x32x16_bf16 -- written here from the
-documented lane maps, not from the header -- over a one-hot-plus-integer input, in the forward's and in the gradient's orientation; the gradient's split
+csrc/bg_extractor.h compiled with g++ under BG_EXT_HOST and driven through a scalar model of v_mfma_f32_32x32x16_bf16 -- tests/first_layer_helpers.py,
+written from the documented lane maps, not from the header -- over a one-hot-plus-integer input, in the forward's and in the gradient's orientation; the gradient's split
 of rows, units and k against tests/extractor_ref.py; the argument checks of `extractor_rows` / `extractor_rows_grad` / `RowExtractor` on CPU stand-ins;
 `from_linear` / `to_linear` / `from_linears` / `to_linears`."""
 import ctypes as C
 import os
-import re
 import shutil
 import subprocess
 
 import pytest
 
 from tests import extractor_ref as ext
+from tests.first_layer_helpers import MODEL_MFMA, _decl
 from tests.helpers import ROOT
 
 CSRC = os.path.join(ROOT, "balatro_gym_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "balatro_mi355x.h")
 
-# The model: lane l of 64 holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][column l & 31] in element j = 0..7 of its fragments;
-# accumulator register g of lane l is D[row (g & 3) + 8 (g >> 2) + 4 (l >> 5)][column l & 31].
 # The input: hand bytes [128][8] with every kind of byte (cards, -1, 52, 127, -128, the same card twice), 31 dense integer columns.
 _PROGRAM = r"""
 #define BG_EXT_HOST
@@ -27,18 +25,7 @@ _PROGRAM = r"""
 #include <string.h>
 #include <vector>
 #include "bg_extractor.h"
-typedef long long i64;
-static void model_mfma(const i64 a[64][8], const i64 b[64][8], i64 c[64][16]) {
-  i64 A[32][16], B[16][32];
-  for (int l = 0; l < 64; l++)
-    for (int j = 0; j < 8; j++) { A[l & 31][8 * (l >> 5) + j] = a[l][j]; B[8 * (l >> 5) + j][l & 31] = b[l][j]; }
-  for (int l = 0; l < 64; l++)
-    for (int g = 0; g < 16; g++) {
-      const int row = (g & 3) + 8 * (g >> 2) + 4 * (l >> 5), col = l & 31;
-      for (int k = 0; k < 16; k++) c[l][g] += A[row][k] * B[k][col];
-    }
-}
-static i64 one(uint16_t bits) { return bits == 0x3f80 ? 1 : bits == 0 ? 0 : 1000000; }   // bfloat16 1.0 / +0.0 as integers; anything else is loud
+""" + MODEL_MFMA + r"""static i64 one(uint16_t bits) { return bits == 0x3f80 ? 1 : bits == 0 ? 0 : 1000000; }   // bfloat16 1.0 / +0.0 as integers; anything else is loud
 int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "groups")) {
     const i64 m = atoll(argv[2]); const int H = atoi(argv[3]);
@@ -131,12 +118,6 @@ int main(int argc, char** argv) {
   return bad != 0;
 }
 """
-
-
-def _decl(hdr, ret, name):
-    m = re.search(r"\b" + ret + r"\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, f"include/balatro_mi355x.h does not declare {name}"
-    return m, [re.sub(r"/\*.*?\*/", "", p).strip() for p in m.group(1).replace("\n", " ").split(",")]
 
 
 def test_header_declares_and_library_exports():

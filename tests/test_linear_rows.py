@@ -10,41 +10,13 @@ import numpy as np
 import pytest
 
 from tests import encode_ref as ref, linear_ref as lin, norm_ref
+from tests.first_layer_helpers import _bf16, _bits, _dev, _f32_bits, _int_indices, _same
 
 pytestmark = pytest.mark.gpu
 
 K = lin.K
 STRIDE = 384
 SENTINEL = -12288.0   # exact in bfloat16
-
-
-def _dev(a):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(a)).cuda()
-
-
-def _bf16(bits):
-    """bfloat16 bit patterns (uint16) -> a torch.bfloat16 device tensor."""
-    import torch
-    return _dev(np.asarray(bits, np.uint16).view(np.int16)).view(torch.bfloat16)
-
-
-def _bits(t):
-    import torch
-    if t.dtype == torch.float32:
-        return t.contiguous().view(torch.int32).cpu().numpy().view(np.uint32)
-    return t.contiguous().view(torch.int16).cpu().numpy().view(np.uint16)
-
-
-def _f32_bits(a):
-    return np.ascontiguousarray(a, np.float32).view(np.uint32)
-
-
-def _same(got, want, what):
-    got, want = np.asarray(got), np.asarray(want)
-    assert got.shape == want.shape, f"{what}: shape {got.shape} != {want.shape}"
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{what}: {len(bad)} of {want.size} elements differ, first {tuple(bad[0])}: {got[tuple(bad[0])]:#x} != {want[tuple(bad[0])]:#x}"
 
 
 @pytest.fixture(scope="module")
@@ -54,13 +26,6 @@ def ints():
     rng = np.random.default_rng(32)
     return {"rows": _dev(ref.pack_records(obs, STRIDE)), "bits": ref.expected_bits("produced", obs), "w": lin.int_weight(1024, 628),
             "b": rng.integers(-9, 10, 1024).astype(np.float32)}
-
-
-def _int_indices(m, store):
-    rng = np.random.default_rng(m)
-    rep = rng.integers(0, store, m)
-    rep[1::3] = rep[0]   # one record many times
-    return {"none": None, "shuffled": rng.permutation(store)[:m], "repeated": rep}
 
 
 def _forward_exact(ints, m, H, index, relu, cols=K):

@@ -1,6 +1,6 @@
 """bg_linear_rows / bg_linear_rows_grad on the CPU (no GPU): the header's declarations and the library's exports; the fragment index functions of
-csrc/bg_linear.h compiled with g++ under BG_LIN_HOST and driven through a scalar model of v_mfma_f32_32x32x16_bf16 -- written here from the documented lane
-maps, not from the header -- over asymmetric integer matrices, in the forward's and in the gradient's orientation; the gradient's split of the rows
+csrc/bg_linear.h compiled with g++ under BG_LIN_HOST and driven through a scalar model of v_mfma_f32_32x32x16_bf16 -- tests/first_layer_helpers.py, written from the
+documented lane maps, not from the header -- over asymmetric integer matrices, in the forward's and in the gradient's orientation; the gradient's split of the rows
 against tests/linear_ref.py; the argument checks of `linear_rows` / `linear_rows_grad` / `RowLinear` on CPU stand-ins; `from_linear` / `to_linear`."""
 import ctypes as C
 import os
@@ -11,13 +11,12 @@ import subprocess
 import pytest
 
 from tests import linear_ref as lin
+from tests.first_layer_helpers import MODEL_MFMA, _decl
 from tests.helpers import ROOT
 
 CSRC = os.path.join(ROOT, "balatro_gym_amd", "csrc")
 HEADER = os.path.join(ROOT, "include", "balatro_mi355x.h")
 
-# The model: lane l of 64 holds A[row l & 31][k = 8 (l >> 5) + j] and B[k = 8 (l >> 5) + j][column l & 31] in element j = 0..7 of its fragments;
-# accumulator register g of lane l is D[row (g & 3) + 8 (g >> 2) + 4 (l >> 5)][column l & 31].
 _PROGRAM = r"""
 #define BG_LIN_HOST
 #include <stdio.h>
@@ -25,18 +24,7 @@ _PROGRAM = r"""
 #include <string.h>
 #include <vector>
 #include "bg_linear.h"
-typedef long long i64;
-static void model_mfma(const i64 a[64][8], const i64 b[64][8], i64 c[64][16]) {
-  i64 A[32][16], B[16][32];
-  for (int l = 0; l < 64; l++)
-    for (int j = 0; j < 8; j++) { A[l & 31][8 * (l >> 5) + j] = a[l][j]; B[8 * (l >> 5) + j][l & 31] = b[l][j]; }
-  for (int l = 0; l < 64; l++)
-    for (int g = 0; g < 16; g++) {
-      const int row = (g & 3) + 8 * (g >> 2) + 4 * (l >> 5), col = l & 31;
-      for (int k = 0; k < 16; k++) c[l][g] += A[row][k] * B[k][col];
-    }
-}
-int main(int argc, char** argv) {
+""" + MODEL_MFMA + r"""int main(int argc, char** argv) {
   if (argc == 4 && !strcmp(argv[1], "groups")) {
     const i64 m = atoll(argv[2]); const int H = atoi(argv[3]);
     printf("%lld %lld %lld\n", (i64)bg_lin_groups(m, H), (i64)bg_lin_blocks_per_group(m, H), (i64)bg_lin_spans(H));
@@ -99,12 +87,6 @@ int main(int argc, char** argv) {
   return bad != 0;
 }
 """
-
-
-def _decl(hdr, ret, name):
-    m = re.search(r"\b" + ret + r"\s+" + name + r"\s*\(([^;]*)\)\s*;", hdr)
-    assert m, f"include/balatro_mi355x.h does not declare {name}"
-    return m, [re.sub(r"/\*.*?\*/", "", p).strip() for p in m.group(1).replace("\n", " ").split(",")]
 
 
 def test_header_declares_and_library_exports():
