@@ -82,7 +82,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_get_states", "bg_set_states", "bg_copy_states",
            "bg_set_episode_summary", "bg_episode_ends_rows",
            "bg_step_many_rows_progress", "bg_progress_terminal_slots",
-           "bg_dqn_loss", "bg_dqn_loss_workspace_bytes", "bg_sample_actions_eps"]
+           "bg_dqn_loss", "bg_dqn_loss_workspace_bytes", "bg_sample_actions_eps",
+           "bg_episode_outcome_rows", "bg_bc_loss", "bg_bc_loss_workspace_bytes"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -98,6 +99,8 @@ HEAD_F32, HEAD_BF16, HEAD_DETERMINISTIC = 0, 1, 1   # bg_sample_actions / bg_eva
 # bg_ppo_loss: the order of stats_dev (BG_PPO_STATS floats) and its flag
 PPO_STATS = ("loss", "policy_loss", "value_loss", "entropy_loss", "approx_kl", "clip_fraction", "adv_mean", "adv_std", "excluded", "m")
 PPO_NORMALIZE_ADV = 1
+# bg_bc_loss: the order of stats_dev (BG_BC_STATS floats)
+BC_STATS = ("loss", "nll_loss", "entropy_loss", "accuracy", "weight_sum", "excluded", "m")
 # bg_dqn_loss: the order of stats_dev (BG_DQN_STATS floats) and its flags
 DQN_STATS = ("loss", "q_mean", "target_mean", "abs_td_mean", "abs_td_max", "done_share", "excluded", "m")
 DQN_MASK_NEXT, DQN_MSE, DQN_TIMEOUT_EXCLUDE = 1, 2, 4
@@ -310,6 +313,10 @@ def load(build_if_missing: bool = True):
     L.bg_ppo_loss_workspace_bytes.argtypes = [i64]
     L.bg_ppo_loss.argtypes = [vp, i32, u64, vp, u64, vp, vp, vp, vp, vp, vp, i64, i64, C.c_float, C.c_float, C.c_float, u32, vp, u64, vp, vp, vp, vp, vp, u64,
                               C.POINTER(C.c_float), vp]
+    L.bg_episode_outcome_rows.argtypes = [vp, u64, i32, i64, C.c_double, vp, vp, vp, vp, vp, vp, vp, vp, vp, C.POINTER(C.c_float), vp]
+    L.bg_bc_loss_workspace_bytes.restype = u64
+    L.bg_bc_loss_workspace_bytes.argtypes = [i64]
+    L.bg_bc_loss.argtypes = [vp, i32, u64, vp, u64, vp, u64, vp, vp, i64, i64, C.c_float, vp, u64, vp, vp, vp, vp, u64, C.POINTER(C.c_float), vp]
     L.bg_dqn_loss_workspace_bytes.restype = u64
     L.bg_dqn_loss_workspace_bytes.argtypes = [i64]
     L.bg_dqn_loss.argtypes = [vp, u64, vp, u64, vp, u64, i32, vp, u64, i64, vp, vp, i64, C.c_float, u32, vp, u64, vp, vp, vp, u64, C.POINTER(C.c_float), vp]

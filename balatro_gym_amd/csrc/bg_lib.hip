@@ -363,6 +363,8 @@ __device__ void bg_mt_twist(const uint32_t* src, uint32_t* dst) {
 #include "bg_norm.h"   // packed records -> VecNormalize's running statistics, normalised observations and rewards (operator-level)
 #include "bg_head.h"   // logits + action masks -> actions, log-probabilities and entropies (operator-level)
 #include "bg_ppo.h"    // logits + stored rollout arrays -> PPO's clipped loss, its diagnostics and its gradient (operator-level)
+#include "bg_outcome.h" // packed records -> the outcome of every step's own episode: steps to the end, final ante, end flags, return (operator-level)
+#include "bg_bc.h"     // logits + stored actions -> behaviour cloning's weighted cross-entropy, its accuracy and its gradient (operator-level)
 #include "bg_dqn.h"    // Q values + a ring of records -> DQN's TD loss and its gradient; epsilon-greedy in the masked head (operator-level)
 #include "bg_linear.h" // packed records -> the network's first layer and its weight gradient on the matrix cores (operator-level)
 #include "bg_snapshot.h" // many envs' state between a handle's arrays and dense blobs, or two handles (bg_get_states / bg_set_states / bg_copy_states)

@@ -525,6 +525,101 @@ int bg_sample_actions_eps(const void* logits_dev, int logits_dtype, uint64_t log
                       actions_dev, nullptr, nullptr, kernel_ms_out, stream, epsilon);
 }
 
+// packed records -> the outcome of every step's own episode (bg_outcome.h): one scan backwards along K, bg_gae_rows' shape
+int bg_episode_outcome_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double gamma, const double* rewards_dev,
+                            const int32_t* tail_steps_dev, const int32_t* tail_ante_dev, const uint8_t* tail_flags_dev, const double* tail_return_dev,
+                            int32_t* steps_to_end_dev, int32_t* end_ante_dev, uint8_t* end_flags_dev, double* returns_dev, float* kernel_ms_out, void* stream) {
+  const void* const ins[] = {rows_dev, rewards_dev, tail_steps_dev, tail_ante_dev, tail_flags_dev, tail_return_dev};
+  const void* const outs[] = {steps_to_end_dev, end_ante_dev, end_flags_dev, returns_dev};
+  bool alias = false;
+  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
+    if (!outs[o]) continue;
+    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
+    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
+  }
+  const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
+  if (bad) {}
+  else if (!steps_to_end_dev && !end_ante_dev && !end_flags_dev && !returns_dev) bad = "at least one of steps_to_end_dev, end_ante_dev, end_flags_dev and returns_dev must be given";
+  else if ((tail_steps_dev && !steps_to_end_dev) || (tail_ante_dev && !end_ante_dev) || (tail_flags_dev && !end_flags_dev) || (tail_return_dev && !returns_dev)) bad = "a tail needs its output";
+  else if (rewards_dev && !returns_dev) bad = "rewards_dev needs returns_dev (no other output reads a reward)";
+  else if (!(gamma == gamma)) bad = "gamma must not be NaN";
+  else if (((uintptr_t)steps_to_end_dev | (uintptr_t)end_ante_dev | (uintptr_t)tail_steps_dev | (uintptr_t)tail_ante_dev) & 3) bad = "int32 arrays must be 4-byte aligned";
+  else if (((uintptr_t)returns_dev | (uintptr_t)rewards_dev | (uintptr_t)tail_return_dev) & 7) bad = "float64 arrays must be 8-byte aligned";
+  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  if (int rc = bg_op_begin("bg_episode_outcome_rows: ", bad, kernel_ms_out)) return rc;
+  if (K == 0 || N == 0) return 0;
+  const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    bg_bool_dispatch(returns_dev != nullptr, returns_dev != nullptr && rewards_dev != nullptr, [&](auto R, auto W) {
+      hipLaunchKernelGGL((bg_outcome_kernel<R(), R() && W()>), dim3(grid), dim3(BG_GAE_BLOCK), 0, s, rows_dev, row_stride_bytes, K, (long long)N, gamma, rewards_dev,
+                         tail_steps_dev, tail_ante_dev, tail_flags_dev, tail_return_dev, steps_to_end_dev, end_ante_dev, end_flags_dev, returns_dev);
+    });
+  });
+}
+
+// logits + stored actions -> behaviour cloning's weighted cross-entropy, its accuracy and its gradient (bg_bc.h).  Workspace: BG_BC_WS_HEAD bytes
+// (Wf, W), one float64 weight sum per 256 rows, four float64 sums per 64 rows.
+uint64_t bg_bc_loss_workspace_bytes(int64_t m) {
+  if (m <= 0) return 0;
+  return BG_BC_WS_HEAD + bg_ppo_stat_parts(m) * sizeof(double) + bg_ppo_row_parts(m) * (BG_BC_SUMS * sizeof(double));
+}
+
+int bg_bc_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes,
+               const int32_t* actions_dev, uint64_t actions_stride_bytes, const float* weights_dev, const int32_t* index_dev, int64_t store_rows, int64_t m,
+               float ent_coef, void* dlogits_dev, uint64_t dlogits_stride_elems, float* log_prob_dev, float* entropy_dev, float* stats_dev,
+               void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
+  const bool bf16 = logits_dtype == BG_HEAD_BF16;
+  const uint64_t es = bf16 ? 2u : 4u;
+  const void* const ins[] = {logits_dev, mask_dev, actions_dev, weights_dev, index_dev};
+  const void* const outs[] = {dlogits_dev, log_prob_dev, entropy_dev, stats_dev, workspace_dev};
+  bool alias = false;
+  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
+    if (!outs[o]) continue;
+    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
+    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
+  }
+  const char* bad = bg_head_shape_args(logits_dtype, m);
+  if (bad) {}
+  else if (!bg_ppo_finite(ent_coef)) bad = "ent_coef must be finite";
+  else if (const char* r = bg_head_logits_args(logits_dev, es, logits_stride_elems)) bad = r;
+  else if (!dlogits_dev || ((uintptr_t)dlogits_dev & (es - 1))) bad = "dlogits_dev must be a device pointer aligned to its element type";
+  else if (dlogits_stride_elems < BG_HEAD_ACTIONS || dlogits_stride_elems > 0xffffffffull) bad = "dlogits_stride_elems must be >= 60";
+  else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
+  else if (!actions_dev || ((uintptr_t)actions_dev & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
+  else if (actions_stride_bytes < 4 || (actions_stride_bytes & 3) || actions_stride_bytes > 0xffffffffull) bad = "actions_stride_bytes must be a multiple of 4, >= 4";
+  else if (((uintptr_t)weights_dev | (uintptr_t)index_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "weights_dev, index_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
+  else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
+  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_BC_STATS floats";
+  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_bc_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_bc_loss_workspace_bytes(m) bytes";
+  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  if (int rc = bg_op_begin("bg_bc_loss: ", bad, kernel_ms_out)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_BC_STATS * sizeof(float), s)); return 0; }
+  const bool stat = weights_dev || index_dev;
+  BgBcArgs A;
+  A.logits = logits_dev; A.lstride = logits_stride_elems; A.lld = bg_head_ld_path(logits_dev, logits_stride_elems, bf16);
+  A.dst = bg_head_ld_path(dlogits_dev, dlogits_stride_elems, bf16);
+  A.mask = mask_dev; A.mstride = mask_stride_bytes; A.mld = bg_head_mask_path(mask_dev, mask_stride_bytes, !index_dev);
+  A.actions = actions_dev; A.astride = actions_stride_bytes; A.weights = weights_dev;
+  A.index = index_dev; A.store_rows = (long long)store_rows; A.m = (long long)m;
+  A.ent_coef = ent_coef; A.fm = (float)m;
+  A.dlogits = dlogits_dev; A.dstride = dlogits_stride_elems; A.log_prob = log_prob_dev; A.entropy = entropy_dev;
+  float* const head = (float*)workspace_dev;
+  double* const wpart = (double*)((uint8_t*)workspace_dev + BG_BC_WS_HEAD);
+  const uint64_t SP = bg_ppo_stat_parts(m), RP = bg_ppo_row_parts(m);
+  A.head = stat ? head : nullptr; A.partials = wpart + SP;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    if (stat) {
+      hipLaunchKernelGGL(bg_bc_weight_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, weights_dev, index_dev, (long long)store_rows, (long long)m, wpart);
+      hipLaunchKernelGGL(bg_bc_weight_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, wpart, (long long)SP, head);
+    }
+    if (bf16) hipLaunchKernelGGL((bg_bc_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+    else hipLaunchKernelGGL((bg_bc_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+    hipLaunchKernelGGL(bg_bc_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, A.head, stats_dev);
+  });
+}
+
 // Q values + the ring of records -> DQN's TD loss, diagnostics and gradient (bg_dqn.h).  Workspace: seven float64 values per 64 rows.
 uint64_t bg_dqn_loss_workspace_bytes(int64_t m) {
   if (m <= 0) return 0;

@@ -1,5 +1,6 @@
 """The learner's side of the packed-record path: everything that works on records or logits and needs no env -- encode_rows, the linear layer,
-the masked policy head, the PPO and DQN losses, the replay ring, GAE, the episode statistics / limits / endings, the curriculum and VecNormalize.
+the masked policy head, the PPO, DQN and behaviour-cloning losses, the replay ring, GAE, the episode statistics / limits / endings / outcomes, the curriculum
+and VecNormalize.
 
 All of it runs in libbalatro_mi355x.so (hand-written HIP, the stateless entry points of csrc/bg_rows_api.h); torch only owns device buffers and the
 stream.  There is no CPU fallback.  `vec_env` re-imports every public name, so `from balatro_gym_amd.vec_env import X` keeps working.
@@ -788,6 +789,96 @@ def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Te
     return loss, stats
 
 
+class BcStats:
+    """What `bc_loss` returns beside the loss: the scalars of `_native.BC_STATS` as 0-dim float32 device tensors (views of `raw`, no host
+    synchronisation), `log_prob` / `entropy` [...] of the minibatch rows (bit for bit `evaluate_actions`'), and the gradient the call produced --
+    `dlogits` [..., 60] in the dtype of the logits.  `kernel_ms` with timing=True."""
+
+    def __init__(self, raw, log_prob, entropy, dlogits, kernel_ms=None):
+        self.raw, self.log_prob, self.entropy, self.dlogits, self.kernel_ms = raw, log_prob, entropy, dlogits, kernel_ms
+        for k, name in enumerate(nat.BC_STATS):
+            setattr(self, name, raw[k])
+
+    def __repr__(self):
+        return "BcStats(" + ", ".join(nat.BC_STATS) + ", log_prob, entropy, dlogits)"
+
+
+_bc_workspaces: dict = {}
+
+
+def _bc_actions(actions, store: tuple, device: torch.device) -> int:
+    """actions of bc_loss: an int32 tensor of shape `store`, contiguous or a strided view whose elements sit one fixed pitch apart in the order of the
+    flattened shape (`RowBuffers.action`, the action view of `store[1:]`) -> that pitch in bytes."""
+    if not isinstance(actions, torch.Tensor) or actions.dtype != torch.int32 or tuple(actions.shape) != store or actions.device != device:
+        raise ValueError(f"actions must be a torch.int32 tensor of shape {list(store)} on {device}")
+    dims = [d for d in range(actions.dim()) if actions.shape[d] != 1]
+    if not dims or actions.numel() == 0:
+        return 4
+    pitch = int(actions.stride(dims[-1]))
+    even = pitch >= 1
+    for hi, lo in zip(dims[:-1], dims[1:]):
+        even = even and actions.stride(hi) == actions.stride(lo) * actions.shape[lo]
+    if not even:
+        raise ValueError("actions must be contiguous or a view whose elements sit one fixed pitch apart (RowBuffers.action)")
+    return pitch * 4
+
+
+def bc_loss(logits: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None, *, weights: Optional[torch.Tensor] = None,
+            index: Optional[torch.Tensor] = None, ent_coef: float = 0.0, timing: bool = False):
+    """Behaviour cloning over the masked head of `sample_actions` (bg_bc_loss): the weighted cross-entropy of stored actions, its accuracy and its
+    gradient, in one pass over the logits -> (loss, stats).  loss: 0-dim float32; when `logits` require grad it carries an autograd node whose backward
+    is grad_output * stats.dlogits -- `loss.backward()` drives the network's own backward with nothing recomputed.  stats: `BcStats` (loss, nll_loss,
+    entropy_loss, accuracy, weight_sum, excluded, m).  The reference's `BehavioralCloning` (train_balatro_agent.py:220-262) stops at its TODO; this is
+    the loss of that loop.
+    logits float32 / bfloat16 [..., 60]: the network's output for the minibatch.  Without `index`, actions (int32), weights (float32) and the mask
+    (forms of `sample_actions`) have the leading shape of logits.  With `index` (int32 [...]) they are STORED arrays of one common shape, read at row
+    index[i]: the minibatch is gathered inside the launch.  actions may be a strided view -- `RowBuffers.action`, or the action view of `store[1:]`
+    for observations `store[:K]` -- and is then read in place.
+    The alignment: a record holds the observation and mask of one decision and the action of the step that LED to it, so the demonstration of
+    observation record `store[t]` is the action in `store[t + 1]`.  The reference's filter ("only use successful trajectories") is
+    `weights = (outcomes.end_ante[1:] >= 5).float()` with `outcomes = episode_outcomes(store)`: the outcome of the step taken from `store[t]` stands
+    at `t + 1`.
+    loss = sum(w * -log_prob) / W + ent_coef * -sum(w * entropy) / W, W the sum of the weights that are finite and >= 0 (of rows whose index is in
+    range); accuracy = the weighted share of rows whose action is `sample_actions(deterministic=True)`'s.  A row that cannot take part (degenerate
+    mask, masked or out-of-range action, non-finite log-probability, negative or non-finite weight, index out of range) is excluded: zero gradient,
+    counted in stats.excluded.  W == 0 gives loss 0 and a zero gradient."""
+    lead, m, pitch = _head_logits(logits)
+    dev = logits.device
+    if index is not None:
+        _check_index(index, lead, dev)
+        if not isinstance(actions, torch.Tensor):
+            raise ValueError("actions must be an int32 tensor")
+        store = tuple(actions.shape)
+    else:
+        store = lead
+    store_rows = int(np.prod(store, dtype=np.int64))
+    if store_rows >= 2 ** 31:
+        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
+    mask, moff, mstride = _head_mask(mask, store, dev)
+    astride = _bc_actions(actions, store, dev)
+    if weights is not None:
+        _check_scan_tensor("weights", weights, torch.float32, store, dev)
+    if isinstance(ent_coef, bool) or not isinstance(ent_coef, (int, float, np.integer, np.floating)) or not np.isfinite(ent_coef):
+        raise ValueError("ent_coef must be a finite number")
+    _check_device(logits, "logits", align=0)
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+    lg = logits.detach()
+    raw = torch.zeros(len(nat.BC_STATS), dtype=torch.float32, device=dev)
+    dlogits = torch.empty(lead + (60,), dtype=logits.dtype, device=dev)
+    log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
+    entropy = torch.empty(lead, dtype=torch.float32, device=dev)
+    ws = _loss_workspace(_bc_workspaces, "bg_bc_loss_workspace_bytes", dev, m)
+    args = (*_head_args(lg, pitch, mask, moff, mstride), _ptr(actions), C.c_uint64(astride), _ptr(weights), _ptr(index), C.c_int64(store_rows), C.c_int64(m),
+            C.c_float(ent_coef), _ptr(dlogits), C.c_uint64(60), _ptr(log_prob), _ptr(entropy), _ptr(raw), _ptr(ws), C.c_uint64(ws.numel()))
+    kernel_ms = _native_call("bg_bc_loss", dev, args, (), timing, empty=m == 0)   # () or (ms,)
+    stats = BcStats(raw, log_prob, entropy, dlogits, *kernel_ms)
+    loss = raw[0]
+    if torch.is_grad_enabled() and logits.requires_grad:
+        loss = _PpoLossGrad.apply(loss, dlogits, None, logits, None)   # the same node: one multiplication
+    return loss, stats
+
+
 class DqnStats:
     """What `dqn_loss` returns beside the loss: the scalars of `_native.DQN_STATS` as 0-dim float32 device tensors (views of `raw`, no host
     synchronisation), `td` float32 [...] (q[a] - y per row, NaN on an excluded row: for prioritised replay), and the gradient the call produced --
@@ -1015,6 +1106,65 @@ def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor
             _ptr(returns))
     name, args = ("bg_gae_rows", args) if rewards is None else ("bg_gae_rows_ex", args + (_ptr(rewards),))
     return _native_call(name, dev, args, (advantages, returns), timing, empty=K * N == 0)   # (empty: an empty tensor has no pointer to hand over)
+
+
+OUTCOME_FIELDS = {"steps_to_end": torch.int32, "end_ante": torch.int32, "end_flags": torch.uint8, "returns": torch.float64}
+
+
+class EpisodeOutcomes:
+    """What `episode_outcomes` returns: per step of a [K, N] rollout the outcome of the step's OWN episode -- `steps_to_end` int32 (0 on the ending
+    step, -1 in an episode that is still open), `end_ante` int32 (-1 open), `end_flags` uint8 (0 open), `returns` float64 (the discounted reward sum
+    from the step to its episode's end) -- each [K, N], or None where it was not asked for.  `kernel_ms` with timing=True."""
+
+    def __init__(self, steps_to_end=None, end_ante=None, end_flags=None, returns=None, kernel_ms=None):
+        self.steps_to_end, self.end_ante, self.end_flags, self.returns, self.kernel_ms = steps_to_end, end_ante, end_flags, returns, kernel_ms
+
+    def tail(self) -> dict:
+        """Row 0 of every field that was computed: what `episode_outcomes(..., tail=)` of the PRECEDING chunk takes."""
+        return {f: getattr(self, f)[0] for f in OUTCOME_FIELDS if getattr(self, f) is not None}
+
+    def __repr__(self):
+        return "EpisodeOutcomes(" + ", ".join(f for f in OUTCOME_FIELDS if getattr(self, f) is not None) + ")"
+
+
+def episode_outcomes(rows: torch.Tensor, gamma: float = 1.0, *, rewards: Optional[torch.Tensor] = None, tail: Optional[dict] = None,
+                     want=("steps_to_end", "end_ante", "end_flags", "returns"), timing: bool = False) -> EpisodeOutcomes:
+    """Every step of a finished [K, N] rollout of packed records learns the outcome of its own episode, in one launch (bg_episode_outcome_rows): the
+    backward pass along K that `end_ante` -- written only into the record of the ENDING step -- needs before it can filter steps, and the Monte-Carlo
+    return of every step.  Bit for bit the numpy loop: per env, t = K-1 .. 0, a set terminated byte gives (0, the record's end ante, its end flags,
+    r), any other step (next.steps + 1 or -1, next.ante, next.flags, r + gamma * next.ret) in float64.
+    rows: contiguous uint8 device tensor [K, N, stride] (`RowBuffers.rows`, `RowReplay.store`) of `step_many(..., limits=EpisodeLimits(...,
+    summary=True))` (without the summary end_ante is 0, without limits end_flags too).  rewards: float64 [K, N] to take instead of the records'
+    rewards (`normalize_reward`'s output).  want: the fields to compute.  tail: `later.tail()` of the same call on the FOLLOWING chunk (a dict field
+    -> [N] tensor), so a long store is processed in pieces from the back; without it an episode that does not end inside the call is open (-1, -1, 0,
+    the sum so far).
+    The alignment: the step taken from observation record `store[t]` is record `store[t + 1]`, so the reference's behaviour-cloning filter over
+    observations `store[:K]` is `weights = (episode_outcomes(store).end_ante[1:] >= 5).float()` -- see `bc_loss`."""
+    (K, N), stride = _check_records(rows, 3)
+    dev = rows.device
+    want = (want,) if isinstance(want, str) else tuple(want)
+    if not want or any(f not in OUTCOME_FIELDS for f in want) or len(set(want)) != len(want):
+        raise ValueError(f"want must name at least one of {list(OUTCOME_FIELDS)}, each once (got {list(want)})")
+    if rewards is not None:
+        _check_scan_tensor("rewards", rewards, torch.float64, (K, N), dev)
+        if "returns" not in want:
+            raise ValueError("rewards are read only for 'returns': ask for it or leave rewards out")
+    tail = {} if tail is None else tail
+    if not isinstance(tail, dict) or any(f not in OUTCOME_FIELDS for f in tail):
+        raise ValueError(f"tail must be a dict with keys from {list(OUTCOME_FIELDS)} (EpisodeOutcomes.tail())")
+    for f, t in tail.items():
+        if f not in want:
+            raise ValueError(f"tail[{f!r}] without its output: add {f!r} to want")
+        _check_scan_tensor(f"tail[{f!r}]", t, OUTCOME_FIELDS[f], (N,), dev)
+    gamma = float(gamma)
+    if np.isnan(gamma):
+        raise ValueError("gamma must not be NaN")
+    _check_device(rows)
+    outs = {f: torch.empty((K, N), dtype=OUTCOME_FIELDS[f], device=dev) if f in want else None for f in OUTCOME_FIELDS}
+    args = (_ptr(rows), C.c_uint64(stride), K, C.c_int64(N), C.c_double(gamma), _ptr(rewards), *(_ptr(tail.get(f)) for f in OUTCOME_FIELDS),
+            *(_ptr(outs[f]) for f in OUTCOME_FIELDS))
+    kernel_ms = _native_call("bg_episode_outcome_rows", dev, args, (), timing, empty=K * N == 0)   # () or (ms,)
+    return EpisodeOutcomes(**outs, kernel_ms=kernel_ms[0] if kernel_ms else None)
 
 
 class EpisodeStats:

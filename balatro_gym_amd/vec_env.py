@@ -16,8 +16,8 @@ import torch
 
 from . import _native as nat
 # the learner's calls over records and logits live in rows.py; every name that used to be defined here stays importable from here
-from .rows import (DqnStats, EpisodeLimits, EpisodeStats, PpoStats, ProgressionRewards, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
-                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, dqn_loss, encode_rows, episode_ends, evaluate_actions,
+from .rows import (BcStats, DqnStats, EpisodeLimits, EpisodeOutcomes, EpisodeStats, PpoStats, ProgressionRewards, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
+                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, bc_loss, dqn_loss, encode_rows, episode_ends, episode_outcomes, evaluate_actions,
                    extractor_rows, extractor_rows_grad, gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
 
 _TORCH_DT = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
@@ -194,6 +194,13 @@ class RowBuffers:
         """The report of these records' ended episodes, int64 [32] on the device (`episode_ends`); with a `RowCurriculum` its state is advanced and
         its raised caps are set (`RowCurriculum.update`)."""
         return episode_ends(self.rows) if curriculum is None else curriculum.update(self.rows, apply=apply)
+
+    def outcomes(self, gamma: float = 1.0, *, rewards: Optional[torch.Tensor] = None, tail: Optional[dict] = None,
+                 want=("steps_to_end", "end_ante", "end_flags", "returns"), timing: bool = False) -> "EpisodeOutcomes":
+        """The outcome of every step's own episode over these records, [steps, n] per field (`episode_outcomes`: one launch, backwards along the
+        steps): steps to the episode's end, its final ante and end flags, the discounted return.  `(outcomes.end_ante >= 5).float()` is the
+        reference's behaviour-cloning filter as `bc_loss(weights=)` takes it."""
+        return episode_outcomes(self.rows, gamma, rewards=rewards, tail=tail, want=want, timing=timing)
 
     def _view(self, off: int, dt: str, shape) -> torch.Tensor:
         item = np.dtype(dt).itemsize

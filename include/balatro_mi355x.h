@@ -812,6 +812,66 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
                 float* stats_dev /* float32[BG_PPO_STATS = 10] */,
                 void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* Behaviour cloning on records, in two stateless calls on caller-owned buffers.  Replaces: `BehavioralCloning` (train_balatro_agent.py:220-262),
+ * reached through the script's `expert_trajectories=` argument: it keeps only the steps of trajectories with final_ante >= 5 ("only use successful
+ * trajectories") and stops at `# TODO: Implement actual BC training loop`.
+ *
+ * bg_episode_outcome_rows (csrc/bg_outcome.h): ONE launch gives every step of a finished [K, N] rollout the outcome of its OWN episode -- the filter
+ * above, the Monte-Carlo return of a step, and the distance to the episode's end.  Records, K, N, alignment, the current device, BG_E_ARG (text
+ * "bg_episode_outcome_rows: ..." in bg_last_error(NULL)) before anything is launched, K == 0 or N == 0 a no-op and kernel_ms_out: as bg_gae_rows.
+ * Per env e, for t = K-1 down to 0; `next` is the state of step t + 1, or the tail at t = K-1:
+ *     the record's byte BG_ROW_TERMINATED is set:  steps = 0;  ante = the record's int16 BG_ROW_END_ANTE;  flags = its byte BG_ROW_END_FLAGS;  ret = r
+ *     elsewhere:  steps = next.steps < 0 ? -1 : next.steps + 1;  ante = next.ante;  flags = next.flags;  ret = r + gamma * next.ret
+ * r is the record's float64 reward, or rewards_dev[t][e] (dense float64 [K, N], as bg_gae_rows_ex; it needs returns_dev).  ret is float64, the product
+ * and the sum each rounded, nothing fused.  The chain is serial in t per env, so every output is bit for bit that loop in numpy.
+ * Outputs, dense [K, N], each nullable but at least one given: steps_to_end_dev int32, end_ante_dev int32, end_flags_dev uint8, returns_dev float64.
+ * Each has a nullable tail input [N] -- the value BEHIND the last step: row 0 of the same call on the following chunk, so a long store is processed in
+ * pieces from the back; a tail without its output is refused.  The defaults are -1, -1, 0 and 0.0: an episode that does not end inside the call and
+ * has no tail is OPEN -- steps -1, ante -1, flags 0, ret the discounted sum so far.  end_ante is 0 in records written without the episode summary
+ * (bg_set_episode_summary).  An output must not be the same pointer as an input or another output; gamma must not be NaN.
+ *
+ * bg_bc_loss (csrc/bg_bc.h, where every order of evaluation is fixed): the weighted cross-entropy of stored actions under the masked head above, its
+ * accuracy and its gradient with respect to the logits, in one pass over the logits.  Row i reads its logits at i; with index_dev (int32 [m]) the
+ * STORED arrays -- mask, actions, weights -- are read at row src = index[i] of store_rows rows, else at i.  The action is the int32 at actions_dev +
+ * src * actions_stride_bytes (a multiple of 4, >= 4: 4 is a dense array; a record pitch reads BG_ROW_ACTION in place -- the demonstration of
+ * observation record t is the action in record t + 1, so actions_dev = rows_dev + row_stride_bytes * N + BG_ROW_ACTION for a [K + 1, N] store); the
+ * mask as in bg_ppo_loss; weights_dev float32 [store_rows], nullable (w = 1).  m_, d[j], e[j], S, A, logS, H are bg_head_row's: log_prob and entropy
+ * are bit for bit bg_evaluate_actions'.  All arithmetic is float32, every operation rounded on its own; the sums across rows are float64.
+ *     W  = the float64 sum of the weights of all rows whose index is in range and whose weight is finite and >= 0 (m without weights and index);
+ *          Wf = float(W);  W == 0: loss 0 and an all-+0.0 gradient
+ *     nll = 0 - log_prob;  hit = 1 where the first maximum among the valid logits is the action (bg_sample_actions' deterministic rule), else 0
+ *     p = e[j] / S;  valid j with e[j] > 0:  dlogits[i, j] = (((ent_coef * p) * ((d[j] - logS) + H) - (1[j == a] - p)) * w) / Wf
+ *     valid j with e[j] == 0: ((0 - 1) * w) / Wf if j == a, else +0.0;  invalid j: +0.0;  padding columns of a strided dlogits are not written
+ *     nll_loss = sum(w nll) / W;  entropy_loss = -sum(w H) / W;  accuracy = sum(w hit) / W;  loss = nll_loss + ent_coef * entropy_loss
+ *     (float64 from the float64 sums, each scalar rounded to float32 once)
+ * An EXCLUDED row -- degenerate for the head, action outside [0, 60) or masked, log_prob not finite, weight not finite or negative, index outside
+ * [0, store_rows) (nothing is read for it; log_prob = entropy = quiet NaN) -- adds nothing to any sum, has a +0.0 dlogits row and is counted; rows
+ * excluded for another reason than their index or weight stay in W, as m stays PPO's divisor.  The sums take bg_ppo_loss' fixed orders (no floating-
+ * point atomics): two calls give the same bits.  stats_dev, float32 [BG_BC_STATS]: loss, nll_loss, entropy_loss, accuracy, weight_sum, excluded rows,
+ * m.  dlogits_dev has the dtype of the logits and its own row stride (>= 60); log_prob_dev, entropy_dev may be NULL.  workspace_dev: 16-byte aligned,
+ * bg_bc_loss_workspace_bytes(m) bytes.  BG_E_ARG (text "bg_bc_loss: ..." in bg_last_error(NULL)) before anything is launched for: wrong alignment, a
+ * stride < 60, an actions stride that is no multiple of 4, an output that is the same pointer as an input or another output, a non-finite ent_coef, a
+ * workspace too small.  m == 0 writes zeros to stats_dev and launches nothing else.  Never synchronises unless timing is asked for.
+ * Out of scope: label smoothing, an L2 term (the optimiser's weight decay), a demonstration ring (a ring of records plus a weight array serves). */
+int bg_episode_outcome_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double gamma,
+                            const double* rewards_dev /*nullable*/,
+                            const int32_t* tail_steps_dev /*nullable*/, const int32_t* tail_ante_dev /*nullable*/,
+                            const uint8_t* tail_flags_dev /*nullable*/, const double* tail_return_dev /*nullable*/,
+                            int32_t* steps_to_end_dev /*nullable*/, int32_t* end_ante_dev /*nullable*/,
+                            uint8_t* end_flags_dev /*nullable*/, double* returns_dev /*nullable*/,
+                            float* kernel_ms_out, void* stream);
+#define BG_BC_STATS 7
+uint64_t bg_bc_loss_workspace_bytes(int64_t m);
+int bg_bc_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems,
+               const int8_t* mask_dev /*nullable*/, uint64_t mask_stride_bytes,
+               const int32_t* actions_dev, uint64_t actions_stride_bytes,
+               const float* weights_dev /*nullable*/,
+               const int32_t* index_dev /*nullable*/, int64_t store_rows, int64_t m, float ent_coef,
+               void* dlogits_dev, uint64_t dlogits_stride_elems,
+               float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+               float* stats_dev /* float32[BG_BC_STATS = 7] */,
+               void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+
 /* DQN over packed records: the temporal-difference loss of SB3's `DQN.train`, its gradient with respect to the online Q values and its diagnostics, in
  * one pass over the minibatch; and epsilon-greedy exploration in the masked head above.  The arithmetic and the order of every operation are
  * csrc/bg_dqn.h.  Replaces: the DQN branch of the reference's main training script (`--algorithm {PPO, DQN, A2C}`, train_balatro_agent.py:344-362:

@@ -11,7 +11,7 @@ A tree is compiled, device code only, to assembly:
 
 (build.py's flags without the host half; minutes per tree, the two trees side by side).  The assembly is split per function -- a kernel's descriptor
 travels with its code, what stands in front of the first function and behind the last one are two pieces of their own --, the function number in
-`.LBB<n>_<m>` / `.Lfunc_begin<n>` / `.Lfunc_end<n>` and the random `__hip_cuid_<hex>` symbol are normalised, and the pieces are compared as text:
+`.LBB<n>_<m>` / `BB<n>_<m>` (loop comments) / `.Lfunc_begin<n>` / `.Lfunc_end<n>` and the random `__hip_cuid_<hex>` symbol are normalised, and the pieces are compared as text:
 no instruction is looked for.  Printed: the line counts of every function whose text differs, or "identical"; then the compiler's per-kernel
 resource table of the step engines in the format of profiles/above_cap_resources.txt (all kernels with --all-kernels).  Exit status 1 when
 something differs."""
@@ -62,7 +62,10 @@ def load(arg: str, label: str, workdir: str) -> tuple[str, str | None]:
 
 
 _START = re.compile(r"^([A-Za-z_$][\w$.]*):\s*; @\1\s*$")
-_NORM = [(re.compile(r"\.LBB\d+_"), ".LBB_"), (re.compile(r"\.Lfunc_(begin|end)\d+"), r".Lfunc_\1"), (re.compile(r"__hip_cuid_[0-9a-f]+"), "__hip_cuid_")]
+# (`BB<n>_<m>` stands in the comments of the blocks of a loop -- `Header=`, `Parent Loop`, `Child Loop`: a function added in front of others renumbers it
+# like the labels, and a number that gains a digit shifts the padding in front of a label's comment)
+_NORM = [(re.compile(r"\.LBB\d+_"), ".LBB_"), (re.compile(r"\.Lfunc_(begin|end)\d+"), r".Lfunc_\1"), (re.compile(r"__hip_cuid_[0-9a-f]+"), "__hip_cuid_"),
+         (re.compile(r"\bBB\d+_"), "BB_"), (re.compile(r"^(\.LBB_\d+:) +;"), r"\1 ;")]
 
 
 def split(asm: str) -> tuple[dict[str, list[str]], set[str]]:
