@@ -83,7 +83,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_set_episode_summary", "bg_episode_ends_rows",
            "bg_step_many_rows_progress", "bg_progress_terminal_slots",
            "bg_dqn_loss", "bg_dqn_loss_workspace_bytes", "bg_sample_actions_eps",
-           "bg_episode_outcome_rows", "bg_bc_loss", "bg_bc_loss_workspace_bytes"]
+           "bg_episode_outcome_rows", "bg_bc_loss", "bg_bc_loss_workspace_bytes",
+           "bg_actor_sample", "bg_actor_evaluate", "bg_actor_ppo_loss", "bg_actor_ppo_loss_workspace_bytes", "bg_actor_ppo_loss_rows_per_group"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -107,6 +108,7 @@ DQN_MASK_NEXT, DQN_MSE, DQN_TIMEOUT_EXCLUDE = 1, 2, 4
 LIN_NONE, LIN_RELU = 0, 1   # bg_linear_rows / bg_linear_rows_grad (BG_LIN_*)
 LIN_ACTIVATIONS = {None: LIN_NONE, "relu": LIN_RELU}
 LIN_K = 153                 # the columns of a first-layer weight that are read: the "produced" ones
+ACTOR_HIN_MIN, ACTOR_HIN_MAX = 32, 1024   # bg_actor_*: the width of the last hidden activation, a multiple of 32
 EXT_K = 447                 # bg_extractor_rows: the columns of the "extractor" layout (416 one-hot, 10 joker ids, 21 state features)
 EXT_SPLITS = (416, 10, 21)  # the inputs of the reference's hand_net / joker_net / game_state_net first layers, in column order
 NORM_COLS = 153   # BG_NORM_COLS: VecNormalize's statistics are one (mean, var) per column of the "produced" layout
@@ -330,5 +332,14 @@ def load(build_if_missing: bool = True):
     L.bg_extractor_rows_workspace_bytes.restype = u64
     L.bg_extractor_rows_workspace_bytes.argtypes = [i64, i32]
     L.bg_extractor_rows_grad.argtypes = [vp, u64, i64, vp, i64, vp, i32, u64, vp, i32, u64, i32, i32, vp, u64, vp, vp, u64, C.POINTER(C.c_float), vp]
+    head = [vp, u64, i32, vp, i32, u64, vp, vp, u64]   # h, its pitch, Hin, weight, its dtype, its pitch, bias, mask, its pitch
+    L.bg_actor_sample.argtypes = head + [i64, u32, u64, u64, u64, vp, vp, vp, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_actor_evaluate.argtypes = head + [i64, vp, vp, vp, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_actor_ppo_loss_workspace_bytes.restype = u64
+    L.bg_actor_ppo_loss_workspace_bytes.argtypes = [i64, i32]
+    L.bg_actor_ppo_loss_rows_per_group.restype = i64
+    L.bg_actor_ppo_loss_rows_per_group.argtypes = [i64, i32]
+    L.bg_actor_ppo_loss.argtypes = head + [vp, vp, vp, vp, vp, vp, i64, i64, C.c_float, C.c_float, C.c_float, u32, vp, i32, u64, vp, vp, vp, vp, vp, vp, vp, u64,
+                                           vp, u64, vp, u64, C.POINTER(C.c_float), vp]
     _lib = L
     return L

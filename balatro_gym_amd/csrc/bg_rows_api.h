@@ -935,3 +935,159 @@ int bg_extractor_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, i
     hipLaunchKernelGGL((bg_extractor_reduce_kernel<BG_EXT_K>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)workspace_dev, groups, H, dweight_dev, dweight_stride_elems, dbias_dev);
   });
 }
+
+// the last hidden activation -> the policy's last layer fused with the masked head and with PPO's loss (bg_actor.h).  Read here for the reason given
+// above bg_extractor.h: kernels added behind every other leave the text of the others as it was.
+extern "C++" {
+#include "bg_actor.h"
+}
+// what the three calls check of (h, Hin, weight, bias, logits_out), behind their own shape checks
+static const char* bg_actor_layer_args(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
+                                       const float* bias_dev, const float* logits_out_dev, uint64_t logits_out_stride_elems) {
+  if (!bg_act_hin_ok(Hin)) return "Hin must be a multiple of 32 in [32, 1024]";
+  if (!h_dev || ((uintptr_t)h_dev & 15)) return "h_dev must be a 16-byte aligned device pointer";
+  if (h_stride_elems < (uint64_t)Hin || (h_stride_elems & 7) || h_stride_elems > 0xffffffffull) return "h_stride_elems must be a multiple of 8, >= Hin";
+  if (weight_dtype != BG_ENC_F32 && weight_dtype != BG_ENC_BF16) return "weight_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  if (!weight_dev || ((uintptr_t)weight_dev & (weight_dtype == BG_ENC_F32 ? 3 : 1))) return "weight_dev must be a device pointer aligned to its element type";
+  if (weight_stride_elems < (uint64_t)Hin || weight_stride_elems > 0xffffffffull) return "weight_stride_elems must be >= Hin";
+  if ((uintptr_t)bias_dev & 3) return "bias_dev must be 4-byte aligned";
+  if ((uintptr_t)logits_out_dev & 3) return "logits_out_dev must be 4-byte aligned";
+  if (logits_out_dev && (logits_out_stride_elems < BG_HEAD_ACTIONS || logits_out_stride_elems > 0xffffffffull)) return "logits_out_stride_elems must be >= 60";
+  return nullptr;
+}
+// an output (nullable) is the same pointer as an input or as another output
+static bool bg_actor_alias(const void* const* ins, size_t ni, const void* const* outs, size_t no) {
+  bool alias = false;
+  for (size_t o = 0; o < no; o++) {
+    if (!outs[o]) continue;
+    for (size_t i = 0; i < ni; i++) alias = alias || outs[o] == ins[i];
+    for (size_t q = o + 1; q < no; q++) alias = alias || outs[o] == outs[q];
+  }
+  return alias;
+}
+static BgActorArgs bg_actor_args(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
+                                 const float* bias_dev, float* logits_out_dev, uint64_t logits_out_stride_elems) {
+  BgActorArgs G;
+  G.h = (const uint16_t*)h_dev; G.hstride = h_stride_elems; G.weight = weight_dev; G.wstride = weight_stride_elems; G.w_bf16 = weight_dtype == BG_ENC_BF16 ? 1 : 0;
+  G.bias = bias_dev; G.Hin = Hin; G.logits_out = logits_out_dev; G.lostride = logits_out_stride_elems;
+  G.lost = logits_out_dev ? bg_head_ld_path(logits_out_dev, logits_out_stride_elems, false) : BG_HEAD_LD_WORD;
+  return G;
+}
+
+static int bg_actor_head_call(const char* who, int mode, const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype,
+                              uint64_t weight_stride_elems, const float* bias_dev, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m, uint64_t seed,
+                              uint64_t index0, uint64_t t, const int32_t* actions_in, int32_t* actions_out, float* log_prob_dev, float* entropy_dev,
+                              float* logits_out_dev, uint64_t logits_out_stride_elems, float* kernel_ms_out, void* stream) {
+  const void* const act = mode == BG_HEAD_EVALUATE ? (const void*)actions_in : (const void*)actions_out;
+  const void* const ins[] = {h_dev, weight_dev, bias_dev, mask_dev, mode == BG_HEAD_EVALUATE ? act : nullptr};
+  const void* const outs[] = {mode == BG_HEAD_EVALUATE ? nullptr : act, log_prob_dev, entropy_dev, logits_out_dev};
+  const char* bad = bg_head_shape_args(BG_HEAD_F32, m);
+  if (bad) {}
+  else if (const char* r = bg_actor_layer_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems)) bad = r;
+  else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
+  else if (!act || ((uintptr_t)act & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
+  else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "log_prob_dev / entropy_dev must be 4-byte aligned";
+  else if (bg_actor_alias(ins, sizeof(ins) / sizeof(ins[0]), outs, sizeof(outs) / sizeof(outs[0]))) bad = "outputs must not be the same pointer as an input or as another output";
+  if (int rc = bg_op_begin(who, bad, kernel_ms_out)) return rc;
+  if (m == 0) return 0;
+  const BgActorArgs G = bg_actor_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems);
+  const int mld = bg_head_mask_path(mask_dev, mask_stride_bytes, true);
+  const unsigned grid = (unsigned)bg_act_blocks(m);
+  const uint64_t wes = weight_dtype == BG_ENC_BF16 ? 2u : 4u;
+  const int wvec = ((uintptr_t)weight_dev & 15) == 0 && (weight_stride_elems * wes) % 16 == 0 ? BG_ACT_W_VEC : 0;
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    bg_enc_pick<BG_HEAD_SAMPLE, BG_HEAD_ARGMAX, BG_HEAD_EVALUATE>(mode, [&](auto M) {
+      hipLaunchKernelGGL((bg_actor_head_kernel<M()>), dim3(grid), dim3(BG_HEAD_BLOCK), 0, s, G, wvec, mask_dev, mld, mask_stride_bytes, (long long)m, seed, index0, t, actions_in, actions_out, log_prob_dev, entropy_dev);
+    });
+  });
+}
+
+int bg_actor_sample(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
+                    const float* bias_dev, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m, uint32_t flags, uint64_t seed, uint64_t index0,
+                    uint64_t t, int32_t* actions_dev, float* log_prob_dev, float* entropy_dev, float* logits_out_dev, uint64_t logits_out_stride_elems,
+                    float* kernel_ms_out, void* stream) {
+  if (flags & ~BG_HEAD_DETERMINISTIC) { g_create_err = "bg_actor_sample: flags must be 0 or BG_HEAD_DETERMINISTIC"; return BG_E_ARG; }
+  return bg_actor_head_call("bg_actor_sample: ", flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE, h_dev, h_stride_elems, Hin, weight_dev, weight_dtype,
+                            weight_stride_elems, bias_dev, mask_dev, mask_stride_bytes, m, seed, index0, t, nullptr, actions_dev, log_prob_dev, entropy_dev,
+                            logits_out_dev, logits_out_stride_elems, kernel_ms_out, stream);
+}
+int bg_actor_evaluate(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
+                      const float* bias_dev, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m, const int32_t* actions_dev, float* log_prob_dev,
+                      float* entropy_dev, float* logits_out_dev, uint64_t logits_out_stride_elems, float* kernel_ms_out, void* stream) {
+  return bg_actor_head_call("bg_actor_evaluate: ", BG_HEAD_EVALUATE, h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, mask_dev,
+                            mask_stride_bytes, m, 0, 0, 0, actions_dev, nullptr, log_prob_dev, entropy_dev, logits_out_dev, logits_out_stride_elems, kernel_ms_out, stream);
+}
+
+uint64_t bg_actor_ppo_loss_workspace_bytes(int64_t m, int Hin) { return bg_act_workspace_bytes(m, Hin); }
+// the rows one group accumulates in float32 before the float64 sum over the groups (what bounds dweight's and dbias' rounding); 0 for a refused shape
+int64_t bg_actor_ppo_loss_rows_per_group(int64_t m, int Hin) { return m > 0 && bg_act_hin_ok(Hin) ? bg_act_blocks_per_group(m, Hin) * BG_ACT_ROWS : 0; }
+
+int bg_actor_ppo_loss(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
+                      const float* bias_dev, const int8_t* mask_dev, uint64_t mask_stride_bytes, const int32_t* actions_dev, const float* old_log_prob_dev,
+                      const float* advantages_dev, const float* values_dev, const float* returns_dev, const int32_t* index_dev, int64_t store_rows, int64_t m,
+                      float clip_range, float ent_coef, float vf_coef, uint32_t flags, void* dh_dev, int dh_dtype, uint64_t dh_stride_elems, float* dweight_dev,
+                      float* dbias_dev, float* dvalues_dev, float* log_prob_dev, float* entropy_dev, float* stats_dev, float* logits_out_dev,
+                      uint64_t logits_out_stride_elems, float* dlogits_out_dev, uint64_t dlogits_out_stride_elems, void* workspace_dev, uint64_t workspace_bytes,
+                      float* kernel_ms_out, void* stream) {
+  const void* const ins[] = {h_dev, weight_dev, bias_dev, mask_dev, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev};
+  const void* const outs[] = {dh_dev, dweight_dev, dbias_dev, dvalues_dev, log_prob_dev, entropy_dev, stats_dev, logits_out_dev, dlogits_out_dev, workspace_dev};
+  const uint64_t ds = dh_dtype == BG_ENC_F32 ? 4u : 2u;
+  const char* bad = bg_head_shape_args(BG_HEAD_F32, m);
+  if (bad) {}
+  else if (flags & ~BG_PPO_NORMALIZE_ADV) bad = "flags must be 0 or BG_PPO_NORMALIZE_ADV";
+  else if (!(clip_range > 0.0f && clip_range < 1.0f)) bad = "clip_range must be in (0, 1)";
+  else if (!bg_ppo_finite(ent_coef) || !bg_ppo_finite(vf_coef)) bad = "ent_coef and vf_coef must be finite";
+  else if (const char* r = bg_actor_layer_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems)) bad = r;
+  else if (dh_dtype != BG_ENC_F32 && dh_dtype != BG_ENC_BF16) bad = "dh_dtype must be BG_ENC_F32 or BG_ENC_BF16";
+  else if (!dh_dev || ((uintptr_t)dh_dev & (ds - 1))) bad = "dh_dev must be a device pointer aligned to its element type";
+  else if (dh_stride_elems < (uint64_t)Hin || dh_stride_elems > 0xffffffffull) bad = "dh_stride_elems must be >= Hin";
+  else if (!dweight_dev || !dbias_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev and dbias_dev must be 4-byte aligned device pointers";
+  else if ((uintptr_t)dlogits_out_dev & 3) bad = "dlogits_out_dev must be 4-byte aligned";
+  else if (dlogits_out_dev && (dlogits_out_stride_elems < BG_HEAD_ACTIONS || dlogits_out_stride_elems > 0xffffffffull)) bad = "dlogits_out_stride_elems must be >= 60";
+  else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
+  else if (!actions_dev || !old_log_prob_dev || !advantages_dev || (((uintptr_t)actions_dev | (uintptr_t)old_log_prob_dev | (uintptr_t)advantages_dev) & 3)) bad = "actions_dev, old_log_prob_dev and advantages_dev must be 4-byte aligned device pointers";
+  else if ((values_dev == nullptr) != (returns_dev == nullptr)) bad = "values_dev and returns_dev go together: both or neither";
+  else if (((uintptr_t)values_dev | (uintptr_t)returns_dev | (uintptr_t)index_dev | (uintptr_t)dvalues_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "values_dev, returns_dev, index_dev, dvalues_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
+  else if (dvalues_dev && !values_dev) bad = "dvalues_dev needs values_dev and returns_dev";
+  else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
+  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_PPO_STATS floats";
+  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_act_workspace_bytes(m, Hin))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_actor_ppo_loss_workspace_bytes(m, Hin) bytes";
+  else if (bg_actor_alias(ins, sizeof(ins) / sizeof(ins[0]), outs, sizeof(outs) / sizeof(outs[0]))) bad = "outputs must not be the same pointer as an input or as another output";
+  if (int rc = bg_op_begin("bg_actor_ppo_loss: ", bad, kernel_ms_out)) return rc;
+  hipStream_t s = (hipStream_t)stream;
+  if (m == 0) {
+    BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_PPO_STATS * sizeof(float), s));
+    BG_HIP0(hipMemsetAsync(dweight_dev, 0, (size_t)BG_HEAD_ACTIONS * Hin * sizeof(float), s));
+    BG_HIP0(hipMemsetAsync(dbias_dev, 0, BG_HEAD_ACTIONS * sizeof(float), s));
+    return 0;
+  }
+  const BgActorArgs G = bg_actor_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems);
+  BgPpoArgs A;
+  A.logits = nullptr; A.lstride = 0; A.lld = BG_HEAD_LD_WORD;
+  A.dst = dlogits_out_dev ? bg_head_ld_path(dlogits_out_dev, dlogits_out_stride_elems, false) : BG_HEAD_LD_WORD;
+  A.mask = mask_dev; A.mstride = mask_stride_bytes; A.mld = bg_head_mask_path(mask_dev, mask_stride_bytes, !index_dev);
+  A.actions = actions_dev; A.old_lp = old_log_prob_dev; A.adv = advantages_dev; A.values = values_dev; A.returns = returns_dev;
+  A.index = index_dev; A.store_rows = (long long)store_rows; A.m = (long long)m;
+  A.c.clip = clip_range; A.c.lo = 1.0f - clip_range; A.c.hi = 1.0f + clip_range; A.c.ent_coef = ent_coef; A.c.vf_coef = vf_coef; A.c.fm = (float)m;
+  A.normalize = flags & BG_PPO_NORMALIZE_ADV ? 1 : 0;
+  A.dlogits = dlogits_out_dev; A.dstride = dlogits_out_stride_elems; A.dvalues = dvalues_dev; A.log_prob = log_prob_dev; A.entropy = entropy_dev;
+  float* const head = (float*)workspace_dev;
+  BgPpoMoments* const mom = (BgPpoMoments*)((uint8_t*)workspace_dev + BG_PPO_WS_HEAD);
+  const uint64_t SP = bg_ppo_stat_parts(m), RP = bg_ppo_row_parts(m);
+  A.head = head; A.partials = (double*)(mom + SP);
+  BgActorGrad R;
+  R.dh = dh_dev; R.dhstride = dh_stride_elems; R.dh_bf16 = dh_dtype == BG_ENC_BF16 ? 1 : 0;
+  R.part = (float*)((uint8_t*)workspace_dev + bg_act_ppo_ws_bytes(m)); R.per = bg_act_blocks_per_group(m, Hin);
+  const long long groups = bg_act_groups(m, Hin);
+  return bg_op_run(kernel_ms_out, s, [&] {
+    if (A.normalize) {
+      hipLaunchKernelGGL(bg_ppo_adv_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, advantages_dev, index_dev, (long long)store_rows, (long long)m, mom);
+      hipLaunchKernelGGL(bg_ppo_adv_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, mom, (long long)SP, head);
+    }
+    hipLaunchKernelGGL((bg_actor_ppo_kernel<BG_PPO_SUMS>), dim3((unsigned)groups, (unsigned)bg_act_spans(Hin)), dim3(BG_ACT_BLOCK), 0, s, A, G, R);
+    hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
+    const long long items = (long long)BG_HEAD_ACTIONS * Hin + BG_HEAD_ACTIONS;
+    hipLaunchKernelGGL((bg_actor_reduce_kernel<BG_HEAD_ACTIONS>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)R.part, groups, Hin, dweight_dev, dbias_dev);
+  });
+}

@@ -789,6 +789,290 @@ def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Te
     return loss, stats
 
 
+# ---------------------------------------------------------------------- the last layer fused with the head and with PPO's loss (bg_actor.h)
+def _actor_layer(h, weight, bias) -> tuple:
+    """(h, weight, bias) of the actor calls -> (leading shape, m, h's row pitch, Hin, weight's row pitch).  h: bfloat16 [..., Hin] with a contiguous last
+    dimension, leading dimensions dense over a row pitch that is a multiple of 8; weight: float32 / bfloat16 [60, Hin] (nn.Linear.weight's
+    orientation) with a contiguous last dimension; bias: contiguous float32 [60] or None."""
+    if not isinstance(h, torch.Tensor) or h.dtype != torch.bfloat16 or h.dim() < 1:
+        raise ValueError("h must be a torch.bfloat16 tensor [..., Hin] (the last hidden activation)")
+    Hin = int(h.shape[-1])
+    if Hin < nat.ACTOR_HIN_MIN or Hin > nat.ACTOR_HIN_MAX or Hin % 32:
+        raise ValueError(f"Hin, the last dimension of h, must be a multiple of 32 in [{nat.ACTOR_HIN_MIN}, {nat.ACTOR_HIN_MAX}] (got {Hin})")
+    pitch = int(h.stride(-2)) if h.dim() >= 2 and h.shape[-2] > 1 else Hin
+    dense = h.stride(-1) == 1 and pitch >= Hin
+    for d in range(h.dim() - 2, 0, -1):
+        dense = dense and h.stride(d - 1) == h.stride(d) * h.shape[d]
+    if not dense or pitch % 8:
+        raise ValueError("h must have a contiguous last dimension and leading dimensions dense over a row pitch that is a multiple of 8 elements")
+    if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.float32, torch.bfloat16) or tuple(weight.shape) != (60, Hin) or weight.stride(1) != 1 \
+            or weight.stride(0) < Hin:
+        raise ValueError(f"weight must be a float32 / bfloat16 tensor [60, {Hin}] (nn.Linear.weight's orientation) with a contiguous last dimension")
+    if weight.device != h.device:
+        raise ValueError(f"weight must be on {h.device}")
+    if bias is not None:
+        _check_vector("bias", bias, 60, h.device)
+    lead = tuple(h.shape[:-1])
+    return lead, int(np.prod(lead, dtype=np.int64)), pitch, Hin, int(weight.stride(0))
+
+
+def _actor_tile_out(name: str, t, lead: tuple, device: torch.device) -> int:
+    """logits_out / dlogits_out: None, or a float32 tensor [..., >= 60] over the leading shape, rows dense over its pitch -> the pitch (60 for None)."""
+    if t is None:
+        return 60
+    ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and tuple(t.shape[:-1]) == lead and t.dim() >= 1 and t.shape[-1] >= 60 \
+        and t.stride(-1) == 1
+    pitch = (int(t.stride(-2)) if t.dim() >= 2 and t.shape[-2] > 1 else int(t.shape[-1])) if ok else 0
+    ok = ok and pitch >= t.shape[-1]
+    for d in range(t.dim() - 2, 0, -1) if ok else ():
+        ok = ok and t.stride(d - 1) == t.stride(d) * t.shape[d]
+    if not ok:
+        raise ValueError(f"{name} must be a torch.float32 tensor {list(lead)} + [>= 60] on {device} with a contiguous last dimension and dense rows")
+    return pitch
+
+
+def _actor_head(h, hpitch: int, Hin: int, weight, wpitch: int, bias, mask, moff: int, mstride: int) -> tuple:
+    """How the three actor calls begin: h, its pitch, Hin, weight, its dtype, its pitch, bias, mask, its pitch."""
+    return (_ptr(h), C.c_uint64(hpitch), Hin, _ptr(weight), _dtype_code(weight.dtype), C.c_uint64(wpitch), _ptr(bias),
+            mask.data_ptr() + moff if mask is not None else None, C.c_uint64(mstride))
+
+
+def _actor_head_call(name: str, h, weight, bias, mask, given, flags: int, seed: int, index0: int, t: int, actions, log_prob, entropy, logits_out, timing: bool):
+    lead, m, hpitch, Hin, wpitch = _actor_layer(h, weight, bias)
+    dev = h.device
+    mask, moff, mstride = _head_mask(mask, lead, dev)
+    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"{what} must be an integer in [0, 2**64)")
+    if given is not None:
+        _check_scan_tensor("actions", given, torch.int32, lead, dev)
+    for what, tt, dt in (("actions", actions, torch.int32), ("log_prob", log_prob, torch.float32), ("entropy", entropy, torch.float32)):
+        if tt is not None:
+            _check_scan_tensor(what, tt, dt, lead, dev)
+    lopitch = _actor_tile_out("logits_out", logits_out, lead, dev)
+    _check_device(h, "h")
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+    if given is None and actions is None:
+        actions = torch.empty(lead, dtype=torch.int32, device=dev)
+    if log_prob is None:
+        log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
+    if entropy is None:
+        entropy = torch.empty(lead, dtype=torch.float32, device=dev)
+    res = (log_prob, entropy) if given is not None else (actions, log_prob, entropy)
+    if m == 0:
+        return _native_call(name, dev, (), res, timing, empty=True)
+    outs = [x.data_ptr() for x in res] + ([logits_out.data_ptr()] if logits_out is not None else [])
+    ins = [x.data_ptr() for x in (h, weight, bias, mask, given) if x is not None]
+    if len(set(outs)) != len(outs) or set(outs) & set(ins):
+        raise ValueError("outputs must not share memory with the inputs or with each other")
+    head = (*_actor_head(h, hpitch, Hin, weight, wpitch, bias, mask, moff, mstride), C.c_int64(m))
+    tail = (_ptr(log_prob), _ptr(entropy), _ptr(logits_out), C.c_uint64(lopitch))
+    if given is None:
+        args = (*head, C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), _ptr(actions), *tail)
+    else:
+        args = (*head, _ptr(given), *tail)
+    return _native_call(name, dev, args, res, timing)
+
+
+def actor_sample(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, *, seed: int, t: int,
+                 index0: int = 0, deterministic: bool = False, actions: Optional[torch.Tensor] = None, log_prob: Optional[torch.Tensor] = None,
+                 entropy: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None, timing: bool = False):
+    """The policy's last layer and the masked head in one launch (bg_actor_sample): h bfloat16 [..., Hin] (the last hidden activation; Hin a multiple
+    of 32 in [32, 1024]), weight float32 / bfloat16 [60, Hin] and bias float32 [60] (SB3's `action_net`) -> (actions int32, log_prob, entropy), each
+    [...].  The logits -- h @ bfloat16(weight).T accumulated in float32 on the matrix cores, + bias -- stay on the CU; `logits_out` (float32
+    [..., >= 60]) receives them when given.  mask, seed, t, index0, deterministic, actions / log_prob / entropy: as `sample_actions`, and the results are
+    bit for bit `sample_actions(logits_out, ...)`'s."""
+    return _actor_head_call("bg_actor_sample", h, weight, bias, mask, None, nat.HEAD_DETERMINISTIC if deterministic else 0, seed, index0, t, actions, log_prob,
+                            entropy, logits_out, timing)
+
+
+def actor_evaluate(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], actions: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                   log_prob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None, logits_out: Optional[torch.Tensor] = None, timing: bool = False):
+    """(log_prob, entropy) of given int32 actions [...] under the distribution `actor_sample` draws from (bg_actor_evaluate): bit for bit
+    `evaluate_actions(logits_out, actions, mask)`.  A forward pass; `actor_ppo_loss` is the call that takes part in autograd."""
+    if not isinstance(actions, torch.Tensor):
+        raise ValueError("actions must be an int32 tensor with the leading shape of h")
+    return _actor_head_call("bg_actor_evaluate", h, weight, bias, mask, actions, 0, 0, 0, 0, None, log_prob, entropy, logits_out, timing)
+
+
+class ActorPpoStats(PpoStats):
+    """`PpoStats` of `actor_ppo_loss`: the scalars, `log_prob`, `entropy` and `dvalues` as `ppo_loss` gives them, and in place of the logits' gradient
+    the layer's -- `dh` [..., Hin], `dweight` float32 [60, Hin], `dbias` float32 [60].  `dlogits` is the float32 tile the caller asked for
+    (dlogits_out=) or None."""
+
+    def __init__(self, raw, log_prob, entropy, dlogits, dvalues, dh, dweight, dbias, kernel_ms=None):
+        super().__init__(raw, log_prob, entropy, dlogits, dvalues, kernel_ms)
+        self.dh, self.dweight, self.dbias = dh, dweight, dbias
+
+    def __repr__(self):
+        return "ActorPpoStats(" + ", ".join(nat.PPO_STATS) + ", log_prob, entropy, dh, dweight, dbias, dvalues)"
+
+
+class _ActorPpoLossGrad(torch.autograd.Function):
+    """The node `actor_ppo_loss` hangs on its loss (`_PpoLossGrad`'s pattern): the forward pass produced every gradient, the backward multiplies the
+    stored ones by the incoming scalar."""
+
+    @staticmethod
+    def forward(ctx, loss, dh, dweight, dbias, dvalues, h, weight, bias, values):
+        ctx.save_for_backward(dh, dweight, dbias, dvalues if dvalues is not None else dbias.new_empty(0))
+        ctx.has_bias, ctx.has_values = bias is not None, dvalues is not None
+        ctx.h_dtype, ctx.w_dtype = h.dtype, weight.dtype
+        return loss.clone()
+
+    @staticmethod
+    def backward(ctx, grad):
+        dh, dweight, dbias, dvalues = ctx.saved_tensors
+        gh = (dh * grad).to(ctx.h_dtype) if ctx.needs_input_grad[5] else None
+        gw = (dweight * grad).to(ctx.w_dtype) if ctx.needs_input_grad[6] else None
+        gb = dbias * grad if ctx.has_bias and ctx.needs_input_grad[7] else None
+        gv = dvalues * grad if ctx.has_values and ctx.needs_input_grad[8] else None
+        return None, None, None, None, None, gh, gw, gb, gv
+
+
+_actor_workspaces: dict = {}
+
+
+def actor_rows_per_group(m: int, Hin: int) -> int:
+    """The consecutive rows whose dweight / dbias terms `actor_ppo_loss` sums in float32 before the float64 sum over the groups
+    (bg_actor_ppo_loss_rows_per_group): what bounds the rounding of those two outputs."""
+    return int(nat.load().bg_actor_ppo_loss_rows_per_group(C.c_int64(m), Hin))
+
+
+def actor_ppo_loss(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor], actions: torch.Tensor, old_log_prob: torch.Tensor,
+                   advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *, values: Optional[torch.Tensor] = None,
+                   returns: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None, clip_range: float = 0.2, ent_coef: float = 0.0,
+                   vf_coef: float = 0.5, normalize_advantage: bool = True, dh_dtype: torch.dtype = torch.bfloat16, logits_out: Optional[torch.Tensor] = None,
+                   dlogits_out: Optional[torch.Tensor] = None, timing: bool = False):
+    """`ppo_loss` with the policy's last layer inside the launch (bg_actor_ppo_loss): h bfloat16 [..., Hin], weight float32 / bfloat16 [60, Hin] and
+    bias float32 [60] or None in place of the logits -> (loss, `ActorPpoStats`).  Every other argument, the excluded rows and the statistics are
+    `ppo_loss`'s, bit for bit on the logits this call computes (`logits_out`, float32 [..., >= 60], receives them; `dlogits_out` their float32 gradient).
+    In place of dlogits the call writes stats.dh [..., Hin] (`dh_dtype`: float32, or bfloat16 = its nearest-even rounding), stats.dweight float32
+    [60, Hin] and stats.dbias float32 [60], from dp = bfloat16(dlogits): dh = dp @ w, dweight = dp.T @ h, dbias = dp.sum(0).  When h, weight, bias or
+    values require grad the loss carries one autograd node whose backward multiplies the stored gradients by the incoming scalar: `loss.backward()`
+    fills weight.grad, bias.grad and h.grad (and so drives the network below) with nothing recomputed."""
+    lead, m, hpitch, Hin, wpitch = _actor_layer(h, weight, bias)
+    dev = h.device
+    if index is not None:
+        _check_index(index, lead, dev)
+        if not isinstance(actions, torch.Tensor):
+            raise ValueError("actions must be an int32 tensor")
+        store = tuple(actions.shape)
+    else:
+        store = lead
+    store_rows = int(np.prod(store, dtype=np.int64))
+    if store_rows >= 2 ** 31:
+        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
+    mask, moff, mstride = _head_mask(mask, store, dev)
+    _check_scan_tensor("actions", actions, torch.int32, store, dev)
+    _check_scan_tensor("old_log_prob", old_log_prob, torch.float32, store, dev)
+    _check_scan_tensor("advantages", advantages, torch.float32, store, dev)
+    if (values is None) != (returns is None):
+        raise ValueError("values and returns go together: both or neither")
+    if values is not None:
+        _check_scan_tensor("values", values, torch.float32, lead, dev)
+        _check_scan_tensor("returns", returns, torch.float32, store, dev)
+    for what, v in (("clip_range", clip_range), ("ent_coef", ent_coef), ("vf_coef", vf_coef)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
+            raise ValueError(f"{what} must be a finite number")
+    if not 0.0 < float(np.float32(clip_range)) < 1.0:
+        raise ValueError("clip_range must be in (0, 1)")
+    if dh_dtype not in (torch.float32, torch.bfloat16):
+        raise ValueError("dh_dtype must be torch.float32 or torch.bfloat16")
+    lopitch = _actor_tile_out("logits_out", logits_out, lead, dev)
+    dlopitch = _actor_tile_out("dlogits_out", dlogits_out, lead, dev)
+    _check_device(h, "h")
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+    if logits_out is not None and dlogits_out is not None and logits_out.data_ptr() == dlogits_out.data_ptr() and m:
+        raise ValueError("logits_out and dlogits_out must not share memory")
+    hd, wd = h.detach(), weight.detach()
+    bd = bias.detach() if bias is not None else None
+    vals = values.detach() if values is not None else None
+    raw = torch.zeros(len(nat.PPO_STATS), dtype=torch.float32, device=dev)
+    dh = torch.empty(lead + (Hin,), dtype=dh_dtype, device=dev)
+    dweight = torch.zeros((60, Hin), dtype=torch.float32, device=dev)
+    dbias = torch.zeros(60, dtype=torch.float32, device=dev)
+    dvalues = torch.empty(lead, dtype=torch.float32, device=dev) if values is not None else None
+    log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
+    entropy = torch.empty(lead, dtype=torch.float32, device=dev)
+    if m == 0:
+        ws = torch.empty(0, dtype=torch.uint8, device=dev)
+    else:
+        need = int(nat.load().bg_actor_ppo_loss_workspace_bytes(C.c_int64(m), Hin))
+        key = (dev, need)
+        if key not in _actor_workspaces:
+            _actor_workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
+        ws = _actor_workspaces[key]
+    args = (*_actor_head(hd, hpitch, Hin, wd, wpitch, bd, mask, moff, mstride), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(vals), _ptr(returns),
+            _ptr(index), C.c_int64(store_rows), C.c_int64(m), C.c_float(clip_range), C.c_float(ent_coef), C.c_float(vf_coef),
+            C.c_uint32(nat.PPO_NORMALIZE_ADV if normalize_advantage else 0), _ptr(dh), _dtype_code(dh_dtype), C.c_uint64(Hin), _ptr(dweight), _ptr(dbias),
+            _ptr(dvalues), _ptr(log_prob), _ptr(entropy), _ptr(raw), _ptr(logits_out), C.c_uint64(lopitch), _ptr(dlogits_out), C.c_uint64(dlopitch), _ptr(ws),
+            C.c_uint64(ws.numel()))
+    kernel_ms = _native_call("bg_actor_ppo_loss", dev, args, (), timing, empty=m == 0)   # () or (ms,)
+    stats = ActorPpoStats(raw, log_prob, entropy, dlogits_out, dvalues, dh, dweight, dbias, *kernel_ms)
+    loss = raw[0]
+    if torch.is_grad_enabled() and (h.requires_grad or weight.requires_grad or (bias is not None and bias.requires_grad)
+                                    or (values is not None and values.requires_grad)):
+        loss = _ActorPpoLossGrad.apply(loss, dh, dweight, dbias, dvalues, h, weight, bias, values)
+    return loss, stats
+
+
+class RowActor(torch.nn.Module):
+    """SB3's `action_net` -- nn.Linear(in_features, 60) -- as the layer the actor calls run: float32 parameters `weight` [60, in_features] and `bias`
+    [60], initialised as nn.Linear, rounded to bfloat16 inside the launch.  in_features: a multiple of 32 in [32, 1024].  dtype: what the gradient of
+    h is written in (bfloat16, or float32 rounded by autograd afterwards).  `from_linear` / `to_linear` carry SB3's parameters both ways."""
+
+    def __init__(self, in_features: int, dtype: torch.dtype = torch.bfloat16, device=None):
+        super().__init__()
+        in_features = int(in_features)
+        if in_features < nat.ACTOR_HIN_MIN or in_features > nat.ACTOR_HIN_MAX or in_features % 32:
+            raise ValueError(f"in_features must be a multiple of 32 in [{nat.ACTOR_HIN_MIN}, {nat.ACTOR_HIN_MAX}] (got {in_features})")
+        if dtype not in (torch.float32, torch.bfloat16):
+            raise ValueError("dtype must be torch.float32 or torch.bfloat16")
+        self.in_features, self.out_features, self.dtype = in_features, 60, dtype
+        lin = torch.nn.Linear(in_features, 60, device=device)   # nn.Linear's own initialisation
+        self.weight = torch.nn.Parameter(lin.weight.detach().clone())
+        self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+
+    @classmethod
+    def from_linear(cls, linear: torch.nn.Linear, dtype: torch.dtype = torch.bfloat16) -> "RowActor":
+        if not isinstance(linear, torch.nn.Linear) or linear.out_features != 60 or linear.bias is None:
+            raise ValueError("from_linear takes an nn.Linear(in_features, 60) with a bias (SB3's action_net)")
+        layer = cls(linear.in_features, dtype=dtype, device=linear.weight.device)
+        with torch.no_grad():
+            layer.weight.copy_(linear.weight)
+            layer.bias.copy_(linear.bias)
+        return layer
+
+    def to_linear(self) -> torch.nn.Linear:
+        lin = torch.nn.Linear(self.in_features, 60, device=self.weight.device)
+        with torch.no_grad():
+            lin.weight.copy_(self.weight)
+            lin.bias.copy_(self.bias)
+        return lin
+
+    def act(self, h: torch.Tensor, mask: Optional[torch.Tensor] = None, *, seed: int, t: int, index0: int = 0, deterministic: bool = False,
+            log_prob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None):
+        """-> (actions, log_prob, entropy): `actor_sample` with this layer's parameters (no autograd: collection)."""
+        return actor_sample(h.detach(), self.weight.detach(), self.bias.detach(), mask, seed=seed, t=t, index0=index0, deterministic=deterministic,
+                            log_prob=log_prob, entropy=entropy)
+
+    def evaluate(self, h: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None):
+        """-> (log_prob, entropy): `actor_evaluate` with this layer's parameters (a forward pass)."""
+        return actor_evaluate(h.detach(), self.weight.detach(), self.bias.detach(), actions, mask)
+
+    def ppo_loss(self, h: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Tensor, advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
+                 values: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None, clip_range: float = 0.2,
+                 ent_coef: float = 0.0, vf_coef: float = 0.5, normalize_advantage: bool = True):
+        """-> (loss, `ActorPpoStats`): `actor_ppo_loss` with this layer's parameters; `loss.backward()` fills weight.grad, bias.grad and h.grad."""
+        return actor_ppo_loss(h, self.weight, self.bias, actions, old_log_prob, advantages, mask, values=values, returns=returns, index=index,
+                              clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, dh_dtype=self.dtype)
+
+    def extra_repr(self) -> str:
+        return f"in_features={self.in_features}, out_features=60, dtype={self.dtype}"
+
+
 class BcStats:
     """What `bc_loss` returns beside the loss: the scalars of `_native.BC_STATS` as 0-dim float32 device tensors (views of `raw`, no host
     synchronisation), `log_prob` / `entropy` [...] of the minibatch rows (bit for bit `evaluate_actions`'), and the gradient the call produced --

@@ -16,8 +16,8 @@ import torch
 
 from . import _native as nat
 # the learner's calls over records and logits live in rows.py; every name that used to be defined here stays importable from here
-from .rows import (BcStats, DqnStats, EpisodeLimits, EpisodeOutcomes, EpisodeStats, PpoStats, ProgressionRewards, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
-                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, bc_loss, dqn_loss, encode_rows, episode_ends, episode_outcomes, evaluate_actions,
+from .rows import (ActorPpoStats, BcStats, DqnStats, EpisodeLimits, EpisodeOutcomes, EpisodeStats, PpoStats, ProgressionRewards, RowActor, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
+                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, actor_evaluate, actor_ppo_loss, actor_sample, bc_loss, dqn_loss, encode_rows, episode_ends, episode_outcomes, evaluate_actions,
                    extractor_rows, extractor_rows_grad, gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
 
 _TORCH_DT = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,

@@ -1036,6 +1036,75 @@ int bg_extractor_rows_grad(const uint8_t* rows_dev, uint64_t row_stride_bytes, i
                            void* workspace_dev, uint64_t workspace_bytes,
                            float* kernel_ms_out, void* stream);
 
+/* The policy's last layer fused with the masked head and with PPO's loss: bg_sample_actions, bg_evaluate_actions and bg_ppo_loss with
+ * (h, weight, bias) in place of the logits.  The arithmetic, the kernels' shape and the serial twin are csrc/bg_actor.h.
+ * Replaces: SB3's `action_net` = nn.Linear(latent, 60) (latent 256 or 512 in every training script of the reference), the [m, 60] logits matrix it
+ * writes for the head to read back, and on the training side the gradient's three more trips: dlogits written by bg_ppo_loss and read twice by the
+ * autograd backward of the layer (dlogits^T @ h and dlogits @ W).  Here a workgroup takes 64 rows of h, the matrix cores
+ * (__builtin_amdgcn_mfma_f32_32x32x16_bf16) put their logits tile into LDS, the row functions of the head / the loss run on it unchanged, and for
+ * training two more products consume the gradient tile before it leaves the CU.
+ *
+ * h_dev: bfloat16 [m, Hin], row i at element i * h_stride_elems; the pointer 16-byte aligned, the stride a multiple of 8, >= Hin.  Hin: a multiple of 32
+ * in [32, 1024]; LDS does not grow with it.  weight_dev: [60, Hin] (nn.Linear.weight's orientation) BG_ENC_F32 or BG_ENC_BF16, row j at element
+ * j * weight_stride_elems (>= Hin), aligned to its element; a float32 weight is rounded to bfloat16 on load (nearest even, NaN -> 0x7fc0): w_b.
+ * bias_dev: float32 [60] or NULL.  mask, seed, index0, t, flags: exactly bg_sample_actions' / bg_evaluate_actions'; mask, actions, old_log_prob,
+ * advantages, values, returns, index_dev, store_rows, clip_range, ent_coef, vf_coef, flags, dvalues, log_prob, entropy, stats: exactly bg_ppo_loss'.
+ *     logit[i][j] = float32(sum over k of h[i][k] * w_b[j][k]) + bias[j]
+ * Every product is exact; the sum is the float32 accumulation of the instruction over k in ascending blocks of 16, the 60 units padded to 64 with zero
+ * weights (padding units never reach the head); the bias is one float32 addition behind the sum (NULL: no addition).  The logits are bounded against
+ * float64 (tests/actor_ref.py), not promised bit for bit against another accumulation order.  logits_out_dev (float32 [m, stride >= 60], nullable)
+ * returns them, and GIVEN them everything behind is exact: actions, log_prob and entropy are bit for bit what bg_sample_actions / bg_evaluate_actions
+ * return for logits_out with the same mask, seed, index0 and t, whether logits_out_dev is given or not; bg_actor_ppo_loss' stats, log_prob, entropy,
+ * dvalues and dlogits_out_dev (float32 [m, stride >= 60], nullable) are bit for bit bg_ppo_loss' on logits_out -- the launch sequence is that call's,
+ * its advantage-statistics kernels and its finishing kernel are reused, and the fused rows kernel writes the same six float64 sums per 64 rows.
+ *
+ * bg_actor_ppo_loss writes, in place of dlogits, the gradients of the layer.  dp[i][j] = bfloat16(dlogits[i][j]) (nearest even; an excluded row: +0.0).
+ *     dh[i][k]      = float32(sum over j of dp[i][j] * w_b[j][k])          dh_dev BG_ENC_F32 or BG_ENC_BF16 [m, dh_stride_elems >= Hin]; a bfloat16 dh is
+ *                                                                            the nearest-even rounding of that float32 value; an excluded row is +0.0
+ *     dweight[j][k] = sum over i of dp[i][j] * h[i][k]                     float32 [60, Hin], dense
+ *     dbias[j]      = sum over i of dp[i][j]                               float32 [60]
+ * dweight and dbias are accumulated in float32 inside a row group -- bg_actor_ppo_loss_rows_per_group(m, Hin) consecutive rows: blocks of 64 rows,
+ * ceil(B / cap) blocks per group with B = ceil(m / 64) and cap = 256 / ceil(Hin / 256) -- and the groups' partials (workspace) are summed in float64 in
+ * index order and rounded once: bg_linear_rows_grad's scheme.  No floating-point atomics: two calls give the same bits.
+ * NON-FINITE INPUTS: a NaN or an infinity in h, weight or bias is carried into the logits it touches and the head's rules decide from there -- at a
+ * valid unit a NaN or +inf makes the row degenerate (action -1, NaN) or excluded from the loss, at a masked unit it is ignored.  The gradient products are
+ * plain IEEE arithmetic: +0.0 times a non-finite operand is NaN, so dh / dweight / dbias are finite only where the operands they multiply are.
+ * workspace_dev: 16-byte aligned, bg_actor_ppo_loss_workspace_bytes(m, Hin) bytes = bg_ppo_loss_workspace_bytes(m) rounded up to 16, plus
+ * groups * (60 * Hin + 64) * 4.  All three calls run on the current device, need no handle and never synchronise unless timing is asked for.
+ * BG_E_ARG (text "bg_actor_sample: ..." / "bg_actor_evaluate: ..." / "bg_actor_ppo_loss: ..." in bg_last_error(NULL)) before anything is launched for:
+ * everything bg_sample_actions / bg_evaluate_actions / bg_ppo_loss refuse; Hin out of range; h_dev misaligned or its stride not a multiple of 8; a stride
+ * below its width; an unknown dtype; an output that is the same pointer as an input or another output; a workspace too small.  m == 0: the head calls
+ * are no-ops; bg_actor_ppo_loss zeroes stats_dev, dweight_dev and dbias_dev and launches nothing else.
+ * Out of scope: the value head, DQN's and behaviour cloning's last layers, epsilon-greedy, temperature, Hin not a multiple of 32. */
+int bg_actor_sample(const void* h_dev, uint64_t h_stride_elems, int Hin,
+                    const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems, const float* bias_dev /*nullable*/,
+                    const int8_t* mask_dev /*nullable*/, uint64_t mask_stride_bytes, int64_t m, uint32_t flags,
+                    uint64_t seed, uint64_t index0, uint64_t t,
+                    int32_t* actions_dev, float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+                    float* logits_out_dev /*nullable*/, uint64_t logits_out_stride_elems,
+                    float* kernel_ms_out, void* stream);
+int bg_actor_evaluate(const void* h_dev, uint64_t h_stride_elems, int Hin,
+                      const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems, const float* bias_dev /*nullable*/,
+                      const int8_t* mask_dev /*nullable*/, uint64_t mask_stride_bytes, int64_t m,
+                      const int32_t* actions_dev, float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+                      float* logits_out_dev /*nullable*/, uint64_t logits_out_stride_elems,
+                      float* kernel_ms_out, void* stream);
+uint64_t bg_actor_ppo_loss_workspace_bytes(int64_t m, int Hin);
+int64_t bg_actor_ppo_loss_rows_per_group(int64_t m, int Hin);
+int bg_actor_ppo_loss(const void* h_dev, uint64_t h_stride_elems, int Hin,
+                      const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems, const float* bias_dev /*nullable*/,
+                      const int8_t* mask_dev /*nullable*/, uint64_t mask_stride_bytes,
+                      const int32_t* actions_dev, const float* old_log_prob_dev, const float* advantages_dev,
+                      const float* values_dev /*nullable*/, const float* returns_dev /*nullable*/,
+                      const int32_t* index_dev /*nullable*/, int64_t store_rows, int64_t m,
+                      float clip_range, float ent_coef, float vf_coef, uint32_t flags,
+                      void* dh_dev, int dh_dtype, uint64_t dh_stride_elems, float* dweight_dev, float* dbias_dev,
+                      float* dvalues_dev /*nullable*/, float* log_prob_dev /*nullable*/, float* entropy_dev /*nullable*/,
+                      float* stats_dev /* float32[BG_PPO_STATS = 10] */,
+                      float* logits_out_dev /*nullable*/, uint64_t logits_out_stride_elems,
+                      float* dlogits_out_dev /*nullable*/, uint64_t dlogits_out_stride_elems,
+                      void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
