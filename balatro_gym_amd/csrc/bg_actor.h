@@ -87,10 +87,7 @@ BG_LIN_FN int64_t bg_act_groups(int64_t m, int Hin) {
 BG_LIN_FN bool bg_act_hin_ok(int Hin) { return Hin >= BG_ACT_HIN_MIN && Hin <= BG_ACT_HIN_MAX && Hin % 32 == 0; }
 BG_LIN_FN uint64_t bg_act_part_floats(int Hin) { return (uint64_t)BG_HEAD_ACTIONS * (uint64_t)Hin + BG_ACT_PART_TAIL; }
 // workspace: bg_ppo_loss' (head, statistics partials, row partials), rounded up to 16 bytes, then one partial per row group
-BG_LIN_FN uint64_t bg_act_ppo_ws_bytes(int64_t m) {
-  const uint64_t b = BG_PPO_WS_HEAD + bg_ppo_stat_parts(m) * sizeof(BgPpoMoments) + bg_ppo_row_parts(m) * (BG_PPO_SUMS * sizeof(double));
-  return (b + 15u) & ~(uint64_t)15u;
-}
+BG_LIN_FN uint64_t bg_act_ppo_ws_bytes(int64_t m) { return (bg_ppo_ws_bytes(m) + 15u) & ~(uint64_t)15u; }
 BG_LIN_FN uint64_t bg_act_workspace_bytes(int64_t m, int Hin) {
   if (m <= 0 || !bg_act_hin_ok(Hin)) return 0;
   return bg_act_ppo_ws_bytes(m) + (uint64_t)bg_act_groups(m, Hin) * bg_act_part_floats(Hin) * sizeof(float);
@@ -459,7 +456,7 @@ __global__ __launch_bounds__(BG_ACT_BLOCK) void bg_actor_ppo_kernel(const BgPpoA
         if (A.entropy) A.entropy[i] = o.entropy;
       }
     }
-    if (first) {   // (uniform over the workgroup) bg_ppo_kernel's tree
+    if (first) {   // (uniform over the workgroup) bg_ppo_kernel's tree: bg_loss_tile_reduce's text, spelled out (calling it moves this kernel: DESIGN.md)
       if (r < BG_HEAD_ROWS) {
 #pragma unroll
         for (int k = 0; k < BG_PPO_SUMS; k++) red[k * BG_HEAD_ROWS + r] = t[k];

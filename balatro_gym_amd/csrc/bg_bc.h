@@ -177,18 +177,11 @@ static inline double bg_bc_host_weight_sum(const BgBcArgs& A) {
       const long long i = (long long)b * BG_PPO_LANES + r;
       t[r] = i < A.m ? bg_bc_weight_of(A.weights, A.index, A.store_rows, i) : 0.0;
     }
-    for (int s = BG_PPO_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = t[r] + t[r + s];
-    part[b] = t[0];
+    part[b] = bg_loss_host_tree(t, BG_PPO_LANES, 0, BgLossSum{});
   }
-  double t[BG_PPO_LANES];
-  const uint64_t per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
-  for (uint64_t q = 0; q < BG_PPO_LANES; q++) {
-    t[q] = 0.0;
-    for (uint64_t k = q * per; k < P && k < (q + 1) * per; k++) t[q] = t[q] + part[k];
-  }
-  for (int s = BG_PPO_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = t[r] + t[r + s];
+  const double W = bg_loss_host_slices(part, P, 1, 0, 0.0, BgLossSum{});
   delete[] part;
-  return t[0];
+  return W;
 }
 
 // bf16: logits and dlogits are bfloat16 bits.  Every pointer is a host pointer; A.head / A.partials / A.fm are not used.
@@ -226,22 +219,10 @@ static inline void bg_bc_host(const BgBcArgs& A, bool bf16, bool keep, float* st
       if (A.log_prob) A.log_prob[i] = o.log_prob;
       if (A.entropy) A.entropy[i] = o.entropy;
     }
-    for (int k = 0; k < BG_BC_SUMS; k++) {
-      for (int s = BG_PPO_ROWS / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[k][r] = t[k][r] + t[k][r + s];
-      part[b * BG_BC_SUMS + k] = t[k][0];
-    }
+    bg_loss_host_tile<BG_BC_SUMS>(t, part + b * BG_BC_SUMS, BgLossSum{});
   }
   double sum[BG_BC_SUMS];
-  const uint64_t per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
-  for (int k = 0; k < BG_BC_SUMS; k++) {
-    double t[BG_PPO_LANES];
-    for (uint64_t q = 0; q < BG_PPO_LANES; q++) {
-      t[q] = 0.0;
-      for (uint64_t p = q * per; p < P && p < (q + 1) * per; p++) t[q] = t[q] + part[p * BG_BC_SUMS + k];
-    }
-    for (int s = BG_PPO_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = t[r] + t[r + s];
-    sum[k] = t[0];
-  }
+  bg_loss_host_finish<BG_BC_SUMS>(part, P, sum, BgLossSum{});
   delete[] part;
   bg_bc_finish_stats(sum, W, A.m, A.ent_coef, stats);
 }
@@ -257,31 +238,15 @@ static inline void bg_bc_host(const BgBcArgs& A, bool bf16, bool keep, float* st
 __global__ __launch_bounds__(BG_PPO_LANES) void bg_bc_weight_partials(const float* __restrict__ weights, const int32_t* __restrict__ index, long long store_rows,
                                                                       long long m, double* __restrict__ part) {
   __shared__ double t[BG_PPO_LANES];
-  const int r = threadIdx.x;
-  const long long i = (long long)blockIdx.x * BG_PPO_LANES + r;
-  t[r] = i < m ? bg_bc_weight_of(weights, index, store_rows, i) : 0.0;
-  __syncthreads();
-  for (int s = BG_PPO_LANES / 2; s; s >>= 1) {
-    if (r < s) t[r] = t[r] + t[r + s];
-    __syncthreads();
-  }
-  if (r == 0) part[blockIdx.x] = t[0];
+  const long long i = (long long)blockIdx.x * BG_PPO_LANES + threadIdx.x;
+  bg_loss_stat_partials(i < m ? bg_bc_weight_of(weights, index, store_rows, i) : 0.0, t, part, BgLossSum{});
 }
 
 // one workgroup: the partial sums -> head: float Wf at 0, double W at byte 8
 __global__ __launch_bounds__(BG_PPO_LANES) void bg_bc_weight_combine(const double* __restrict__ part, long long P, float* __restrict__ head) {
   __shared__ double t[BG_PPO_LANES];
-  const int r = threadIdx.x;
-  const long long per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
-  double v = 0.0;
-  for (long long k = r * per; k < P && k < (r + 1) * per; k++) v = v + part[k];
-  t[r] = v;
-  __syncthreads();
-  for (int s = BG_PPO_LANES / 2; s; s >>= 1) {
-    if (r < s) t[r] = t[r] + t[r + s];
-    __syncthreads();
-  }
-  if (r == 0) {
+  bg_loss_stat_combine(part, P, 0.0, t, BgLossSum{});
+  if (threadIdx.x == 0) {
     head[0] = (float)t[0];
     head[1] = 0.0f;
     reinterpret_cast<double*>(head)[1] = t[0];
@@ -296,11 +261,7 @@ __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_bc_kernel(const BgBcArgs A) 
   __shared__ double red[BG_BC_SUMS * BG_HEAD_ROWS];
   const long long rec0 = (long long)blockIdx.x * BG_HEAD_ROWS;
   const int nrow = (int)(A.m - rec0 < BG_HEAD_ROWS ? A.m - rec0 : BG_HEAD_ROWS);
-  bg_head_stage_logits<BF16>(A.logits, A.lld, A.lstride, rec0, nrow, lg);
-  if (A.mld != BG_HEAD_LD_NONE) {
-    if (A.index) bg_ppo_stage_mask_gather(A.mask, A.mld, A.mstride, A.index, A.store_rows, rec0, nrow, mk);
-    else bg_head_stage_mask(A.mask, A.mld, A.mstride, rec0, nrow, mk);
-  }
+  bg_loss_stage<BF16>(A.logits, A.lld, A.lstride, A.mask, A.mld, A.mstride, A.index, A.store_rows, rec0, nrow, lg, mk);
   __syncthreads();
   const int r = threadIdx.x;
   double t[BG_BC_SUMS];
@@ -323,19 +284,7 @@ __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_bc_kernel(const BgBcArgs A) 
     if (A.log_prob) A.log_prob[i] = o.log_prob;
     if (A.entropy) A.entropy[i] = o.entropy;
   }
-  if (r < BG_HEAD_ROWS) {
-#pragma unroll
-    for (int k = 0; k < BG_BC_SUMS; k++) red[k * BG_HEAD_ROWS + r] = t[k];
-  }
-  __syncthreads();
-  for (int s = BG_HEAD_ROWS / 2; s; s >>= 1) {
-    if (r < s) {
-#pragma unroll
-      for (int k = 0; k < BG_BC_SUMS; k++) red[k * BG_HEAD_ROWS + r] = red[k * BG_HEAD_ROWS + r] + red[k * BG_HEAD_ROWS + r + s];
-    }
-    __syncthreads();
-  }
-  if (r < BG_BC_SUMS) A.partials[(size_t)blockIdx.x * BG_BC_SUMS + r] = red[r * BG_HEAD_ROWS];
+  bg_loss_tile_reduce<BG_BC_SUMS>(t, red, A.partials, blockIdx.x, BgLossSum{});
   bg_ppo_store_rows<BF16>(A.dlogits, A.dst, A.dstride, rec0, nrow, lg);
 }
 

@@ -56,6 +56,7 @@
 
 BG_HEAD_FN uint64_t bg_dqn_row_parts(long long m) { return ((uint64_t)m + BG_DQN_ROWS - 1) / BG_DQN_ROWS; }
 BG_HEAD_FN double bg_dqn_fold(int k, double a, double b) { return k == BG_DQN_MAX ? (b > a ? b : a) : a + b; }
+struct BgDqnFold { BG_LOSS_FOLD double operator()(int k, double a, double b) const { return bg_dqn_fold(k, a, b); } };
 
 struct BgDqnTerms {
   float term, qa, y, absd, td, dq;
@@ -231,22 +232,10 @@ static inline void bg_dqn_host(const BgDqnArgs& A, bool bf16, float* stats) {
       }
       if (A.td) A.td[i] = o.td;
     }
-    for (int k = 0; k < BG_DQN_SUMS; k++) {
-      for (int s = BG_DQN_ROWS / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[k][r] = bg_dqn_fold(k, t[k][r], t[k][r + s]);
-      part[b * BG_DQN_SUMS + k] = t[k][0];
-    }
+    bg_loss_host_tile<BG_DQN_SUMS>(t, part + b * BG_DQN_SUMS, BgDqnFold{});
   }
   double sum[BG_DQN_SUMS];
-  const uint64_t per = (P + BG_DQN_LANES - 1) / BG_DQN_LANES;
-  for (int k = 0; k < BG_DQN_SUMS; k++) {
-    double t[BG_DQN_LANES];
-    for (uint64_t q = 0; q < BG_DQN_LANES; q++) {
-      t[q] = 0.0;
-      for (uint64_t p = q * per; p < P && p < (q + 1) * per; p++) t[q] = bg_dqn_fold(k, t[q], part[p * BG_DQN_SUMS + k]);
-    }
-    for (int s = BG_DQN_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = bg_dqn_fold(k, t[r], t[r + s]);
-    sum[k] = t[0];
-  }
+  bg_loss_host_finish<BG_DQN_SUMS>(part, P, sum, BgDqnFold{});
   delete[] part;
   bg_dqn_finish_stats(sum, A.m, stats);
 }
@@ -309,19 +298,7 @@ __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_dqn_kernel(const BgDqnArgs A
     t[5] = (double)o.excluded;
     if (A.td) A.td[i] = o.td;
   }
-  if (r < BG_HEAD_ROWS) {
-#pragma unroll
-    for (int k = 0; k < BG_DQN_SUMS; k++) red[k * BG_HEAD_ROWS + r] = t[k];
-  }
-  __syncthreads();
-  for (int s = BG_HEAD_ROWS / 2; s; s >>= 1) {
-    if (r < s) {
-#pragma unroll
-      for (int k = 0; k < BG_DQN_SUMS; k++) red[k * BG_HEAD_ROWS + r] = bg_dqn_fold(k, red[k * BG_HEAD_ROWS + r], red[k * BG_HEAD_ROWS + r + s]);
-    }
-    __syncthreads();
-  }
-  if (r < BG_DQN_SUMS) A.partials[(size_t)blockIdx.x * BG_DQN_SUMS + r] = red[r * BG_HEAD_ROWS];
+  bg_loss_tile_reduce<BG_DQN_SUMS>(t, red, A.partials, blockIdx.x, BgDqnFold{});
   bg_ppo_store_rows<BF16>(A.dq, A.dst, A.dstride, rec0, nrow, qn);
 }
 

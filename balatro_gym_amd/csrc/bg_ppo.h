@@ -33,9 +33,7 @@
 //                them by the TREE; the workgroups' partials (caller's workspace) are summed by SLICES-THEN-TREE in a one-workgroup kernel.  Then, in
 //                float64, policy_loss = sum / m, value_loss = sum / m, entropy_loss = -(sum H) / m, approx_kl = sum / m, clip_fraction = sum / m,
 //                loss = policy_loss + ent_coef * entropy_loss + vf_coef * value_loss, each rounded to float32 once.
-//   TREE         over t[0 .. n), n a power of two (rows beyond m hold zero): for s = n / 2, n / 4, .. 1:  t[r] = t[r] (+) t[r + s] for r < s; the result is t[0].
-//   SLICES-THEN-TREE  over P partials with 256 lanes: per = ceil(P / 256); lane q folds partials [q * per, min(P, (q + 1) * per)) in ascending order from
-//                zero; the 256 lane values go through the TREE.
+//   TREE, SLICES-THEN-TREE  the two orders every sum across rows of this header, bg_bc.h, bg_dqn.h and bg_actor.h takes: stated once, at THE REDUCTION ORDER below.
 // No floating-point atomics, and the launch sequence is fixed (statistics partials, statistics, rows, finish), so the result is a function of the
 // arguments alone: two calls give the same bits.  expf / logf as in bg_head.h: bounded by tests/ppo_ref.py, not promised another library's bits.
 // Out of scope: clip_range_vf, temperature, target_kl (the caller reads approx_kl), gradient clipping, the optimiser.
@@ -78,6 +76,10 @@ BG_HEAD_FN uint16_t bg_ppo_bf16(float f) {   // round to nearest even
 }
 BG_HEAD_FN uint64_t bg_ppo_stat_parts(long long m) { return ((uint64_t)m + BG_PPO_LANES - 1) / BG_PPO_LANES; }
 BG_HEAD_FN uint64_t bg_ppo_row_parts(long long m) { return ((uint64_t)m + BG_PPO_ROWS - 1) / BG_PPO_ROWS; }
+// bg_ppo_loss_workspace_bytes(m) for m > 0: the head, one triple per statistics partial, BG_PPO_SUMS float64 per row partial
+BG_HEAD_FN uint64_t bg_ppo_ws_bytes(long long m) {
+  return BG_PPO_WS_HEAD + bg_ppo_stat_parts(m) * sizeof(BgPpoMoments) + bg_ppo_row_parts(m) * (BG_PPO_SUMS * sizeof(double));
+}
 
 struct BgPpoTerms {
   float log_prob, entropy, policy, value, kl, dvalue;
@@ -196,33 +198,118 @@ struct BgPpoArgs {
   double* partials;    // workspace: [row partials][BG_PPO_SUMS]
 };
 
+// ---- THE REDUCTION ORDER of the loss calls (bg_ppo_loss, bg_bc_loss, bg_dqn_loss, bg_actor_ppo_loss), stated once: the device helpers and the host
+// template below are the two spellings of it, and the g++ tests hold them to each other bit for bit. ----
+//   TREE         over t[0 .. n), n a power of two (rows beyond m hold zero): for s = n / 2, n / 4, .. 1:  t[r] = t[r] (+) t[r + s] for r < s; the result is t[0].
+//   SLICES-THEN-TREE  over P partials with L = 256 lanes: per = ceil(P / L); lane q folds partials [q * per, min(P, (q + 1) * per)) in ascending order from
+//                zero; the L lane values go through the TREE.
+// A row pass: a workgroup is 64 consecutive rows, every term of a row is one float64, term k of the 64 rows goes through the TREE and the workgroup's
+// partial is [SUMS] values at partials[workgroup * SUMS]; one workgroup of 256 lanes then takes the partials of every term through SLICES-THEN-TREE
+// (the finish).  A pre-pass (PPO's advantage moments, BC's weight sum): 256 consecutive rows per workgroup by the TREE, the workgroups' values by
+// SLICES-THEN-TREE (the combine).  (+) is a fold functor called as fold(k, a, b), k the term: BgLossSum, BgPpoMerge, bg_dqn.h's BgDqnFold.
+// Spelled out where sharing moved the compiled kernel ("Source-only changes"): the three finish kernels (bg_ppo_finish, bg_bc_finish,
+// bg_dqn_finish: SLICES-THEN-TREE per term, then their *_finish_stats) and the tail of bg_actor_ppo_kernel (bg_loss_tile_reduce's text).
+#ifdef BG_PPO_HOST
+#define BG_LOSS_FOLD inline   /* a member: BG_HEAD_FN is `static inline` under g++ */
+#else
+#define BG_LOSS_FOLD BG_HEAD_FN
+#endif
+struct BgLossSum { BG_LOSS_FOLD double operator()(int, double a, double b) const { return a + b; } };
+struct BgPpoMerge { BG_LOSS_FOLD BgPpoMoments operator()(int, BgPpoMoments a, BgPpoMoments b) const { return bg_ppo_merge(a, b); } };
+#ifdef BG_PPO_HOST
+// TREE over t[0 .. n) in place -> t[0]
+template <class T, class F>
+static inline T bg_loss_host_tree(T* t, int n, int k, F fold) {
+  for (int s = n / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = fold(k, t[r], t[r + s]);
+  return t[0];
+}
+// SLICES-THEN-TREE over part[p * stride + k], p in [0, P)
+template <class T, class F>
+static inline T bg_loss_host_slices(const T* part, uint64_t P, int stride, int k, T zero, F fold) {
+  T t[BG_PPO_LANES];
+  const uint64_t per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
+  for (uint64_t q = 0; q < BG_PPO_LANES; q++) {
+    t[q] = zero;
+    for (uint64_t p = q * per; p < P && p < (q + 1) * per; p++) t[q] = fold(k, t[q], part[p * stride + k]);
+  }
+  return bg_loss_host_tree(t, BG_PPO_LANES, k, fold);
+}
+// the row pass' two levels: t[k][r] of one workgroup -> its partial; the partials -> sum[SUMS]
+template <int SUMS, class F>
+static inline void bg_loss_host_tile(double (*t)[BG_PPO_ROWS], double* part, F fold) {
+  for (int k = 0; k < SUMS; k++) part[k] = bg_loss_host_tree(t[k], BG_PPO_ROWS, k, fold);
+}
+template <int SUMS, class F>
+static inline void bg_loss_host_finish(const double* part, uint64_t P, double* sum, F fold) {
+  for (int k = 0; k < SUMS; k++) sum[k] = bg_loss_host_slices(part, P, SUMS, k, 0.0, fold);
+}
+#else
+static_assert((BG_HEAD_ROWS & (BG_HEAD_ROWS - 1)) == 0 && BG_HEAD_ROWS <= BG_HEAD_BLOCK, "the sums of a workgroup go through a power-of-two tree");
+// the tail of a row pass: the lane's terms t[SUMS] (zero beyond the rows) -> red (LDS, [SUMS][BG_HEAD_ROWS]) -> the partial of workgroup `block`
+template <int SUMS, class F>
+__device__ __forceinline__ void bg_loss_tile_reduce(const double* t, double* red, double* partials, size_t block, F fold) {
+  const int r = threadIdx.x;
+  if (r < BG_HEAD_ROWS) {
+#pragma unroll
+    for (int k = 0; k < SUMS; k++) red[k * BG_HEAD_ROWS + r] = t[k];
+  }
+  __syncthreads();
+  for (int s = BG_HEAD_ROWS / 2; s; s >>= 1) {
+    if (r < s) {
+#pragma unroll
+      for (int k = 0; k < SUMS; k++) red[k * BG_HEAD_ROWS + r] = fold(k, red[k * BG_HEAD_ROWS + r], red[k * BG_HEAD_ROWS + r + s]);
+    }
+    __syncthreads();
+  }
+  if (r < SUMS) partials[block * SUMS + r] = red[r * BG_HEAD_ROWS];
+}
+// a pre-pass: the lane's value v of 256 consecutive rows -> part[workgroup]; and one workgroup: the P parts -> t[0] (read it behind the call).  t: LDS, [256]
+template <class T, class F>
+__device__ __forceinline__ void bg_loss_stat_partials(T v, T* t, T* __restrict__ part, F fold) {
+  const int r = threadIdx.x;
+  t[r] = v;
+  __syncthreads();
+  for (int s = BG_PPO_LANES / 2; s; s >>= 1) {
+    if (r < s) t[r] = fold(0, t[r], t[r + s]);
+    __syncthreads();
+  }
+  if (r == 0) part[blockIdx.x] = t[0];
+}
+template <class T, class F>
+__device__ __forceinline__ void bg_loss_stat_combine(const T* __restrict__ part, long long P, T v, T* t, F fold) {
+  const int r = threadIdx.x;
+  const long long per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
+  for (long long k = r * per; k < P && k < (r + 1) * per; k++) v = fold(0, v, part[k]);
+  t[r] = v;
+  __syncthreads();
+  for (int s = BG_PPO_LANES / 2; s; s >>= 1) {
+    if (r < s) t[r] = fold(0, t[r], t[r + s]);
+    __syncthreads();
+  }
+}
+#endif
+
 #ifdef BG_PPO_HOST
 // ---- the serial twin: the launch sequence below, one "workgroup" after the other, in the orders of the contract ----
 static inline BgPpoMoments bg_ppo_host_moments(const BgPpoArgs& A) {
   const uint64_t P = bg_ppo_stat_parts(A.m);
+  const BgPpoMoments zero = {0.0, 0.0, 0.0};
   BgPpoMoments* part = new BgPpoMoments[P ? P : 1];
   for (uint64_t b = 0; b < P; b++) {
     BgPpoMoments t[BG_PPO_LANES];
     for (int r = 0; r < BG_PPO_LANES; r++) {
       const long long i = (long long)b * BG_PPO_LANES + r;
-      t[r].n = 0.0; t[r].mean = 0.0; t[r].m2 = 0.0;
+      t[r] = zero;
       if (i < A.m) {
         const long long src = A.index ? A.index[i] : i;
         if (!A.index || (src >= 0 && src < A.store_rows)) { t[r].n = 1.0; t[r].mean = (double)A.adv[src]; }
       }
     }
-    for (int s = BG_PPO_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = bg_ppo_merge(t[r], t[r + s]);
-    part[b] = t[0];
+    part[b] = bg_loss_host_tree(t, BG_PPO_LANES, 0, BgPpoMerge{});
   }
-  BgPpoMoments t[BG_PPO_LANES];
-  const uint64_t per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
-  for (uint64_t q = 0; q < BG_PPO_LANES; q++) {
-    t[q].n = 0.0; t[q].mean = 0.0; t[q].m2 = 0.0;
-    for (uint64_t k = q * per; k < P && k < (q + 1) * per; k++) t[q] = bg_ppo_merge(t[q], part[k]);
-  }
-  for (int s = BG_PPO_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = bg_ppo_merge(t[r], t[r + s]);
+  const BgPpoMoments all = bg_loss_host_slices(part, P, 1, 0, zero, BgPpoMerge{});
   delete[] part;
-  return t[0];
+  return all;
 }
 
 // logits_bf16: logits and dlogits are bfloat16 bits.  Every pointer is a host pointer; A.head / A.partials are not used.
@@ -270,22 +357,10 @@ static inline void bg_ppo_host(const BgPpoArgs& A, bool bf16, bool keep, float* 
       if (A.log_prob) A.log_prob[i] = o.log_prob;
       if (A.entropy) A.entropy[i] = o.entropy;
     }
-    for (int k = 0; k < BG_PPO_SUMS; k++) {
-      for (int s = BG_PPO_ROWS / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[k][r] = t[k][r] + t[k][r + s];
-      part[b * BG_PPO_SUMS + k] = t[k][0];
-    }
+    bg_loss_host_tile<BG_PPO_SUMS>(t, part + b * BG_PPO_SUMS, BgLossSum{});
   }
   double sum[BG_PPO_SUMS];
-  const uint64_t per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
-  for (int k = 0; k < BG_PPO_SUMS; k++) {
-    double t[BG_PPO_LANES];
-    for (uint64_t q = 0; q < BG_PPO_LANES; q++) {
-      t[q] = 0.0;
-      for (uint64_t p = q * per; p < P && p < (q + 1) * per; p++) t[q] = t[q] + part[p * BG_PPO_SUMS + k];
-    }
-    for (int s = BG_PPO_LANES / 2; s; s >>= 1) for (int r = 0; r < s; r++) t[r] = t[r] + t[r + s];
-    sum[k] = t[0];
-  }
+  bg_loss_host_finish<BG_PPO_SUMS>(part, P, sum, BgLossSum{});
   delete[] part;
   bg_ppo_finish_stats(sum, A.m, A.c.ent_coef, A.c.vf_coef, mean, sd, stats);
 }
@@ -302,7 +377,6 @@ static inline void bg_ppo_host(const BgPpoArgs& A, bool bf16, bool keep, float* 
 //      halves, chosen by the alignment of dlogits -- never as 240-byte-strided scalar stores.
 // LDS: 15 616 bytes of logits / gradient + 3 840 of masks + 3 072 of sums (+ 15 616 with -DBG_PPO_KEEP_E, the development build that keeps e[j] in a
 // second tile instead of calling expf again; DESIGN.md has both, measured).
-static_assert((BG_HEAD_ROWS & (BG_HEAD_ROWS - 1)) == 0 && BG_HEAD_ROWS <= BG_HEAD_BLOCK, "the sums of a workgroup go through a power-of-two tree");
 #ifdef BG_PPO_KEEP_E
 #define BG_PPO_KEEP true
 #else
@@ -336,6 +410,18 @@ __device__ __forceinline__ void bg_ppo_stage_mask_gather(const int8_t* __restric
       const long long src = index[rec0 + r];
       mk[u] = (src < 0 || src >= store_rows) ? 0u : *reinterpret_cast<const uint32_t*>(base + (size_t)src * stride + w * 4);
     }
+  }
+}
+
+// phase 1 of bg_ppo_kernel and bg_bc_kernel: the logits, and the masks flat (rows in order) or gathered through the index
+template <bool BF16>
+__device__ __forceinline__ void bg_loss_stage(const void* __restrict__ logits, int lld, uint64_t lstride, const int8_t* __restrict__ mask, int mld,
+                                              uint64_t mstride, const int32_t* __restrict__ index, long long store_rows, long long rec0, int nrow, float* lg,
+                                              uint32_t* mk) {
+  bg_head_stage_logits<BF16>(logits, lld, lstride, rec0, nrow, lg);
+  if (mld != BG_HEAD_LD_NONE) {
+    if (index) bg_ppo_stage_mask_gather(mask, mld, mstride, index, store_rows, rec0, nrow, mk);
+    else bg_head_stage_mask(mask, mld, mstride, rec0, nrow, mk);
   }
 }
 
@@ -399,38 +485,23 @@ __device__ __forceinline__ void bg_ppo_store_rows(void* __restrict__ out, int st
 __global__ __launch_bounds__(BG_PPO_LANES) void bg_ppo_adv_partials(const float* __restrict__ adv, const int32_t* __restrict__ index, long long store_rows,
                                                                     long long m, BgPpoMoments* __restrict__ part) {
   __shared__ BgPpoMoments t[BG_PPO_LANES];
-  const int r = threadIdx.x;
-  const long long i = (long long)blockIdx.x * BG_PPO_LANES + r;
+  const long long i = (long long)blockIdx.x * BG_PPO_LANES + threadIdx.x;
   BgPpoMoments v;
   v.n = 0.0; v.mean = 0.0; v.m2 = 0.0;
   if (i < m) {
     const long long src = index ? (long long)index[i] : i;
     if (!index || (src >= 0 && src < store_rows)) { v.n = 1.0; v.mean = (double)adv[src]; }
   }
-  t[r] = v;
-  __syncthreads();
-  for (int s = BG_PPO_LANES / 2; s; s >>= 1) {
-    if (r < s) t[r] = bg_ppo_merge(t[r], t[r + s]);
-    __syncthreads();
-  }
-  if (r == 0) part[blockIdx.x] = t[0];
+  bg_loss_stat_partials(v, t, part, BgPpoMerge{});
 }
 
 // one workgroup: the triples -> head[0] = mean, head[1] = std, head[2] = apply (n > 1)
 __global__ __launch_bounds__(BG_PPO_LANES) void bg_ppo_adv_combine(const BgPpoMoments* __restrict__ part, long long P, float* __restrict__ head) {
   __shared__ BgPpoMoments t[BG_PPO_LANES];
-  const int r = threadIdx.x;
-  const long long per = (P + BG_PPO_LANES - 1) / BG_PPO_LANES;
   BgPpoMoments v;
   v.n = 0.0; v.mean = 0.0; v.m2 = 0.0;
-  for (long long k = r * per; k < P && k < (r + 1) * per; k++) v = bg_ppo_merge(v, part[k]);
-  t[r] = v;
-  __syncthreads();
-  for (int s = BG_PPO_LANES / 2; s; s >>= 1) {
-    if (r < s) t[r] = bg_ppo_merge(t[r], t[r + s]);
-    __syncthreads();
-  }
-  if (r == 0) {
+  bg_loss_stat_combine(part, P, v, t, BgPpoMerge{});
+  if (threadIdx.x == 0) {
     const bool apply = t[0].n > 1.0;
     head[0] = (float)t[0].mean;
     head[1] = apply ? (float)sqrt(t[0].m2 / (t[0].n - 1.0)) : 0.0f;
@@ -446,11 +517,7 @@ __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_ppo_kernel(const BgPpoArgs A
   __shared__ double red[BG_PPO_SUMS * BG_HEAD_ROWS];
   const long long rec0 = (long long)blockIdx.x * BG_HEAD_ROWS;
   const int nrow = (int)(A.m - rec0 < BG_HEAD_ROWS ? A.m - rec0 : BG_HEAD_ROWS);
-  bg_head_stage_logits<BF16>(A.logits, A.lld, A.lstride, rec0, nrow, lg);
-  if (A.mld != BG_HEAD_LD_NONE) {
-    if (A.index) bg_ppo_stage_mask_gather(A.mask, A.mld, A.mstride, A.index, A.store_rows, rec0, nrow, mk);
-    else bg_head_stage_mask(A.mask, A.mld, A.mstride, rec0, nrow, mk);
-  }
+  bg_loss_stage<BF16>(A.logits, A.lld, A.lstride, A.mask, A.mld, A.mstride, A.index, A.store_rows, rec0, nrow, lg, mk);
   __syncthreads();
   const int r = threadIdx.x;
   double t[BG_PPO_SUMS];
@@ -477,19 +544,7 @@ __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_ppo_kernel(const BgPpoArgs A
     if (A.log_prob) A.log_prob[i] = o.log_prob;
     if (A.entropy) A.entropy[i] = o.entropy;
   }
-  if (r < BG_HEAD_ROWS) {
-#pragma unroll
-    for (int k = 0; k < BG_PPO_SUMS; k++) red[k * BG_HEAD_ROWS + r] = t[k];
-  }
-  __syncthreads();
-  for (int s = BG_HEAD_ROWS / 2; s; s >>= 1) {
-    if (r < s) {
-#pragma unroll
-      for (int k = 0; k < BG_PPO_SUMS; k++) red[k * BG_HEAD_ROWS + r] = red[k * BG_HEAD_ROWS + r] + red[k * BG_HEAD_ROWS + r + s];
-    }
-    __syncthreads();
-  }
-  if (r < BG_PPO_SUMS) A.partials[(size_t)blockIdx.x * BG_PPO_SUMS + r] = red[r * BG_HEAD_ROWS];
+  bg_loss_tile_reduce<BG_PPO_SUMS>(t, red, A.partials, blockIdx.x, BgLossSum{});
   bg_ppo_store_rows<BF16>(A.dlogits, A.dst, A.dstride, rec0, nrow, lg);
 }
 

@@ -108,6 +108,17 @@ static void bg_bool_dispatch(bool a, bool b, F launch) {
   if (a) { if (b) launch(std::true_type{}, std::true_type{}); else launch(std::true_type{}, std::false_type{}); }
   else { if (b) launch(std::false_type{}, std::true_type{}); else launch(std::false_type{}, std::false_type{}); }
 }
+// an output (nullable) is the same pointer as an input or as another output
+template <size_t NI, size_t NO>
+static bool bg_alias(const void* const (&ins)[NI], const void* const (&outs)[NO]) {
+  bool alias = false;
+  for (size_t o = 0; o < NO; o++) {
+    if (!outs[o]) continue;
+    for (size_t i = 0; i < NI; i++) alias = alias || outs[o] == ins[i];
+    for (size_t q = o + 1; q < NO; q++) alias = alias || outs[o] == outs[q];
+  }
+  return alias;
+}
 }   // extern "C++"
 
 int bg_classify_batch_ex(const uint8_t* cards_dev, const uint8_t* n_dev, uint8_t* hand_type_dev, int64_t m, int lanes_per_case,
@@ -448,11 +459,77 @@ int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logit
                       nullptr, log_prob_dev, entropy_dev, kernel_ms_out, stream);
 }
 
+// What the four loss calls (bg_ppo_loss, bg_bc_loss, bg_dqn_loss, bg_actor_ppo_loss) share.  The tests of the statistics, the workspace and a
+// gradient matrix return a verdict only: the refusal names the caller's own constant or function, so its literal stays whole with the caller.
+static bool bg_loss_bad_stats(const float* stats_dev) { return !stats_dev || ((uintptr_t)stats_dev & 3); }
+static bool bg_loss_bad_workspace(int64_t m, const void* workspace_dev, uint64_t workspace_bytes, uint64_t need) {
+  return m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < need);
+}
+static bool bg_loss_bad_matrix(const void* p, uint64_t es, uint64_t stride) { return !p || ((uintptr_t)p & (es - 1)) || stride < BG_HEAD_ACTIONS || stride > 0xffffffffull; }
+static const char* bg_loss_dlogits_args(const void* dlogits_dev, uint64_t es, uint64_t dlogits_stride_elems) {
+  if (!dlogits_dev || ((uintptr_t)dlogits_dev & (es - 1))) return "dlogits_dev must be a device pointer aligned to its element type";
+  if (dlogits_stride_elems < BG_HEAD_ACTIONS || dlogits_stride_elems > 0xffffffffull) return "dlogits_stride_elems must be >= 60";
+  return nullptr;
+}
+// m == 0: the statistics are zeros and nothing is launched
+static int bg_loss_empty(float* stats_dev, int count, hipStream_t s) {
+  BG_HIP0(hipMemsetAsync(stats_dev, 0, count * sizeof(float), s));
+  return 0;
+}
+
 // logits + the stored arrays of a rollout -> PPO's loss, diagnostics and gradient (bg_ppo.h).  Workspace: BG_PPO_WS_HEAD bytes (mean, std, apply), one
 // (n, mean, M2) triple per 256 rows, six float64 sums per 64 rows.
-uint64_t bg_ppo_loss_workspace_bytes(int64_t m) {
-  if (m <= 0) return 0;
-  return BG_PPO_WS_HEAD + bg_ppo_stat_parts(m) * sizeof(BgPpoMoments) + bg_ppo_row_parts(m) * (BG_PPO_SUMS * sizeof(double));
+uint64_t bg_ppo_loss_workspace_bytes(int64_t m) { return m > 0 ? bg_ppo_ws_bytes(m) : 0; }
+
+// What bg_ppo_loss and bg_actor_ppo_loss share beside the logits: the coefficients, and the stored arrays with the per-row outputs and the statistics.
+// Each call makes the two checks around its own (the logits, or the layer), so every bad call gets the message it got.
+struct BgPpoStored {
+  const int8_t* mask_dev; uint64_t mask_stride_bytes;
+  const int32_t* actions_dev; const float* old_log_prob_dev; const float* advantages_dev; const float* values_dev; const float* returns_dev;
+  const int32_t* index_dev; int64_t store_rows;
+  float* dvalues_dev; float* log_prob_dev; float* entropy_dev; float* stats_dev;
+};
+static const char* bg_ppo_coef_args(uint32_t flags, float clip_range, float ent_coef, float vf_coef) {
+  if (flags & ~BG_PPO_NORMALIZE_ADV) return "flags must be 0 or BG_PPO_NORMALIZE_ADV";
+  if (!(clip_range > 0.0f && clip_range < 1.0f)) return "clip_range must be in (0, 1)";
+  if (!bg_ppo_finite(ent_coef) || !bg_ppo_finite(vf_coef)) return "ent_coef and vf_coef must be finite";
+  return nullptr;
+}
+static const char* bg_ppo_stored_args(const BgPpoStored& S) {
+  if (const char* r = bg_head_mask_args(S.mask_dev, S.mask_stride_bytes)) return r;
+  if (!S.actions_dev || !S.old_log_prob_dev || !S.advantages_dev || (((uintptr_t)S.actions_dev | (uintptr_t)S.old_log_prob_dev | (uintptr_t)S.advantages_dev) & 3)) return "actions_dev, old_log_prob_dev and advantages_dev must be 4-byte aligned device pointers";
+  if ((S.values_dev == nullptr) != (S.returns_dev == nullptr)) return "values_dev and returns_dev go together: both or neither";
+  if (((uintptr_t)S.values_dev | (uintptr_t)S.returns_dev | (uintptr_t)S.index_dev | (uintptr_t)S.dvalues_dev | (uintptr_t)S.log_prob_dev | (uintptr_t)S.entropy_dev) & 3) return "values_dev, returns_dev, index_dev, dvalues_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
+  if (S.dvalues_dev && !S.values_dev) return "dvalues_dev needs values_dev and returns_dev";
+  if (S.index_dev && (S.store_rows < 0 || S.store_rows > 0x7fffffffll)) return "store_rows must be in [0, 2**31) when index_dev is given";
+  if (bg_loss_bad_stats(S.stats_dev)) return "stats_dev must be a 4-byte aligned device pointer to BG_PPO_STATS floats";
+  return nullptr;
+}
+// The kernels' arguments, but for the logits and their gradient (lld, dst and the four fields of the two matrices: the caller's), with the workspace
+// carved up: head, statistics partials, row partials.
+static BgPpoArgs bg_ppo_args(const BgPpoStored& S, int64_t m, float clip_range, float ent_coef, float vf_coef, uint32_t flags, void* workspace_dev) {
+  BgPpoArgs A;
+  A.mask = S.mask_dev; A.mstride = S.mask_stride_bytes; A.mld = bg_head_mask_path(S.mask_dev, S.mask_stride_bytes, !S.index_dev);
+  A.actions = S.actions_dev; A.old_lp = S.old_log_prob_dev; A.adv = S.advantages_dev; A.values = S.values_dev; A.returns = S.returns_dev;
+  A.index = S.index_dev; A.store_rows = (long long)S.store_rows; A.m = (long long)m;
+  A.c.clip = clip_range; A.c.lo = 1.0f - clip_range; A.c.hi = 1.0f + clip_range; A.c.ent_coef = ent_coef; A.c.vf_coef = vf_coef; A.c.fm = (float)m;
+  A.normalize = flags & BG_PPO_NORMALIZE_ADV ? 1 : 0;
+  A.dvalues = S.dvalues_dev; A.log_prob = S.log_prob_dev; A.entropy = S.entropy_dev;
+  A.head = (const float*)workspace_dev;
+  A.partials = (double*)((BgPpoMoments*)((uint8_t*)workspace_dev + BG_PPO_WS_HEAD) + bg_ppo_stat_parts(m));
+  return A;
+}
+// the launches in front of and behind the row pass: the advantage statistics (with BG_PPO_NORMALIZE_ADV), and the finish
+static void bg_ppo_launch_adv(const BgPpoArgs& A, hipStream_t s) {
+  if (!A.normalize) return;
+  float* const head = (float*)A.head;
+  BgPpoMoments* const mom = (BgPpoMoments*)((uint8_t*)head + BG_PPO_WS_HEAD);
+  const uint64_t SP = bg_ppo_stat_parts(A.m);
+  hipLaunchKernelGGL(bg_ppo_adv_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, A.adv, A.index, A.store_rows, A.m, mom);
+  hipLaunchKernelGGL(bg_ppo_adv_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, mom, (long long)SP, head);
+}
+static void bg_ppo_launch_finish(const BgPpoArgs& A, float* stats_dev, hipStream_t s) {
+  hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)bg_ppo_row_parts(A.m), A.m, A.c.ent_coef, A.c.vf_coef, A.normalize, A.head, stats_dev);
 }
 
 int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes,
@@ -464,53 +541,28 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
   const uint64_t es = bf16 ? 2u : 4u;
   const void* const ins[] = {logits_dev, mask_dev, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev};
   const void* const outs[] = {dlogits_dev, dvalues_dev, log_prob_dev, entropy_dev, stats_dev, workspace_dev};
-  bool alias = false;
-  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
-  }
+  const BgPpoStored S = {mask_dev, mask_stride_bytes, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev, store_rows,
+                         dvalues_dev, log_prob_dev, entropy_dev, stats_dev};
   const char* bad = bg_head_shape_args(logits_dtype, m);
   if (bad) {}
-  else if (flags & ~BG_PPO_NORMALIZE_ADV) bad = "flags must be 0 or BG_PPO_NORMALIZE_ADV";
-  else if (!(clip_range > 0.0f && clip_range < 1.0f)) bad = "clip_range must be in (0, 1)";
-  else if (!bg_ppo_finite(ent_coef) || !bg_ppo_finite(vf_coef)) bad = "ent_coef and vf_coef must be finite";
+  else if (const char* r = bg_ppo_coef_args(flags, clip_range, ent_coef, vf_coef)) bad = r;
   else if (const char* r = bg_head_logits_args(logits_dev, es, logits_stride_elems)) bad = r;
-  else if (!dlogits_dev || ((uintptr_t)dlogits_dev & (es - 1))) bad = "dlogits_dev must be a device pointer aligned to its element type";
-  else if (dlogits_stride_elems < BG_HEAD_ACTIONS || dlogits_stride_elems > 0xffffffffull) bad = "dlogits_stride_elems must be >= 60";
-  else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
-  else if (!actions_dev || !old_log_prob_dev || !advantages_dev || (((uintptr_t)actions_dev | (uintptr_t)old_log_prob_dev | (uintptr_t)advantages_dev) & 3)) bad = "actions_dev, old_log_prob_dev and advantages_dev must be 4-byte aligned device pointers";
-  else if ((values_dev == nullptr) != (returns_dev == nullptr)) bad = "values_dev and returns_dev go together: both or neither";
-  else if (((uintptr_t)values_dev | (uintptr_t)returns_dev | (uintptr_t)index_dev | (uintptr_t)dvalues_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "values_dev, returns_dev, index_dev, dvalues_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
-  else if (dvalues_dev && !values_dev) bad = "dvalues_dev needs values_dev and returns_dev";
-  else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
-  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_PPO_STATS floats";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_ppo_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_ppo_loss_workspace_bytes(m) bytes";
-  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  else if (const char* r = bg_loss_dlogits_args(dlogits_dev, es, dlogits_stride_elems)) bad = r;
+  else if (const char* r = bg_ppo_stored_args(S)) bad = r;
+  else if (bg_loss_bad_workspace(m, workspace_dev, workspace_bytes, bg_ppo_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_ppo_loss_workspace_bytes(m) bytes";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin("bg_ppo_loss: ", bad, kernel_ms_out)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_PPO_STATS * sizeof(float), s)); return 0; }
-  BgPpoArgs A;
+  if (m == 0) return bg_loss_empty(stats_dev, BG_PPO_STATS, s);
+  BgPpoArgs A = bg_ppo_args(S, m, clip_range, ent_coef, vf_coef, flags, workspace_dev);
   A.logits = logits_dev; A.lstride = logits_stride_elems; A.lld = bg_head_ld_path(logits_dev, logits_stride_elems, bf16);
-  A.dst = bg_head_ld_path(dlogits_dev, dlogits_stride_elems, bf16);
-  A.mask = mask_dev; A.mstride = mask_stride_bytes; A.mld = bg_head_mask_path(mask_dev, mask_stride_bytes, !index_dev);
-  A.actions = actions_dev; A.old_lp = old_log_prob_dev; A.adv = advantages_dev; A.values = values_dev; A.returns = returns_dev;
-  A.index = index_dev; A.store_rows = (long long)store_rows; A.m = (long long)m;
-  A.c.clip = clip_range; A.c.lo = 1.0f - clip_range; A.c.hi = 1.0f + clip_range; A.c.ent_coef = ent_coef; A.c.vf_coef = vf_coef; A.c.fm = (float)m;
-  A.normalize = flags & BG_PPO_NORMALIZE_ADV ? 1 : 0;
-  A.dlogits = dlogits_dev; A.dstride = dlogits_stride_elems; A.dvalues = dvalues_dev; A.log_prob = log_prob_dev; A.entropy = entropy_dev;
-  float* const head = (float*)workspace_dev;
-  BgPpoMoments* const mom = (BgPpoMoments*)((uint8_t*)workspace_dev + BG_PPO_WS_HEAD);
-  const uint64_t SP = bg_ppo_stat_parts(m), RP = bg_ppo_row_parts(m);
-  A.head = head; A.partials = (double*)(mom + SP);
+  A.dlogits = dlogits_dev; A.dstride = dlogits_stride_elems; A.dst = bg_head_ld_path(dlogits_dev, dlogits_stride_elems, bf16);
   return bg_op_run(kernel_ms_out, s, [&] {
-    if (A.normalize) {
-      hipLaunchKernelGGL(bg_ppo_adv_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, advantages_dev, index_dev, (long long)store_rows, (long long)m, mom);
-      hipLaunchKernelGGL(bg_ppo_adv_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, mom, (long long)SP, head);
-    }
-    if (bf16) hipLaunchKernelGGL((bg_ppo_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL((bg_ppo_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-    hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
+    bg_ppo_launch_adv(A, s);
+    bg_bool_dispatch(bf16, false, [&](auto BF16, auto) {
+      hipLaunchKernelGGL((bg_ppo_kernel<BF16()>), dim3((unsigned)bg_ppo_row_parts(m)), dim3(BG_HEAD_BLOCK), 0, s, A);
+    });
+    bg_ppo_launch_finish(A, stats_dev, s);
   });
 }
 
@@ -531,12 +583,6 @@ int bg_episode_outcome_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, 
                             int32_t* steps_to_end_dev, int32_t* end_ante_dev, uint8_t* end_flags_dev, double* returns_dev, float* kernel_ms_out, void* stream) {
   const void* const ins[] = {rows_dev, rewards_dev, tail_steps_dev, tail_ante_dev, tail_flags_dev, tail_return_dev};
   const void* const outs[] = {steps_to_end_dev, end_ante_dev, end_flags_dev, returns_dev};
-  bool alias = false;
-  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
-  }
   const char* bad = bg_scan_args(rows_dev, row_stride_bytes, K, N);
   if (bad) {}
   else if (!steps_to_end_dev && !end_ante_dev && !end_flags_dev && !returns_dev) bad = "at least one of steps_to_end_dev, end_ante_dev, end_flags_dev and returns_dev must be given";
@@ -545,7 +591,7 @@ int bg_episode_outcome_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, 
   else if (!(gamma == gamma)) bad = "gamma must not be NaN";
   else if (((uintptr_t)steps_to_end_dev | (uintptr_t)end_ante_dev | (uintptr_t)tail_steps_dev | (uintptr_t)tail_ante_dev) & 3) bad = "int32 arrays must be 4-byte aligned";
   else if (((uintptr_t)returns_dev | (uintptr_t)rewards_dev | (uintptr_t)tail_return_dev) & 7) bad = "float64 arrays must be 8-byte aligned";
-  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin("bg_episode_outcome_rows: ", bad, kernel_ms_out)) return rc;
   if (K == 0 || N == 0) return 0;
   const unsigned grid = (unsigned)((N + BG_GAE_ENVS - 1) / BG_GAE_ENVS);
@@ -573,29 +619,22 @@ int bg_bc_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_
   const uint64_t es = bf16 ? 2u : 4u;
   const void* const ins[] = {logits_dev, mask_dev, actions_dev, weights_dev, index_dev};
   const void* const outs[] = {dlogits_dev, log_prob_dev, entropy_dev, stats_dev, workspace_dev};
-  bool alias = false;
-  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
-  }
   const char* bad = bg_head_shape_args(logits_dtype, m);
   if (bad) {}
   else if (!bg_ppo_finite(ent_coef)) bad = "ent_coef must be finite";
   else if (const char* r = bg_head_logits_args(logits_dev, es, logits_stride_elems)) bad = r;
-  else if (!dlogits_dev || ((uintptr_t)dlogits_dev & (es - 1))) bad = "dlogits_dev must be a device pointer aligned to its element type";
-  else if (dlogits_stride_elems < BG_HEAD_ACTIONS || dlogits_stride_elems > 0xffffffffull) bad = "dlogits_stride_elems must be >= 60";
+  else if (const char* r = bg_loss_dlogits_args(dlogits_dev, es, dlogits_stride_elems)) bad = r;
   else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
   else if (!actions_dev || ((uintptr_t)actions_dev & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
   else if (actions_stride_bytes < 4 || (actions_stride_bytes & 3) || actions_stride_bytes > 0xffffffffull) bad = "actions_stride_bytes must be a multiple of 4, >= 4";
   else if (((uintptr_t)weights_dev | (uintptr_t)index_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "weights_dev, index_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
   else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
-  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_BC_STATS floats";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_bc_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_bc_loss_workspace_bytes(m) bytes";
-  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  else if (bg_loss_bad_stats(stats_dev)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_BC_STATS floats";
+  else if (bg_loss_bad_workspace(m, workspace_dev, workspace_bytes, bg_bc_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_bc_loss_workspace_bytes(m) bytes";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin("bg_bc_loss: ", bad, kernel_ms_out)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_BC_STATS * sizeof(float), s)); return 0; }
+  if (m == 0) return bg_loss_empty(stats_dev, BG_BC_STATS, s);
   const bool stat = weights_dev || index_dev;
   BgBcArgs A;
   A.logits = logits_dev; A.lstride = logits_stride_elems; A.lld = bg_head_ld_path(logits_dev, logits_stride_elems, bf16);
@@ -614,8 +653,9 @@ int bg_bc_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride_
       hipLaunchKernelGGL(bg_bc_weight_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, weights_dev, index_dev, (long long)store_rows, (long long)m, wpart);
       hipLaunchKernelGGL(bg_bc_weight_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, wpart, (long long)SP, head);
     }
-    if (bf16) hipLaunchKernelGGL((bg_bc_kernel<true>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
-    else hipLaunchKernelGGL((bg_bc_kernel<false>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+    bg_bool_dispatch(bf16, false, [&](auto BF16, auto) {
+      hipLaunchKernelGGL((bg_bc_kernel<BF16()>), dim3((unsigned)RP), dim3(BG_HEAD_BLOCK), 0, s, A);
+    });
     hipLaunchKernelGGL(bg_bc_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, A.head, stats_dev);
   });
 }
@@ -634,33 +674,26 @@ int bg_dqn_loss(const void* q_dev, uint64_t q_stride_elems, const void* q_next_d
   const uint64_t es = bf16 ? 2u : 4u;
   const void* const ins[] = {q_dev, q_next_dev, q_next_online_dev, rows_dev, next_index_dev, rewards_dev};
   const void* const outs[] = {dq_dev, td_dev, stats_dev, workspace_dev};
-  bool alias = false;
-  for (size_t o = 0; o < sizeof(outs) / sizeof(outs[0]); o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < sizeof(ins) / sizeof(ins[0]); i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < sizeof(outs) / sizeof(outs[0]); q++) alias = alias || outs[o] == outs[q];
-  }
-  auto bad_matrix = [&](const void* p, uint64_t stride) { return !p || ((uintptr_t)p & (es - 1)) || stride < BG_HEAD_ACTIONS || stride > 0xffffffffull; };
   const char* bad = nullptr;
   if (q_dtype != BG_HEAD_F32 && q_dtype != BG_HEAD_BF16) bad = "q_dtype must be BG_HEAD_F32 or BG_HEAD_BF16";
   else if (m < 0 || m > (int64_t)BG_HEAD_ROWS * 0x7fffffffll) bad = "m out of range";
   else if (flags & ~(BG_DQN_MASK_NEXT | BG_DQN_MSE | BG_DQN_TIMEOUT_EXCLUDE)) bad = "flags must be a combination of BG_DQN_MASK_NEXT, BG_DQN_MSE and BG_DQN_TIMEOUT_EXCLUDE";
   else if (!(gamma >= 0.0f && gamma <= 1.0f)) bad = "gamma must be in [0, 1]";
-  else if (bad_matrix(q_dev, q_stride_elems)) bad = "q_dev must be a device pointer aligned to its element type, q_stride_elems >= 60";
-  else if (bad_matrix(q_next_dev, q_next_stride_elems)) bad = "q_next_dev must be a device pointer aligned to its element type, q_next_stride_elems >= 60";
-  else if (q_next_online_dev && bad_matrix(q_next_online_dev, q_next_online_stride_elems)) bad = "q_next_online_dev must be aligned to its element type, q_next_online_stride_elems >= 60";
-  else if (bad_matrix(dq_dev, dq_stride_elems)) bad = "dq_dev must be a device pointer aligned to its element type, dq_stride_elems >= 60";
+  else if (bg_loss_bad_matrix(q_dev, es, q_stride_elems)) bad = "q_dev must be a device pointer aligned to its element type, q_stride_elems >= 60";
+  else if (bg_loss_bad_matrix(q_next_dev, es, q_next_stride_elems)) bad = "q_next_dev must be a device pointer aligned to its element type, q_next_stride_elems >= 60";
+  else if (q_next_online_dev && bg_loss_bad_matrix(q_next_online_dev, es, q_next_online_stride_elems)) bad = "q_next_online_dev must be aligned to its element type, q_next_online_stride_elems >= 60";
+  else if (bg_loss_bad_matrix(dq_dev, es, dq_stride_elems)) bad = "dq_dev must be a device pointer aligned to its element type, dq_stride_elems >= 60";
   else if (!rows_dev || ((uintptr_t)rows_dev & 15)) bad = "rows_dev must be a 16-byte aligned device pointer";
   else if (row_stride_bytes < BG_ROW_BYTES || (row_stride_bytes & 15) || row_stride_bytes > 0xffffffffull) bad = "row_stride_bytes must be a multiple of 16, >= BG_ROW_BYTES";
   else if (store_rows < 0 || store_rows > 0x7fffffffll) bad = "store_rows must be in [0, 2**31)";
   else if (!next_index_dev || ((uintptr_t)next_index_dev & 3)) bad = "next_index_dev must be a 4-byte aligned device pointer";
   else if (((uintptr_t)rewards_dev | (uintptr_t)td_dev) & 3) bad = "rewards_dev and td_dev must be 4-byte aligned";
-  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_DQN_STATS floats";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_dqn_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_dqn_loss_workspace_bytes(m) bytes";
-  else if (alias) bad = "outputs must not be the same pointer as an input or as another output";
+  else if (bg_loss_bad_stats(stats_dev)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_DQN_STATS floats";
+  else if (bg_loss_bad_workspace(m, workspace_dev, workspace_bytes, bg_dqn_loss_workspace_bytes(m))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_dqn_loss_workspace_bytes(m) bytes";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin("bg_dqn_loss: ", bad, kernel_ms_out)) return rc;
   hipStream_t s = (hipStream_t)stream;
-  if (m == 0) { BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_DQN_STATS * sizeof(float), s)); return 0; }
+  if (m == 0) return bg_loss_empty(stats_dev, BG_DQN_STATS, s);
   BgDqnArgs A;
   A.q = q_dev; A.qstride = q_stride_elems;
   A.qn = q_next_dev; A.nstride = q_next_stride_elems; A.nld = bg_head_ld_path(q_next_dev, q_next_stride_elems, bf16);
@@ -955,16 +988,6 @@ static const char* bg_actor_layer_args(const void* h_dev, uint64_t h_stride_elem
   if (logits_out_dev && (logits_out_stride_elems < BG_HEAD_ACTIONS || logits_out_stride_elems > 0xffffffffull)) return "logits_out_stride_elems must be >= 60";
   return nullptr;
 }
-// an output (nullable) is the same pointer as an input or as another output
-static bool bg_actor_alias(const void* const* ins, size_t ni, const void* const* outs, size_t no) {
-  bool alias = false;
-  for (size_t o = 0; o < no; o++) {
-    if (!outs[o]) continue;
-    for (size_t i = 0; i < ni; i++) alias = alias || outs[o] == ins[i];
-    for (size_t q = o + 1; q < no; q++) alias = alias || outs[o] == outs[q];
-  }
-  return alias;
-}
 static BgActorArgs bg_actor_args(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
                                  const float* bias_dev, float* logits_out_dev, uint64_t logits_out_stride_elems) {
   BgActorArgs G;
@@ -987,7 +1010,7 @@ static int bg_actor_head_call(const char* who, int mode, const void* h_dev, uint
   else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
   else if (!act || ((uintptr_t)act & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
   else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "log_prob_dev / entropy_dev must be 4-byte aligned";
-  else if (bg_actor_alias(ins, sizeof(ins) / sizeof(ins[0]), outs, sizeof(outs) / sizeof(outs[0]))) bad = "outputs must not be the same pointer as an input or as another output";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin(who, bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
   const BgActorArgs G = bg_actor_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems);
@@ -1032,12 +1055,12 @@ int bg_actor_ppo_loss(const void* h_dev, uint64_t h_stride_elems, int Hin, const
                       float* kernel_ms_out, void* stream) {
   const void* const ins[] = {h_dev, weight_dev, bias_dev, mask_dev, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev};
   const void* const outs[] = {dh_dev, dweight_dev, dbias_dev, dvalues_dev, log_prob_dev, entropy_dev, stats_dev, logits_out_dev, dlogits_out_dev, workspace_dev};
+  const BgPpoStored S = {mask_dev, mask_stride_bytes, actions_dev, old_log_prob_dev, advantages_dev, values_dev, returns_dev, index_dev, store_rows,
+                         dvalues_dev, log_prob_dev, entropy_dev, stats_dev};
   const uint64_t ds = dh_dtype == BG_ENC_F32 ? 4u : 2u;
   const char* bad = bg_head_shape_args(BG_HEAD_F32, m);
   if (bad) {}
-  else if (flags & ~BG_PPO_NORMALIZE_ADV) bad = "flags must be 0 or BG_PPO_NORMALIZE_ADV";
-  else if (!(clip_range > 0.0f && clip_range < 1.0f)) bad = "clip_range must be in (0, 1)";
-  else if (!bg_ppo_finite(ent_coef) || !bg_ppo_finite(vf_coef)) bad = "ent_coef and vf_coef must be finite";
+  else if (const char* r = bg_ppo_coef_args(flags, clip_range, ent_coef, vf_coef)) bad = r;
   else if (const char* r = bg_actor_layer_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems)) bad = r;
   else if (dh_dtype != BG_ENC_F32 && dh_dtype != BG_ENC_BF16) bad = "dh_dtype must be BG_ENC_F32 or BG_ENC_BF16";
   else if (!dh_dev || ((uintptr_t)dh_dev & (ds - 1))) bad = "dh_dev must be a device pointer aligned to its element type";
@@ -1045,48 +1068,28 @@ int bg_actor_ppo_loss(const void* h_dev, uint64_t h_stride_elems, int Hin, const
   else if (!dweight_dev || !dbias_dev || (((uintptr_t)dweight_dev | (uintptr_t)dbias_dev) & 3)) bad = "dweight_dev and dbias_dev must be 4-byte aligned device pointers";
   else if ((uintptr_t)dlogits_out_dev & 3) bad = "dlogits_out_dev must be 4-byte aligned";
   else if (dlogits_out_dev && (dlogits_out_stride_elems < BG_HEAD_ACTIONS || dlogits_out_stride_elems > 0xffffffffull)) bad = "dlogits_out_stride_elems must be >= 60";
-  else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
-  else if (!actions_dev || !old_log_prob_dev || !advantages_dev || (((uintptr_t)actions_dev | (uintptr_t)old_log_prob_dev | (uintptr_t)advantages_dev) & 3)) bad = "actions_dev, old_log_prob_dev and advantages_dev must be 4-byte aligned device pointers";
-  else if ((values_dev == nullptr) != (returns_dev == nullptr)) bad = "values_dev and returns_dev go together: both or neither";
-  else if (((uintptr_t)values_dev | (uintptr_t)returns_dev | (uintptr_t)index_dev | (uintptr_t)dvalues_dev | (uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "values_dev, returns_dev, index_dev, dvalues_dev, log_prob_dev and entropy_dev must be 4-byte aligned";
-  else if (dvalues_dev && !values_dev) bad = "dvalues_dev needs values_dev and returns_dev";
-  else if (index_dev && (store_rows < 0 || store_rows > 0x7fffffffll)) bad = "store_rows must be in [0, 2**31) when index_dev is given";
-  else if (!stats_dev || ((uintptr_t)stats_dev & 3)) bad = "stats_dev must be a 4-byte aligned device pointer to BG_PPO_STATS floats";
-  else if (m > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_act_workspace_bytes(m, Hin))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_actor_ppo_loss_workspace_bytes(m, Hin) bytes";
-  else if (bg_actor_alias(ins, sizeof(ins) / sizeof(ins[0]), outs, sizeof(outs) / sizeof(outs[0]))) bad = "outputs must not be the same pointer as an input or as another output";
+  else if (const char* r = bg_ppo_stored_args(S)) bad = r;
+  else if (bg_loss_bad_workspace(m, workspace_dev, workspace_bytes, bg_act_workspace_bytes(m, Hin))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_actor_ppo_loss_workspace_bytes(m, Hin) bytes";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin("bg_actor_ppo_loss: ", bad, kernel_ms_out)) return rc;
   hipStream_t s = (hipStream_t)stream;
   if (m == 0) {
-    BG_HIP0(hipMemsetAsync(stats_dev, 0, BG_PPO_STATS * sizeof(float), s));
     BG_HIP0(hipMemsetAsync(dweight_dev, 0, (size_t)BG_HEAD_ACTIONS * Hin * sizeof(float), s));
     BG_HIP0(hipMemsetAsync(dbias_dev, 0, BG_HEAD_ACTIONS * sizeof(float), s));
-    return 0;
+    return bg_loss_empty(stats_dev, BG_PPO_STATS, s);
   }
   const BgActorArgs G = bg_actor_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems);
-  BgPpoArgs A;
+  BgPpoArgs A = bg_ppo_args(S, m, clip_range, ent_coef, vf_coef, flags, workspace_dev);
   A.logits = nullptr; A.lstride = 0; A.lld = BG_HEAD_LD_WORD;
-  A.dst = dlogits_out_dev ? bg_head_ld_path(dlogits_out_dev, dlogits_out_stride_elems, false) : BG_HEAD_LD_WORD;
-  A.mask = mask_dev; A.mstride = mask_stride_bytes; A.mld = bg_head_mask_path(mask_dev, mask_stride_bytes, !index_dev);
-  A.actions = actions_dev; A.old_lp = old_log_prob_dev; A.adv = advantages_dev; A.values = values_dev; A.returns = returns_dev;
-  A.index = index_dev; A.store_rows = (long long)store_rows; A.m = (long long)m;
-  A.c.clip = clip_range; A.c.lo = 1.0f - clip_range; A.c.hi = 1.0f + clip_range; A.c.ent_coef = ent_coef; A.c.vf_coef = vf_coef; A.c.fm = (float)m;
-  A.normalize = flags & BG_PPO_NORMALIZE_ADV ? 1 : 0;
-  A.dlogits = dlogits_out_dev; A.dstride = dlogits_out_stride_elems; A.dvalues = dvalues_dev; A.log_prob = log_prob_dev; A.entropy = entropy_dev;
-  float* const head = (float*)workspace_dev;
-  BgPpoMoments* const mom = (BgPpoMoments*)((uint8_t*)workspace_dev + BG_PPO_WS_HEAD);
-  const uint64_t SP = bg_ppo_stat_parts(m), RP = bg_ppo_row_parts(m);
-  A.head = head; A.partials = (double*)(mom + SP);
+  A.dlogits = dlogits_out_dev; A.dstride = dlogits_out_stride_elems; A.dst = dlogits_out_dev ? bg_head_ld_path(dlogits_out_dev, dlogits_out_stride_elems, false) : BG_HEAD_LD_WORD;
   BgActorGrad R;
   R.dh = dh_dev; R.dhstride = dh_stride_elems; R.dh_bf16 = dh_dtype == BG_ENC_BF16 ? 1 : 0;
   R.part = (float*)((uint8_t*)workspace_dev + bg_act_ppo_ws_bytes(m)); R.per = bg_act_blocks_per_group(m, Hin);
   const long long groups = bg_act_groups(m, Hin);
   return bg_op_run(kernel_ms_out, s, [&] {
-    if (A.normalize) {
-      hipLaunchKernelGGL(bg_ppo_adv_partials, dim3((unsigned)SP), dim3(BG_PPO_LANES), 0, s, advantages_dev, index_dev, (long long)store_rows, (long long)m, mom);
-      hipLaunchKernelGGL(bg_ppo_adv_combine, dim3(1), dim3(BG_PPO_LANES), 0, s, mom, (long long)SP, head);
-    }
+    bg_ppo_launch_adv(A, s);
     hipLaunchKernelGGL((bg_actor_ppo_kernel<BG_PPO_SUMS>), dim3((unsigned)groups, (unsigned)bg_act_spans(Hin)), dim3(BG_ACT_BLOCK), 0, s, A, G, R);
-    hipLaunchKernelGGL(bg_ppo_finish, dim3(1), dim3(BG_PPO_LANES), 0, s, A.partials, (long long)RP, (long long)m, ent_coef, vf_coef, A.normalize, head, stats_dev);
+    bg_ppo_launch_finish(A, stats_dev, s);
     const long long items = (long long)BG_HEAD_ACTIONS * Hin + BG_HEAD_ACTIONS;
     hipLaunchKernelGGL((bg_actor_reduce_kernel<BG_HEAD_ACTIONS>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)R.part, groups, Hin, dweight_dev, dbias_dev);
   });

@@ -582,6 +582,11 @@ def _head_mask(mask, lead: tuple, device: torch.device) -> tuple:
     return mask, off, stride
 
 
+def _check_mask_aligned(mask, moff: int) -> None:
+    if mask is not None and (mask.data_ptr() + moff) % 4:
+        raise ValueError("mask must be 4-byte aligned")
+
+
 def _head_args(logits, pitch: int, mask, moff: int, mstride: int) -> tuple:
     """(logits_dev, logits_dtype, logits_stride_elems, mask_dev, mask_stride_bytes): how the head calls and the PPO loss begin."""
     return (_ptr(logits), nat.HEAD_F32 if logits.dtype == torch.float32 else nat.HEAD_BF16, C.c_uint64(pitch),
@@ -604,8 +609,7 @@ def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: in
         if tt is not None:
             _check_scan_tensor(what, tt, dt, lead, dev)
     _check_device(logits, "logits", align=0)
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
+    _check_mask_aligned(mask, moff)
     if given is None and actions is None:
         actions = torch.empty(lead, dtype=torch.int32, device=dev)
     if log_prob is None:
@@ -642,8 +646,7 @@ def _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, ind
     if actions is not None:
         _check_scan_tensor("actions", actions, torch.int32, lead, dev)
     _check_device(logits, "logits", align=0)
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
+    _check_mask_aligned(mask, moff)
     if actions is None:
         actions = torch.empty(lead, dtype=torch.int32, device=dev)
     res = (actions, None, None)
@@ -719,15 +722,59 @@ _ppo_workspaces: dict = {}
 _dqn_workspaces: dict = {}
 
 
-def _loss_workspace(cache: dict, size_fn: str, dev: torch.device, m: int) -> torch.Tensor:
-    """The workspace of a loss call over m rows, kept per (device, size) in `cache`; m == 0 needs none and loads nothing."""
+def _loss_workspace(cache: dict, size_fn: str, dev: torch.device, m: int, *more) -> torch.Tensor:
+    """The workspace of a loss call over m rows, kept per (device, size) in `cache`; m == 0 needs none and loads nothing.  more: what the size
+    function takes behind m."""
     if m == 0:
         return torch.empty(0, dtype=torch.uint8, device=dev)
-    need = int(getattr(nat.load(), size_fn)(C.c_int64(m)))
+    need = int(getattr(nat.load(), size_fn)(C.c_int64(m), *more))
     key = (dev, need)
     if key not in cache:
         cache[key] = torch.empty(need, dtype=torch.uint8, device=dev)
     return cache[key]
+
+
+def _stored_rows(lead: tuple, index, actions, mask, dev: torch.device) -> tuple:
+    """How ppo_loss, actor_ppo_loss and bc_loss begin: the shape of the STORED arrays -- that of `actions` with an index, else the minibatch's -- and
+    the mask over it -> (store, store_rows, mask, moff, mstride)."""
+    if index is not None:
+        _check_index(index, lead, dev)
+        if not isinstance(actions, torch.Tensor):
+            raise ValueError("actions must be an int32 tensor")
+        store = tuple(actions.shape)
+    else:
+        store = lead
+    store_rows = int(np.prod(store, dtype=np.int64))
+    if store_rows >= 2 ** 31:
+        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
+    return (store, store_rows, *_head_mask(mask, store, dev))
+
+
+def _check_coef(name: str, value) -> None:
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.integer, np.floating)) or not np.isfinite(value):
+        raise ValueError(f"{name} must be a finite number")
+
+
+def _ppo_inputs(lead: tuple, store: tuple, dev: torch.device, actions, old_log_prob, advantages, values, returns, clip_range, ent_coef, vf_coef) -> None:
+    """The refusals ppo_loss and actor_ppo_loss share behind `_stored_rows`: the five tensors, then the coefficients."""
+    _check_scan_tensor("actions", actions, torch.int32, store, dev)
+    _check_scan_tensor("old_log_prob", old_log_prob, torch.float32, store, dev)
+    _check_scan_tensor("advantages", advantages, torch.float32, store, dev)
+    if (values is None) != (returns is None):
+        raise ValueError("values and returns go together: both or neither")
+    if values is not None:
+        _check_scan_tensor("values", values, torch.float32, lead, dev)
+        _check_scan_tensor("returns", returns, torch.float32, store, dev)
+    for what, v in (("clip_range", clip_range), ("ent_coef", ent_coef), ("vf_coef", vf_coef)):
+        _check_coef(what, v)
+    if not 0.0 < float(np.float32(clip_range)) < 1.0:
+        raise ValueError("clip_range must be in (0, 1)")
+
+
+def _ppo_outputs(lead: tuple, values, dev: torch.device) -> tuple:
+    """(raw, dvalues, log_prob, entropy) of the two PPO calls: allocated behind their last refusal, so not part of `_ppo_inputs`."""
+    return (torch.zeros(len(nat.PPO_STATS), dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.float32, device=dev) if values is not None else None,
+            torch.empty(lead, dtype=torch.float32, device=dev), torch.empty(lead, dtype=torch.float32, device=dev))
 
 
 def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Tensor, advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
@@ -743,40 +790,14 @@ def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Te
     input, index out of range) is excluded: zero gradient, counted in stats.excluded, the divisor stays m.  values / returns: both or neither."""
     lead, m, pitch = _head_logits(logits)
     dev = logits.device
-    if index is not None:
-        _check_index(index, lead, dev)
-        if not isinstance(actions, torch.Tensor):
-            raise ValueError("actions must be an int32 tensor")
-        store = tuple(actions.shape)
-    else:
-        store = lead
-    store_rows = int(np.prod(store, dtype=np.int64))
-    if store_rows >= 2 ** 31:
-        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
-    mask, moff, mstride = _head_mask(mask, store, dev)
-    _check_scan_tensor("actions", actions, torch.int32, store, dev)
-    _check_scan_tensor("old_log_prob", old_log_prob, torch.float32, store, dev)
-    _check_scan_tensor("advantages", advantages, torch.float32, store, dev)
-    if (values is None) != (returns is None):
-        raise ValueError("values and returns go together: both or neither")
-    if values is not None:
-        _check_scan_tensor("values", values, torch.float32, lead, dev)
-        _check_scan_tensor("returns", returns, torch.float32, store, dev)
-    for what, v in (("clip_range", clip_range), ("ent_coef", ent_coef), ("vf_coef", vf_coef)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"{what} must be a finite number")
-    if not 0.0 < float(np.float32(clip_range)) < 1.0:
-        raise ValueError("clip_range must be in (0, 1)")
+    store, store_rows, mask, moff, mstride = _stored_rows(lead, index, actions, mask, dev)
+    _ppo_inputs(lead, store, dev, actions, old_log_prob, advantages, values, returns, clip_range, ent_coef, vf_coef)
     _check_device(logits, "logits", align=0)
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
+    _check_mask_aligned(mask, moff)
     lg = logits.detach()
     vals = values.detach() if values is not None else None
-    raw = torch.zeros(len(nat.PPO_STATS), dtype=torch.float32, device=dev)
+    raw, dvalues, log_prob, entropy = _ppo_outputs(lead, values, dev)
     dlogits = torch.empty(lead + (60,), dtype=logits.dtype, device=dev)
-    dvalues = torch.empty(lead, dtype=torch.float32, device=dev) if values is not None else None
-    log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
-    entropy = torch.empty(lead, dtype=torch.float32, device=dev)
     ws = _loss_workspace(_ppo_workspaces, "bg_ppo_loss_workspace_bytes", dev, m)
     args = (*_head_args(lg, pitch, mask, moff, mstride), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(vals), _ptr(returns), _ptr(index),
             C.c_int64(store_rows), C.c_int64(m), C.c_float(clip_range), C.c_float(ent_coef), C.c_float(vf_coef), C.c_uint32(nat.PPO_NORMALIZE_ADV if normalize_advantage else 0), _ptr(dlogits),
@@ -851,8 +872,7 @@ def _actor_head_call(name: str, h, weight, bias, mask, given, flags: int, seed: 
             _check_scan_tensor(what, tt, dt, lead, dev)
     lopitch = _actor_tile_out("logits_out", logits_out, lead, dev)
     _check_device(h, "h")
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
+    _check_mask_aligned(mask, moff)
     if given is None and actions is None:
         actions = torch.empty(lead, dtype=torch.int32, device=dev)
     if log_prob is None:
@@ -953,57 +973,24 @@ def actor_ppo_loss(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     fills weight.grad, bias.grad and h.grad (and so drives the network below) with nothing recomputed."""
     lead, m, hpitch, Hin, wpitch = _actor_layer(h, weight, bias)
     dev = h.device
-    if index is not None:
-        _check_index(index, lead, dev)
-        if not isinstance(actions, torch.Tensor):
-            raise ValueError("actions must be an int32 tensor")
-        store = tuple(actions.shape)
-    else:
-        store = lead
-    store_rows = int(np.prod(store, dtype=np.int64))
-    if store_rows >= 2 ** 31:
-        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
-    mask, moff, mstride = _head_mask(mask, store, dev)
-    _check_scan_tensor("actions", actions, torch.int32, store, dev)
-    _check_scan_tensor("old_log_prob", old_log_prob, torch.float32, store, dev)
-    _check_scan_tensor("advantages", advantages, torch.float32, store, dev)
-    if (values is None) != (returns is None):
-        raise ValueError("values and returns go together: both or neither")
-    if values is not None:
-        _check_scan_tensor("values", values, torch.float32, lead, dev)
-        _check_scan_tensor("returns", returns, torch.float32, store, dev)
-    for what, v in (("clip_range", clip_range), ("ent_coef", ent_coef), ("vf_coef", vf_coef)):
-        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v):
-            raise ValueError(f"{what} must be a finite number")
-    if not 0.0 < float(np.float32(clip_range)) < 1.0:
-        raise ValueError("clip_range must be in (0, 1)")
+    store, store_rows, mask, moff, mstride = _stored_rows(lead, index, actions, mask, dev)
+    _ppo_inputs(lead, store, dev, actions, old_log_prob, advantages, values, returns, clip_range, ent_coef, vf_coef)
     if dh_dtype not in (torch.float32, torch.bfloat16):
         raise ValueError("dh_dtype must be torch.float32 or torch.bfloat16")
     lopitch = _actor_tile_out("logits_out", logits_out, lead, dev)
     dlopitch = _actor_tile_out("dlogits_out", dlogits_out, lead, dev)
     _check_device(h, "h")
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
+    _check_mask_aligned(mask, moff)
     if logits_out is not None and dlogits_out is not None and logits_out.data_ptr() == dlogits_out.data_ptr() and m:
         raise ValueError("logits_out and dlogits_out must not share memory")
     hd, wd = h.detach(), weight.detach()
     bd = bias.detach() if bias is not None else None
     vals = values.detach() if values is not None else None
-    raw = torch.zeros(len(nat.PPO_STATS), dtype=torch.float32, device=dev)
+    raw, dvalues, log_prob, entropy = _ppo_outputs(lead, values, dev)
     dh = torch.empty(lead + (Hin,), dtype=dh_dtype, device=dev)
     dweight = torch.zeros((60, Hin), dtype=torch.float32, device=dev)
     dbias = torch.zeros(60, dtype=torch.float32, device=dev)
-    dvalues = torch.empty(lead, dtype=torch.float32, device=dev) if values is not None else None
-    log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
-    entropy = torch.empty(lead, dtype=torch.float32, device=dev)
-    if m == 0:
-        ws = torch.empty(0, dtype=torch.uint8, device=dev)
-    else:
-        need = int(nat.load().bg_actor_ppo_loss_workspace_bytes(C.c_int64(m), Hin))
-        key = (dev, need)
-        if key not in _actor_workspaces:
-            _actor_workspaces[key] = torch.empty(need, dtype=torch.uint8, device=dev)
-        ws = _actor_workspaces[key]
+    ws = _loss_workspace(_actor_workspaces, "bg_actor_ppo_loss_workspace_bytes", dev, m, Hin)
     args = (*_actor_head(hd, hpitch, Hin, wd, wpitch, bd, mask, moff, mstride), _ptr(actions), _ptr(old_log_prob), _ptr(advantages), _ptr(vals), _ptr(returns),
             _ptr(index), C.c_int64(store_rows), C.c_int64(m), C.c_float(clip_range), C.c_float(ent_coef), C.c_float(vf_coef),
             C.c_uint32(nat.PPO_NORMALIZE_ADV if normalize_advantage else 0), _ptr(dh), _dtype_code(dh_dtype), C.c_uint64(Hin), _ptr(dweight), _ptr(dbias),
@@ -1128,25 +1115,13 @@ def bc_loss(logits: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Te
     counted in stats.excluded.  W == 0 gives loss 0 and a zero gradient."""
     lead, m, pitch = _head_logits(logits)
     dev = logits.device
-    if index is not None:
-        _check_index(index, lead, dev)
-        if not isinstance(actions, torch.Tensor):
-            raise ValueError("actions must be an int32 tensor")
-        store = tuple(actions.shape)
-    else:
-        store = lead
-    store_rows = int(np.prod(store, dtype=np.int64))
-    if store_rows >= 2 ** 31:
-        raise ValueError("the stored arrays hold at most 2**31 - 1 rows")
-    mask, moff, mstride = _head_mask(mask, store, dev)
+    store, store_rows, mask, moff, mstride = _stored_rows(lead, index, actions, mask, dev)
     astride = _bc_actions(actions, store, dev)
     if weights is not None:
         _check_scan_tensor("weights", weights, torch.float32, store, dev)
-    if isinstance(ent_coef, bool) or not isinstance(ent_coef, (int, float, np.integer, np.floating)) or not np.isfinite(ent_coef):
-        raise ValueError("ent_coef must be a finite number")
+    _check_coef("ent_coef", ent_coef)
     _check_device(logits, "logits", align=0)
-    if mask is not None and (mask.data_ptr() + moff) % 4:
-        raise ValueError("mask must be 4-byte aligned")
+    _check_mask_aligned(mask, moff)
     lg = logits.detach()
     raw = torch.zeros(len(nat.BC_STATS), dtype=torch.float32, device=dev)
     dlogits = torch.empty(lead + (60,), dtype=logits.dtype, device=dev)
