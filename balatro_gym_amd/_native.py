@@ -84,7 +84,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_step_many_rows_progress", "bg_progress_terminal_slots",
            "bg_dqn_loss", "bg_dqn_loss_workspace_bytes", "bg_sample_actions_eps",
            "bg_episode_outcome_rows", "bg_bc_loss", "bg_bc_loss_workspace_bytes",
-           "bg_actor_sample", "bg_actor_evaluate", "bg_actor_ppo_loss", "bg_actor_ppo_loss_workspace_bytes", "bg_actor_ppo_loss_rows_per_group"]
+           "bg_actor_sample", "bg_actor_evaluate", "bg_actor_ppo_loss", "bg_actor_ppo_loss_workspace_bytes", "bg_actor_ppo_loss_rows_per_group",
+           "bg_optim_step", "bg_optim_workspace_size"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -111,6 +112,12 @@ LIN_K = 153                 # the columns of a first-layer weight that are read:
 ACTOR_HIN_MIN, ACTOR_HIN_MAX = 32, 1024   # bg_actor_*: the width of the last hidden activation, a multiple of 32
 EXT_K = 447                 # bg_extractor_rows: the columns of the "extractor" layout (416 one-hot, 10 joker ids, 21 state features)
 EXT_SPLITS = (416, 10, 21)  # the inputs of the reference's hand_net / joker_net / game_state_net first layers, in column order
+# bg_optim_step (BG_OPTIM_*; csrc/bg_optim.h): algorithms, flags, the table's geometry and the fields of the 32-byte stats block
+OPTIM_ADAM, OPTIM_RMSPROP_TF = 0, 1
+OPTIM_ALGORITHMS = {"adam": OPTIM_ADAM, "rmsprop_tf": OPTIM_RMSPROP_TF}
+OPTIM_ZERO_GRAD, OPTIM_SHADOW_ONLY = 1, 2
+OPTIM_MAX_TENSORS, OPTIM_CHUNK, OPTIM_ENTRY_BYTES, OPTIM_STATS_BYTES, OPTIM_CARRY_BYTES = 1024, 1024, 64, 32, 32
+OPTIM_STATS = ("grad_norm", "clip_coef", "skipped", "nonfinite", "step")
 NORM_COLS = 153   # BG_NORM_COLS: VecNormalize's statistics are one (mean, var) per column of the "produced" layout
 # the keys BalatroEnvFixed zero-fills (train_balatro_fixed.py:125-207), in the order of its observation space, with their element counts
 ENC_ZERO_KEYS = [("hand_one_hot", 416), ("hand_suits", 8), ("hand_ranks", 8), ("rank_counts", 13), ("suit_counts", 4), ("straight_potential", 1),
@@ -341,5 +348,8 @@ def load(build_if_missing: bool = True):
     L.bg_actor_ppo_loss_rows_per_group.argtypes = [i64, i32]
     L.bg_actor_ppo_loss.argtypes = head + [vp, vp, vp, vp, vp, vp, i64, i64, C.c_float, C.c_float, C.c_float, u32, vp, i32, u64, vp, vp, vp, vp, vp, vp, vp, u64,
                                            vp, u64, vp, u64, C.POINTER(C.c_float), vp]
+    L.bg_optim_workspace_size.restype = u64
+    L.bg_optim_workspace_size.argtypes = [i64]
+    L.bg_optim_step.argtypes = [vp, i32, i64, i32, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, u32, vp, vp, vp, C.POINTER(C.c_float), vp]
     _lib = L
     return L

@@ -1094,3 +1094,48 @@ int bg_actor_ppo_loss(const void* h_dev, uint64_t h_stride_elems, int Hin, const
     hipLaunchKernelGGL((bg_actor_reduce_kernel<BG_HEAD_ACTIONS>), dim3((unsigned)((items + 255) / 256)), dim3(256), 0, s, (const float*)R.part, groups, Hin, dweight_dev, dbias_dev);
   });
 }
+
+// every parameter tensor's gradient -> the clipped Adam / RMSpropTFLike step, the bfloat16 shadows, DQN's target update and the zeroing (bg_optim.h).
+// Read here, behind every other header, for the reason given above bg_extractor.h.
+extern "C++" {
+#include "bg_optim.h"
+}
+uint64_t bg_optim_workspace_size(int64_t chunks) { return bg_optim_ws_bytes((long long)chunks); }
+
+int bg_optim_step(const void* table_dev, int ntensors, int64_t chunks, int algo, double lr, double beta1, double beta2, double eps, double weight_decay,
+                  double max_norm, double tau, uint32_t flags, void* carry_dev, void* workspace_dev, void* stats_dev, float* kernel_ms_out, void* stream) {
+  const bool shadow_only = (flags & BG_OPTIM_SHADOW_ONLY) != 0u;
+  const char* bad = nullptr;
+  if (ntensors < 0 || ntensors > BG_OPTIM_MAX_TENSORS) bad = "ntensors must be in [0, 1024]";
+  else if (chunks < 0 || chunks > 0x7fffffffll || (ntensors == 0) != (chunks == 0) || chunks < ntensors) bad = "chunks must be the table's chunk count: in [ntensors, 2**31), 0 for an empty table";
+  else if (algo != BG_OPTIM_ADAM && algo != BG_OPTIM_RMSPROP_TF) bad = "algo must be BG_OPTIM_ADAM or BG_OPTIM_RMSPROP_TF";
+  else if (flags & ~(BG_OPTIM_ZERO_GRAD | BG_OPTIM_SHADOW_ONLY)) bad = "flags must be a combination of BG_OPTIM_ZERO_GRAD and BG_OPTIM_SHADOW_ONLY";
+  else if (!(lr >= 0.0 && lr < 1e30)) bad = "lr must be finite and >= 0";
+  else if (!(beta1 >= 0.0 && beta1 < 1.0) || !(beta2 >= 0.0 && beta2 < 1.0)) bad = "beta1 (alpha) and beta2 must be in [0, 1)";
+  else if (!(eps >= 0.0 && eps < 1e30) || !(weight_decay >= 0.0 && weight_decay < 1e30)) bad = "eps and weight_decay must be finite and >= 0";
+  else if (!(max_norm < 1e30)) bad = "max_norm must be a number below 1e30 (<= 0: no clipping)";
+  else if (!(tau >= 0.0 && tau <= 1.0)) bad = "tau must be in [0, 1]";
+  else if (ntensors && (!table_dev || ((uintptr_t)table_dev & 15))) bad = "table_dev must be a 16-byte aligned device pointer";
+  else if (ntensors && !shadow_only && (!carry_dev || ((uintptr_t)carry_dev & 7))) bad = "carry_dev must be an 8-byte aligned device pointer to 32 bytes";
+  else if (ntensors && !shadow_only && (!workspace_dev || ((uintptr_t)workspace_dev & 15))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_optim_workspace_size(chunks) bytes";
+  else if (ntensors && !shadow_only && (!stats_dev || ((uintptr_t)stats_dev & 7))) bad = "stats_dev must be an 8-byte aligned device pointer to BG_OPTIM_STATS_BYTES bytes";
+  else if (ntensors && !shadow_only && (carry_dev == stats_dev || carry_dev == workspace_dev || stats_dev == workspace_dev || table_dev == carry_dev || table_dev == workspace_dev || table_dev == stats_dev)) bad = "table, carry, workspace and stats must be four different buffers";
+  if (int rc = bg_op_begin("bg_optim_step: ", bad, kernel_ms_out)) return rc;
+  if (ntensors == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  const BgOptHyper h = bg_optim_hyper(algo, lr, beta1, beta2, eps, weight_decay, max_norm, tau, flags);
+  const BgOptTensor* const table = (const BgOptTensor*)table_dev;
+  BgOptHead* const head = (BgOptHead*)workspace_dev;
+  BgOptPart* const part = (BgOptPart*)((uint8_t*)workspace_dev + BG_OPT_WS_HEAD);
+  const dim3 grid((unsigned)chunks), block(BG_OPT_LANES);
+  return bg_op_run(kernel_ms_out, s, [&] {
+    if (shadow_only) {
+      hipLaunchKernelGGL((bg_optim_update<BG_OPTIM_ADAM, true>), grid, block, 0, s, table, ntensors, h, (const BgOptHead*)nullptr);
+      return;
+    }
+    hipLaunchKernelGGL((bg_optim_norm_partials<BG_OPT_LANES>), grid, block, 0, s, table, ntensors, part);
+    hipLaunchKernelGGL((bg_optim_combine<BG_OPT_LANES>), dim3(1), block, 0, s, (const BgOptPart*)part, (long long)chunks, h, (BgOptCarry*)carry_dev, head, (BgOptStats*)stats_dev);
+    if (algo == BG_OPTIM_ADAM) hipLaunchKernelGGL((bg_optim_update<BG_OPTIM_ADAM, false>), grid, block, 0, s, table, ntensors, h, (const BgOptHead*)head);
+    else hipLaunchKernelGGL((bg_optim_update<BG_OPTIM_RMSPROP_TF, false>), grid, block, 0, s, table, ntensors, h, (const BgOptHead*)head);
+  });
+}

@@ -263,6 +263,14 @@ def _grad_as_dout(grad: torch.Tensor) -> torch.Tensor:
     return grad.to(torch.float32).contiguous()
 
 
+def _live_shadow(module):
+    """The bfloat16 copy of `module.weight` that `RowOptimizer.attach` keeps (balatro_gym_amd/optim.py), or None: it is used only while the version
+    recorded with it is still the weight's `_version` -- any torch in-place write to the weight bumps that, and the module casts again until
+    `RowOptimizer.refresh()`.  (A write through `.data` does not bump it: call `refresh()` after one.)"""
+    wb = module.weight_bf16
+    return wb if wb is not None and module._weight_bf16_version == module.weight._version else None
+
+
 class _RowFirstLayer(torch.nn.Module):
     """What RowLinear and RowExtractor share: the constructor's checks, float32 parameters initialised as nn.Linear(in_features, out_features), and the
     copies to and from an nn.Linear."""
@@ -279,6 +287,7 @@ class _RowFirstLayer(torch.nn.Module):
         lin = torch.nn.Linear(in_features, out_features, device=device)   # nn.Linear's own initialisation
         self.weight = torch.nn.Parameter(lin.weight.detach().clone())
         self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+        self.weight_bf16, self._weight_bf16_version = None, -1   # RowOptimizer.attach: a bfloat16 copy kept by the update pass (`_live_shadow`)
 
     def _load(self, linear: torch.nn.Linear):
         with torch.no_grad():
@@ -350,8 +359,8 @@ class _RowLinearFn(torch.autograd.Function):
     """out = linear_rows(records); backward = ONE bg_linear_rows_grad call.  The records carry no gradient."""
 
     @staticmethod
-    def forward(ctx, weight, bias, rows, index, norm, layout, activation, dtype):
-        out = linear_rows(rows, weight.detach().to(torch.bfloat16), bias.detach() if bias is not None else None, index=index, norm=norm, layout=layout,
+    def forward(ctx, weight, bias, rows, index, norm, layout, activation, dtype, weight_bf16=None):
+        out = linear_rows(rows, weight_bf16 if weight_bf16 is not None else weight.detach().to(torch.bfloat16), bias.detach() if bias is not None else None, index=index, norm=norm, layout=layout,
                           activation=activation, dtype=dtype)
         ctx.save_for_backward(out)
         ctx.call = (rows, index, norm, layout, activation, tuple(weight.shape), bias is not None)
@@ -364,14 +373,15 @@ class _RowLinearFn(torch.autograd.Function):
         dweight = torch.zeros(wshape, dtype=torch.float32, device=rows.device)   # columns at or beyond 153: zero, their exact gradient
         dweight, dbias = linear_rows_grad(rows, _grad_as_dout(grad), out=out if activation == "relu" else None, index=index, norm=norm, layout=layout,
                                           activation=activation, dweight=dweight, bias=has_bias)
-        return dweight, dbias, None, None, None, None, None, None
+        return dweight, dbias, None, None, None, None, None, None, None
 
 
 class RowLinear(_RowFirstLayer):
     """The first `nn.Linear` of a policy over packed records: `forward(rows)` is `linear_rows` and its backward one `linear_rows_grad` call, so neither pass
     materialises the feature matrix.  Parameters are float32 -- weight [out_features, 628] ("fixed": SB3's MultiInputPolicy over BalatroEnvFixed) or
     [out_features, 153] ("produced"), bias [out_features] -- initialised as nn.Linear; `from_linear` / `to_linear` move them to and from an nn.Linear, so a
-    policy trained here loads into SB3's module and back.  The weight is cast to bfloat16 for every call (the master copy stays float32); columns at or
+    policy trained here loads into SB3's module and back.  The weight is cast to bfloat16 for every call (the master copy stays float32) unless
+    `RowOptimizer.attach` keeps a bfloat16 copy current; columns at or
     beyond 153 of a 628-wide weight get a zero gradient, which is their exact gradient: their inputs are zero."""
 
     def __init__(self, out_features: int, in_layout: str = "fixed", activation: Optional[str] = None, dtype: torch.dtype = torch.bfloat16, device=None):
@@ -389,7 +399,7 @@ class RowLinear(_RowFirstLayer):
     def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None) -> torch.Tensor:
         _linear_common(rows, index, norm, self.in_layout, self.activation)
         self._check_same_gpu(rows)
-        return _RowLinearFn.apply(self.weight, self.bias, rows, index, norm, self.in_layout, self.activation, self.dtype)
+        return _RowLinearFn.apply(self.weight, self.bias, rows, index, norm, self.in_layout, self.activation, self.dtype, _live_shadow(self))
 
     def extra_repr(self) -> str:
         return f"in_layout={self.in_layout!r}, out_features={self.out_features}, activation={self.activation!r}, dtype={self.dtype}"
@@ -451,9 +461,11 @@ class _RowExtractorFn(torch.autograd.Function):
     """out = extractor_rows(records); backward = ONE bg_extractor_rows_grad call.  The records carry no gradient."""
 
     @staticmethod
-    def forward(ctx, weight, bias, rows, index, activation, dtype, mask):
-        wb = torch.empty((weight.shape[0], nat.EXT_K + 1), dtype=torch.bfloat16, device=weight.device)[:, :nat.EXT_K]   # pitch 448: 16-byte lines
-        wb.copy_(weight.detach())
+    def forward(ctx, weight, bias, rows, index, activation, dtype, mask, weight_bf16=None):
+        wb = weight_bf16
+        if wb is None:
+            wb = torch.empty((weight.shape[0], nat.EXT_K + 1), dtype=torch.bfloat16, device=weight.device)[:, :nat.EXT_K]   # pitch 448: 16-byte lines
+            wb.copy_(weight.detach())
         out = extractor_rows(rows, wb, bias.detach(), index=index, activation=activation, dtype=dtype)
         ctx.save_for_backward(out)
         ctx.call = (rows, index, activation, mask)
@@ -466,14 +478,14 @@ class _RowExtractorFn(torch.autograd.Function):
         dweight, dbias = extractor_rows_grad(rows, _grad_as_dout(grad), out=out if activation == "relu" else None, index=index, activation=activation)
         if mask is not None:
             dweight.mul_(mask)
-        return dweight, dbias, None, None, None, None, None
+        return dweight, dbias, None, None, None, None, None, None
 
 
 class RowExtractor(_RowFirstLayer):
     """The first layer of a network over BalatroFeaturesExtractor's input (train_balatro_agent.py:84-119), from packed records: `forward(rows)` is
     `extractor_rows` and its backward one `extractor_rows_grad` call, so neither pass materialises the [m, 447] matrix.  Parameters are float32 --
     weight [out_features, 447], bias [out_features] -- initialised as nn.Linear(447, out_features); `from_linear` / `to_linear` move them to and from an
-    nn.Linear.  The weight is cast to bfloat16 for every call (the master copy stays float32).
+    nn.Linear.  The weight is cast to bfloat16 for every call (the master copy stays float32) unless `RowOptimizer.attach` keeps a pitch-448 copy current.
     `from_linears(hand, joker, state)` stacks the first layers of the reference's `hand_net`, `joker_net` and `game_state_net` (416, 10 and 21 inputs)
     as ONE block-structured [h + j + s, 447] weight: `.splits == (h, j, s)`, so `out.split(layer.splits, dim=1)` gives the three sub-networks'
     activations; the block mask is a buffer and multiplies dweight in backward, so off-block weights stay exactly zero under any optimiser;
@@ -532,7 +544,7 @@ class RowExtractor(_RowFirstLayer):
     def forward(self, rows: torch.Tensor, index: Optional[torch.Tensor] = None) -> torch.Tensor:
         _first_layer_common(rows, index, self.activation)
         self._check_same_gpu(rows)
-        return _RowExtractorFn.apply(self.weight, self.bias, rows, index, self.activation, self.dtype, self.block_mask)
+        return _RowExtractorFn.apply(self.weight, self.bias, rows, index, self.activation, self.dtype, self.block_mask, _live_shadow(self))
 
     def extra_repr(self) -> str:
         return f"in_features={self.in_features}, out_features={self.out_features}, splits={self.splits}, activation={self.activation!r}, dtype={self.dtype}"
@@ -963,15 +975,20 @@ def actor_ppo_loss(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
                    advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *, values: Optional[torch.Tensor] = None,
                    returns: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None, clip_range: float = 0.2, ent_coef: float = 0.0,
                    vf_coef: float = 0.5, normalize_advantage: bool = True, dh_dtype: torch.dtype = torch.bfloat16, logits_out: Optional[torch.Tensor] = None,
-                   dlogits_out: Optional[torch.Tensor] = None, timing: bool = False):
+                   dlogits_out: Optional[torch.Tensor] = None, timing: bool = False, weight_bf16: Optional[torch.Tensor] = None):
     """`ppo_loss` with the policy's last layer inside the launch (bg_actor_ppo_loss): h bfloat16 [..., Hin], weight float32 / bfloat16 [60, Hin] and
     bias float32 [60] or None in place of the logits -> (loss, `ActorPpoStats`).  Every other argument, the excluded rows and the statistics are
     `ppo_loss`'s, bit for bit on the logits this call computes (`logits_out`, float32 [..., >= 60], receives them; `dlogits_out` their float32 gradient).
     In place of dlogits the call writes stats.dh [..., Hin] (`dh_dtype`: float32, or bfloat16 = its nearest-even rounding), stats.dweight float32
     [60, Hin] and stats.dbias float32 [60], from dp = bfloat16(dlogits): dh = dp @ w, dweight = dp.T @ h, dbias = dp.sum(0).  When h, weight, bias or
     values require grad the loss carries one autograd node whose backward multiplies the stored gradients by the incoming scalar: `loss.backward()`
-    fills weight.grad, bias.grad and h.grad (and so drives the network below) with nothing recomputed."""
+    fills weight.grad, bias.grad and h.grad (and so drives the network below) with nothing recomputed.  weight_bf16: a bfloat16 [60, Hin] copy of a float32
+    `weight` that the launch reads in its place (`RowOptimizer.attach` keeps one); the gradient still belongs to `weight`."""
     lead, m, hpitch, Hin, wpitch = _actor_layer(h, weight, bias)
+    if weight_bf16 is not None:
+        if weight.dtype != torch.float32 or not isinstance(weight_bf16, torch.Tensor) or weight_bf16.dtype != torch.bfloat16:
+            raise ValueError("weight_bf16 must be a torch.bfloat16 copy of a float32 weight")
+        wpitch = _actor_layer(h, weight_bf16, bias)[4]
     dev = h.device
     store, store_rows, mask, moff, mstride = _stored_rows(lead, index, actions, mask, dev)
     _ppo_inputs(lead, store, dev, actions, old_log_prob, advantages, values, returns, clip_range, ent_coef, vf_coef)
@@ -983,7 +1000,7 @@ def actor_ppo_loss(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
     _check_mask_aligned(mask, moff)
     if logits_out is not None and dlogits_out is not None and logits_out.data_ptr() == dlogits_out.data_ptr() and m:
         raise ValueError("logits_out and dlogits_out must not share memory")
-    hd, wd = h.detach(), weight.detach()
+    hd, wd = h.detach(), weight.detach() if weight_bf16 is None else weight_bf16
     bd = bias.detach() if bias is not None else None
     vals = values.detach() if values is not None else None
     raw, dvalues, log_prob, entropy = _ppo_outputs(lead, values, dev)
@@ -1007,7 +1024,7 @@ def actor_ppo_loss(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.T
 
 class RowActor(torch.nn.Module):
     """SB3's `action_net` -- nn.Linear(in_features, 60) -- as the layer the actor calls run: float32 parameters `weight` [60, in_features] and `bias`
-    [60], initialised as nn.Linear, rounded to bfloat16 inside the launch.  in_features: a multiple of 32 in [32, 1024].  dtype: what the gradient of
+    [60], initialised as nn.Linear, rounded to bfloat16 inside the launch (or read from the bfloat16 copy `RowOptimizer.attach` keeps).  in_features: a multiple of 32 in [32, 1024].  dtype: what the gradient of
     h is written in (bfloat16, or float32 rounded by autograd afterwards).  `from_linear` / `to_linear` carry SB3's parameters both ways."""
 
     def __init__(self, in_features: int, dtype: torch.dtype = torch.bfloat16, device=None):
@@ -1021,6 +1038,7 @@ class RowActor(torch.nn.Module):
         lin = torch.nn.Linear(in_features, 60, device=device)   # nn.Linear's own initialisation
         self.weight = torch.nn.Parameter(lin.weight.detach().clone())
         self.bias = torch.nn.Parameter(lin.bias.detach().clone())
+        self.weight_bf16, self._weight_bf16_version = None, -1   # RowOptimizer.attach: a bfloat16 copy kept by the update pass (`_live_shadow`)
 
     @classmethod
     def from_linear(cls, linear: torch.nn.Linear, dtype: torch.dtype = torch.bfloat16) -> "RowActor":
@@ -1039,22 +1057,28 @@ class RowActor(torch.nn.Module):
             lin.bias.copy_(self.bias)
         return lin
 
+    def _w(self) -> torch.Tensor:
+        """What the forward-only calls read: the bfloat16 copy `RowOptimizer.attach` keeps while it is current, else the float32 weight (rounded in the launch)."""
+        wb = _live_shadow(self)
+        return wb if wb is not None else self.weight.detach()
+
     def act(self, h: torch.Tensor, mask: Optional[torch.Tensor] = None, *, seed: int, t: int, index0: int = 0, deterministic: bool = False,
             log_prob: Optional[torch.Tensor] = None, entropy: Optional[torch.Tensor] = None):
         """-> (actions, log_prob, entropy): `actor_sample` with this layer's parameters (no autograd: collection)."""
-        return actor_sample(h.detach(), self.weight.detach(), self.bias.detach(), mask, seed=seed, t=t, index0=index0, deterministic=deterministic,
+        return actor_sample(h.detach(), self._w(), self.bias.detach(), mask, seed=seed, t=t, index0=index0, deterministic=deterministic,
                             log_prob=log_prob, entropy=entropy)
 
     def evaluate(self, h: torch.Tensor, actions: torch.Tensor, mask: Optional[torch.Tensor] = None):
         """-> (log_prob, entropy): `actor_evaluate` with this layer's parameters (a forward pass)."""
-        return actor_evaluate(h.detach(), self.weight.detach(), self.bias.detach(), actions, mask)
+        return actor_evaluate(h.detach(), self._w(), self.bias.detach(), actions, mask)
 
     def ppo_loss(self, h: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Tensor, advantages: torch.Tensor, mask: Optional[torch.Tensor] = None, *,
                  values: Optional[torch.Tensor] = None, returns: Optional[torch.Tensor] = None, index: Optional[torch.Tensor] = None, clip_range: float = 0.2,
                  ent_coef: float = 0.0, vf_coef: float = 0.5, normalize_advantage: bool = True):
         """-> (loss, `ActorPpoStats`): `actor_ppo_loss` with this layer's parameters; `loss.backward()` fills weight.grad, bias.grad and h.grad."""
         return actor_ppo_loss(h, self.weight, self.bias, actions, old_log_prob, advantages, mask, values=values, returns=returns, index=index,
-                              clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, dh_dtype=self.dtype)
+                              clip_range=clip_range, ent_coef=ent_coef, vf_coef=vf_coef, normalize_advantage=normalize_advantage, dh_dtype=self.dtype,
+                              weight_bf16=_live_shadow(self))
 
     def extra_repr(self) -> str:
         return f"in_features={self.in_features}, out_features=60, dtype={self.dtype}"

@@ -1105,6 +1105,49 @@ int bg_actor_ppo_loss(const void* h_dev, uint64_t h_stride_elems, int Hin,
                       float* dlogits_out_dev /*nullable*/, uint64_t dlogits_out_stride_elems,
                       void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 
+/* ---- bg_optim_step: gradient clipping, Adam / RMSpropTFLike, the L2 term, the bfloat16 weight copies and DQN's target update, for ALL parameter
+ * tensors in three launches (csrc/bg_optim.h has the contract, the kernels and the serial twin; tests/optim_ref.py restates it in numpy).
+ * Replaces: `clip_grad_norm_(params, 0.5); optimizer.step(); optimizer.zero_grad()` of every training script of the reference (max_grad_norm 0.5;
+ * Adam with SB3's eps 1e-5 for PPO and DQN; SB3's RMSpropTFLike for `--algorithm A2C`), the per-call float32 -> bfloat16 weight casts of the first
+ * layers and the actor, and SB3's polyak_update of DQN's target network (tau 1.0 every 1000 steps).
+ *
+ * table_dev: 16-byte aligned; ntensors (<= 1024) entries of 64 bytes --
+ *     float* param, grad, state1, state2;  uint16_t* shadow (nullable);  float* target (nullable);  uint64_t numel;  uint32_t cols, pitch;
+ * every float32 array contiguous with numel elements (4-byte aligned; four 16-byte aligned pointers take the 16-byte path), shadow bfloat16 with
+ * element i at (i / cols) * pitch + i % cols, pitch >= cols >= 1 -- followed by uint32 prefix[ntensors + 1]: prefix[t] = the chunks of the tensors
+ * before t, a tensor having ceil(numel / 1024) chunks (numel >= 1).  chunks = prefix[ntensors].  The library trusts the table: it is device memory.
+ * carry_dev: 32 bytes owned by the caller's optimiser and carried from call to call: int64 step, float64 b1pow, float64 b2pow, 8 bytes unused; start it
+ * at (0, 1.0, 1.0).  workspace_dev: 16-byte aligned, bg_optim_workspace_size(chunks) bytes = 32 + 16 * chunks.  stats_dev: BG_OPTIM_STATS_BYTES bytes:
+ * float32 grad_norm, float32 clip_coef, int32 skipped, int32 0, int64 nonfinite, int64 step.
+ *     norm  = float32(sqrt(sum of (double)g * (double)g))   in THE REDUCTION ORDER of bg_ppo.h over chunks of 1 024 elements: the same bits on every run
+ *     c     = min(1, max_norm / (norm + 1e-6f)), or 1 with max_norm <= 0
+ *     a non-finite norm SKIPS the step: nothing but the gradients (BG_OPTIM_ZERO_GRAD) is written and the carried state is not advanced
+ *     g = g * c;  g = g + p * weight_decay (when non-zero)
+ *     BG_OPTIM_ADAM:        m = m + (g - m) * (1 - beta1);  v = v * beta2 + ((1 - beta2) * g) * g;  p = p + (m / (sqrt(v) / s2 + eps)) * (-a)
+ *                           a = float32(lr / (1 - beta1 ** step)), s2 = float32(sqrt(1 - beta2 ** step)), the powers carried as iterated float64 products
+ *     BG_OPTIM_RMSPROP_TF:  sq = sq * alpha + ((1 - alpha) * g) * g;  p = p + (g / sqrt(sq + eps)) * (-lr)     (state1 = sq starts at ones, state2
+ *                           unused and may be NULL; alpha travels in beta1)
+ *     shadow = bfloat16(p) to nearest even;  with tau > 0: target = target * (1 - tau) + p * tau (tau == 1: a copy);  BG_OPTIM_ZERO_GRAD: grad = 0
+ * every operation a float32 one rounded on its own.  BG_OPTIM_SHADOW_ONLY: one launch that writes the shadows from the current parameters and nothing
+ * else; carry_dev, workspace_dev and stats_dev may be NULL then.  The call never synchronises unless timing is asked for: the step count and the bias
+ * corrections live on the device.
+ * BG_E_ARG (text "bg_optim_step: ..." in bg_last_error(NULL)) before anything is launched for: ntensors outside [0, 1024]; chunks not in
+ * [ntensors, 2**31) or zero for a non-empty table; an unknown algo or flag; lr, eps or weight_decay negative or not finite; a beta outside [0, 1); tau
+ * outside [0, 1]; a NULL or misaligned block; two blocks at one address.  An empty table returns 0 and launches nothing.
+ * Out of scope: AdamW, amsgrad, momentum or centred RMSprop, parameter groups, sparse or non-float32 parameters, lr as a device scalar, multi-GPU
+ * gradient reduction. */
+#define BG_OPTIM_ADAM 0
+#define BG_OPTIM_RMSPROP_TF 1
+#define BG_OPTIM_ZERO_GRAD 1u
+#define BG_OPTIM_SHADOW_ONLY 2u
+#define BG_OPTIM_MAX_TENSORS 1024
+#define BG_OPTIM_CHUNK 1024
+#define BG_OPTIM_STATS_BYTES 32
+uint64_t bg_optim_workspace_size(int64_t chunks);
+int bg_optim_step(const void* table_dev, int ntensors, int64_t chunks, int algo, double lr, double beta1 /* RMSprop: alpha */, double beta2, double eps,
+                  double weight_decay, double max_norm, double tau, uint32_t flags, void* carry_dev, void* workspace_dev, void* stats_dev,
+                  float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
