@@ -1139,3 +1139,72 @@ int bg_optim_step(const void* table_dev, int ntensors, int64_t chunks, int algo,
     else hipLaunchKernelGGL((bg_optim_update<BG_OPTIM_RMSPROP_TF, false>), grid, block, 0, s, table, ntensors, h, (const BgOptHead*)head);
   });
 }
+
+// a finished [K + 1, N] store + a weight per candidate row -> the kept demonstration steps compacted into a device ring, and uniform draws over its
+// filled slots (bg_demo.h).  Read here, behind every other header, for the reason given above bg_extractor.h.  Workspace: BG_DEMO_WS_HEAD bytes
+// (T0 mod capacity, the drop threshold), one uint32 per chunk of 1 024 candidate rows.
+extern "C++" {
+#include "bg_demo.h"
+}
+uint64_t bg_demo_workspace_bytes(int64_t store_rows) { return bg_demo_ws_bytes(store_rows); }
+
+// [a, a + an) and [b, b + bn) share a byte
+static bool bg_demo_overlap(const void* a, uint64_t an, const void* b, uint64_t bn) {
+  return (uintptr_t)a < (uintptr_t)b + bn && (uintptr_t)b < (uintptr_t)a + an;
+}
+
+int bg_demo_append_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, const float* weights_dev, const double* returns_dev,
+                        uint8_t* demo_dev, uint64_t demo_stride_bytes, int64_t capacity, float* demo_weight_dev, int32_t* demo_source_dev,
+                        int64_t* cursor_dev, void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream) {
+  const void* const ins[] = {rows_dev, weights_dev, returns_dev};
+  const void* const outs[] = {demo_dev, demo_weight_dev, demo_source_dev, cursor_dev, workspace_dev};
+  const bool range = N >= 0 && K >= 0 && (N == 0 || (K >= 1 && (uint64_t)K * (uint64_t)N < 0x80000000ull));
+  const int64_t M = range ? (int64_t)K * N : 0;
+  const char* bad = nullptr;
+  if (!range) bad = "K must be >= 1 (with N > 0), N >= 0 and K * N < 2**31";
+  else if (capacity < 1 || capacity >= 0x80000000ll) bad = "capacity must be in [1, 2**31)";
+  else if (const char* r = bg_rows_args(rows_dev, row_stride_bytes)) bad = r;
+  else if (!demo_dev || demo_stride_bytes < BG_ROW_BYTES || (demo_stride_bytes & 15) || ((uintptr_t)demo_dev & 15) || demo_stride_bytes > 0xffffffffull) bad = "demo_dev must be 16-byte aligned and demo_stride_bytes a multiple of 16, >= BG_ROW_BYTES";
+  else if (!weights_dev || !demo_weight_dev || !cursor_dev) bad = "weights_dev, demo_weight_dev and cursor_dev must be device pointers";
+  else if (((uintptr_t)weights_dev | (uintptr_t)demo_weight_dev | (uintptr_t)demo_source_dev) & 3) bad = "weights_dev, demo_weight_dev and demo_source_dev must be 4-byte aligned";
+  else if (((uintptr_t)returns_dev | (uintptr_t)cursor_dev) & 7) bad = "returns_dev and cursor_dev must be 8-byte aligned";
+  else if (bg_demo_overlap(rows_dev, ((uint64_t)M + (uint64_t)N) * row_stride_bytes, demo_dev, (uint64_t)capacity * demo_stride_bytes)) bad = "the ring must not overlap the store";
+  else if (M > 0 && (!workspace_dev || ((uintptr_t)workspace_dev & 15) || workspace_bytes < bg_demo_ws_bytes(M))) bad = "workspace_dev must be a 16-byte aligned device buffer of bg_demo_workspace_bytes(K * N) bytes";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
+  if (int rc = bg_op_begin("bg_demo_append_rows: ", bad, kernel_ms_out)) return rc;
+  if (M == 0) return 0;
+  const int64_t chunks = (int64_t)bg_demo_chunks_of(M);
+  int64_t* const head = (int64_t*)workspace_dev;
+  uint32_t* const offs = (uint32_t*)((uint8_t*)workspace_dev + BG_DEMO_WS_HEAD);
+  BgDemoArgs A;
+  A.rows = rows_dev; A.stride = row_stride_bytes; A.N = N; A.M = M;
+  A.wbits = (const uint32_t*)weights_dev; A.vec = ((uintptr_t)weights_dev & 15) == 0 ? 1 : 0;
+  A.ret_bits = (const uint64_t*)returns_dev;
+  A.demo = demo_dev; A.dstride = demo_stride_bytes; A.capacity = capacity;
+  A.demo_weight = (uint32_t*)demo_weight_dev; A.demo_source = demo_source_dev;
+  A.head = head; A.offs = offs;
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    hipLaunchKernelGGL((bg_demo_count_kernel<BG_DEMO_LANES>), dim3((unsigned)chunks), dim3(BG_DEMO_LANES), 0, s, A.wbits, M, A.vec, offs);
+    hipLaunchKernelGGL((bg_demo_scan_kernel<BG_DEMO_LANES>), dim3(1), dim3(BG_DEMO_LANES), 0, s, offs, chunks, capacity, cursor_dev, head);
+    bg_bool_dispatch(returns_dev != nullptr, false, [&](auto R, auto) {
+      hipLaunchKernelGGL((bg_demo_scatter_kernel<R(), BG_DEMO_NT != 0>), dim3((unsigned)chunks), dim3(BG_DEMO_LANES), 0, s, A);
+    });
+  });
+}
+
+int bg_demo_sample(const int64_t* cursor_dev, int64_t capacity, uint64_t seed, uint64_t index0, uint64_t t, int32_t* index_dev, int64_t m,
+                   float* kernel_ms_out, void* stream) {
+  const char* bad = nullptr;
+  if (m < 0 || m > (int64_t)BG_DEMO_LANES * 0x7fffffffll) bad = "m out of range";
+  else if (capacity < 1 || capacity >= 0x80000000ll) bad = "capacity must be in [1, 2**31)";
+  else if (!cursor_dev || ((uintptr_t)cursor_dev & 7)) bad = "cursor_dev must be an 8-byte aligned device pointer to int64[2]";
+  else if (!index_dev || ((uintptr_t)index_dev & 3)) bad = "index_dev must be a 4-byte aligned device pointer";
+  else if ((const void*)cursor_dev == (const void*)index_dev) bad = "index_dev must not be the same pointer as cursor_dev";
+  if (int rc = bg_op_begin("bg_demo_sample: ", bad, kernel_ms_out)) return rc;
+  if (m == 0) return 0;
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    hipLaunchKernelGGL((bg_demo_sample_kernel<BG_DEMO_LANES>), dim3((unsigned)((m + BG_DEMO_LANES - 1) / BG_DEMO_LANES)), dim3(BG_DEMO_LANES), 0, s, cursor_dev, capacity, seed, index0, t, index_dev, m);
+  });
+}

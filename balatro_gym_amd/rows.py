@@ -1,5 +1,5 @@
 """The learner's side of the packed-record path: everything that works on records or logits and needs no env -- encode_rows, the linear layer,
-the masked policy head, the PPO, DQN and behaviour-cloning losses, the replay ring, GAE, the episode statistics / limits / endings / outcomes, the curriculum
+the masked policy head, the PPO, DQN and behaviour-cloning losses, the replay ring, the demonstration ring, GAE, the episode statistics / limits / endings / outcomes, the curriculum
 and VecNormalize.
 
 All of it runs in libbalatro_mi355x.so (hand-written HIP, the stateless entry points of csrc/bg_rows_api.h); torch only owns device buffers and the
@@ -1348,6 +1348,117 @@ class RowReplay:
             raise ValueError("the state's head / filled do not describe a ring of this capacity")
         self.store.copy_(state["store"])
         self._head, self._filled = head, filled
+
+
+class DemoBuffer:
+    """Behaviour cloning's data set as a ring of self-contained demo records on the device (bg_demo_append_rows / bg_demo_sample): the reference's
+    `self.expert_trajectories` (train_balatro_agent.py:220-262), which holds only the steps of the kept episodes and grows call by call.
+    `rows` uint8 [capacity, stride] (128-byte aligned), `weight` float32 [capacity], `source` int32 [capacity] (the flat index t * N + e the slot came
+    from in ITS call), `cursor` int64 [2] on the device: rows ever kept, rows kept by the last `add`.  `actions` (int32) and `returns` (float64) are
+    strided views of bytes 172..175 and 136..143 of the ring.
+    A demo record is the observation record of a kept step with the action, the terminated byte / end flags / end ante / round / chips and the
+    reward (or the return handed to `add`) of the step that FOLLOWED, so `rows` goes to `encode_rows(index=)`, `RowLinear`, `RowExtractor` and
+    `bc_loss(logits, demo.actions, demo.rows, weights=demo.weight, index=)` as it is, and the store it came from can be dropped.
+    `add` and `sample` never synchronise: the count of kept rows, the write position and the number of filled slots stay on the device.  `len(demo)` /
+    `demo.filled()` read the cursor -- the one synchronisation, for logging.
+    Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs, an expert policy."""
+
+    def __init__(self, capacity: int, device, row_stride: int = 384):
+        C_, stride = int(capacity), int(row_stride)
+        if C_ < 1 or C_ >= 2 ** 31:
+            raise ValueError("capacity must be in [1, 2**31) (int32 slot indices)")
+        if stride < nat.ROW_BYTES or stride % 16:
+            raise ValueError(f"row_stride must be a multiple of 16 and >= the {nat.ROW_BYTES}-byte record")
+        self.capacity, self.row_stride = C_, stride
+        self.device = torch.device(device if not isinstance(device, int) else f"cuda:{device}")
+        nbytes = C_ * stride
+        self._flat = torch.zeros(nbytes + 128, dtype=torch.uint8, device=self.device)
+        off = (-self._flat.data_ptr()) % 128
+        self.rows = self._flat[off:off + nbytes].view(C_, stride)
+        self.weight = torch.zeros(C_, dtype=torch.float32, device=self.device)
+        self.source = torch.full((C_,), -1, dtype=torch.int32, device=self.device)
+        self.cursor = torch.zeros(2, dtype=torch.int64, device=self.device)
+        a, r = nat.ROW_EXTRA["action"][0], nat.ROW_EXTRA["reward"][0]
+        self.actions = self.rows[:, a:a + 4].view(torch.int32)[:, 0]
+        self.returns = self.rows[:, r:r + 8].view(torch.float64)[:, 0]
+        self._workspaces: dict = {}
+
+    def filled(self) -> int:
+        """Slots that hold a record: min(rows ever kept, capacity).  Reads the cursor: a host synchronisation."""
+        return min(int(self.cursor[0].item()), self.capacity)
+
+    def __len__(self) -> int:
+        return self.filled()
+
+    def clear(self) -> None:
+        """Forget every record (the cursor returns to zero; no synchronisation)."""
+        self.cursor.zero_()
+
+    def add(self, store: torch.Tensor, weights: torch.Tensor, *, returns: Optional[torch.Tensor] = None, timing: bool = False):
+        """Append the KEPT steps of a finished store in one call of three launches, no synchronisation.  store: contiguous uint8 device tensor
+        [K + 1, N, stride] (the record before the first step in front of the K step records: `RowBuffers.to_demo`, or a chain held elsewhere);
+        candidate row (t, e), t < K, pairs observation record `store[t][e]` with `store[t + 1][e]`.  weights float32 [K, N]: a row is kept iff its
+        weight is finite and > 0 -- `(episode_outcomes(store).end_ante[1:] >= 5).float()` is the reference's filter.  returns: float64 [K, N] to
+        write into the demo records' reward field (`episode_outcomes(store).returns[1:].contiguous()`); without it the field is the step's reward.
+        Kept rows go to consecutive slots in the order of t * N + e, wrapping; of more than `capacity` kept rows the last `capacity` survive.
+        Returns None; timing=True returns the kernel milliseconds."""
+        (K1, N), stride = _check_records(store, 3)
+        K = K1 - 1
+        if N > 0 and K < 1:
+            raise ValueError("store must be [K + 1, N, stride] with K >= 1: an observation record and the record of the step taken from it")
+        if max(K, 0) * N >= 2 ** 31:
+            raise ValueError("K * N must be below 2**31 (int32 row indices)")
+        dev = store.device
+        _check_scan_tensor("weights", weights, torch.float32, (max(K, 0), N), dev)
+        if returns is not None:
+            _check_scan_tensor("returns", returns, torch.float64, (max(K, 0), N), dev)
+        if dev != self.device:
+            raise ValueError(f"the ring is on {self.device}, store is on {dev}")
+        if store.numel() and store.data_ptr() < self.rows.data_ptr() + self.rows.numel() and self.rows.data_ptr() < store.data_ptr() + store.numel():
+            raise ValueError("the ring must not overlap the store")
+        mine = {t.data_ptr() for t in (self.rows, self.weight, self.source, self.cursor)}
+        if K * N > 0 and (weights.data_ptr() in mine or (returns is not None and returns.data_ptr() in mine)):
+            raise ValueError("weights / returns must not share memory with the ring's own arrays")
+        _check_device(store, "store")
+        M = max(K, 0) * N
+        ws = _loss_workspace(self._workspaces, "bg_demo_workspace_bytes", dev, M)
+        args = (_ptr(store), C.c_uint64(stride), max(K, 0), C.c_int64(N), _ptr(weights), _ptr(returns), _ptr(self.rows), C.c_uint64(self.row_stride),
+                C.c_int64(self.capacity), _ptr(self.weight), _ptr(self.source), _ptr(self.cursor), _ptr(ws), C.c_uint64(ws.numel()))
+        kernel_ms = _native_call("bg_demo_append_rows", dev, args, (), timing, empty=M == 0)   # () or (ms,)
+        return kernel_ms[0] if kernel_ms else None
+
+    def sample(self, m: int, *, seed: int, t: int, index0: int = 0, timing: bool = False):
+        """int32 [m] on the device: uniform draws over the filled slots from the counter hash of `sample_actions` over (seed, index0 + i, t), so a
+        draw does not depend on m.  An empty ring gives -1 on every row, the index `bc_loss` excludes and `encode_rows` zeroes.  No synchronisation.
+        timing=True returns (index, kernel milliseconds)."""
+        m = int(m)
+        if m < 0:
+            raise ValueError("m must be >= 0")
+        for name, v in (("seed", seed), ("t", t), ("index0", index0)):
+            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 64:
+                raise ValueError(f"{name} must be an integer in [0, 2**64)")
+        _check_device(self.cursor, "the ring", align=0)
+        index = torch.empty(m, dtype=torch.int32, device=self.device)
+        args = (_ptr(self.cursor), C.c_int64(self.capacity), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), _ptr(index), C.c_int64(m))
+        return _native_call("bg_demo_sample", self.device, args, index, timing, empty=m == 0)
+
+    def state_dict(self) -> dict:
+        return {"rows": self.rows.clone(), "weight": self.weight.clone(), "source": self.source.clone(), "cursor": self.cursor.clone(),
+                "capacity": self.capacity, "row_stride": self.row_stride}
+
+    def load_state_dict(self, state: dict) -> None:
+        shape = (int(state["capacity"]), int(state["row_stride"]))
+        if shape != (self.capacity, self.row_stride):
+            raise ValueError(f"the state is of a ring {list(shape)}, this one is {[self.capacity, self.row_stride]}")
+        cursor = torch.as_tensor(state["cursor"])
+        if cursor.dtype != torch.int64 or tuple(cursor.shape) != (2,):
+            raise ValueError("the state's cursor must be int64 [2]")
+        if int(cursor[0]) < 0 or not 0 <= int(cursor[1]) <= int(cursor[0]):
+            raise ValueError("the state's cursor must hold 0 <= rows kept by the last call <= rows ever kept")
+        self.rows.copy_(state["rows"])
+        self.weight.copy_(state["weight"])
+        self.source.copy_(state["source"])
+        self.cursor.copy_(cursor)
 
 
 def _check_scan_tensor(name: str, t, dtype: torch.dtype, shape: tuple, device: torch.device):

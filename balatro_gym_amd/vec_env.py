@@ -16,7 +16,7 @@ import torch
 
 from . import _native as nat
 # the learner's calls over records and logits live in rows.py; every name that used to be defined here stays importable from here
-from .rows import (ActorPpoStats, BcStats, DqnStats, EpisodeLimits, EpisodeOutcomes, EpisodeStats, PpoStats, ProgressionRewards, RowActor, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
+from .rows import (ActorPpoStats, BcStats, DemoBuffer, DqnStats, EpisodeLimits, EpisodeOutcomes, EpisodeStats, PpoStats, ProgressionRewards, RowActor, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
                    RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, actor_evaluate, actor_ppo_loss, actor_sample, bc_loss, dqn_loss, encode_rows, episode_ends, episode_outcomes, evaluate_actions,
                    extractor_rows, extractor_rows_grad, gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
 
@@ -201,6 +201,19 @@ class RowBuffers:
         steps): steps to the episode's end, its final ante and end flags, the discounted return.  `(outcomes.end_ante >= 5).float()` is the
         reference's behaviour-cloning filter as `bc_loss(weights=)` takes it."""
         return episode_outcomes(self.rows, gamma, rewards=rewards, tail=tail, want=want, timing=timing)
+
+    def to_demo(self, demo: "DemoBuffer", first_record: torch.Tensor, weights: torch.Tensor, *, returns: Optional[torch.Tensor] = None,
+                timing: bool = False):
+        """Append the kept steps of these records to a `DemoBuffer` (`demo.add`: three launches, no synchronisation).  first_record: the record
+        BEFORE the first step ([n, stride]: `env.obs_rows` as it stood before `step_many`); it is put in front of the K step records so that candidate
+        row (t, e) pairs the observation of decision t with the step taken from it.  THAT IS A FULL COPY of these records into a new [steps + 1, n] store
+        on every call (2.5 GB at 65 536 x 100: more memory and traffic than the append itself): a convenience for small rollouts.  The path without
+        the copy is a [K + 1, N] store that the rollout is written into behind its first record, handed to `demo.add` as it is.  weights float32
+        [steps, n], returns float64 [steps, n] or None: as `DemoBuffer.add`."""
+        if not isinstance(first_record, torch.Tensor) or first_record.dtype != torch.uint8 or tuple(first_record.shape) != (self.n, self.row_stride) \
+                or first_record.device != self.rows.device:
+            raise ValueError(f"first_record must be a uint8 tensor [{self.n}, {self.row_stride}] of packed records on {self.rows.device}")
+        return demo.add(torch.cat([first_record[None], self.rows]), weights, returns=returns, timing=timing)
 
     def _view(self, off: int, dt: str, shape) -> torch.Tensor:
         item = np.dtype(dt).itemsize

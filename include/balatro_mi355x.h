@@ -852,7 +852,7 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
  * bg_bc_loss_workspace_bytes(m) bytes.  BG_E_ARG (text "bg_bc_loss: ..." in bg_last_error(NULL)) before anything is launched for: wrong alignment, a
  * stride < 60, an actions stride that is no multiple of 4, an output that is the same pointer as an input or another output, a non-finite ent_coef, a
  * workspace too small.  m == 0 writes zeros to stats_dev and launches nothing else.  Never synchronises unless timing is asked for.
- * Out of scope: label smoothing, an L2 term (the optimiser's weight decay), a demonstration ring (a ring of records plus a weight array serves). */
+ * Out of scope: label smoothing, an L2 term (the optimiser's weight decay), the expert policy itself (the demonstration ring is bg_demo_append_rows). */
 int bg_episode_outcome_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double gamma,
                             const double* rewards_dev /*nullable*/,
                             const int32_t* tail_steps_dev /*nullable*/, const int32_t* tail_ante_dev /*nullable*/,
@@ -1147,6 +1147,51 @@ uint64_t bg_optim_workspace_size(int64_t chunks);
 int bg_optim_step(const void* table_dev, int ntensors, int64_t chunks, int algo, double lr, double beta1 /* RMSprop: alpha */, double beta2, double eps,
                   double weight_decay, double max_norm, double tau, uint32_t flags, void* carry_dev, void* workspace_dev, void* stats_dev,
                   float* kernel_ms_out, void* stream);
+
+/* ---- bg_demo_append_rows / bg_demo_sample: the kept demonstration steps of a finished store, compacted into a ring of self-contained records on the
+ * device (csrc/bg_demo.h has the contract, the kernels and the serial twin; tests/demo_ref.py restates it in numpy).
+ * Replaces: `self.expert_trajectories` of the reference's `BehavioralCloning` (train_balatro_agent.py:220-262) -- a dense data set that holds only the
+ * steps of the kept episodes and grows call by call -- and the torch composite that would build it (`nonzero()`, which synchronises the host on the
+ * count, two gathers of records through int64 indices, the patch copies and a ring write with wrap).
+ *
+ * rows_dev: the [K + 1, N] store of records (row_stride_bytes a multiple of 16, >= BG_ROW_BYTES).  Candidate row i = t * N + e, 0 <= t < K, pairs the
+ * observation record store[t][e] with the next record store[t + 1][e].  weights_dev float32 [K * N]: row i is KEPT iff its weight is finite and > 0.
+ * All of the call is integer work and is held bit for bit:
+ *     kept = the kept rows of the call;  T0 = cursor[0] before it;  the rank r of a kept row = the number of kept rows with a smaller i
+ *     the kept row of rank r goes to slot (T0 + r) mod capacity
+ *     kept > capacity: the rows of rank r < kept - capacity are written nowhere -- the last `capacity` kept rows survive, no two meet in a slot
+ *     afterwards cursor[0] = T0 + kept, cursor[1] = kept;  the ring holds min(cursor[0], capacity) records
+ *     the record written = bytes 0..351 of the observation record with three fields of the step that followed:
+ *         bytes 136..143 (BG_ROW_REWARD)  returns_dev[i] (float64 [K * N], nullable), else the next record's reward
+ *         bytes 172..175 (BG_ROW_ACTION)  the next record's
+ *         bytes 342..351 (BG_ROW_TERMINATED, BG_ROW_END_FLAGS, BG_ROW_END_ANTE, BG_ROW_END_ROUND, BG_ROW_END_CHIPS)  the next record's
+ *     bytes 340..341 (boss_blind_active, boss_blind_type) are observation and stay;  bytes 352 and above of a ring slot are never written
+ *     demo_weight_dev[slot] = weights_dev[i];  demo_source_dev[slot] = i (int32 [capacity], nullable)
+ * A demo record is self-contained: the ring goes to bg_encode_rows_ex / bg_linear_rows / bg_extractor_rows as rows_dev, and to bg_bc_loss as mask_dev
+ * (demo_dev + BG_ROW_ACTION_MASK, the ring's stride) and actions_dev (demo_dev + BG_ROW_ACTION, the ring's stride), with demo_weight_dev as weights.
+ * cursor_dev: int64[2] on the device, carried by the caller from call to call (start it at zeros; cursor[0] >= 0); it never leaves the device.
+ * workspace_dev: 16-byte aligned, bg_demo_workspace_bytes(K * N) bytes = 16 + 4 per 1 024 candidate rows, rounded up to 16.
+ * Three launches (count per chunk, one scan, scatter per chunk), no atomics: two calls on the same inputs give the same bytes.  Never synchronises
+ * unless timing is asked for.  N == 0 is a no-op.  BG_E_ARG (text "bg_demo_append_rows: ..." in bg_last_error(NULL)) before anything is launched
+ * for: K < 1 with N > 0; K * N >= 2**31; capacity outside [1, 2**31); a stride below BG_ROW_BYTES or no multiple of 16; a record pointer that is not
+ * 16-byte aligned; the ring overlapping the store; an output that is the same pointer as an input or another output; a workspace too small; a NULL
+ * required pointer.
+ *
+ * bg_demo_sample: m uniform draws over the ring's filled slots, on the device.  filled = min(cursor[0], capacity);
+ *     index[i] = (int32)(((uint64)h * filled) >> 32),  h = the counter hash of bg_sample_actions over (seed, index0 + i, t)
+ * so a draw depends on (seed, index0 + i, t) alone, whatever m.  filled == 0 gives -1 on every row: the index bg_bc_loss excludes and
+ * bg_encode_rows_ex zeroes.  The multiply-high draw is biased by at most filled / 2**32 per slot.  The slots of a full ring are all equally old as far
+ * as a learner cares: the draw is over slots, not over age.
+ * Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs, an expert policy. */
+uint64_t bg_demo_workspace_bytes(int64_t store_rows);
+int bg_demo_append_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
+                        const float* weights_dev, const double* returns_dev /*nullable*/,
+                        uint8_t* demo_dev, uint64_t demo_stride_bytes, int64_t capacity,
+                        float* demo_weight_dev, int32_t* demo_source_dev /*nullable*/,
+                        int64_t* cursor_dev /* int64[2] */,
+                        void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
+int bg_demo_sample(const int64_t* cursor_dev, int64_t capacity, uint64_t seed, uint64_t index0, uint64_t t,
+                   int32_t* index_dev, int64_t m, float* kernel_ms_out, void* stream);
 
 #ifdef __cplusplus
 }
