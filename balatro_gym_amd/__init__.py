@@ -8,12 +8,12 @@ from .constants import Action, Phase  # noqa: F401
 
 __all__ = ["Action", "Phase", "BalatroEnv", "BalatroVecEnv", "BalatroSB3VecEnv", "ShardedBalatroVecEnv", "make_balatro_env",
            "shard_range", "classify_batch", "score_hand_batch", "sim_evaluate_batch", "sim_score_batch", "encode_rows",
-           "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "RowOptimizer", "OptimStats", "DemoBuffer"]
+           "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "RowOptimizer", "OptimStats", "DemoBuffer", "expert_actions"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch / the GPU
     if name in ("BalatroVecEnv", "ObsBuffers", "RowBuffers", "classify_batch", "score_hand_batch", "sim_evaluate_batch", "sim_score_batch", "encode_rows",
-                "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "PpoStats", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "DemoBuffer"):
+                "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "PpoStats", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "DemoBuffer", "expert_actions"):
         from . import vec_env
         return getattr(vec_env, name)
     if name in ("RowOptimizer", "OptimStats"):

@@ -86,7 +86,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_episode_outcome_rows", "bg_bc_loss", "bg_bc_loss_workspace_bytes",
            "bg_actor_sample", "bg_actor_evaluate", "bg_actor_ppo_loss", "bg_actor_ppo_loss_workspace_bytes", "bg_actor_ppo_loss_rows_per_group",
            "bg_optim_step", "bg_optim_workspace_size",
-           "bg_demo_append_rows", "bg_demo_sample", "bg_demo_workspace_bytes"]
+           "bg_demo_append_rows", "bg_demo_sample", "bg_demo_workspace_bytes",
+           "bg_expert_actions", "bg_expert_actions_ex"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -356,5 +357,7 @@ def load(build_if_missing: bool = True):
     L.bg_demo_workspace_bytes.argtypes = [i64]
     L.bg_demo_append_rows.argtypes = [vp, u64, i32, i64, vp, vp, vp, u64, i64, vp, vp, vp, vp, u64, C.POINTER(C.c_float), vp]
     L.bg_demo_sample.argtypes = [vp, i64, u64, u64, u64, vp, i64, C.POINTER(C.c_float), vp]
+    L.bg_expert_actions.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp]
+    L.bg_expert_actions_ex.argtypes = [vp, i64, i64, vp, i64, vp, vp, i32, C.POINTER(C.c_float), vp]
     _lib = L
     return L

@@ -36,7 +36,7 @@
 //   stats        BG_BC_STATS floats: loss, nll_loss, entropy_loss, accuracy, weight_sum (= float(W)), excluded, m.
 // TREE and SLICES-THEN-TREE are bg_ppo.h's.  No floating-point atomics, and the launch sequence is fixed (weight partials, combine, rows, finish), so
 // the result is a function of the arguments alone: two calls give the same bits.  expf / logf as in bg_head.h.
-// Out of scope: label smoothing, an L2 term (the optimiser's weight decay), the expert policy itself (the demonstration ring is bg_demo.h).
+// Out of scope: label smoothing, an L2 term (the optimiser's weight decay), (the demonstration ring is bg_demo.h; the expert policy is bg_expert_actions, bg_expert.h).
 #ifndef BG_BC_H
 #define BG_BC_H
 #if defined(BG_BC_HOST) && !defined(BG_PPO_HOST)

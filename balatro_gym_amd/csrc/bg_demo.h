@@ -37,7 +37,7 @@
 //
 // The per-row functions are plain C++ behind BG_HEAD_FN: define BG_DEMO_HOST before including and the text the GPU runs compiles with g++, with a
 // serial twin of the three launches (bg_demo_append_host) and of the draw (bg_demo_sample_host).
-// Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs, an expert policy.
+// Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs.  (The expert policy that fills the ring is bg_expert_actions, bg_expert.h.)
 #ifndef BG_DEMO_H
 #define BG_DEMO_H
 #if defined(BG_DEMO_HOST) && !defined(BG_HEAD_HOST)

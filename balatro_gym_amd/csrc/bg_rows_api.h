@@ -1208,3 +1208,44 @@ int bg_demo_sample(const int64_t* cursor_dev, int64_t capacity, uint64_t seed, u
     hipLaunchKernelGGL((bg_demo_sample_kernel<BG_DEMO_LANES>), dim3((unsigned)((m + BG_DEMO_LANES - 1) / BG_DEMO_LANES)), dim3(BG_DEMO_LANES), 0, s, cursor_dev, capacity, seed, index0, t, index_dev, m);
   });
 }
+
+// packed records -> the scripted expert's action per record (bg_expert.h): stateless, one launch, one store per output per record.  Read here, behind
+// every other header, for the reason given above bg_extractor.h.  lanes_per_record: the lane group that shares a record's subsets
+// (bg_expert_kernel<G>); 0 = bg_expert_lanes(m), the measured choice.
+extern "C++" {
+#include "bg_expert.h"
+}
+int bg_expert_actions_ex(const void* rows_dev, int64_t row_stride_bytes, int64_t m, const int32_t* index_dev, int64_t store_rows, int32_t* actions_dev,
+                         int32_t* detail_dev, int lanes_per_record, float* kernel_ms_out, void* stream) {
+  const void* const ins[] = {rows_dev, index_dev};
+  const void* const outs[] = {actions_dev, detail_dev};
+  const uint64_t span = store_rows > 0 && row_stride_bytes > 0 ? (uint64_t)store_rows * (uint64_t)row_stride_bytes : 0;
+  const char* bad = nullptr;
+  if (m < 0 || m >= 0x80000000ll) bad = "m must be in [0, 2**31)";
+  else if (store_rows < 0 || store_rows > 0x7fffffffffffll) bad = "store_rows must be in [0, 2**47)";
+  else if (index_dev && store_rows > 0x7fffffffll) bad = "store_rows must be in [0, 2**31) when index_dev is given";
+  else if (!index_dev && m > store_rows) bad = "m must be <= store_rows when index_dev is NULL";
+  else if (row_stride_bytes < 0) bad = "rows_dev must be 16-byte aligned and row_stride_bytes a multiple of 16, >= BG_ROW_BYTES";
+  else if (const char* r = bg_rows_args(rows_dev, (uint64_t)row_stride_bytes)) bad = r;
+  else if ((uintptr_t)index_dev & 3) bad = "index_dev must be 4-byte aligned";
+  else if (!actions_dev || (((uintptr_t)actions_dev | (uintptr_t)detail_dev) & 3)) bad = "actions_dev must be a 4-byte aligned device pointer (detail_dev 4-byte aligned)";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as each other";
+  else if (bg_demo_overlap(rows_dev, span, actions_dev, (uint64_t)m * 4u) || (detail_dev && bg_demo_overlap(rows_dev, span, detail_dev, (uint64_t)m * 4u))) bad = "outputs must not overlap the records";
+  else if (lanes_per_record != 0 && lanes_per_record != 1 && lanes_per_record != 8 && lanes_per_record != 64) bad = "lanes_per_record must be 0, 1, 8 or 64";
+  if (int rc = bg_op_begin("bg_expert_actions: ", bad, kernel_ms_out)) return rc;
+  if (m == 0) return 0;
+  const int G = lanes_per_record ? lanes_per_record : bg_expert_lanes(m);
+  const unsigned grid = (unsigned)(((uint64_t)m * (uint64_t)G + BG_EXPERT_BLOCK - 1) / BG_EXPERT_BLOCK);
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    bg_enc_pick<1, 8, 64>(G, [&](auto LG) {
+      bg_bool_dispatch(detail_dev != nullptr, false, [&](auto D, auto) {
+        hipLaunchKernelGGL((bg_expert_kernel<LG(), D()>), dim3(grid), dim3(BG_EXPERT_BLOCK), 0, s, (const uint8_t*)rows_dev, (uint64_t)row_stride_bytes, (long long)m, index_dev, (long long)store_rows, actions_dev, detail_dev);
+      });
+    });
+  });
+}
+int bg_expert_actions(const void* rows_dev, int64_t row_stride_bytes, int64_t m, const int32_t* index_dev, int64_t store_rows, int32_t* actions_dev,
+                      int32_t* detail_dev, void* stream) {
+  return bg_expert_actions_ex(rows_dev, row_stride_bytes, m, index_dev, store_rows, actions_dev, detail_dev, 0, nullptr, stream);
+}

@@ -1361,7 +1361,7 @@ class DemoBuffer:
     `bc_loss(logits, demo.actions, demo.rows, weights=demo.weight, index=)` as it is, and the store it came from can be dropped.
     `add` and `sample` never synchronise: the count of kept rows, the write position and the number of filled slots stay on the device.  `len(demo)` /
     `demo.filled()` read the cursor -- the one synchronisation, for logging.
-    Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs, an expert policy."""
+    Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs.  The expert policy that fills the ring is `expert_actions`."""
 
     def __init__(self, capacity: int, device, row_stride: int = 384):
         C_, stride = int(capacity), int(row_stride)
@@ -1500,6 +1500,52 @@ def gae_rows(rows: torch.Tensor, values: torch.Tensor, last_values: torch.Tensor
             _ptr(returns))
     name, args = ("bg_gae_rows", args) if rewards is None else ("bg_gae_rows_ex", args + (_ptr(rewards),))
     return _native_call(name, dev, args, (advantages, returns), timing, empty=K * N == 0)   # (empty: an empty tensor has no pointer to hand over)
+
+
+def expert_actions(rows: torch.Tensor, *, index: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, detail=None, timing: bool = False,
+                   lanes: int = 0):
+    """The scripted expert's action for every packed record, in one launch (bg_expert_actions; csrc/bg_expert.h has the rule): blind select takes the
+    first valid of 45, 46, 47; the shop buys the cheapest valid joker, else leaves; a pack is skipped; in play every subset of up to five hand cards
+    is valued as (base chips at the hand's level + card chips) * base mult, the best one is selected card by card and played -- or, when a discard
+    is worth more, the five cheapest other cards are selected and discarded.  Stateless: a pure function of one record.
+
+    rows: a contiguous uint8 device tensor [m, stride] or [K, N, stride] -> int32 actions [m] or [K, N] (`out`: a contiguous int32 tensor of that
+    shape to fill).  index: contiguous int32 [j] of record numbers into the flattened rows -> actions [j]; an entry outside the store gives -1.
+    detail: True, or a contiguous int32 tensor of the actions' shape, also returns the detail word per record -- bits 0-7 the slot mask the expert
+    is selecting towards, 8-11 the best subset's hand type, 12 discard mode, 13 the fallback was used, 16-31 the subset's value -- as
+    (actions, detail).  An action of -1 (no valid action, or an index outside the store) is invalid to every step call and excluded by `bc_loss`.
+    Two uses: `env.expert_act()` in a collection loop fills a `DemoBuffer` with no network and no host round trip; `expert_actions(store[:K])`
+    relabels a finished store of the learner's own states for `bc_loss(actions=)` (DAgger).  lanes: the lane group per record (0: the library's
+    choice; 1, 8, 64: the mappings measured in profiles/expert_rows.txt)."""
+    lead, stride = _check_records(rows)
+    if len(lead) not in (1, 2):
+        raise ValueError("rows must be a contiguous uint8 tensor [m, stride] or [K, N, stride] of packed records")
+    store = 1
+    for d in lead:
+        store *= int(d)
+    dev = rows.device
+    if index is not None:
+        _check_index(index, None, dev)
+        lead = (int(index.numel()),)
+    m = 1
+    for d in lead:
+        m *= int(d)
+    for name, t in (("out", out), ("detail", detail)):
+        if t is None or (name == "detail" and isinstance(t, bool)):
+            continue
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.int32 or tuple(t.shape) != lead or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"{name} must be a contiguous int32 tensor of shape {list(lead)} on {dev}" + (", True or None" if name == "detail" else ""))
+    if lanes not in (0, 1, 8, 64):
+        raise ValueError("lanes must be 0, 1, 8 or 64")
+    _check_device(rows)
+    if out is None:
+        out = torch.empty(lead, dtype=torch.int32, device=dev)
+    if detail is True:
+        detail = torch.empty(lead, dtype=torch.int32, device=dev)
+    elif detail is False:
+        detail = None
+    args = (_ptr(rows), C.c_int64(stride), C.c_int64(m), _ptr(index), C.c_int64(store), _ptr(out), _ptr(detail), int(lanes))
+    return _native_call("bg_expert_actions_ex", dev, args, out if detail is None else (out, detail), timing, empty=m == 0)
 
 
 OUTCOME_FIELDS = {"steps_to_end": torch.int32, "end_ante": torch.int32, "end_flags": torch.uint8, "returns": torch.float64}

@@ -17,7 +17,7 @@ import torch
 from . import _native as nat
 # the learner's calls over records and logits live in rows.py; every name that used to be defined here stays importable from here
 from .rows import (ActorPpoStats, BcStats, DemoBuffer, DqnStats, EpisodeLimits, EpisodeOutcomes, EpisodeStats, PpoStats, ProgressionRewards, RowActor, RowCurriculum, RowExtractor, RowLinear, RowNormalizer,  # noqa: F401
-                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, actor_evaluate, actor_ppo_loss, actor_sample, bc_loss, dqn_loss, encode_rows, episode_ends, episode_outcomes, evaluate_actions,
+                   RowReplay, _check_scan_tensor, _dqn_workspaces, _ppo_workspaces, actor_evaluate, actor_ppo_loss, actor_sample, bc_loss, dqn_loss, encode_rows, episode_ends, episode_outcomes, evaluate_actions, expert_actions,
                    extractor_rows, extractor_rows_grad, gae_rows, linear_rows, linear_rows_grad, ppo_loss, sample_actions)
 
 _TORCH_DT = {"int8": torch.int8, "int16": torch.int16, "int32": torch.int32, "int64": torch.int64,
@@ -161,6 +161,11 @@ class RowBuffers:
         required): the mask a record carries is the one after its step, i.e. the mask of the action to take next.  epsilon= gives the
         epsilon-greedy actions of `sample_actions(epsilon=)` instead: (actions, None, None)."""
         return sample_actions(logits, self.rows[step], **kwargs)
+
+    def expert(self, step: int = -1, **kwargs):
+        """The scripted expert's int32 [n] actions for the decisions of record row `step` (`expert_actions`; out=, detail=, timing= as there): the
+        record after a step holds the observation and mask of the next decision, so this is the action to take next."""
+        return expert_actions(self.rows[step], **kwargs)
 
     def bootstrap_rewards(self, limits: "EpisodeLimits", terminal_values: torch.Tensor, gamma: float = 0.99,
                           rewards: Optional[torch.Tensor] = None) -> torch.Tensor:
@@ -313,6 +318,13 @@ class BalatroVecEnv:
         receive what PPO stores.  epsilon: epsilon-greedy over `logits` as Q values instead (`sample_actions(epsilon=)`: DQN's exploration, per env)."""
         mask = self._rowbuf.rows[0] if self._rowbuf is not None else self._obs.tensors["action_mask"]
         return sample_actions(logits, mask, seed=seed, t=t, deterministic=deterministic, log_prob=log_prob, entropy=entropy, epsilon=epsilon)[0]
+
+    def expert_act(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """int32 [N] actions for `step()` from the scripted expert over the live records of an obs_layout="rows" env (`expert_actions`): the place of
+        `act(logits, ...)` in a collection loop that needs no network.  Never an invalid action while the mask has a valid one."""
+        if self._rowbuf is None:
+            raise ValueError("expert_act() reads the packed records of an obs_layout='rows' env")
+        return expert_actions(self._rowbuf.rows[0], out=out)
 
     @property
     def obs_flat(self) -> torch.Tensor:

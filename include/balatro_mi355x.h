@@ -852,7 +852,7 @@ int bg_ppo_loss(const void* logits_dev, int logits_dtype, uint64_t logits_stride
  * bg_bc_loss_workspace_bytes(m) bytes.  BG_E_ARG (text "bg_bc_loss: ..." in bg_last_error(NULL)) before anything is launched for: wrong alignment, a
  * stride < 60, an actions stride that is no multiple of 4, an output that is the same pointer as an input or another output, a non-finite ent_coef, a
  * workspace too small.  m == 0 writes zeros to stats_dev and launches nothing else.  Never synchronises unless timing is asked for.
- * Out of scope: label smoothing, an L2 term (the optimiser's weight decay), the expert policy itself (the demonstration ring is bg_demo_append_rows). */
+ * Out of scope: label smoothing, an L2 term (the optimiser's weight decay), (the demonstration ring is bg_demo_append_rows; the expert policy is bg_expert_actions). */
 int bg_episode_outcome_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N, double gamma,
                             const double* rewards_dev /*nullable*/,
                             const int32_t* tail_steps_dev /*nullable*/, const int32_t* tail_ante_dev /*nullable*/,
@@ -1182,7 +1182,7 @@ int bg_optim_step(const void* table_dev, int ntensors, int64_t chunks, int algo,
  * so a draw depends on (seed, index0 + i, t) alone, whatever m.  filled == 0 gives -1 on every row: the index bg_bc_loss excludes and
  * bg_encode_rows_ex zeroes.  The multiply-high draw is biased by at most filled / 2**32 per slot.  The slots of a full ring are all equally old as far
  * as a learner cares: the draw is over slots, not over age.
- * Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs, an expert policy. */
+ * Out of scope: prioritised or age-aware sampling, deduplication of identical records, a ring shared between GPUs.  (The expert policy that fills the ring is bg_expert_actions.) */
 uint64_t bg_demo_workspace_bytes(int64_t store_rows);
 int bg_demo_append_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int K, int64_t N,
                         const float* weights_dev, const double* returns_dev /*nullable*/,
@@ -1192,6 +1192,38 @@ int bg_demo_append_rows(const uint8_t* rows_dev, uint64_t row_stride_bytes, int 
                         void* workspace_dev, uint64_t workspace_bytes, float* kernel_ms_out, void* stream);
 int bg_demo_sample(const int64_t* cursor_dev, int64_t capacity, uint64_t seed, uint64_t index0, uint64_t t,
                    int32_t* index_dev, int64_t m, float* kernel_ms_out, void* stream);
+
+/* ---- bg_expert_actions: a scripted expert policy over packed records, one action per record (csrc/bg_expert.h has the rule, the kernel and the
+ * serial twin; tests/expert_ref.py restates the rule in numpy).
+ * Replaces: the reference's expert_agent.py (`BalatroExpertAgent`), which calls three methods it never defines and whose evaluate_hand is
+ * `len(cards) * 10  # Placeholder`.  Its intent is kept: in play enumerate every combination of up to five hand cards, value each, select the best set
+ * card by card, then PLAY_HAND; in the shop buy a joker if one can be bought, otherwise leave.  The value is ScoringEngine.score_hand's formula
+ * (scoring_engine.py:103-122) over bg_classify / bg_hand_base / bg_card_chips: (base chips at the hand's level + the cards' chips) * base mult.
+ *
+ * Stateless, no handle: record i is rows_dev + i * row_stride_bytes (index_dev NULL, m <= store_rows) or rows_dev + index_dev[i] * row_stride_bytes;
+ * an index outside [0, store_rows) gives action -1 and detail 0.  actions_dev int32 [m]; detail_dev int32 [m], nullable:
+ *     bits 0-7    T, the 8-bit slot mask the expert is selecting towards (the cards to play, or to discard)
+ *     bits 8-11   the hand type of the best subset P
+ *     bit 12      discard mode (T is a discard);  bit 13  FELLBACK: the intended action was masked (or the phase unknown) and the fallback order
+ *                 45, 46, 47, 31, 55, 0, 1..59 gave the action -- -1 when the whole mask is zero
+ *     bits 16-31  min(value(P), 65535)
+ * and 0 outside the play phase but for FELLBACK.  By phase: blind select takes the first valid of 45, 46, 47 (never a skip); the shop buys the
+ * cheapest valid joker slot (20 + i with shop_items[i] == 3, ties to the smaller i), else leaves with 31 (never a reroll); a pack is skipped with 55;
+ * play is the subset search, PLAY_HAND when a discard is not worth it (no discards left, the last hand, value * hands_left >= the chips still
+ * needed, or nothing else in the hand), else a DISCARD of the five cheapest cards outside P; stale selections are deselected first.  Between two
+ * PLAY_HAND / DISCARD actions of an env lie at most 13 card toggles.  The action is the `actions` of bg_step_rows (collection) and the
+ * `actions_dev` of bg_bc_loss (relabelling a finished store of the learner's own states).
+ * One launch, no atomics, one store per output per record; the records are not written; two calls give the same bytes.  m == 0 is a no-op.
+ * BG_E_ARG (text "bg_expert_actions: ..." in bg_last_error(NULL)) before anything is launched for: a stride below BG_ROW_BYTES or no multiple of 16;
+ * a record, index or output pointer that is misaligned (16, 4, 4 bytes); m < 0 or m >= 2**31; m > store_rows without an index; store_rows >= 2**31
+ * with one; an output that overlaps the records or is the same pointer as the index or the other output.
+ * bg_expert_actions_ex: the same with the lane mapping chosen (lanes_per_record 1, 8 or 64 share one record's subsets; 0 = the library's choice)
+ * and the kernel time by events on the stream (kernel_ms_out, nullable; asking for it synchronises).
+ * Out of scope: consumables, packs, vouchers, rerolls, selling, joker-aware valuation, any search beyond one hand. */
+int bg_expert_actions(const void* rows_dev, int64_t row_stride_bytes, int64_t m, const int32_t* index_dev, int64_t store_rows,
+                      int32_t* actions_dev, int32_t* detail_dev /*nullable*/, void* stream);
+int bg_expert_actions_ex(const void* rows_dev, int64_t row_stride_bytes, int64_t m, const int32_t* index_dev, int64_t store_rows,
+                         int32_t* actions_dev, int32_t* detail_dev /*nullable*/, int lanes_per_record, float* kernel_ms_out, void* stream);
 
 #ifdef __cplusplus
 }
