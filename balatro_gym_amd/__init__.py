@@ -8,7 +8,7 @@ from .constants import Action, Phase  # noqa: F401
 
 __all__ = ["Action", "Phase", "BalatroEnv", "BalatroVecEnv", "BalatroSB3VecEnv", "ShardedBalatroVecEnv", "make_balatro_env",
            "shard_range", "classify_batch", "score_hand_batch", "sim_evaluate_batch", "sim_score_batch", "encode_rows",
-           "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "RowOptimizer", "OptimStats", "DemoBuffer", "expert_actions"]
+           "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "RowOptimizer", "OptimStats", "DemoBuffer", "expert_actions", "RowDense", "RowPolicy"]
 
 
 def __getattr__(name):  # lazy: importing the package must not need torch / the GPU
@@ -16,6 +16,9 @@ def __getattr__(name):  # lazy: importing the package must not need torch / the 
                 "gae_rows", "EpisodeStats", "EpisodeLimits", "ProgressionRewards", "RowCurriculum", "episode_ends", "RowNormalizer", "sample_actions", "evaluate_actions", "ppo_loss", "PpoStats", "linear_rows", "linear_rows_grad", "RowLinear", "extractor_rows", "extractor_rows_grad", "RowExtractor", "dqn_loss", "DqnStats", "RowReplay", "bc_loss", "BcStats", "episode_outcomes", "EpisodeOutcomes", "actor_sample", "actor_evaluate", "actor_ppo_loss", "ActorPpoStats", "RowActor", "DemoBuffer", "expert_actions"):
         from . import vec_env
         return getattr(vec_env, name)
+    if name in ("RowDense", "RowPolicy"):
+        from . import policy
+        return getattr(policy, name)
     if name in ("RowOptimizer", "OptimStats"):
         from . import optim
         return getattr(optim, name)

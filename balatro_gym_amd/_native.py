@@ -87,7 +87,8 @@ EXPORTS = ["bg_create", "bg_destroy", "bg_last_error", "bg_num_envs", "bg_max_fu
            "bg_actor_sample", "bg_actor_evaluate", "bg_actor_ppo_loss", "bg_actor_ppo_loss_workspace_bytes", "bg_actor_ppo_loss_rows_per_group",
            "bg_optim_step", "bg_optim_workspace_size",
            "bg_demo_append_rows", "bg_demo_sample", "bg_demo_workspace_bytes",
-           "bg_expert_actions", "bg_expert_actions_ex"]
+           "bg_expert_actions", "bg_expert_actions_ex",
+           "bg_policy_forward", "bg_policy_check", "bg_policy_tap_cols"]
 # state-blob geometry (csrc/bg_device.h; tests/test_cabi_and_host.py checks these against the header): 16-byte chunks per env of the
 # hot / deck / cold / template arrays, words per stored MT19937 block, words per shop-stream ring slot and where its seed sits
 BLOB_NHOT, BLOB_NDECK, BLOB_NCOLD, BLOB_NTMPL, BLOB_NCST, BLOB_MTS, BLOB_SSEED = 8, 4, 7, 2, 7, 640, 128
@@ -120,6 +121,11 @@ OPTIM_ALGORITHMS = {"adam": OPTIM_ADAM, "rmsprop_tf": OPTIM_RMSPROP_TF}
 OPTIM_ZERO_GRAD, OPTIM_SHADOW_ONLY = 1, 2
 OPTIM_MAX_TENSORS, OPTIM_CHUNK, OPTIM_ENTRY_BYTES, OPTIM_STATS_BYTES, OPTIM_CARRY_BYTES = 1024, 1024, 64, 32, 32
 OPTIM_STATS = ("grad_norm", "clip_coef", "skipped", "nonfinite", "step")
+# bg_policy_forward (BG_POLICY_*; csrc/bg_policy.h): the envelope, the activations, the flag beside HEAD_DETERMINISTIC and the host table's geometry
+POLICY_WIDTH_MIN, POLICY_WIDTH_MAX, POLICY_MAX_SECTION, POLICY_MAX_LAYERS = 32, 512, 4, 14
+POLICY_ACTIVATIONS = {None: 0, "relu": 1, "tanh": 2}
+POLICY_EVALUATE = 2
+POLICY_NET_BYTES, POLICY_LAYER_BYTES = 480, 32
 NORM_COLS = 153   # BG_NORM_COLS: VecNormalize's statistics are one (mean, var) per column of the "produced" layout
 # the keys BalatroEnvFixed zero-fills (train_balatro_fixed.py:125-207), in the order of its observation space, with their element counts
 ENC_ZERO_KEYS = [("hand_one_hot", 416), ("hand_suits", 8), ("hand_ranks", 8), ("rank_counts", 13), ("suit_counts", 4), ("straight_potential", 1),
@@ -359,5 +365,8 @@ def load(build_if_missing: bool = True):
     L.bg_demo_sample.argtypes = [vp, i64, u64, u64, u64, vp, i64, C.POINTER(C.c_float), vp]
     L.bg_expert_actions.argtypes = [vp, i64, i64, vp, i64, vp, vp, vp]
     L.bg_expert_actions_ex.argtypes = [vp, i64, i64, vp, i64, vp, vp, i32, C.POINTER(C.c_float), vp]
+    L.bg_policy_check.argtypes = [vp]
+    L.bg_policy_tap_cols.argtypes = [vp]
+    L.bg_policy_forward.argtypes = [vp, vp, u64, vp, u64, i64, u32, u64, u64, u64, vp, vp, vp, vp, vp, u64, vp, u64, C.POINTER(C.c_float), vp]
     _lib = L
     return L

@@ -12,7 +12,7 @@ import sys
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 SRC = os.path.join(HERE, "csrc", "bg_lib.hip")
-DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("bg_device.h", "bg_step.h", "bg_tables.h", "bg_ops.h", "bg_sim.h", "bg_engine.h", "bg_engine3.h", "bg_safe.h", "bg_progress.h", "bg_encode.h", "bg_gae.h", "bg_ends.h", "bg_norm.h", "bg_head.h", "bg_ppo.h", "bg_outcome.h", "bg_bc.h", "bg_dqn.h", "bg_linear.h", "bg_extractor.h", "bg_actor.h", "bg_optim.h", "bg_demo.h", "bg_expert.h", "bg_snapshot.h", "bg_rows_api.h")] + [
+DEPS = [SRC] + [os.path.join(HERE, "csrc", f) for f in ("bg_device.h", "bg_step.h", "bg_tables.h", "bg_ops.h", "bg_sim.h", "bg_engine.h", "bg_engine3.h", "bg_safe.h", "bg_progress.h", "bg_encode.h", "bg_gae.h", "bg_ends.h", "bg_norm.h", "bg_head.h", "bg_ppo.h", "bg_outcome.h", "bg_bc.h", "bg_dqn.h", "bg_linear.h", "bg_extractor.h", "bg_actor.h", "bg_optim.h", "bg_demo.h", "bg_expert.h", "bg_policy.h", "bg_snapshot.h", "bg_rows_api.h")] + [
     os.path.join(os.path.dirname(HERE), "include", "balatro_mi355x.h")]
 LIB = os.path.join(HERE, "libbalatro_mi355x.so")
 ARCH = "gfx950"

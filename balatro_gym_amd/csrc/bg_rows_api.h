@@ -1249,3 +1249,67 @@ int bg_expert_actions(const void* rows_dev, int64_t row_stride_bytes, int64_t m,
                       int32_t* detail_dev, void* stream) {
   return bg_expert_actions_ex(rows_dev, row_stride_bytes, m, index_dev, store_rows, actions_dev, detail_dev, 0, nullptr, stream);
 }
+
+// the first layer's output -> every hidden layer, action_net, the masked head and value_net in one launch (bg_policy.h).  Read here, behind every other
+// header, for the reason given above bg_extractor.h.  The net is a HOST table: checked on every call, carried to the kernel as a launch argument.
+extern "C++" {
+#include "bg_policy.h"
+}
+static_assert(sizeof(BgPolicyLayer) == sizeof(BgPolLayer) && sizeof(BgPolicyNet) == sizeof(BgPolNet) && offsetof(BgPolicyNet, layer) == offsetof(BgPolNet, layer) &&
+              offsetof(BgPolicyLayer, weight_stride_elems) == offsetof(BgPolLayer, wpitch) && offsetof(BgPolicyLayer, out_features) == offsetof(BgPolLayer, out) &&
+              offsetof(BgPolicyLayer, activation) == offsetof(BgPolLayer, act), "bg_policy.h reads the header's table");
+static_assert(BG_POLICY_ACT_NONE == BG_POL_NONE && BG_POLICY_ACT_RELU == BG_POL_RELU && BG_POLICY_ACT_TANH == BG_POL_TANH && BG_POLICY_MAX_LAYERS == BG_POL_LAYERS_MAX &&
+              BG_POLICY_MAX_SECTION == BG_POL_SECTION_MAX && BG_POLICY_MAX_WIDTH == BG_POL_WMAX, "the header's constants");
+
+int bg_policy_check(const BgPolicyNet* net) {
+  if (const char* r = bg_pol_check((const BgPolNet*)net)) { g_create_err = std::string("bg_policy_check: ") + r; return BG_E_ARG; }
+  return 0;
+}
+int bg_policy_tap_cols(const BgPolicyNet* net) {
+  if (bg_policy_check(net)) return BG_E_ARG;
+  return bg_pol_tap_cols(*(const BgPolNet*)net);
+}
+
+int bg_policy_forward(const BgPolicyNet* net, const void* h_dev, uint64_t h_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
+                      uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, int32_t* actions_dev, float* log_prob_dev, float* entropy_dev, float* values_dev,
+                      void* taps_dev, uint64_t taps_stride_elems, float* logits_out_dev, uint64_t logits_out_stride_elems, float* kernel_ms_out, void* stream) {
+  const BgPolNet* const N = (const BgPolNet*)net;
+  const bool evaluate = (flags & BG_POLICY_EVALUATE) != 0u;
+  const void* const ins[] = {h_dev, mask_dev, evaluate ? (const void*)actions_dev : nullptr};
+  const void* const outs[] = {evaluate ? nullptr : (const void*)actions_dev, log_prob_dev, entropy_dev, values_dev, taps_dev, logits_out_dev};
+  const char* bad = bg_pol_check(N);
+  if (bad) {}
+  else if ((flags & ~(BG_HEAD_DETERMINISTIC | BG_POLICY_EVALUATE)) || flags == (BG_HEAD_DETERMINISTIC | BG_POLICY_EVALUATE)) bad = "flags must be 0, BG_HEAD_DETERMINISTIC or BG_POLICY_EVALUATE";
+  else if (m < 0 || m > (int64_t)BG_POL_ROWS * 0x7fffffffll) bad = "m out of range";
+  else if (!h_dev || ((uintptr_t)h_dev & 15)) bad = "h_dev must be a 16-byte aligned device pointer";
+  else if (h_stride_elems < (uint64_t)N->in0 || (h_stride_elems & 7) || h_stride_elems > 0xffffffffull) bad = "h_stride_elems must be a multiple of 8, >= in0";
+  else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
+  else if (!actions_dev || ((uintptr_t)actions_dev & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
+  else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev | (uintptr_t)values_dev) & 3) bad = "log_prob_dev / entropy_dev / values_dev must be 4-byte aligned";
+  else if (values_dev && !N->has_value) bad = "values_dev needs the value layer (has_value)";
+  else if ((uintptr_t)taps_dev & 1) bad = "taps_dev must be 2-byte aligned";
+  else if (taps_dev && (taps_stride_elems < (uint64_t)bg_pol_tap_cols(*N) || taps_stride_elems > 0xffffffffull)) bad = "taps_stride_elems must be >= bg_policy_tap_cols(net)";
+  else if ((uintptr_t)logits_out_dev & 3) bad = "logits_out_dev must be 4-byte aligned";
+  else if (logits_out_dev && (logits_out_stride_elems < BG_HEAD_ACTIONS || logits_out_stride_elems > 0xffffffffull)) bad = "logits_out_stride_elems must be >= 60";
+  else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
+  if (int rc = bg_op_begin("bg_policy_forward: ", bad, kernel_ms_out)) return rc;
+  if (m == 0) return 0;
+  BgPolIo O;
+  O.h = (const uint16_t*)h_dev; O.hstride = h_stride_elems;
+  O.mask = mask_dev; O.mstride = mask_stride_bytes; O.mld = bg_head_mask_path(mask_dev, mask_stride_bytes, true);
+  O.m = (long long)m; O.seed = seed; O.index0 = index0; O.t = t;
+  O.actions_in = evaluate ? actions_dev : nullptr; O.actions_out = evaluate ? nullptr : actions_dev;
+  O.log_prob = log_prob_dev; O.entropy = entropy_dev; O.values = values_dev;
+  O.taps = (uint16_t*)taps_dev; O.tstride = taps_stride_elems;
+  O.logits_out = logits_out_dev; O.lostride = logits_out_stride_elems;
+  O.lost = logits_out_dev ? bg_head_ld_path(logits_out_dev, logits_out_stride_elems, false) : BG_HEAD_LD_WORD;
+  const int mode = evaluate ? BG_HEAD_EVALUATE : flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE;
+  const unsigned grid = (unsigned)((m + BG_POL_ROWS - 1) / BG_POL_ROWS);
+  const BgPolNet net_arg = *N;
+  hipStream_t s = (hipStream_t)stream;
+  return bg_op_run(kernel_ms_out, s, [&] {
+    bg_enc_pick<BG_HEAD_SAMPLE, BG_HEAD_ARGMAX, BG_HEAD_EVALUATE>(mode, [&](auto M) {
+      hipLaunchKernelGGL((bg_policy_kernel<M()>), dim3(grid), dim3(BG_POL_BLOCK), 0, s, net_arg, O);
+    });
+  });
+}

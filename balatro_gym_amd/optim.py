@@ -14,6 +14,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
+from .policy import RowDense, RowPolicy
 from .rows import RowActor, RowExtractor, RowLinear, _native_call, _ptr
 
 _ENTRY = np.dtype([("param", "<u8"), ("grad", "<u8"), ("state1", "<u8"), ("state2", "<u8"), ("shadow", "<u8"), ("target", "<u8"), ("numel", "<u8"),
@@ -116,13 +117,18 @@ class RowOptimizer:
         raise ValueError(f"{what} is not one of this optimiser's parameters")
 
     def attach(self, module) -> None:
-        """Keep a bfloat16 copy of `module.weight` -- a RowLinear, RowExtractor (pitch 448) or RowActor whose weight this optimiser steps -- written by
+        """Keep a bfloat16 copy of `module.weight` -- a RowLinear, RowExtractor (pitch 448), RowActor or RowDense whose weight this optimiser steps
+        (a RowPolicy: every one of its layers) -- written by
         the update pass itself, and let the module read it in place of its per-call cast: `module.weight_bf16` is set together with the weight's
         `_version` at this moment, and the module uses the copy only while that version still holds.  Any torch in-place write (`load_state_dict`,
         `copy_` under no_grad) bumps the version: the module falls back to its cast, still correct, until `refresh()`.  A write through `.data` does NOT
         bump the version: call `refresh()` after one."""
-        if not isinstance(module, (RowLinear, RowExtractor, RowActor)):
-            raise ValueError("attach takes a RowLinear, a RowExtractor or a RowActor")
+        if isinstance(module, RowPolicy):   # every layer of the policy, in the table's order
+            for layer in module.layers():
+                self.attach(layer)
+            return
+        if not isinstance(module, (RowLinear, RowExtractor, RowActor, RowDense)):
+            raise ValueError("attach takes a RowLinear, a RowExtractor, a RowActor, a RowDense or a RowPolicy")
         w = module.weight
         self._index_of(w, "module.weight")
         rows, cols = int(w.shape[0]), int(w.shape[1])

@@ -1225,6 +1225,63 @@ int bg_expert_actions(const void* rows_dev, int64_t row_stride_bytes, int64_t m,
 int bg_expert_actions_ex(const void* rows_dev, int64_t row_stride_bytes, int64_t m, const int32_t* index_dev, int64_t store_rows,
                          int32_t* actions_dev, int32_t* detail_dev /*nullable*/, int lanes_per_record, float* kernel_ms_out, void* stream);
 
+/* ---- bg_policy_forward: everything between the network's first layer and the env in ONE launch, for collection and evaluation (csrc/bg_policy.h
+ * has the kernel and the serial twin; tests/policy_ref.py the float64 statement and the bounds).
+ * Replaces: the hidden layers the reference's policies run in torch behind their first layer -- the extractor's second layers and combined_net
+ * (train_balatro_agent.py:54-82), SB3's mlp_extractor (net_arch pi / vf, train_balatro_agent.py:338-342), action_net, the masked draw and value_net --
+ * about twenty launches that each write an [m, <= 512] activation.  Here no hidden activation and no logits matrix is written.
+ *
+ * net: a BgPolicyNet in HOST memory, checked on every call and carried to the kernel as a launch argument (nothing is uploaded; a table outside the
+ * envelope never reaches the kernel).  layer[] holds, in this order: n_trunk trunk layers, n_pi and n_vf branch layers (each section 0..4 layers; both
+ * branches read the trunk's output, or h where the trunk is empty), the action layer [60, latent_pi], and with has_value the value layer
+ * [1, latent_vf].  THE ENVELOPE: every width, in0 included, a multiple of 32 in [32, 512]; a layer's in_features is the width of what it reads; every
+ * weight bfloat16 [out_features, in_features] in nn.Linear's orientation, 16-byte aligned, weight_stride_elems a multiple of 8 and >= in_features;
+ * every bias float32 [out_features], required; activation BG_POLICY_ACT_* on hidden layers, NONE on the two last; vf layers need the value layer.
+ * h_dev: bfloat16 [m, in0], 16-byte aligned, h_stride_elems a multiple of 8 and >= in0 (what bg_extractor_rows / bg_linear_rows write, or a column
+ * slice of it).  The mask: as bg_sample_actions (records at stride 384 or int8 [m, 60]; NULL: every action valid).
+ *     one layer   y[i][j] = act(float32(sum_k x[i][k] * w[j][k]) + b[j]), rounded to nearest-even bfloat16 for the next layer: the products are exact,
+ *                 the sum is the float32 accumulation of __builtin_amdgcn_mfma_f32_32x32x16_bf16 over k in ascending 16-blocks, the bias ONE
+ *                 float32 addition.  relu keeps a NaN.  tanh(y) = sign(y) * (1 - 2 / (expf(2 |y|) + 1)), every operation rounded to float32.
+ *                 Bounded by tests/policy_ref.py, not promised bit for bit against another order of accumulation.
+ *     last layers the 60 logits and the value stay float32.
+ *     head        GIVEN these logits (logits_out_dev returns them) actions, log_prob and entropy are bit for bit bg_sample_actions' (flags 0 or
+ *                 BG_HEAD_DETERMINISTIC, with seed, index0, t) / bg_evaluate_actions' (flags BG_POLICY_EVALUATE: actions_dev is read).
+ *     outputs     actions_dev int32 [m]; log_prob_dev, entropy_dev, values_dev float32 [m], each nullable (values_dev needs has_value).
+ *     test outputs  taps_dev bfloat16 [m, bg_policy_tap_cols(net)] at taps_stride_elems: every hidden layer's output in table order; logits_out_dev
+ *                 float32 [m, 60] at logits_out_stride_elems.  Asking for them changes no other output bit.
+ * A row's outputs depend on its own inputs and (seed, index0 + i, t) only: not on m, not on the launch shape; two calls give the same bits.
+ * LDS does not grow with the net: three activation images of 32 rows x 520 bfloat16.  One launch on `stream` of the current device, no workspace, no
+ * handle; m == 0 is a no-op; kernel_ms_out as in bg_classify_batch_ex.  bg_policy_check(net): 0, or BG_E_ARG with the text in bg_last_error(NULL).
+ * BG_E_ARG (text "bg_policy_forward: ..." in bg_last_error(NULL)) before anything is launched for: a net outside the envelope; flags other than the
+ * three; a misaligned pointer or pitch; values_dev without has_value; an output that is the same pointer as an input or as another output.
+ * Out of scope: a backward pass (training keeps autograd for the hidden layers), DQN's epsilon draw, a temperature, the first layer inside the same
+ * launch, a network policy inside the rollout engine. */
+#define BG_POLICY_ACT_NONE 0
+#define BG_POLICY_ACT_RELU 1
+#define BG_POLICY_ACT_TANH 2
+#define BG_POLICY_EVALUATE 2u /* flags, beside BG_HEAD_DETERMINISTIC */
+#define BG_POLICY_MAX_SECTION 4
+#define BG_POLICY_MAX_LAYERS 14
+#define BG_POLICY_MAX_WIDTH 512
+typedef struct BgPolicyLayer {
+  const void* weight_dev;  /* bfloat16 [out_features, in_features] */
+  const float* bias_dev;   /* float32 [out_features] */
+  uint32_t weight_stride_elems;
+  uint16_t in_features, out_features;
+  uint32_t activation;     /* BG_POLICY_ACT_* */
+  uint32_t reserved;       /* 0 */
+} BgPolicyLayer;
+typedef struct BgPolicyNet {
+  uint32_t n_trunk, n_pi, n_vf, has_value, in0, reserved[3];
+  BgPolicyLayer layer[BG_POLICY_MAX_LAYERS];
+} BgPolicyNet;
+int bg_policy_check(const BgPolicyNet* net);
+int bg_policy_tap_cols(const BgPolicyNet* net); /* the sum of the hidden widths, or BG_E_ARG */
+int bg_policy_forward(const BgPolicyNet* net, const void* h_dev, uint64_t h_stride_elems, const int8_t* mask_dev /*nullable*/, uint64_t mask_stride_bytes,
+                      int64_t m, uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, int32_t* actions_dev, float* log_prob_dev /*nullable*/,
+                      float* entropy_dev /*nullable*/, float* values_dev /*nullable*/, void* taps_dev /*nullable*/, uint64_t taps_stride_elems,
+                      float* logits_out_dev /*nullable*/, uint64_t logits_out_stride_elems, float* kernel_ms_out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
