@@ -107,18 +107,10 @@ struct BgActorGrad {
 
 #ifdef BG_ACTOR_HOST
 // ---- the serial twin ----
-// One instruction: acc[lane][g] += sum over the 16 k of the step, in ascending k, each product exact, every addition rounded to float32.  The operands
-// are read from the images through the lane's fragment offsets, the results land in the lane's accumulator registers: the maps under test.
+// One instruction (bg_lin_host_mfma): both operands are read from the images through the lane's fragment offsets.
 static inline void bg_act_host_mfma(const uint16_t* a_img, int a_tile, const uint16_t* b_img, int b_tile, int step, float acc[64][16]) {
-  float A[BG_LIN_TILE][BG_LIN_KSTEP], B[BG_LIN_KSTEP][BG_LIN_TILE];
-  for (int l = 0; l < 64; l++)
-    for (int j = 0; j < 8; j++) {
-      A[bg_lin_frag_rc(l)][bg_lin_frag_k(l, 0, j)] = bg_head_widen_bf16(a_img[bg_act_frag_off(a_tile, l, step) + j]);
-      B[bg_lin_frag_k(l, 0, j)][bg_lin_frag_rc(l)] = bg_head_widen_bf16(b_img[bg_act_frag_off(b_tile, l, step) + j]);
-    }
-  for (int l = 0; l < 64; l++)
-    for (int g = 0; g < 16; g++)
-      for (int k = 0; k < BG_LIN_KSTEP; k++) acc[l][g] = acc[l][g] + A[bg_lin_acc_row(l, g)][k] * B[k][bg_lin_acc_col(l)];
+  bg_lin_host_mfma([&](int l, int j) { return bg_head_widen_bf16(a_img[bg_act_frag_off(a_tile, l, step) + j]); },
+                   [&](int l, int j) { return bg_head_widen_bf16(b_img[bg_act_frag_off(b_tile, l, step) + j]); }, acc);
 }
 static inline uint16_t bg_act_host_w(const BgActorArgs& G, int j, int k) {
   if (j >= BG_HEAD_ACTIONS || k >= G.Hin) return 0;
@@ -348,9 +340,7 @@ __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_actor_head_kernel(const BgAc
                                                                       long long m, uint64_t seed, uint64_t index0, uint64_t t,
                                                                       const int32_t* __restrict__ actions_in, int32_t* __restrict__ actions_out,
                                                                       float* __restrict__ log_prob, float* __restrict__ entropy) {
-  __shared__ float lg[BG_HEAD_ROWS * BG_HEAD_LPITCH];
-  __shared__ float pf[MODE == BG_HEAD_SAMPLE ? BG_HEAD_ROWS * BG_HEAD_LPITCH : 1];
-  __shared__ uint32_t mk[BG_HEAD_ROWS * BG_HEAD_MWORDS];
+  BG_HEAD_LDS(MODE, BG_HEAD_ROWS);   // lg, pf, mk
   const long long rec0 = (long long)blockIdx.x * BG_ACT_ROWS;
   const int nrow = (int)(m - rec0 < BG_ACT_ROWS ? m - rec0 : BG_ACT_ROWS);
   const int lane = threadIdx.x;

@@ -120,7 +120,15 @@ BG_HEAD_FN BgHeadOut bg_head_row(const float* l, const uint32_t* kw, float* P, f
   return o;
 }
 
-#ifndef BG_HEAD_HOST
+#ifdef BG_HEAD_HOST
+// The serial twins' row: the run-time choice among the six instantiations, with the draw of row `row` = index0 + i in BG_HEAD_SAMPLE
+static inline BgHeadOut bg_head_row_host(int mode, bool masked, const float* l, const uint32_t* kw, float* P, uint64_t seed, uint64_t row, uint64_t t, int32_t given) {
+  const float u = mode == BG_HEAD_SAMPLE ? bg_head_u(bg_head_hash(seed, row, t)) : 0.0f;
+  if (mode == BG_HEAD_SAMPLE) return masked ? bg_head_row<BG_HEAD_SAMPLE, true>(l, kw, P, u, given) : bg_head_row<BG_HEAD_SAMPLE, false>(l, kw, P, u, given);
+  if (mode == BG_HEAD_ARGMAX) return masked ? bg_head_row<BG_HEAD_ARGMAX, true>(l, kw, P, u, given) : bg_head_row<BG_HEAD_ARGMAX, false>(l, kw, P, u, given);
+  return masked ? bg_head_row<BG_HEAD_EVALUATE, true>(l, kw, P, u, given) : bg_head_row<BG_HEAD_EVALUATE, false>(l, kw, P, u, given);
+}
+#else
 // ---- the kernel ----
 // The contract fixes the order of the additions inside a row, so the parallelism is across rows: lane = row.  Read that way from HBM, consecutive
 // lanes would sit 240 (120) bytes apart, so a workgroup -- ONE wave, BG_HEAD_ROWS = 64 consecutive rows; 4 096 rows are 64 workgroups on 64 CUs, as the
@@ -241,15 +249,20 @@ __device__ __forceinline__ void bg_head_stage_mask(const int8_t* __restrict__ ma
   }
 }
 
+// The LDS of a head-ended kernel (this one, bg_actor_head_kernel, bg_policy_kernel) in mode MODE for ROWS rows: it DECLARES lg, the float32 logits tile;
+// pf, the prefix sums of BG_HEAD_SAMPLE; mk, the mask words.  A macro because three arrays compile to another text than one object that holds them.
+#define BG_HEAD_LDS(MODE, ROWS)                                               \
+  __shared__ float lg[(ROWS) * BG_HEAD_LPITCH];                               \
+  __shared__ float pf[(MODE) == BG_HEAD_SAMPLE ? (ROWS) * BG_HEAD_LPITCH : 1];  \
+  __shared__ uint32_t mk[(ROWS) * BG_HEAD_MWORDS]
+
 // MODE: BG_HEAD_SAMPLE / BG_HEAD_ARGMAX write actions_out; BG_HEAD_EVALUATE reads actions_in.  log_prob / entropy may be NULL.  m >= 1.
 template <int MODE>
 __global__ __launch_bounds__(BG_HEAD_BLOCK) void bg_head_kernel(const void* __restrict__ logits, int bf16, int lld, uint64_t lstride,
                                                                 const int8_t* __restrict__ mask, int mld, uint64_t mstride, long long m, uint64_t seed,
                                                                 uint64_t index0, uint64_t t, const int32_t* __restrict__ actions_in,
                                                                 int32_t* __restrict__ actions_out, float* __restrict__ log_prob, float* __restrict__ entropy) {
-  __shared__ float lg[BG_HEAD_ROWS * BG_HEAD_LPITCH];
-  __shared__ float pf[MODE == BG_HEAD_SAMPLE ? BG_HEAD_ROWS * BG_HEAD_LPITCH : 1];
-  __shared__ uint32_t mk[BG_HEAD_ROWS * BG_HEAD_MWORDS];
+  BG_HEAD_LDS(MODE, BG_HEAD_ROWS);   // lg, pf, mk
   const long long rec0 = (long long)blockIdx.x * BG_HEAD_ROWS;
   const int nrow = (int)(m - rec0 < BG_HEAD_ROWS ? m - rec0 : BG_HEAD_ROWS);
   if (bf16) bg_head_stage_logits<true>(logits, lld, lstride, rec0, nrow, lg);

@@ -35,6 +35,23 @@ BG_LIN_FN int bg_lin_acc_row(int lane, int reg) { return (reg & 3) + 8 * (reg >>
 BG_LIN_FN int bg_lin_acc_col(int lane) { return lane & 31; }
 // element offset of the lane's fragment (8 consecutive elements) in an image [row of A | column of B][reduction index] of `pitch` elements per line
 BG_LIN_FN int bg_lin_frag_off(int lane, int step, int pitch) { return bg_lin_frag_rc(lane) * pitch + bg_lin_frag_k(lane, step, 0); }
+#ifdef BG_LIN_HOST
+// The serial twins' scalar model of one instruction (bg_actor.h, bg_policy.h): acc[lane][g] += the sum over the step's 16 k, in ascending k, each product
+// exact, every addition rounded to float32.  a(lane, j) / b(lane, j): element j of the lane's fragment, widened from bfloat16, fetched as the caller's kernel
+// fetches it; the maps above place the operands and the results: they are what is under test.
+template <class FA, class FB>
+static inline void bg_lin_host_mfma(FA a, FB b, float acc[64][16]) {
+  float A[BG_LIN_TILE][BG_LIN_KSTEP], B[BG_LIN_KSTEP][BG_LIN_TILE];
+  for (int l = 0; l < 64; l++)
+    for (int j = 0; j < 8; j++) {
+      A[bg_lin_frag_rc(l)][bg_lin_frag_k(l, 0, j)] = a(l, j);
+      B[bg_lin_frag_k(l, 0, j)][bg_lin_frag_rc(l)] = b(l, j);
+    }
+  for (int l = 0; l < 64; l++)
+    for (int g = 0; g < 16; g++)
+      for (int k = 0; k < BG_LIN_KSTEP; k++) acc[l][g] = acc[l][g] + A[bg_lin_acc_row(l, g)][k] * B[k][bg_lin_acc_col(l)];
+}
+#endif
 
 // a gradient's split of m rows (this layer's and bg_extractor.h's): blocks of BG_LIN_ROWS rows, `per` consecutive blocks per row group, `groups` groups
 // (= partials), for a grid of bg_lin_spans(H) x `kspans` workgroups per row group: kspans is 1 here, the k spans there

@@ -151,16 +151,10 @@ struct BgPolIo {
 // One instruction of one tile: the A operand through the lane's fragment offsets in the image, the B operand through the lane's unit and k in the
 // weight; units at or beyond `nunits` are zero weights.
 static inline void bg_pol_host_mfma(const uint16_t* img, const BgPolLayer& L, int unit0, int nunits, int step, float acc[64][16]) {
-  float A[BG_LIN_TILE][BG_LIN_KSTEP], B[BG_LIN_KSTEP][BG_LIN_TILE];
-  for (int l = 0; l < 64; l++)
-    for (int j = 0; j < 8; j++) {
-      A[bg_lin_frag_rc(l)][bg_lin_frag_k(l, 0, j)] = bg_head_widen_bf16(img[bg_pol_a_off(l, step) + j]);
-      const int u = bg_pol_b_unit(unit0, l);
-      B[bg_lin_frag_k(l, 0, j)][bg_lin_frag_rc(l)] = u < nunits ? bg_head_widen_bf16(L.w[(size_t)u * L.wpitch + bg_pol_b_k(l, step) + j]) : 0.f;
-    }
-  for (int l = 0; l < 64; l++)
-    for (int g = 0; g < 16; g++)
-      for (int k = 0; k < BG_LIN_KSTEP; k++) acc[l][g] = acc[l][g] + A[bg_lin_acc_row(l, g)][k] * B[k][bg_lin_acc_col(l)];
+  bg_lin_host_mfma([&](int l, int j) { return bg_head_widen_bf16(img[bg_pol_a_off(l, step) + j]); }, [&](int l, int j) {
+    const int u = bg_pol_b_unit(unit0, l);
+    return u < nunits ? bg_head_widen_bf16(L.w[(size_t)u * L.wpitch + bg_pol_b_k(l, step) + j]) : 0.f;
+  }, acc);
 }
 static inline void bg_pol_host_tile(const uint16_t* img, const BgPolLayer& L, int unit0, int nunits, float acc[64][16]) {
   for (int l = 0; l < 64; l++)
@@ -226,12 +220,7 @@ static inline void bg_policy_host(const BgPolNet& N, int mode, const uint16_t* h
         for (int j = 0; j < BG_HEAD_ACTIONS; j++) logits[(size_t)i * BG_HEAD_ACTIONS + j] = l[j];
       uint32_t kw[BG_HEAD_ACTIONS / 4] = {};
       if (mask) __builtin_memcpy(kw, mask + (size_t)i * mstride, BG_HEAD_ACTIONS);
-      const float u = mode == BG_HEAD_SAMPLE ? bg_head_u(bg_head_hash(seed, index0 + (uint64_t)i, t)) : 0.0f;
-      const int32_t given = mode == BG_HEAD_EVALUATE ? actions[i] : 0;
-      BgHeadOut o;
-      if (mode == BG_HEAD_SAMPLE) o = mask ? bg_head_row<BG_HEAD_SAMPLE, true>(l, kw, pf, u, given) : bg_head_row<BG_HEAD_SAMPLE, false>(l, kw, pf, u, given);
-      else if (mode == BG_HEAD_ARGMAX) o = mask ? bg_head_row<BG_HEAD_ARGMAX, true>(l, kw, pf, u, given) : bg_head_row<BG_HEAD_ARGMAX, false>(l, kw, pf, u, given);
-      else o = mask ? bg_head_row<BG_HEAD_EVALUATE, true>(l, kw, pf, u, given) : bg_head_row<BG_HEAD_EVALUATE, false>(l, kw, pf, u, given);
+      const BgHeadOut o = bg_head_row_host(mode, mask != nullptr, l, kw, pf, seed, index0 + (uint64_t)i, t, mode == BG_HEAD_EVALUATE ? actions[i] : 0);
       if (mode != BG_HEAD_EVALUATE) actions[i] = o.action;
       if (log_prob) log_prob[i] = o.log_prob;
       if (entropy) entropy[i] = o.entropy;
@@ -303,9 +292,7 @@ __device__ __forceinline__ void bg_pol_layer(const BgPolLayer& L, const uint16_t
 template <int MODE>
 __global__ __launch_bounds__(BG_POL_BLOCK) void bg_policy_kernel(const BgPolNet N, const BgPolIo O) {
   __shared__ __attribute__((aligned(16))) uint16_t img[BG_POL_IMAGES][BG_POL_ROWS * BG_POL_PITCH];
-  __shared__ float lg[BG_POL_ROWS * BG_HEAD_LPITCH];
-  __shared__ float pf[MODE == BG_HEAD_SAMPLE ? BG_POL_ROWS * BG_HEAD_LPITCH : 1];
-  __shared__ uint32_t mk[BG_POL_ROWS * BG_HEAD_MWORDS];
+  BG_HEAD_LDS(MODE, BG_POL_ROWS);   // lg, pf, mk
   const long long rec0 = (long long)blockIdx.x * BG_POL_ROWS;
   const int nrow = (int)(O.m - rec0 < BG_POL_ROWS ? O.m - rec0 : BG_POL_ROWS);
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -348,7 +335,6 @@ __global__ __launch_bounds__(BG_POL_BLOCK) void bg_policy_kernel(const BgPolNet 
     section(nt + npi, hidden);
   }
   if (wave == 2 && N.has_value) {   // the value layer: unit 0 of one tile
-   // the value layer: unit 0 of one tile
     const BgPolLayer& L = N.layer[hidden + 1];
     const bg_lin_c16 acc = bg_pol_tile(img[bg_pol_branch_last(nt, nvf)], L, 0, 1, lane);
     if (bg_lin_acc_col(lane) == 0 && O.values) {

@@ -417,21 +417,41 @@ static const char* bg_head_mask_args(const int8_t* mask_dev, uint64_t mask_strid
   return nullptr;
 }
 
+// What the head-ended calls (bg_head_call, bg_actor_head_call, bg_policy_forward) share behind their own inputs.  `act`: the call's one actions pointer,
+// read by BG_HEAD_EVALUATE and written by the two drawing modes.
+static const char* bg_head_out_args(const void* act, const float* log_prob_dev, const float* entropy_dev) {
+  if (!act || ((uintptr_t)act & 3)) return "actions_dev must be a 4-byte aligned device pointer";
+  if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) return "log_prob_dev / entropy_dev must be 4-byte aligned";
+  return nullptr;
+}
+static int bg_head_mode(uint32_t flags, bool evaluate = false) { return evaluate ? BG_HEAD_EVALUATE : flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE; }
+// logits_out (nullable, float32 [m, >= 60]) of the calls that compute their logits: its checks and its store path
+static const char* bg_head_logits_out_args(const float* logits_out_dev, uint64_t logits_out_stride_elems) {
+  if ((uintptr_t)logits_out_dev & 3) return "logits_out_dev must be 4-byte aligned";
+  if (logits_out_dev && (logits_out_stride_elems < BG_HEAD_ACTIONS || logits_out_stride_elems > 0xffffffffull)) return "logits_out_stride_elems must be >= 60";
+  return nullptr;
+}
+static int bg_head_logits_out_path(const float* p, uint64_t stride_elems) { return p ? bg_head_ld_path(p, stride_elems, false) : BG_HEAD_LD_WORD; }
+// h (bfloat16 [m, width], read by 16-byte fragments) as verdicts: the refusal names the caller's own width, so its literal stays whole with the caller
+static bool bg_head_bad_h(const void* h_dev) { return !h_dev || ((uintptr_t)h_dev & 15); }
+static bool bg_head_bad_h_stride(uint64_t h_stride_elems, uint64_t width) { return h_stride_elems < width || (h_stride_elems & 7) || h_stride_elems > 0xffffffffull; }
+
 static int bg_head_call(const char* who, int mode, const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev,
                         uint64_t mask_stride_bytes, int64_t m, uint64_t seed, uint64_t index0, uint64_t t, const int32_t* actions_in, int32_t* actions_out,
                         float* log_prob_dev, float* entropy_dev, float* kernel_ms_out, void* stream, float epsilon = 0.0f) {
   const bool bf16 = logits_dtype == BG_HEAD_BF16;
   const uint64_t es = bf16 ? 2u : 4u;
   const void* const act = mode == BG_HEAD_EVALUATE ? (const void*)actions_in : (const void*)actions_out;
+  const void* const none[] = {nullptr};
+  const void* const ins[] = {logits_dev, mask_dev};
+  const void* const outs[] = {act, log_prob_dev, entropy_dev};   // (this call counts `act` among the outputs in every mode)
   const char* bad = bg_head_shape_args(logits_dtype, m);
   if (bad) {}
   else if (const char* r = bg_head_logits_args(logits_dev, es, logits_stride_elems)) bad = r;
   else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
-  else if (!act || ((uintptr_t)act & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
-  else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "log_prob_dev / entropy_dev must be 4-byte aligned";
-  else if ((log_prob_dev && log_prob_dev == entropy_dev) || (const void*)log_prob_dev == act || (const void*)entropy_dev == act) bad = "actions_dev, log_prob_dev and entropy_dev must not be the same pointer";
-  else if (act == logits_dev || act == (const void*)mask_dev || (log_prob_dev && ((const void*)log_prob_dev == logits_dev || (const void*)log_prob_dev == (const void*)mask_dev)) ||
-           (entropy_dev && ((const void*)entropy_dev == logits_dev || (const void*)entropy_dev == (const void*)mask_dev))) bad = "outputs must not alias the logits or the masks";
+  else if (const char* r = bg_head_out_args(act, log_prob_dev, entropy_dev)) bad = r;
+  else if (bg_alias(none, outs)) bad = "actions_dev, log_prob_dev and entropy_dev must not be the same pointer";
+  else if (bg_alias(ins, outs)) bad = "outputs must not alias the logits or the masks";
   if (int rc = bg_op_begin(who, bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
   const int lld = bg_head_ld_path(logits_dev, logits_stride_elems, bf16);
@@ -450,7 +470,7 @@ int bg_sample_actions(const void* logits_dev, int logits_dtype, uint64_t logits_
                       uint32_t flags, uint64_t seed, uint64_t index0, uint64_t t, int32_t* actions_dev, float* log_prob_dev, float* entropy_dev,
                       float* kernel_ms_out, void* stream) {
   if (flags & ~BG_HEAD_DETERMINISTIC) { g_create_err = "bg_sample_actions: flags must be 0 or BG_HEAD_DETERMINISTIC"; return BG_E_ARG; }
-  return bg_head_call("bg_sample_actions: ", flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE, logits_dev, logits_dtype, logits_stride_elems, mask_dev,
+  return bg_head_call("bg_sample_actions: ", bg_head_mode(flags), logits_dev, logits_dtype, logits_stride_elems, mask_dev,
                       mask_stride_bytes, m, seed, index0, t, nullptr, actions_dev, log_prob_dev, entropy_dev, kernel_ms_out, stream);
 }
 int bg_evaluate_actions(const void* logits_dev, int logits_dtype, uint64_t logits_stride_elems, const int8_t* mask_dev, uint64_t mask_stride_bytes, int64_t m,
@@ -978,22 +998,20 @@ extern "C++" {
 static const char* bg_actor_layer_args(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
                                        const float* bias_dev, const float* logits_out_dev, uint64_t logits_out_stride_elems) {
   if (!bg_act_hin_ok(Hin)) return "Hin must be a multiple of 32 in [32, 1024]";
-  if (!h_dev || ((uintptr_t)h_dev & 15)) return "h_dev must be a 16-byte aligned device pointer";
-  if (h_stride_elems < (uint64_t)Hin || (h_stride_elems & 7) || h_stride_elems > 0xffffffffull) return "h_stride_elems must be a multiple of 8, >= Hin";
+  if (bg_head_bad_h(h_dev)) return "h_dev must be a 16-byte aligned device pointer";
+  if (bg_head_bad_h_stride(h_stride_elems, (uint64_t)Hin)) return "h_stride_elems must be a multiple of 8, >= Hin";
   if (weight_dtype != BG_ENC_F32 && weight_dtype != BG_ENC_BF16) return "weight_dtype must be BG_ENC_F32 or BG_ENC_BF16";
   if (!weight_dev || ((uintptr_t)weight_dev & (weight_dtype == BG_ENC_F32 ? 3 : 1))) return "weight_dev must be a device pointer aligned to its element type";
   if (weight_stride_elems < (uint64_t)Hin || weight_stride_elems > 0xffffffffull) return "weight_stride_elems must be >= Hin";
   if ((uintptr_t)bias_dev & 3) return "bias_dev must be 4-byte aligned";
-  if ((uintptr_t)logits_out_dev & 3) return "logits_out_dev must be 4-byte aligned";
-  if (logits_out_dev && (logits_out_stride_elems < BG_HEAD_ACTIONS || logits_out_stride_elems > 0xffffffffull)) return "logits_out_stride_elems must be >= 60";
-  return nullptr;
+  return bg_head_logits_out_args(logits_out_dev, logits_out_stride_elems);
 }
 static BgActorArgs bg_actor_args(const void* h_dev, uint64_t h_stride_elems, int Hin, const void* weight_dev, int weight_dtype, uint64_t weight_stride_elems,
                                  const float* bias_dev, float* logits_out_dev, uint64_t logits_out_stride_elems) {
   BgActorArgs G;
   G.h = (const uint16_t*)h_dev; G.hstride = h_stride_elems; G.weight = weight_dev; G.wstride = weight_stride_elems; G.w_bf16 = weight_dtype == BG_ENC_BF16 ? 1 : 0;
   G.bias = bias_dev; G.Hin = Hin; G.logits_out = logits_out_dev; G.lostride = logits_out_stride_elems;
-  G.lost = logits_out_dev ? bg_head_ld_path(logits_out_dev, logits_out_stride_elems, false) : BG_HEAD_LD_WORD;
+  G.lost = bg_head_logits_out_path(logits_out_dev, logits_out_stride_elems);
   return G;
 }
 
@@ -1008,8 +1026,7 @@ static int bg_actor_head_call(const char* who, int mode, const void* h_dev, uint
   if (bad) {}
   else if (const char* r = bg_actor_layer_args(h_dev, h_stride_elems, Hin, weight_dev, weight_dtype, weight_stride_elems, bias_dev, logits_out_dev, logits_out_stride_elems)) bad = r;
   else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
-  else if (!act || ((uintptr_t)act & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
-  else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev) & 3) bad = "log_prob_dev / entropy_dev must be 4-byte aligned";
+  else if (const char* r = bg_head_out_args(act, log_prob_dev, entropy_dev)) bad = r;
   else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin(who, bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
@@ -1031,7 +1048,7 @@ int bg_actor_sample(const void* h_dev, uint64_t h_stride_elems, int Hin, const v
                     uint64_t t, int32_t* actions_dev, float* log_prob_dev, float* entropy_dev, float* logits_out_dev, uint64_t logits_out_stride_elems,
                     float* kernel_ms_out, void* stream) {
   if (flags & ~BG_HEAD_DETERMINISTIC) { g_create_err = "bg_actor_sample: flags must be 0 or BG_HEAD_DETERMINISTIC"; return BG_E_ARG; }
-  return bg_actor_head_call("bg_actor_sample: ", flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE, h_dev, h_stride_elems, Hin, weight_dev, weight_dtype,
+  return bg_actor_head_call("bg_actor_sample: ", bg_head_mode(flags), h_dev, h_stride_elems, Hin, weight_dev, weight_dtype,
                             weight_stride_elems, bias_dev, mask_dev, mask_stride_bytes, m, seed, index0, t, nullptr, actions_dev, log_prob_dev, entropy_dev,
                             logits_out_dev, logits_out_stride_elems, kernel_ms_out, stream);
 }
@@ -1281,16 +1298,15 @@ int bg_policy_forward(const BgPolicyNet* net, const void* h_dev, uint64_t h_stri
   if (bad) {}
   else if ((flags & ~(BG_HEAD_DETERMINISTIC | BG_POLICY_EVALUATE)) || flags == (BG_HEAD_DETERMINISTIC | BG_POLICY_EVALUATE)) bad = "flags must be 0, BG_HEAD_DETERMINISTIC or BG_POLICY_EVALUATE";
   else if (m < 0 || m > (int64_t)BG_POL_ROWS * 0x7fffffffll) bad = "m out of range";
-  else if (!h_dev || ((uintptr_t)h_dev & 15)) bad = "h_dev must be a 16-byte aligned device pointer";
-  else if (h_stride_elems < (uint64_t)N->in0 || (h_stride_elems & 7) || h_stride_elems > 0xffffffffull) bad = "h_stride_elems must be a multiple of 8, >= in0";
+  else if (bg_head_bad_h(h_dev)) bad = "h_dev must be a 16-byte aligned device pointer";
+  else if (bg_head_bad_h_stride(h_stride_elems, N->in0)) bad = "h_stride_elems must be a multiple of 8, >= in0";
   else if (const char* r = bg_head_mask_args(mask_dev, mask_stride_bytes)) bad = r;
-  else if (!actions_dev || ((uintptr_t)actions_dev & 3)) bad = "actions_dev must be a 4-byte aligned device pointer";
+  else if (const char* r = bg_head_out_args(actions_dev, nullptr, nullptr)) bad = r;   // (log_prob / entropy: with values_dev, below)
   else if (((uintptr_t)log_prob_dev | (uintptr_t)entropy_dev | (uintptr_t)values_dev) & 3) bad = "log_prob_dev / entropy_dev / values_dev must be 4-byte aligned";
   else if (values_dev && !N->has_value) bad = "values_dev needs the value layer (has_value)";
   else if ((uintptr_t)taps_dev & 1) bad = "taps_dev must be 2-byte aligned";
   else if (taps_dev && (taps_stride_elems < (uint64_t)bg_pol_tap_cols(*N) || taps_stride_elems > 0xffffffffull)) bad = "taps_stride_elems must be >= bg_policy_tap_cols(net)";
-  else if ((uintptr_t)logits_out_dev & 3) bad = "logits_out_dev must be 4-byte aligned";
-  else if (logits_out_dev && (logits_out_stride_elems < BG_HEAD_ACTIONS || logits_out_stride_elems > 0xffffffffull)) bad = "logits_out_stride_elems must be >= 60";
+  else if (const char* r = bg_head_logits_out_args(logits_out_dev, logits_out_stride_elems)) bad = r;
   else if (bg_alias(ins, outs)) bad = "outputs must not be the same pointer as an input or as another output";
   if (int rc = bg_op_begin("bg_policy_forward: ", bad, kernel_ms_out)) return rc;
   if (m == 0) return 0;
@@ -1302,8 +1318,8 @@ int bg_policy_forward(const BgPolicyNet* net, const void* h_dev, uint64_t h_stri
   O.log_prob = log_prob_dev; O.entropy = entropy_dev; O.values = values_dev;
   O.taps = (uint16_t*)taps_dev; O.tstride = taps_stride_elems;
   O.logits_out = logits_out_dev; O.lostride = logits_out_stride_elems;
-  O.lost = logits_out_dev ? bg_head_ld_path(logits_out_dev, logits_out_stride_elems, false) : BG_HEAD_LD_WORD;
-  const int mode = evaluate ? BG_HEAD_EVALUATE : flags & BG_HEAD_DETERMINISTIC ? BG_HEAD_ARGMAX : BG_HEAD_SAMPLE;
+  O.lost = bg_head_logits_out_path(logits_out_dev, logits_out_stride_elems);
+  const int mode = bg_head_mode(flags, evaluate);
   const unsigned grid = (unsigned)((m + BG_POL_ROWS - 1) / BG_POL_ROWS);
   const BgPolNet net_arg = *N;
   hipStream_t s = (hipStream_t)stream;

@@ -19,7 +19,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .rows import RowActor, _check_device, _check_mask_aligned, _check_scan_tensor, _head_mask, _live_shadow, _native_call, _ptr
+from .rows import RowActor, _check_counters, _check_device, _check_h, _check_mask_aligned, _check_scan_tensor, _head_mask, _live_shadow, _native_call, _ptr
 
 _LAYER = np.dtype([("weight", "<u8"), ("bias", "<u8"), ("pitch", "<u4"), ("in", "<u2"), ("out", "<u2"), ("act", "<u4"), ("reserved", "<u4")])
 _NET = np.dtype([("n_trunk", "<u4"), ("n_pi", "<u4"), ("n_vf", "<u4"), ("has_value", "<u4"), ("in0", "<u4"), ("reserved", "<u4", (3,)),
@@ -242,24 +242,12 @@ class RowPolicy(torch.nn.Module):
         return net
 
     def _call(self, h, mask, given, flags: int, seed: int, index0: int, t: int, entropy: bool, taps: bool, timing: bool):
-        if not isinstance(h, torch.Tensor) or h.dtype != torch.bfloat16 or h.dim() < 1:
-            raise ValueError("h must be a torch.bfloat16 tensor [..., in_features] (the first layer's output)")
-        if int(h.shape[-1]) != self.in_features:
-            raise ValueError(f"the last dimension of h must be in_features = {self.in_features} (got {int(h.shape[-1])})")
-        pitch = int(h.stride(-2)) if h.dim() >= 2 and h.shape[-2] > 1 else self.in_features
-        dense = h.stride(-1) == 1 and pitch >= self.in_features
-        for d in range(h.dim() - 2, 0, -1):
-            dense = dense and h.stride(d - 1) == h.stride(d) * h.shape[d]
-        if not dense or pitch % 8:
-            raise ValueError("h must have a contiguous last dimension and leading dimensions dense over a row pitch that is a multiple of 8 elements")
-        lead = tuple(h.shape[:-1])
-        m = int(np.prod(lead, dtype=np.int64))
+        lead, m, _, pitch = _check_h(h, "h must be a torch.bfloat16 tensor [..., in_features] (the first layer's output)", (self.in_features,),
+                                     f"the last dimension of h must be in_features = {self.in_features} (got %d)")
         dev = h.device
         mask, moff, mstride = _head_mask(mask, lead, dev)
-        for what, v in (("seed", seed), ("index0", index0), ("t", t)):
-            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
-                raise ValueError(f"{what} must be an integer in [0, 2**64)")
-        if given is not None:
+        _check_counters(seed, index0, t)
+        if given is not None:   # (the only tensor of `_head_outputs` that is the caller's: every output is allocated below)
             _check_scan_tensor("actions", given, torch.int32, lead, dev)
         if self.action.weight.device != dev:
             raise ValueError(f"the policy's parameters are on {self.action.weight.device}, h is on {dev}")

@@ -104,6 +104,29 @@ def _check_index(index, shape: Optional[tuple], device: torch.device) -> None:
         raise ValueError(f"index must be a contiguous torch.int32 tensor of shape {list(shape) if shape is not None else '[m]'} on {device}")
 
 
+def _row_pitch(t: torch.Tensor, width: int, lone_row_is_width: bool) -> tuple:
+    """Is `t` (at least one dimension, rows of at least `width` elements) "last dimension contiguous, leading dimensions one run of rows", and at which
+    pitch -> (ok, row pitch in elements).  One dimension: the pitch is `width`.  Where shape[-2] <= 1 the callers have two conventions, and each
+    keeps its own:
+      lone_row_is_width False  stride(-2) all the same: `encode_rows`' out; the logits of the head and loss calls; an int8 mask, in every call
+      lone_row_is_width True   `width`: h of the actor calls and of `RowPolicy`; logits_out / dlogits_out of the actor calls"""
+    stride, shape = t.stride(), t.shape
+    pitch = stride[-2] if len(stride) >= 2 and not (lone_row_is_width and shape[-2] <= 1) else width
+    ok = stride[-1] == 1 and pitch >= width
+    for d in range(len(stride) - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
+        ok = ok and stride[d - 1] == stride[d] * shape[d]
+    return ok, pitch
+
+
+def _check_counters(*values, names: tuple = ("seed", "index0", "t")) -> None:
+    """The words of the counter hash: each an integer (no bool) in [0, 2**64), refused in the order passed (`names`: that order, where it is another)."""
+    for k, v in enumerate(values):
+        if type(v) is int and 0 <= v < 2 ** 64:   # (the common case, at a third of the cost of the full test)
+            continue
+        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
+            raise ValueError(f"{names[k]} must be an integer in [0, 2**64)")
+
+
 def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype = torch.float32, out: Optional[torch.Tensor] = None,
                 timing: bool = False, *, index: Optional[torch.Tensor] = None, norm: Optional["RowNormalizer"] = None):
     """Packed records -> the float matrix a policy network reads, in one launch (bg_encode_rows).  rows: a contiguous uint8 device tensor
@@ -139,10 +162,7 @@ def encode_rows(rows: torch.Tensor, layout: str = "produced", dtype: torch.dtype
             raise ValueError(f"out must be a {dtype} tensor on {rows.device}")
         if tuple(out.shape[:-1]) != lead or out.shape[-1] < D:
             raise ValueError(f"out must have shape {lead + ('>= %d' % D,)} (got {tuple(out.shape)})")
-        pitch = int(out.stride(-2)) if out.dim() >= 2 else int(out.shape[-1])
-        dense = out.stride(-1) == 1 and pitch >= out.shape[-1]
-        for d in range(out.dim() - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
-            dense = dense and out.stride(d - 1) == out.stride(d) * out.shape[d]
+        dense, pitch = _row_pitch(out, int(out.shape[-1]), False)
         if not dense:
             raise ValueError("out must have a contiguous last dimension and leading dimensions that are dense over its row pitch")
     _check_device(rows)
@@ -555,10 +575,7 @@ def _head_logits(logits) -> tuple:
     row pitch (e.g. 60 columns of a wider matrix) -> (leading shape, m, row pitch in elements)."""
     if not isinstance(logits, torch.Tensor) or logits.dtype not in (torch.float32, torch.bfloat16) or logits.dim() < 1 or logits.shape[-1] != 60:
         raise ValueError("logits must be a float32 or bfloat16 tensor [..., 60]")
-    pitch = int(logits.stride(-2)) if logits.dim() >= 2 else 60
-    dense = logits.stride(-1) == 1 and pitch >= 60
-    for d in range(logits.dim() - 2, 0, -1):   # leading dimensions: one run of rows `pitch` elements apart
-        dense = dense and logits.stride(d - 1) == logits.stride(d) * logits.shape[d]
+    dense, pitch = _row_pitch(logits, 60, False)
     if not dense:
         raise ValueError("logits must have a contiguous last dimension and leading dimensions that are dense over its row pitch")
     lead = tuple(logits.shape[:-1])
@@ -578,10 +595,7 @@ def _head_mask(mask, lead: tuple, device: torch.device) -> tuple:
             raise ValueError(f"a uint8 mask is a contiguous tensor [..., stride] of packed records: stride a multiple of 16, >= {nat.ROW_BYTES}")
         off = nat.ROW_OFFSETS["action_mask"]
     elif mask.dtype == torch.int8 and mask.shape[-1] == 60:
-        stride = int(mask.stride(-2)) if mask.dim() >= 2 else 60
-        dense = mask.stride(-1) == 1 and stride >= 60
-        for d in range(mask.dim() - 2, 0, -1):
-            dense = dense and mask.stride(d - 1) == mask.stride(d) * mask.shape[d]
+        dense, stride = _row_pitch(mask, 60, False)
         if not dense or stride % 4:
             raise ValueError("an int8 mask must have a contiguous last dimension and leading dimensions dense over a row pitch that is a multiple of 4")
         off = 0
@@ -605,6 +619,33 @@ def _head_args(logits, pitch: int, mask, moff: int, mstride: int) -> tuple:
             mask.data_ptr() + moff if mask is not None else None, C.c_uint64(mstride))
 
 
+def _head_outputs(lead: tuple, dev: torch.device, given, actions, log_prob, entropy):
+    """The outputs of a head-ended call, in two steps around the caller's last refusals.  Now: `given` (the actions to evaluate) and whichever of
+    actions / log_prob / entropy were passed are contiguous tensors of shape `lead` on `dev`.  The function returned, called behind the last refusal,
+    allocates what was not passed -> res: (log_prob, entropy) with `given`, else (actions, log_prob, entropy)."""
+    if given is not None:
+        _check_scan_tensor("actions", given, torch.int32, lead, dev)
+    if actions is not None or log_prob is not None or entropy is not None:   # (seldom: most callers let the call allocate)
+        for what, tt, dt in (("actions", actions, torch.int32), ("log_prob", log_prob, torch.float32), ("entropy", entropy, torch.float32)):
+            if tt is not None:
+                _check_scan_tensor(what, tt, dt, lead, dev)
+
+    def allocate() -> tuple:
+        lp = log_prob if log_prob is not None else torch.empty(lead, dtype=torch.float32, device=dev)
+        ent = entropy if entropy is not None else torch.empty(lead, dtype=torch.float32, device=dev)
+        if given is not None:
+            return lp, ent
+        return actions if actions is not None else torch.empty(lead, dtype=torch.int32, device=dev), lp, ent
+    return allocate
+
+
+def _check_no_alias(ins, outs) -> None:
+    """No output starts where an input or another output does (None: not passed).  For non-empty tensors: an empty one has no pointer."""
+    outs = [x.data_ptr() for x in outs if x is not None]
+    if len(set(outs)) != len(outs) or set(outs) & {x.data_ptr() for x in ins if x is not None}:
+        raise ValueError("outputs must not share memory with the inputs or with each other")
+
+
 def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: int, t: int, actions, log_prob, entropy, timing: bool,
                epsilon: Optional[float] = None):
     lead, m, pitch = _head_logits(logits)
@@ -612,39 +653,22 @@ def _head_call(name: str, logits, mask, given, flags: int, seed: int, index0: in
     mask, moff, mstride = _head_mask(mask, lead, dev)
     if epsilon is not None:
         return _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, index0, t, actions, log_prob, entropy, timing, epsilon)
-    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
-            raise ValueError(f"{what} must be an integer in [0, 2**64)")
-    if given is not None:
-        _check_scan_tensor("actions", given, torch.int32, lead, dev)
-    for what, tt, dt in (("actions", actions, torch.int32), ("log_prob", log_prob, torch.float32), ("entropy", entropy, torch.float32)):
-        if tt is not None:
-            _check_scan_tensor(what, tt, dt, lead, dev)
+    _check_counters(seed, index0, t)
+    allocate = _head_outputs(lead, dev, given, actions, log_prob, entropy)
     _check_device(logits, "logits", align=0)
     _check_mask_aligned(mask, moff)
-    if given is None and actions is None:
-        actions = torch.empty(lead, dtype=torch.int32, device=dev)
-    if log_prob is None:
-        log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
-    if entropy is None:
-        entropy = torch.empty(lead, dtype=torch.float32, device=dev)
-    res = (log_prob, entropy) if given is not None else (actions, log_prob, entropy)
+    res = allocate()
     if m == 0:   # nothing to launch (an empty tensor has no pointer to hand over)
         return _native_call(name, dev, (), res, timing, empty=True)
-    outs = [x.data_ptr() for x in res]
-    ins = [logits.data_ptr()] + ([mask.data_ptr()] if mask is not None else []) + ([given.data_ptr()] if given is not None else [])
-    if len(set(outs)) != len(outs) or set(outs) & set(ins):
-        raise ValueError("outputs must not share memory with the inputs or with each other")
+    _check_no_alias((logits, mask, given), res)
     head = (*_head_args(logits, pitch, mask, moff, mstride), C.c_int64(m))
-    if given is None:
-        args = (*head, C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), _ptr(actions), _ptr(log_prob), _ptr(entropy))
-    else:
-        args = (*head, _ptr(given), _ptr(log_prob), _ptr(entropy))
-    return _native_call(name, dev, args, res, timing)
+    front = (_ptr(given),) if given is not None else (C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)))
+    return _native_call(name, dev, (*head, *front, *map(_ptr, res)), res, timing)
 
 
 def _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, index0, t, actions, log_prob, entropy, timing, epsilon):
-    """bg_sample_actions_eps: the checks of `_head_call` for the sampling form, then the epsilon-greedy launch -> (actions, None, None)."""
+    """bg_sample_actions_eps: what is the epsilon-greedy form's own -- epsilon, no deterministic, ONE output (so it checks and compares that one itself) --
+    around the counters of `_head_call` -> (actions, None, None)."""
     dev = logits.device
     if isinstance(epsilon, bool) or not isinstance(epsilon, (int, float, np.integer, np.floating)) or not 0.0 <= float(epsilon) <= 1.0:
         raise ValueError("epsilon must be a number in [0, 1] (or None: the categorical head)")
@@ -652,9 +676,7 @@ def _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, ind
         raise ValueError("epsilon and deterministic=True exclude each other (epsilon=0.0 is the greedy rule)")
     if log_prob is not None or entropy is not None:
         raise ValueError("an epsilon-greedy action has no categorical log_prob / entropy: pass neither with epsilon")
-    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
-            raise ValueError(f"{what} must be an integer in [0, 2**64)")
+    _check_counters(seed, index0, t)
     if actions is not None:
         _check_scan_tensor("actions", actions, torch.int32, lead, dev)
     _check_device(logits, "logits", align=0)
@@ -664,7 +686,7 @@ def _head_call_eps(logits, lead, m, pitch, mask, moff, mstride, flags, seed, ind
     res = (actions, None, None)
     if m == 0:
         return _native_call("bg_sample_actions_eps", dev, (), res, timing, empty=True)
-    if actions.data_ptr() in {logits.data_ptr()} | ({mask.data_ptr()} if mask is not None else set()):
+    if actions.data_ptr() == logits.data_ptr() or (mask is not None and actions.data_ptr() == mask.data_ptr()):
         raise ValueError("outputs must not share memory with the inputs or with each other")
     args = (*_head_args(logits, pitch, mask, moff, mstride), C.c_int64(m), C.c_uint32(0), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)),
             C.c_float(float(epsilon)), _ptr(actions), None, None)
@@ -823,21 +845,30 @@ def ppo_loss(logits: torch.Tensor, actions: torch.Tensor, old_log_prob: torch.Te
 
 
 # ---------------------------------------------------------------------- the last layer fused with the head and with PPO's loss (bg_actor.h)
-def _actor_layer(h, weight, bias) -> tuple:
-    """(h, weight, bias) of the actor calls -> (leading shape, m, h's row pitch, Hin, weight's row pitch).  h: bfloat16 [..., Hin] with a contiguous last
-    dimension, leading dimensions dense over a row pitch that is a multiple of 8; weight: float32 / bfloat16 [60, Hin] (nn.Linear.weight's
-    orientation) with a contiguous last dimension; bias: contiguous float32 [60] or None."""
+def _check_h(h, not_h: str, widths, bad_width: str) -> tuple:
+    """h of the actor calls and of `RowPolicy`: bfloat16 [..., width], width in `widths`, with a contiguous last dimension and leading dimensions
+    dense over a row pitch that is a multiple of 8 -> (leading shape, m, width, row pitch).  The caller's own literals: `not_h` refuses what is no
+    such tensor, `bad_width` a width outside `widths` (its "%d" is the width h has)."""
     if not isinstance(h, torch.Tensor) or h.dtype != torch.bfloat16 or h.dim() < 1:
-        raise ValueError("h must be a torch.bfloat16 tensor [..., Hin] (the last hidden activation)")
-    Hin = int(h.shape[-1])
-    if Hin < nat.ACTOR_HIN_MIN or Hin > nat.ACTOR_HIN_MAX or Hin % 32:
-        raise ValueError(f"Hin, the last dimension of h, must be a multiple of 32 in [{nat.ACTOR_HIN_MIN}, {nat.ACTOR_HIN_MAX}] (got {Hin})")
-    pitch = int(h.stride(-2)) if h.dim() >= 2 and h.shape[-2] > 1 else Hin
-    dense = h.stride(-1) == 1 and pitch >= Hin
-    for d in range(h.dim() - 2, 0, -1):
-        dense = dense and h.stride(d - 1) == h.stride(d) * h.shape[d]
+        raise ValueError(not_h)
+    width = int(h.shape[-1])
+    if width not in widths:
+        raise ValueError(bad_width % width)
+    dense, pitch = _row_pitch(h, width, True)
     if not dense or pitch % 8:
         raise ValueError("h must have a contiguous last dimension and leading dimensions dense over a row pitch that is a multiple of 8 elements")
+    lead = tuple(h.shape[:-1])
+    return lead, int(np.prod(lead, dtype=np.int64)), width, pitch
+
+
+_ACTOR_HINS = range(nat.ACTOR_HIN_MIN, nat.ACTOR_HIN_MAX + 1, 32)
+_ACTOR_BAD_HIN = f"Hin, the last dimension of h, must be a multiple of 32 in [{nat.ACTOR_HIN_MIN}, {nat.ACTOR_HIN_MAX}] (got %d)"
+
+
+def _actor_layer(h, weight, bias) -> tuple:
+    """(h, weight, bias) of the actor calls -> (leading shape, m, h's row pitch, Hin, weight's row pitch).  h: `_check_h`; weight: float32 / bfloat16
+    [60, Hin] (nn.Linear.weight's orientation) with a contiguous last dimension; bias: contiguous float32 [60] or None."""
+    lead, m, Hin, pitch = _check_h(h, "h must be a torch.bfloat16 tensor [..., Hin] (the last hidden activation)", _ACTOR_HINS, _ACTOR_BAD_HIN)
     if not isinstance(weight, torch.Tensor) or weight.dtype not in (torch.float32, torch.bfloat16) or tuple(weight.shape) != (60, Hin) or weight.stride(1) != 1 \
             or weight.stride(0) < Hin:
         raise ValueError(f"weight must be a float32 / bfloat16 tensor [60, {Hin}] (nn.Linear.weight's orientation) with a contiguous last dimension")
@@ -845,20 +876,15 @@ def _actor_layer(h, weight, bias) -> tuple:
         raise ValueError(f"weight must be on {h.device}")
     if bias is not None:
         _check_vector("bias", bias, 60, h.device)
-    lead = tuple(h.shape[:-1])
-    return lead, int(np.prod(lead, dtype=np.int64)), pitch, Hin, int(weight.stride(0))
+    return lead, m, pitch, Hin, int(weight.stride(0))
 
 
 def _actor_tile_out(name: str, t, lead: tuple, device: torch.device) -> int:
     """logits_out / dlogits_out: None, or a float32 tensor [..., >= 60] over the leading shape, rows dense over its pitch -> the pitch (60 for None)."""
     if t is None:
         return 60
-    ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and tuple(t.shape[:-1]) == lead and t.dim() >= 1 and t.shape[-1] >= 60 \
-        and t.stride(-1) == 1
-    pitch = (int(t.stride(-2)) if t.dim() >= 2 and t.shape[-2] > 1 else int(t.shape[-1])) if ok else 0
-    ok = ok and pitch >= t.shape[-1]
-    for d in range(t.dim() - 2, 0, -1) if ok else ():
-        ok = ok and t.stride(d - 1) == t.stride(d) * t.shape[d]
+    ok = isinstance(t, torch.Tensor) and t.dtype == torch.float32 and t.device == device and tuple(t.shape[:-1]) == lead and t.dim() >= 1 and t.shape[-1] >= 60
+    ok, pitch = _row_pitch(t, int(t.shape[-1]), True) if ok else (False, 0)
     if not ok:
         raise ValueError(f"{name} must be a torch.float32 tensor {list(lead)} + [>= 60] on {device} with a contiguous last dimension and dense rows")
     return pitch
@@ -874,37 +900,18 @@ def _actor_head_call(name: str, h, weight, bias, mask, given, flags: int, seed: 
     lead, m, hpitch, Hin, wpitch = _actor_layer(h, weight, bias)
     dev = h.device
     mask, moff, mstride = _head_mask(mask, lead, dev)
-    for what, v in (("seed", seed), ("index0", index0), ("t", t)):
-        if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not 0 <= int(v) < 2 ** 64:
-            raise ValueError(f"{what} must be an integer in [0, 2**64)")
-    if given is not None:
-        _check_scan_tensor("actions", given, torch.int32, lead, dev)
-    for what, tt, dt in (("actions", actions, torch.int32), ("log_prob", log_prob, torch.float32), ("entropy", entropy, torch.float32)):
-        if tt is not None:
-            _check_scan_tensor(what, tt, dt, lead, dev)
+    _check_counters(seed, index0, t)
+    allocate = _head_outputs(lead, dev, given, actions, log_prob, entropy)
     lopitch = _actor_tile_out("logits_out", logits_out, lead, dev)
     _check_device(h, "h")
     _check_mask_aligned(mask, moff)
-    if given is None and actions is None:
-        actions = torch.empty(lead, dtype=torch.int32, device=dev)
-    if log_prob is None:
-        log_prob = torch.empty(lead, dtype=torch.float32, device=dev)
-    if entropy is None:
-        entropy = torch.empty(lead, dtype=torch.float32, device=dev)
-    res = (log_prob, entropy) if given is not None else (actions, log_prob, entropy)
+    res = allocate()
     if m == 0:
         return _native_call(name, dev, (), res, timing, empty=True)
-    outs = [x.data_ptr() for x in res] + ([logits_out.data_ptr()] if logits_out is not None else [])
-    ins = [x.data_ptr() for x in (h, weight, bias, mask, given) if x is not None]
-    if len(set(outs)) != len(outs) or set(outs) & set(ins):
-        raise ValueError("outputs must not share memory with the inputs or with each other")
+    _check_no_alias((h, weight, bias, mask, given), (*res, logits_out))
     head = (*_actor_head(h, hpitch, Hin, weight, wpitch, bias, mask, moff, mstride), C.c_int64(m))
-    tail = (_ptr(log_prob), _ptr(entropy), _ptr(logits_out), C.c_uint64(lopitch))
-    if given is None:
-        args = (*head, C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), _ptr(actions), *tail)
-    else:
-        args = (*head, _ptr(given), *tail)
-    return _native_call(name, dev, args, res, timing)
+    front = (_ptr(given),) if given is not None else (C.c_uint32(flags), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)))
+    return _native_call(name, dev, (*head, *front, *map(_ptr, res), _ptr(logits_out), C.c_uint64(lopitch)), res, timing)
 
 
 def actor_sample(h: torch.Tensor, weight: torch.Tensor, bias: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None, *, seed: int, t: int,
@@ -1434,9 +1441,7 @@ class DemoBuffer:
         m = int(m)
         if m < 0:
             raise ValueError("m must be >= 0")
-        for name, v in (("seed", seed), ("t", t), ("index0", index0)):
-            if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not 0 <= int(v) < 2 ** 64:
-                raise ValueError(f"{name} must be an integer in [0, 2**64)")
+        _check_counters(seed, t, index0, names=("seed", "t", "index0"))
         _check_device(self.cursor, "the ring", align=0)
         index = torch.empty(m, dtype=torch.int32, device=self.device)
         args = (_ptr(self.cursor), C.c_int64(self.capacity), C.c_uint64(int(seed)), C.c_uint64(int(index0)), C.c_uint64(int(t)), _ptr(index), C.c_int64(m))

@@ -52,7 +52,7 @@ extern "C" void eps_host(const float* logits, const int8_t* mask, int64_t m, uin
     const float u = bg_head_u(bg_head_hash(seed, index0 + (uint64_t)i, t));
     const uint32_t h2 = bg_head_hash(seed + BG_DQN_EPS_SALT, index0 + (uint64_t)i, t);
     actions[i] = mask ? bg_head_eps_row<true>(l, k, u, epsilon, h2) : bg_head_eps_row<false>(l, k, u, epsilon, h2);
-    greedy[i] = (mask ? bg_head_row<BG_HEAD_ARGMAX, true>(l, k, P, 0.0f, 0) : bg_head_row<BG_HEAD_ARGMAX, false>(l, k, P, 0.0f, 0)).action;
+    greedy[i] = bg_head_row_host(BG_HEAD_ARGMAX, mask != nullptr, l, k, P, 0, 0, 0, 0).action;
   }
 }
 """

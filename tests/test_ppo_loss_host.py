@@ -48,8 +48,7 @@ extern "C" void head_evaluate(const float* logits, const int8_t* mask, const int
     float P[BG_HEAD_ACTIONS];
     uint32_t k[BG_HEAD_ACTIONS / 4] = {};
     if (mask) memcpy(k, mask + i * BG_HEAD_ACTIONS, BG_HEAD_ACTIONS);
-    const BgHeadOut o = mask ? bg_head_row<BG_HEAD_EVALUATE, true>(logits + i * BG_HEAD_ACTIONS, k, P, 0.0f, actions[i])
-                             : bg_head_row<BG_HEAD_EVALUATE, false>(logits + i * BG_HEAD_ACTIONS, k, P, 0.0f, actions[i]);
+    const BgHeadOut o = bg_head_row_host(BG_HEAD_EVALUATE, mask != nullptr, logits + i * BG_HEAD_ACTIONS, k, P, 0, 0, 0, actions[i]);
     log_prob[i] = o.log_prob; entropy[i] = o.entropy;
   }
 }

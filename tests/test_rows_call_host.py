@@ -1,5 +1,6 @@
-"""rows._native_call on the CPU (no GPU, no library): the one place where the learner calls of balatro_gym_amd/rows.py meet the C ABI.  A stand-in
-library object records what it is handed; torch's device guard and current stream are stand-ins too, since neither exists without a device."""
+"""What the learner calls of balatro_gym_amd/rows.py share, on the CPU (no GPU, no library).  rows._native_call: the one place where they meet the
+C ABI.  A stand-in library object records what it is handed; torch's device guard and current stream are stand-ins too, since neither exists without a
+device.  rows._row_pitch: the row pitch of a strided tensor under the two conventions of its callers, and which public call has which."""
 import contextlib
 import ctypes as C
 
@@ -94,3 +95,72 @@ def test_native_call(lib):
     assert rows._native_call("bg_fake", dev, (), "R", True, empty=True) == ("R", 0.0)
     assert rows._native_call("bg_fake", dev, (), ("A", "B"), True, empty=True) == ("A", "B", 0.0)
     assert lib.loads == [] and lib.calls == [] and lib.guards == []
+
+
+def _strided(shape, stride, dtype=torch.float32):
+    return torch.zeros(4096, dtype=dtype).as_strided(shape, stride)
+
+
+# (shape, strides) -> (ok, pitch) with lone_row_is_width False, then True.  Read off the code `_row_pitch` replaced -- `_head_logits` (False) and
+# `_actor_layer` / `_actor_tile_out` (True) of the commit before it -- and confirmed by running those on these tensors.  Width 60 throughout.
+_PITCH_TABLE = [
+    ((60,), (1,), (True, 60), (True, 60)),                          # one dimension: the width
+    ((1, 60), (64, 1), (True, 64), (True, 60)),                     # [1, 60] of [1, 64]: the two conventions part on a lone row
+    ((3, 60), (64, 1), (True, 64), (True, 64)),                     # [3, 60] of [3, 64]
+    ((2, 1, 60), (60, 60, 1), (True, 60), (True, 60)),              # [2, 1, 60], contiguous
+    # KNOWN DEFECT, pinned because this table is about keeping every caller's pitch: for [2, 1, 60] of [2, 1, 64] True reports 60 for rows that are 64 apart
+    # ("The head calls have had it too": left to a pull request of its own).  The fix changes the last pair of THIS row to (True, 64); that is no regression.
+    ((2, 1, 60), (64, 64, 1), (True, 64), (True, 60)),
+    ((2, 3, 60), (192, 64, 1), (True, 64), (True, 64)),             # [2, 3, 60] over pitch 64
+    ((2, 3, 60), (256, 64, 1), (False, 64), (False, 64)),           # [2, 3, 60] of [2, 4, 64]: the leading dimension is not dense
+    ((3, 60), (120, 2), (False, 120), (False, 120)),                # a last stride of 2
+    ((3, 60), (32, 1), (False, 32), (False, 32)),                   # rows that overlap
+    ((1, 60), (8, 1), (False, 8), (True, 60)),                      # a lone row with an arbitrary stride: refused by False alone
+    ((0, 60), (60, 1), (True, 60), (True, 60)),                     # an empty leading shape
+    ((0, 60), (64, 1), (True, 64), (True, 60)),                     # ... of [0, 64]
+    ((2, 0, 60), (0, 64, 1), (True, 64), (True, 60)),
+]
+
+
+@pytest.mark.parametrize("shape,stride,plain,lone", _PITCH_TABLE)
+def test_row_pitch(shape, stride, plain, lone):
+    t = _strided(shape, stride)
+    assert rows._row_pitch(t, 60, False) == plain
+    assert rows._row_pitch(t, 60, True) == lone
+
+
+def test_row_pitch_conventions_of_the_calls():
+    """Each public call keeps its convention: a lone row whose stride(-2) its convention reads (False) or ignores (True) is refused for that stride or
+    passes every shape check and meets the last refusal, the device's."""
+    on_device = "must be a device tensor"
+    dense = "dense over"
+    lone = _strided((1, 60), (8, 1))                                  # False: pitch 8 < 60, refused; True: pitch 60
+    # lone_row_is_width False: encode_rows' out, the logits, the int8 mask
+    records = torch.zeros((1, 384), dtype=torch.uint8)
+    with pytest.raises(ValueError, match="out must have a contiguous last dimension and leading dimensions that are " + dense):
+        rows.encode_rows(records, out=_strided((1, 153), (8, 1)))
+    with pytest.raises(ValueError, match=on_device):
+        rows.encode_rows(records, out=_strided((1, 153), (160, 1)))
+    for call in (lambda lg, mk: rows.sample_actions(lg, mk, seed=1, t=0), lambda lg, mk: rows.sample_actions(lg, mk, seed=1, t=0, epsilon=0.5),
+                 lambda lg, mk: rows.evaluate_actions(lg, torch.zeros(1, dtype=torch.int32), mk)):
+        with pytest.raises(ValueError, match="logits must have a contiguous last dimension and leading dimensions that are " + dense):
+            call(lone, None)
+        with pytest.raises(ValueError, match="an int8 mask must have .* a row pitch that is a multiple of 4"):
+            call(_strided((1, 60), (64, 1)), _strided((1, 60), (62, 1), torch.int8))       # False: pitch 62; True would say 60 and pass
+        with pytest.raises(ValueError, match="logits " + on_device):
+            call(_strided((1, 60), (64, 1)), _strided((1, 60), (64, 1), torch.int8))
+    # lone_row_is_width True: h and logits_out of the actor calls, h of RowPolicy
+    h = _strided((1, 32), (36, 1), torch.bfloat16)                    # True: pitch 32; False would say 36, no multiple of 8
+    weight = torch.zeros((60, 32))
+    with pytest.raises(ValueError, match="h " + on_device):
+        rows.actor_sample(h, weight, seed=1, t=0, logits_out=lone)
+    with pytest.raises(ValueError, match="h " + on_device):
+        rows.actor_evaluate(h, weight, None, torch.zeros(1, dtype=torch.int32), logits_out=lone)
+    with pytest.raises(ValueError, match="h must have .* a row pitch that is a multiple of 8"):
+        rows.actor_sample(_strided((2, 32), (36, 1), torch.bfloat16), weight, seed=1, t=0)
+    from balatro_gym_amd.policy import RowPolicy
+    policy = RowPolicy([], [], [], rows.RowActor(32))
+    with pytest.raises(ValueError, match="h " + on_device):
+        policy.act(h, seed=1, t=0)
+    with pytest.raises(ValueError, match="h must have .* a row pitch that is a multiple of 8"):
+        policy.act(_strided((2, 32), (36, 1), torch.bfloat16), seed=1, t=0)
