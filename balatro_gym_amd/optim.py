@@ -131,6 +131,8 @@ class RowOptimizer:
             raise ValueError("attach takes a RowLinear, a RowExtractor, a RowActor, a RowDense or a RowPolicy")
         w = module.weight
         self._index_of(w, "module.weight")
+        if isinstance(module, RowDense):
+            module.apply_mask()   # a masked layer: the copy is masked_weight(), and the update pass keeps a zero at zero
         rows, cols = int(w.shape[0]), int(w.shape[1])
         pitch = cols + 1 if isinstance(module, RowExtractor) else cols   # 448: 16-byte lines, what bg_extractor_rows stages fastest
         store = torch.zeros((rows, pitch), dtype=torch.bfloat16, device=w.device)
@@ -142,11 +144,15 @@ class RowOptimizer:
 
     def refresh(self) -> None:
         """Write every attached bfloat16 copy from the current parameters (one launch) and record the weights' versions again: the remedy after
-        `load_state_dict`, a `copy_`, or a write through `.data`."""
+        `load_state_dict`, a `copy_`, or a write through `.data`.  The off-block entries of a masked `RowDense` are set to zero first."""
         ids = [i for i, p in enumerate(self.params) if id(p) in self._shadows]
         if not ids:
             return
         self._check_gpu()
+        for i in ids:
+            module = self._shadows[id(self.params[i])][3]
+            if isinstance(module, RowDense):
+                module.apply_mask()   # (after a load_state_dict with off-block entries: the copy is masked_weight() again)
         table, chunks = self._build_table(ids, shadow_only=True)
         args = (_ptr(table), len(ids), C.c_int64(chunks), nat.OPTIM_ADAM, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, C.c_uint32(nat.OPTIM_SHADOW_ONLY), None, None, None)
         _native_call("bg_optim_step", self.device, args, None, False)

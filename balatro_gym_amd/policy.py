@@ -8,7 +8,8 @@ bfloat16 and feeds `policy.action.ppo_loss`.
 Two implementations of one network have one consequence.  `act`'s log_prob (float32 accumulation on the matrix cores in ascending 16-blocks of k, the
 tanh of csrc/bg_policy.h) and the log_prob the first epoch computes through `latent` (rocBLAS' accumulation order, torch's tanh) are the same number up
 to those roundings, each followed by the same rounding to bfloat16 per layer: PPO's first ratio is near 1, not exactly 1.  tests/policy_ref.py bounds
-the kernel's side of that difference per layer.  There is no CPU fallback for `act` / `evaluate`.
+the kernel's side of that difference per layer; tests/test_policy_train.py holds |log_prob(act) - log_prob(latent)| below log(1.2) on every row (measured: at most
+0.039 on the reference's topology).  There is no CPU fallback for `act` / `evaluate`.
 """
 from __future__ import annotations
 
@@ -39,7 +40,11 @@ class RowDense(torch.nn.Module):
     activation None, "relu" or "tanh".  in_features and out_features: multiples of 32 in [32, 512]; out_features 1 is the value layer.  The launch reads
     a bfloat16 copy of the weight: the one `RowOptimizer.attach` keeps while it is current (`weight_bf16`, the shadow protocol of `RowActor`), else a
     cast per call.  mask: a 0 / 1 float32 [out_features, in_features] buffer (`block_mask`); `forward` multiplies the weight by it, so the gradient of an
-    off-block entry is exactly zero and an entry that starts at zero stays zero under Adam and RMSprop without weight decay.
+    off-block entry is exactly zero and an entry that is zero stays zero under Adam and RMSprop, with L2 weight decay too (its term is wd * 0).
+    THE INVARIANT of a masked layer: whatever a launch, an attached copy or `to_linear()` reads is `masked_weight()`.  It holds because the parameter
+    itself obeys the mask wherever its raw value is read: the constructor zeroes the off-block entries (+0.0) behind nn.Linear's initialisation,
+    `RowOptimizer.attach` and `RowOptimizer.refresh()` zero them again (`apply_mask`) before they copy the weight and record its version, the per-call
+    cast and `to_linear()` go through `masked_weight()`, and `load_state_dict` bumps the version, so the masked cast serves until `refresh()`.
     `forward(x)` is the torch path (training): F.linear in x's dtype, then the activation."""
 
     def __init__(self, in_features: int, out_features: int, activation: Optional[str] = None, mask: Optional[torch.Tensor] = None, device=None):
@@ -59,6 +64,7 @@ class RowDense(torch.nn.Module):
                 raise ValueError(f"mask must be a tensor [{out_features}, {in_features}]")
             mask = (mask != 0).to(dtype=torch.float32, device=self.weight.device)
         self.register_buffer("block_mask", mask)
+        self.apply_mask()
         self.weight_bf16, self._weight_bf16_version = None, -1   # RowOptimizer.attach: a bfloat16 copy kept by the update pass (`_live_shadow`)
 
     @classmethod
@@ -74,9 +80,15 @@ class RowDense(torch.nn.Module):
     def to_linear(self) -> torch.nn.Linear:
         lin = torch.nn.Linear(self.in_features, self.out_features, device=self.weight.device)
         with torch.no_grad():
-            lin.weight.copy_(self.weight)
+            lin.weight.copy_(self.masked_weight())
             lin.bias.copy_(self.bias)
         return lin
+
+    def apply_mask(self) -> None:
+        """Set the off-block entries of the parameter to +0.0 (the invariant above).  Written through `.data`: the weight's version does not move, so
+        the callers that copy the weight right behind it (`RowOptimizer.attach`, `refresh()`) record the version they read."""
+        if self.block_mask is not None:
+            self.weight.data.masked_fill_(self.block_mask == 0, 0.0)
 
     def masked_weight(self) -> torch.Tensor:
         return self.weight if self.block_mask is None else self.weight * self.block_mask

@@ -41,8 +41,11 @@ EXACT = {
     "4+4+4x32": dict(in0=32, trunk=[(32, "relu"), (32, None), (32, "relu"), (32, "relu")], pi=[(32, "relu"), (32, "relu"), (32, None), (32, "relu")],
                      vf=[(32, None), (32, "relu"), (32, "relu"), (32, "relu")], value=True),
     "512-per-section": dict(in0=96, trunk=[(512, "relu")], pi=[(512, "relu")], vf=[(512, None)], value=True),
+    # k-steps that end inside a batch of 8 behind the first batch (in 160: 10 steps, in 288: 18); tiles that give waves 0 and 1 two tiles and the others
+    # one (out 288 over 8 waves x 32 units), and waves 3..7 none (out 96)
+    "in160-288-96|pi288|vf96": dict(in0=160, trunk=[(288, "relu"), (96, None)], pi=[(288, "relu")], vf=[(96, "relu")], value=True),
 }
-MS = (1, 65, 130)
+MS = (1, 32, 64, 65, 130)   # 32, 64: the last workgroup is full (nrow == 32)
 
 
 class Layer:
@@ -86,7 +89,12 @@ class Net:
 
 def layer(xb, l):
     """-> (ref float64 [m, out], bound) of one layer (module docstring)."""
-    x, w, b = widen(xb), widen(l.wb), l.bias.astype(np.float64)
+    return layer64(widen(xb), l)
+
+
+def layer64(x, l):
+    """`layer` over float64 activations x (the values, not bfloat16 bits)."""
+    w, b = widen(l.wb), l.bias.astype(np.float64)
     s = x @ w.T + b
     bound = 2 * (x.shape[1] + 2) * U * (np.abs(x) @ np.abs(w).T + np.abs(b)) + U * np.abs(s)
     if l.act == "relu":
@@ -121,6 +129,20 @@ def check_taps(net, hb, taps, logits, values, what):
     if net.value is not None:
         ref, bound = layer(lat_vf, net.value)
         check_close(values, ref[:, 0], bound[:, 0], what + ": values")
+
+
+def chain64(net, hb):
+    """-> (logits float64 [m, 60], values float64 [m] or None): `layer64` applied layer by layer to float64 activations, NO rounding between the
+    layers -- the network itself, which both the kernel and the bfloat16 torch path approximate with one rounding to bfloat16 per layer."""
+    x = widen(hb)
+    for l in net.trunk:
+        x = layer64(x, l)[0]
+    p = v = x
+    for l in net.pi:
+        p = layer64(p, l)[0]
+    for l in net.vf:
+        v = layer64(v, l)[0]
+    return layer64(p, net.action)[0], layer64(v, net.value)[0][:, 0] if net.value is not None else None
 
 
 # ---------------------------------------------------------------------- the nets
@@ -211,3 +233,112 @@ def to_policy(net, device):
         return d
     return RowPolicy([dense(l) for l in net.trunk], [dense(l) for l in net.pi], [dense(l) for l in net.vf], dense(net.action, RowActor),
                      dense(net.value) if net.value is not None else None)
+
+
+# ---------------------------------------------------------------------- the activations at their special values
+# One hidden layer 64 -> 64 whose weight is the identity and whose bias is zero: unit j has ONE non-zero product, x[j] * 1, and every other product is
+# x[k] * 0.  For finite x those are zeros of either sign, the accumulator starts at +0.0, and a float32 sum of x[j] with zeros is x[j] in any order:
+# the pre-activation IS x[j] -- with one exception the contract itself makes: for x[j] = -0.0 the sum (+0.0) + (-0.0) is +0.0 in round-to-nearest, so
+# the pre-activation of -0.0 is +0.0.  For a row that holds +-inf or NaN in column c the exact products inf * 0 and NaN * 0 are NaN: every unit but c
+# is NaN (0x7fc0 behind bg_ppo_bf16), unit c is x[c] itself.  The action and value layers have zero weights and zero bias: a finite row's logits and
+# value are 0.0, a non-finite row's are NaN (tap * 0), and the head answers such a row with action -1 and NaN (bg_head.h, "degenerate").
+SPECIAL_FINITE = (0.0, 2.0 ** -126, 1e-3, 0.5, 1.0, 9.0, 44.0, 45.0, 88.0, 3e38)   # and their negatives; +-inf, NaN and the subnormal: rows of their own
+SPECIAL_M = 33            # a full workgroup that holds every special row, and one row of a second
+SPECIAL_ROWS = {"+inf": (20, 5, 0x7F80), "-inf": (21, 37, 0xFF80), "nan": (22, 11, 0x7FC0)}   # name -> (row, column, bits)
+SPECIAL_SUB_ROW = 23      # +2**-130 (bits 0x0008) in column 3, -2**-130 (0x8008) in column 40, +0.0 elsewhere: a bfloat16 subnormal OPERAND
+SPECIAL_SUB = ((3, 0x0008), (40, 0x8008))
+QNAN = 0x7FC0
+
+
+def special_case(act):
+    """-> dict(net, hb [33, 64] bits, hb_finite (the three non-finite rows replaced by +0.0 rows), lo / hi (bits [33, 64]: the tap must lie in
+    [lo, hi]; lo == hi: those bits exactly; QNAN in both: 0x7fc0 exactly), nonfinite (row indices), pairs (the (row, col), (row, col') places that hold
+    x and -x for a finite non-zero x).  The expectation is the contract of csrc/bg_policy.h (comment above)."""
+    assert act in ACT
+    n = Net()
+    n.in0 = 64
+    n.trunk = [Layer(to_bf16_bits(np.eye(64, dtype=np.float32)), np.zeros(64, np.float32), act)]
+    n.pi, n.vf = [], []
+    n.action = Layer(np.zeros((UNITS, 64), np.uint16), np.zeros(UNITS, np.float32), None)
+    n.value = Layer(np.zeros((1, 64), np.uint16), np.zeros(1, np.float32), None)
+    pos = to_bf16_bits(np.array(SPECIAL_FINITE, np.float32))
+    table = np.concatenate([pos, pos ^ 0x8000]).astype(np.uint16)   # 20 finite values, -0.0 among them
+    assert np.isfinite(widen(table)).all() and len(table) == 20
+    r, c = np.meshgrid(np.arange(SPECIAL_M), np.arange(64), indexing="ij")
+    hb = table[(r + c) % len(table)]
+    for row, col, bits in SPECIAL_ROWS.values():
+        hb[row, col] = bits
+    hb[SPECIAL_SUB_ROW] = 0
+    for col, bits in SPECIAL_SUB:
+        hb[SPECIAL_SUB_ROW, col] = bits
+    nonfinite = sorted(row for row, _, _ in SPECIAL_ROWS.values())
+    hb_finite = hb.copy()
+    hb_finite[nonfinite] = 0
+    # the expectation, element by element, from the pre-activation y = x (y = +0.0 for x = -0.0)
+    y = hb.copy()
+    y[y == 0x8000] = 0
+    yv = widen(y)
+    if act is None:
+        lo = hi = y
+    elif act == "relu":   # bg_lin_relu: v > 0 ? v : NaN kept : +0.0
+        lo = hi = np.where(yv > 0, y, np.where(np.isnan(yv), QNAN, 0)).astype(np.uint16)
+    else:
+        with np.errstate(invalid="ignore"):
+            t = np.tanh(yv)
+            lo, hi = rne_bits(t - TANH_ABS), rne_bits(t + TANH_ABS)
+        one = np.where(yv < 0, 0xBF80, 0x3F80).astype(np.uint16)
+        sat = np.abs(yv) >= 45.0   # e = expf(2 |y|) is +inf from |y| > 44.4 on: r = 1 - 2 / inf = 1 exactly, and at inf
+        lo, hi = np.where(sat, one, lo).astype(np.uint16), np.where(sat, one, hi).astype(np.uint16)
+        zero = yv == 0   # t = 0, e = 1, r = 1 - 2 / 2 = +0.0 exactly
+        lo, hi = np.where(zero, 0, lo).astype(np.uint16), np.where(zero, 0, hi).astype(np.uint16)
+    lo, hi = lo.copy(), hi.copy()
+    for row, col, bits in SPECIAL_ROWS.values():   # inf * 0 and NaN * 0 are NaN in every unit but `col`; a NaN in `col` stays one
+        others = np.arange(64) != col
+        lo[row, others] = hi[row, others] = QNAN
+        if bits == QNAN:
+            lo[row, col] = hi[row, col] = QNAN
+    pairs = []
+    for row in range(SPECIAL_M):
+        if row in nonfinite or row == SPECIAL_SUB_ROW:
+            continue
+        for col in range(64 - 10):   # table[k] and table[k + 10] = -table[k] stand ten columns apart
+            if (row + col) % 20 < 10 and (hb[row, col] & 0x7FFF) != 0:
+                assert hb[row, col + 10] == hb[row, col] ^ 0x8000
+                pairs.append((row, col, col + 10))
+    return dict(net=n, hb=hb, hb_finite=hb_finite, lo=lo, hi=hi, nonfinite=nonfinite, pairs=np.array(pairs), act=act)
+
+
+def check_special(case, taps, logits, values, actions, log_prob, what):
+    """The taps of `special_case` against the contract, bit for bit where it fixes the bits; the logits / values / head of finite and non-finite rows."""
+    taps, lo, hi = np.asarray(taps, np.uint16), case["lo"], case["hi"]
+    assert taps.shape == lo.shape, f"{what}: shape {taps.shape}"
+    exact = lo == hi
+    bad = exact & (taps != lo)
+    assert not bad.any(), (f"{what}: {int(bad.sum())} taps differ from the bits the contract fixes; first at {np.argwhere(bad)[0]}: "
+                           f"got {taps[tuple(np.argwhere(bad)[0])]:#06x}, want {lo[tuple(np.argwhere(bad)[0])]:#06x}")
+    with np.errstate(invalid="ignore"):
+        g, l, h = widen(taps), widen(lo), widen(hi)
+        out = ~exact & ~((g >= l) & (g <= h))
+    assert not out.any(), f"{what}: {int(out.sum())} taps outside [rne(tanh - TANH_ABS), rne(tanh + TANH_ABS)]; first at {np.argwhere(out)[0]}"
+    if case["act"] != "relu":   # tanh puts the sign of y back on r: an odd function to the bit (so is the identity)
+        p = case["pairs"]
+        odd = taps[p[:, 0], p[:, 1]] ^ 0x8000 != taps[p[:, 0], p[:, 2]]
+        assert len(p) > 400 and not odd.any(), f"{what}: tap(-x) is not tap(x) with the sign flipped at {p[odd][:3]}"
+    nf = np.zeros(len(taps), bool)
+    nf[case["nonfinite"]] = True
+    logits, values = np.asarray(logits), np.asarray(values)
+    assert np.isnan(logits[nf]).all() and np.isnan(values[nf]).all(), f"{what}: a non-finite row's logits and value are NaN (tap * 0)"
+    assert (logits[~nf] == 0).all() and (values[~nf] == 0).all(), f"{what}: a finite row's logits and value are 0"
+    actions, log_prob = np.asarray(actions), np.asarray(log_prob)
+    assert (actions[nf] == -1).all() and np.isnan(log_prob[nf]).all(), f"{what}: the head answers NaN logits with -1 and NaN"
+    assert ((actions[~nf] >= 0) & (actions[~nf] < UNITS)).all() and np.isfinite(log_prob[~nf]).all()
+
+
+def pitched(bits, pitch, fill):
+    """-> (a [rows, pitch] uint16 array whose first columns are `bits` and whose padding is `fill`, 16-byte aligned; the storage that keeps it alive)."""
+    bits = np.asarray(bits, np.uint16)
+    storage = np.full(bits.shape[0] * pitch + 8, fill, np.uint16)
+    off = (-storage.ctypes.data % 16) // 2
+    a = storage[off:off + bits.shape[0] * pitch].reshape(bits.shape[0], pitch)
+    a[:, :bits.shape[1]] = bits
+    return a, storage

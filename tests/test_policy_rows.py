@@ -1,5 +1,8 @@
 """bg_policy_forward (RowPolicy.act / .evaluate) on the MI355X, against tests/policy_ref.py.
-  1  the exact cases: taps, logits and values EQUAL the integers, at m in {1, 65, 130} (a partial workgroup, past two, past four);
+  1  the exact cases: taps, logits and values EQUAL the integers, at m in {1, 32, 64, 65, 130} (a partial workgroup, full last workgroups, past two,
+     past four); widths that give some waves two tiles and others one or none, k-steps that end inside a batch of 8;
+  1a the activations at their special values (+-0, tanh's saturation, +-inf, NaN, a subnormal operand) against the contract, bit for bit;
+  1b weights, h, taps and logits at pitches wider than their columns, through the C ABI: the integers, and every padding element keeps its fill;
   2  the reference's topology on random data, h a column slice of a wider tensor: every hidden layer's tapped output inside the interval around the
      float64 value of its own tapped input, logits and values inside their bounds;
   3  the head: actions / log_prob / entropy bit for bit sample_actions / evaluate_actions on the tapped logits, under the masks of real records and
@@ -73,6 +76,77 @@ def test_exact_cases_equal_the_integers(name):
         else:
             assert np.array_equal(v.cpu().numpy().astype(np.float64), values), f"{name} m {m}: values"
         assert ((a >= 0) & (a < 60)).all() and bool(lp.isfinite().all())
+
+
+@pytest.mark.parametrize("act", ["tanh", "relu", None])
+def test_activations_at_their_special_values(act):
+    """policy_ref.special_case through an identity layer: +-0, the smallest normal, tanh's saturation (0x3f80 / 0xbf80 from |x| >= 45 on and at inf),
+    tanh odd to the bit, +-inf and NaN in rows of their own (inf * 0 is NaN in every other unit of the row), one row with a bfloat16 SUBNORMAL operand
+    (+-2**-130), whose tap the contract says is the operand itself under none / relu; and the finite rows of the same 32-row workgroup do not notice
+    the non-finite rows beside them: every output bit for bit the run without them."""
+    c = pr.special_case(act)
+    policy = pr.to_policy(c["net"], "cuda")
+    kw = dict(seed=3, t=1, entropy=True, taps=True)
+    a, lp, v, en, tp, lg = policy.act(_bf16(c["hb"]), **kw)
+    sub = _u16(tp)[pr.SPECIAL_SUB_ROW]
+    print(f"{act}: the subnormal operands' taps {[f'{int(sub[col]):#06x}' for col, _ in pr.SPECIAL_SUB]} (operands {[f'{b:#06x}' for _, b in pr.SPECIAL_SUB]})")
+    pr.check_special(c, _u16(tp), lg.cpu().numpy(), v.cpu().numpy(), a.cpu().numpy(), lp.cpu().numpy(), f"special values, {act}")
+    assert bool(en[c["nonfinite"]].isnan().all())
+    q = policy.act(_bf16(c["hb_finite"]), **kw)
+    keep = np.setdiff1d(np.arange(pr.SPECIAL_M), c["nonfinite"])
+    for k, name in enumerate(("actions", "log_prob", "values", "entropy", "taps", "logits")):
+        g, w = _bits((a, lp, v, en, tp, lg)[k])[keep], _bits(q[k])[keep]
+        assert np.array_equal(g, w), f"{act}: {name} of the finite rows beside the non-finite ones"
+    assert bool(q[5].isfinite().all()) and bool((q[0] >= 0).all())
+
+
+def test_pitched_weights_taps_and_logits_through_the_c_abi():
+    """wpitch > in, h_stride > in0, taps_stride > tap cols, logits_out_stride > 60: the exact case 64-32|pi32|novf at m = 33 equals the integers, and
+    every padding element and every element behind row m keeps its fill (the weights' and h's padding is NaN: a read of it would show)."""
+    import torch
+    from balatro_gym_amd import _native as nat
+    from balatro_gym_amd.policy import _NET
+    net, m = pr.exact_net(pr.EXACT["64-32|pi32|novf"], 11), 33
+    hb = pr.exact_h(m, net.in0, 5 + m)
+    taps, logits, values = pr.exact_forward(net, hb)
+    tcols = net.tap_cols()
+    assert values is None and tcols == 64
+    nan, dev = float("nan"), "cuda"
+
+    def pitched(bits, pitch):
+        t = torch.full((bits.shape[0], pitch), nan, dtype=torch.bfloat16, device=dev)
+        t[:, :bits.shape[1]] = _bf16(bits)
+        return t
+    t = np.zeros(1, _NET)
+    n, keep = t[0], []
+    n["n_trunk"], n["n_pi"], n["n_vf"], n["has_value"], n["in0"] = 1, 1, 0, 0, net.in0
+    for k, l in enumerate(net.hidden() + [net.action]):
+        w, b = pitched(l.wb, l.in_ + 8), torch.from_numpy(l.bias).to(dev)
+        keep += [w, b]
+        e = n["layer"][k]
+        e["weight"], e["bias"], e["pitch"], e["in"], e["out"], e["act"] = w.data_ptr(), b.data_ptr(), l.in_ + 8, l.in_, l.out, pr.ACT[l.act]
+    L = nat.load()
+    assert L.bg_policy_check(t.ctypes.data) == 0 and L.bg_policy_tap_cols(t.ctypes.data) == tcols
+    h = pitched(hb, net.in0 + 8)
+    TS, LS, FILL = tcols + 8, 64, 0x7B7B
+    tp = torch.full((m + 2, TS), FILL, dtype=torch.int16, device=dev)
+    lg = torch.full((m + 2, LS), -777.0, device=dev)
+    a = torch.full((m + 2,), 123, dtype=torch.int32, device=dev)
+    lp, en = torch.full((m + 2,), -777.0, device=dev), torch.full((m + 2,), -777.0, device=dev)
+    rc = L.bg_policy_forward(t.ctypes.data, h.data_ptr(), net.in0 + 8, None, 0, m, 0, 1, 0, m, a.data_ptr(), lp.data_ptr(), en.data_ptr(), None, tp.data_ptr(), TS,
+                             lg.data_ptr(), LS, None, torch.cuda.current_stream().cuda_stream)
+    assert rc == 0, L.bg_last_error(None)
+    torch.cuda.synchronize()
+    tpn, lgn = tp.cpu().numpy().view(np.uint16), lg.cpu().numpy()
+    assert np.array_equal(tpn[:m, :tcols], taps), "taps at a pitch"
+    assert np.array_equal(lgn[:m, :60].astype(np.float64), logits), "logits at a pitch"
+    assert (tpn[:m, tcols:] == FILL).all() and (tpn[m:] == FILL).all(), "the taps' padding and the rows behind m keep their fill"
+    assert (lgn[:m, 60:] == -777.0).all() and (lgn[m:] == -777.0).all(), "the logits' padding and the rows behind m keep their fill"
+    assert bool((a[m:] == 123).all()) and bool((lp[m:] == -777.0).all()) and bool((en[m:] == -777.0).all()), "nothing is written behind row m"
+    # the other outputs are those of the dense call on the same net
+    wa, wlp, _, wen = pr.to_policy(net, dev).act(_bf16(hb), seed=1, t=m, entropy=True)
+    _same(a[:m], wa, "actions"); _same(lp[:m], wlp, "log_prob"); _same(en[:m], wen, "entropy")
+    assert bool(((wa >= 0) & (wa < 60)).all()) and bool(wlp.isfinite().all())
 
 
 def test_reference_topology_is_inside_the_per_layer_intervals():

@@ -1,7 +1,8 @@
 """bg_policy_forward on the CPU (no GPU): the header's declarations and the library's exports; csrc/bg_policy.h compiled with g++ under BG_POLICY_HOST --
 the fragment, image and table index functions the kernel uses and the serial twin that drives them through a scalar model of
 v_mfma_f32_32x32x16_bf16 -- held to tests/policy_ref.py: EQUAL on the exact cases (any accumulation order is exact there, so a wrong lane map, image
-swap or layer order cannot pass), inside the derived per-layer intervals on the reference's topology; the envelope check; the argument checks of
+swap or layer order cannot pass), inside the derived per-layer intervals on the reference's topology, to the contract's bits on the activations'
+special values (policy_ref.special_case) and on pitched weights; the envelope check; the argument checks of
 RowDense / RowPolicy on CPU stand-ins; from_modules / to_modules; stack_blocks and its mask under an optimiser step; latent() against plain modules."""
 import ctypes as C
 import os
@@ -155,6 +156,46 @@ def test_twin_equals_the_integers_on_the_exact_cases(host, name):
             assert np.array_equal(o["logits"].astype(np.float64), logits), (name, m, kw)
             if values is not None:
                 assert np.array_equal(o["values"].astype(np.float64), values), (name, m, kw)
+
+
+@pytest.mark.parametrize("act", ["tanh", "relu", None])
+def test_twin_activations_at_their_special_values(host, act):
+    """policy_ref.special_case: +-0, the smallest normal, tanh's saturation, +-inf, NaN and a subnormal operand through an identity layer; the finite
+    rows of the workgroup do not notice the non-finite ones beside them."""
+    c = pr.special_case(act)
+    o = host.run(c["net"], c["hb"], seed=3, t=1)
+    pr.check_special(c, o["taps"], o["logits"], o["values"], o["actions"], o["log_prob"], f"twin, {act}")
+    q = host.run(c["net"], c["hb_finite"], seed=3, t=1)
+    keep = np.setdiff1d(np.arange(pr.SPECIAL_M), c["nonfinite"])
+    for k in ("actions", "log_prob", "entropy", "values", "taps", "logits"):
+        assert np.array_equal(o[k][keep].view(np.uint8), q[k][keep].view(np.uint8)), (act, k)
+    assert np.isfinite(q["logits"]).all() and (q["actions"] >= 0).all()
+
+
+def test_twin_reads_pitched_weights_and_equals_the_integers(host):
+    """The case tests/test_policy_rows.py sends through the C ABI with pitched weights, taps and logits: the twin's taps and logits are dense by
+    construction, so the weights' pitch (in + 8, NaN padding) and h's are what it can show."""
+    from balatro_gym_amd.policy import _NET
+    net, m = pr.exact_net(pr.EXACT["64-32|pi32|novf"], 11), 33
+    hb = pr.exact_h(m, net.in0, 5 + m)
+    taps, logits, values = pr.exact_forward(net, hb)
+    assert values is None
+    t = np.zeros(1, _NET)
+    n, keep = t[0], []
+    n["n_trunk"], n["n_pi"], n["n_vf"], n["has_value"], n["in0"] = 1, 1, 0, 0, net.in0
+    for k, l in enumerate(net.hidden() + [net.action]):
+        w, storage = pr.pitched(l.wb, l.in_ + 8, pr.QNAN)
+        keep += [storage, l.bias]
+        e = n["layer"][k]
+        e["weight"], e["bias"], e["pitch"], e["in"], e["out"], e["act"] = w.ctypes.data, l.bias.ctypes.data, l.in_ + 8, l.in_, l.out, pr.ACT[l.act]
+    assert host.check(t) is None
+    h, hkeep = pr.pitched(hb, net.in0 + 8, pr.QNAN)
+    got_t, got_l = np.full((m, net.tap_cols()), 0x7B7B, np.uint16), np.full((m, 60), -777.0, np.float32)
+    a, lp, en = np.full(m, -7, np.int32), np.empty(m, np.float32), np.empty(m, np.float32)
+    host.lib.pol_host(t.ctypes.data, SAMPLE, h.ctypes.data, net.in0 + 8, None, 60, m, 1, 0, m, a.ctypes.data, lp.ctypes.data, en.ctypes.data, None,
+                      got_t.ctypes.data, got_l.ctypes.data)
+    assert np.array_equal(got_t, taps) and np.array_equal(got_l.astype(np.float64), logits)
+    assert ((a >= 0) & (a < 60)).all() and np.isfinite(lp).all()
 
 
 def test_twin_is_inside_the_intervals_on_the_reference_topology(host):
